@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s + I2_S matmul HBM GB/s (% roofline) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): bitnet-b1.58-2B-4T shapes, I2_S ternary weights
@@ -18,6 +18,12 @@ replica ("replicas only", weak scaling); value = N * K / max-over-ranks time.
 
 Prints ONE JSON line (rank 0).  `--workload c3` switches to the QK256 no-scale format
 (BASELINE.json configs[2], the reference's live decode path).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the line.  `--full` adds everything
+else to the same line, outside the timed region: roofline and per-kernel probes, the exact / oracle step checks, i2s_stream,
+the c4 prefill check and roofline, cpu_baseline, the `also` workloads and, with N > 1, the token-parallel prefill.
+`--dump-outputs DIR` writes what the last timed step handed its caller (logits; the greedy tokens of the timed steps) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -36,6 +42,14 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy ceiling ~6290
 PROMPT_LEN = 128
+
+
+def dump_outputs(out_dir: str, **arrays) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy, float32 (float64 for integers, which it holds exactly)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float64 if a.dtype.kind in "iu" else np.float32))
 
 
 def build_model_from_gguf(pkg, synth, path: str, max_pos: int):
@@ -631,7 +645,7 @@ def main():
     ap.add_argument("--stream-format", default="i2s", choices=["i2s", "qk256"])
     ap.add_argument("--stream-isolated", action="store_true", help="stream workload: isolated launches only, no back-to-back bursts (the profiler's trace pass: "
                     "rocprofv3's per-kernel duration is then the one i2s_stream.us_per_launch reports)")
-    ap.add_argument("--no-stream", action="store_true", help="skip the i2s_stream object of the default line")
+    ap.add_argument("--no-stream", action="store_true", help="--full: skip the i2s_stream object")
     ap.add_argument("--no-exact-check", action="store_true", help="skip exact_step_check (the profiler passes: its reference-order kernels would fill the kernel table)")
     ap.add_argument("--prompt", type=int, default=None, help="prompt length (default 128; 4096 for c4)")
     ap.add_argument("--digits", type=int, default=2, help="c4 / c5 prefill: fixed-point digits per activation row in the tiled matmuls (2: 15 bits of the row "
@@ -639,17 +653,23 @@ def main():
                     "same sampled token -- tools/perf_prefill_digits.py; 3 or 4 for tighter)")
     ap.add_argument("--layers", type=int, default=None, help="debug only: fewer layers (result is then not the benchmark)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the `also` object (c3, c4 and the BitNet32-F16 prefill measured after the c2 line, same process)")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the `also` object (c3, c4 and the BitNet32-F16 prefill measured after the c2 line, same process)")
     ap.add_argument("--eager", action="store_true", help="launch kernels one by one instead of replaying the step graph")
     ap.add_argument("--c5-timeout", type=float, default=240.0, help="N > 1: seconds the token-parallel prefill part may take before the line is printed without it")
     ap.add_argument("--gguf", default=None, help="a real model file instead of synthetic weights (default: $BITNET_GGUF if set); the line then says data: gguf")
-    ap.add_argument("--no-c5", action="store_true", help="N > 1: skip the token-parallel prefill that normally rides in the same line")
+    ap.add_argument("--no-c5", action="store_true", help="--full, N > 1: skip the token-parallel prefill that otherwise rides in the same line")
     ap.add_argument("--c5-prompt", type=int, default=8192, help="prompt length of that prefill (a multiple of 128 x N)")
     ap.add_argument("--kv16", action="store_true", help="f16 KV cache (half the bytes of the long-context attention stream; the reference's cache is f32): the default of "
                     "the long-context workload c4, where the K/V stream outweighs the weights; parity-tested against the oracle at 2k+ keys (tests/test_decode_parity.py)")
     ap.add_argument("--kv32", action="store_true", help="c4: keep the f32 KV cache (the reference's type, T:1171-1202)")
     ap.add_argument("--exact-act", action="store_true", help="exact f32 activations between the kernels (round 1's path) instead of QAct")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline, in the same line: roofline and per-kernel probes, the exact / "
+                    "oracle step checks, i2s_stream, the c4 prefill check and roofline, cpu_baseline, the `also` workloads, N > 1: prefill_c5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="decode workloads: write what the last timed step computed (logits; the greedy "
+                    "tokens of the timed steps) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("c5", "stream"):
+        ap.error("--dump-outputs: decode workloads only (c2, c3, c4)")
     if args.steps is None:
         args.steps = 512 if args.workload == "c4" else 256
 
@@ -744,43 +764,47 @@ def main():
     value = dist_.aggregate_throughput(r, args.steps, elapsed)
     tokens = dec.history(kv0 + args.steps)
 
-    # dominant kernel: the fused gate|up GEMV (largest byte stream of a layer).  Every
-    # layer's instance back to back (distinct weights: 30 x 13-17 MB > L2, cycling the
-    # whole model through HBM), HIP events on the launch stream, mean per launch.
-    us, abytes = dec.probe_gateup(50)
-    achieved = abytes / us / 1e3  # GB/s
-    roofline = {
-        "bound": "hbm",
-        "kernel": ("k_gemv_q" if dec.act_mode() else "k_gemv_mfma") + " (fused LayerNorm -> gate|up GEMV -> silu*mul)",
-        "achieved": round(achieved, 1),
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 4),
-        "traffic": load_traffic(args.workload),
-        "traffic_source": f"profiles/traffic_{args.workload}.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this bench's own launch path (tools/profile_round.sh), per launch; not collected inside this run",
-        "bytes_per_launch": int(abytes),
-        "us_per_launch": round(us, 3),
-    }
-    # quote the fraction against the vendor figure AND a stream ceiling measured on this box
-    # (read-only non-temporal stream over 2 GiB, best of 10 passes; bitnet_hip_hbm_read_ceiling)
-    ceil_best, ceil_mean = hip.hbm_read_ceiling(2 << 30, 10)
-    roofline["measured_read_ceiling"] = round(ceil_best, 1)
-    roofline["frac_of_measured_ceiling"] = round(achieved / ceil_best, 4)
-    kernel_table = {}
-    for kind, name in enumerate(("qkv", "attention", "o_proj", "gate_up", "down", "logits")):
-        k_us, k_bytes = dec.probe_kernel(kind, 20)
-        kernel_table[name] = {"us_per_launch": round(k_us, 2), "GBps": round(k_bytes / k_us / 1e3, 1)}
-    # outside the timed region: the fast step against the UNFUSED step on the reference-order (bit-exact) kernels, same
-    # weights, same short prompt, at the full model size -- a wrong fast kernel cannot hide behind a plausible rate
-    check = exact_step_check(dec, synth, cfg) if not args.no_exact_check else None
-    oracle_check = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not gguf:
-        oracle_check = oracle_step_check(dec, synth, cfg, "qk256" if args.workload in ("c3", "c4", "c5") else "i2s")
-    stream_res = None
-    if not args.no_stream and args.workload in ("c2", "c3") and n_gpus == 1 and not gguf and not args.layers:
-        stream_res = i2s_stream(hip, synth, "i2s" if args.workload == "c2" else "qk256", args.stream_layers)
-    prefill_chk = prefill_check(dec, prompt, PROMPT_LEN, args.digits, prefill_state) if prefill_state is not None else None
-    prefill_roof = prefill_roofline(hip, dec, cfg, PROMPT_LEN, args.digits, True) if prefill_state is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logits=dec.last_logits(), tokens=tokens[-args.steps:])
+
+    if args.full:
+        # dominant kernel: the fused gate|up GEMV (largest byte stream of a layer).  Every
+        # layer's instance back to back (distinct weights: 30 x 13-17 MB > L2, cycling the
+        # whole model through HBM), HIP events on the launch stream, mean per launch.
+        us, abytes = dec.probe_gateup(50)
+        achieved = abytes / us / 1e3  # GB/s
+        roofline = {
+            "bound": "hbm",
+            "kernel": ("k_gemv_q" if dec.act_mode() else "k_gemv_mfma") + " (fused LayerNorm -> gate|up GEMV -> silu*mul)",
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": load_traffic(args.workload),
+            "traffic_source": f"profiles/traffic_{args.workload}.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this bench's own launch path (tools/profile_round.sh), per launch; not collected inside this run",
+            "bytes_per_launch": int(abytes),
+            "us_per_launch": round(us, 3),
+        }
+        # quote the fraction against the vendor figure AND a stream ceiling measured on this box
+        # (read-only non-temporal stream over 2 GiB, best of 10 passes; bitnet_hip_hbm_read_ceiling)
+        ceil_best, ceil_mean = hip.hbm_read_ceiling(2 << 30, 10)
+        roofline["measured_read_ceiling"] = round(ceil_best, 1)
+        roofline["frac_of_measured_ceiling"] = round(achieved / ceil_best, 4)
+        kernel_table = {}
+        for kind, name in enumerate(("qkv", "attention", "o_proj", "gate_up", "down", "logits")):
+            k_us, k_bytes = dec.probe_kernel(kind, 20)
+            kernel_table[name] = {"us_per_launch": round(k_us, 2), "GBps": round(k_bytes / k_us / 1e3, 1)}
+        # outside the timed region: the fast step against the UNFUSED step on the reference-order (bit-exact) kernels, same
+        # weights, same short prompt, at the full model size -- a wrong fast kernel cannot hide behind a plausible rate
+        check = exact_step_check(dec, synth, cfg) if not args.no_exact_check else None
+        oracle_check = None
+        if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not gguf:
+            oracle_check = oracle_step_check(dec, synth, cfg, "qk256" if args.workload in ("c3", "c4", "c5") else "i2s")
+        stream_res = None
+        if not args.no_stream and args.workload in ("c2", "c3") and n_gpus == 1 and not gguf and not args.layers:
+            stream_res = i2s_stream(hip, synth, "i2s" if args.workload == "c2" else "qk256", args.stream_layers)
+        prefill_chk = prefill_check(dec, prompt, PROMPT_LEN, args.digits, prefill_state) if prefill_state is not None else None
+        prefill_roof = prefill_roofline(hip, dec, cfg, PROMPT_LEN, args.digits, True) if prefill_state is not None else None
     # whole-step view of the same metric: all I2_S matrices of one token / step time
     wb = dec.weight_bytes()
     i2s_gbs = wb / (elapsed / args.steps) / 1e9
@@ -817,26 +841,25 @@ def main():
             "i2s_matmul_frac_of_hbm_peak_whole_step": round(i2s_gbs / HBM_PEAK_GBS, 4),
             "i2s_weight_bytes_per_token": int(wb),
             "event_ms_per_step": round(ev_ms / args.steps, 4),
-            "roofline": roofline,
-            "per_kernel": kernel_table,
             "last_tokens": [int(t) for t in tokens[-4:]],
             "distinct_tokens_in_timed_steps": int(len(set(int(t) for t in tokens[-args.steps:]))),
-            "exact_step_check": check,
-            "oracle_step_check": oracle_check,
         }
-        if stream_res is not None:
-            out["i2s_stream"] = stream_res
+        if args.full:
+            out.update({"roofline": roofline, "per_kernel": kernel_table, "exact_step_check": check, "oracle_step_check": oracle_check})
+            if stream_res is not None:
+                out["i2s_stream"] = stream_res
         if prefill_ms is not None:
             flops = 2.0 * 2_084_044_800 * (cfg.n_layers / 30) * PROMPT_LEN + 4.0 * PROMPT_LEN * PROMPT_LEN / 2 * cfg.n_heads * cfg.head_dim * cfg.n_layers
             out["prefill"] = {"tokens": PROMPT_LEN, "ms": round(prefill_ms, 2), "tokens_per_s": round(PROMPT_LEN / prefill_ms * 1e3, 1),
                               "digits": args.digits, "eff_TFLOPs": round(flops / prefill_ms / 1e9, 1),
                               "note": "whole-prompt forward incl. first sampled token; QK256: q|k|v and gate|up on i8 MFMA digit planes behind their LayerNorm, o / down on f16 MFMA straight from the f16 rows their producers wrote (hybrid, DESIGN 4.6); BitNet32-F16: the f16 activation chain; attention on f16 MFMA",
-                              "last_matmul_tile": prefill_tile,  # the prompt's last matmul (a 2560-row down-projection: f16 MFMA in 320-row workgroups at 4096 rows); roofline.tile = gate|up's
-                              "prefill_check": prefill_chk, "roofline": prefill_roof}
-        if n_gpus == 1 and not args.no_cpu_baseline:
+                              "last_matmul_tile": prefill_tile}  # the prompt's last matmul (a 2560-row down-projection: f16 MFMA in 320-row workgroups at 4096 rows); roofline.tile = gate|up's
+            if args.full:
+                out["prefill"].update({"prefill_check": prefill_chk, "roofline": prefill_roof})
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, synth)
     also_failed = False
-    if n_gpus == 1 and args.workload == "c2" and not args.no_also and not gguf and not args.layers and not args.exact_act:
+    if args.full and n_gpus == 1 and args.workload == "c2" and not args.no_also and not gguf and not args.layers and not args.exact_act:
         dec.close()  # the headline model's memory goes back first
         try:
             out["also"] = also_workloads(args, pkg, synth, hip, use_graph)
@@ -845,9 +868,9 @@ def main():
             out["failed"] = "also: c3 / c4 / BitNet32-F16 prefill did not complete (exit code 1)"
             also_failed = True
     # N > 1: the decode line above is N independent replicas (batch-1 decode does not shard); the path's ONE real collective
-    # -- the token-parallel prefill of BASELINE configs[4] -- runs here too, over the same ranks, and rides in the same line
+    # -- the token-parallel prefill of BASELINE configs[4] -- runs here too with --full, over the same ranks, and rides in the same line
     c5 = None
-    if n_gpus > 1 and args.workload in ("c2", "c3") and not args.no_c5:
+    if args.full and n_gpus > 1 and args.workload in ("c2", "c3") and not args.no_c5:
         # The decode numbers above must reach the driver whatever this first multi-GPU execution of the collective does:
         # every rank arms the same timer; if the prefill has not finished by then, rank 0 prints the line with the reason and
         # every rank leaves (a rank that waits in a collective for one that failed would otherwise sit there until the

@@ -3,9 +3,12 @@
 Each test names the reference test it replays (file:line under /root/reference).
 CPU only; runs in seconds.
 """
+import os
+
 import numpy as np
 import pytest
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 Q = "crates/bitnet-quantization/src"
 K = "crates/bitnet-kernels/src"
 M = "crates/bitnet-models/src"
@@ -438,17 +441,18 @@ def test_pack_unpack_2bit(oracle):
 
 
 def test_vendored_ggml_pins_lut_and_bit_order(oracle):
-    """The reference's own C (ggml-quants.c:59-72), compiled where it lies,
-    pins: sizeof(block_iq2_s)=82, LSB-first extraction, qmap {-2,-1,1,2},
-    f16 d conversion.  Compared against the oracle's restatement."""
-    if not oracle.ref_available():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(7)
-    y = oracle.ref_dequantize_row_iq2_s(F16_ONE, np.full(64, 0xE4, np.uint8))
-    assert y[:4].tolist() == [-2.0, -1.0, 1.0, 2.0]
-    for d_bits in (0x3C00, 0x4000, 0x3555, 0x2E66, 0x0400, 0x03FF, 0x0001, 0x5640):
-        qs = rng.integers(0, 256, 64, dtype=np.uint8)
-        y = oracle.ref_dequantize_row_iq2_s(d_bits, qs)
+    """The reference's own C (ggml-quants.c:59-72) pins: sizeof(block_iq2_s)=82, LSB-first extraction, qmap {-2,-1,1,2},
+    f16 d conversion.  Its outputs are recorded in tests/golden/iq2s_ref_dequant.npz (tests/golden/make_iq2s_ref_fixture.py)
+    and compared against the oracle's restatement; where oracle/_ref is built, the live library must reproduce the recording."""
+    golden = np.load(os.path.join(GOLDEN, "iq2s_ref_dequant.npz"))
+    d_all, qs_all, y_all = golden["d_bits"], golden["qs"], golden["y"]
+    assert d_all[0] == F16_ONE and np.all(qs_all[0] == 0xE4)
+    assert y_all[0, :4].tolist() == [-2.0, -1.0, 1.0, 2.0]
+    if oracle.ref_available():
+        for d_bits, qs, y in zip(d_all, qs_all, y_all):
+            assert np.array_equal(oracle.ref_dequantize_row_iq2_s(int(d_bits), qs), y)
+    for d_bits, qs, y in zip(d_all[1:], qs_all[1:], y_all[1:]):
+        d_bits = int(d_bits)
         codes = oracle.unpack_qk256_block(qs)
         d = np.float32(oracle.f16_to_f32(d_bits))
         mine = np.array([np.float32(d * np.float32(oracle.code_to_f32(int(c)))) for c in codes], np.float32)

@@ -4,7 +4,7 @@ TAG=$1; shift
 export TMPDIR=/tmp
 OUT=gpurun_out/ks_$TAG
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 32 --warmup 4 --no-cpu-baseline "$@" > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --steps 32 --warmup 4 --no-cpu-baseline "$@" > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
 python3 - $OUT <<'P'
 import csv,glob,sys
 f=glob.glob(sys.argv[1]+'/**/*kernel_stats.csv',recursive=True)[0]

@@ -38,12 +38,12 @@ for WL in $PASSES; do
     D="$OUT/$WL"
     case $WL in
     c2|c3|c4)
-        TRACE_ARGS="--workload $WL --steps 64 --warmup 4 --no-cpu-baseline --no-stream --no-exact-check --no-also"
-        PMC_ARGS="--workload $WL --prompt 8 --steps 8 --warmup 0 --no-cpu-baseline --no-stream --no-exact-check --no-also"
-        if [ "$WL" = c4 ]; then PMC_ARGS="--workload c4 --steps 8 --warmup 0 --no-cpu-baseline --no-stream --no-exact-check --layers 4"; fi
+        TRACE_ARGS="--workload $WL --full --steps 64 --warmup 4 --no-cpu-baseline --no-stream --no-exact-check --no-also"
+        PMC_ARGS="--workload $WL --full --prompt 8 --steps 8 --warmup 0 --no-cpu-baseline --no-stream --no-exact-check --no-also"
+        if [ "$WL" = c4 ]; then PMC_ARGS="--workload c4 --full --steps 8 --warmup 0 --no-cpu-baseline --no-stream --no-exact-check --layers 4"; fi
         three_passes "$D" python3 bench.py || exit 1
         STEPS=128; if [ "$WL" = c4 ]; then STEPS=512; fi   # configs[3] as written: 4096-token prefill + 512 decode
-        python3 bench.py --workload $WL --steps $STEPS --warmup 8 > "$D/bench.json" 2> "$D/bench.err" || { tail -5 "$D/bench.err"; exit 1; }
+        python3 bench.py --workload $WL --full --steps $STEPS --warmup 8 > "$D/bench.json" 2> "$D/bench.err" || { tail -5 "$D/bench.err"; exit 1; }
         python3 tools/profile_summary.py "$D" "$TAG" "$WL" || exit 1 ;;
     stream)
         for F in i2s qk256; do

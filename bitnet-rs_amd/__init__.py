@@ -165,6 +165,15 @@ class HipLib:
         L.bitnet_hip_logits_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_argmax_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _vp]
         L.bitnet_hip_hbm_read_ceiling.argtypes = [_sz, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]
+        # the sampler entries are bound here, with the rest, never lazily (a handle bound on first use crashed a process once)
+        L.bitnet_hip_sampler_create.argtypes = [_sz, C.POINTER(SamplingConfig), C.POINTER(_vp)]
+        L.bitnet_hip_sampler_destroy.argtypes = [_vp]
+        L.bitnet_hip_sampler_destroy.restype = None
+        L.bitnet_hip_sampler_configure.argtypes = [_vp, C.POINTER(SamplingConfig)]
+        L.bitnet_hip_sampler_reset.argtypes = [_vp]
+        L.bitnet_hip_sampler_draws.argtypes = [_vp, C.POINTER(C.c_uint64)]
+        L.bitnet_hip_sample_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_sample_host.argtypes = [_vp, _f32p, _sz, C.POINTER(C.c_uint32), _sz, C.POINTER(C.c_uint32)]
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -527,11 +536,74 @@ class HipLib:
     def argmax_dev(self, v, n: int, scratch, n_wg: int, token, stream: int = 0) -> None:
         self._check(self.c.bitnet_hip_argmax_dev(_ptr(v), n, _ptr(scratch), n_wg, _ptr(token), _vp(stream)))
 
+    def sampler(self, vocab: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                seed: int | None = None) -> "Sampler":
+        """A device sampler (bitnet_hip_sampler_*): the reference's Sampler::new(temperature, top_k, top_p, repetition_penalty, seed)."""
+        return Sampler(self, vocab, SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed))
+
     def hbm_read_ceiling(self, nbytes: int = 2 << 30, iters: int = 10, stream: int = 0):
         """Measured read-only stream ceiling of the device: (best, mean) GB/s."""
         best, mean = C.c_double(0.0), C.c_double(0.0)
         self._check(self.c.bitnet_hip_hbm_read_ceiling(nbytes, iters, C.byref(best), C.byref(mean), _vp(stream)))
         return best.value, mean.value
+
+
+class SamplingConfig(C.Structure):
+    """bitnet_hip_sampling_config"""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repetition_penalty", C.c_float), ("seed", C.c_uint64)]
+
+    @classmethod
+    def make(cls, temperature: float, top_k: int, top_p: float, repetition_penalty: float, seed: int | None = None) -> "SamplingConfig":
+        if seed is None:  # the reference seeds from entropy when --seed is absent
+            seed = int.from_bytes(os.urandom(8), "little")
+        return cls(float(temperature), int(top_k), float(top_p), float(repetition_penalty), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+class Sampler:
+    """One bitnet_hip_sampler: state (config, ChaCha20 key, word counter, token counts) in device memory."""
+
+    def __init__(self, lib: HipLib, vocab: int, cfg: SamplingConfig):
+        self.lib, self.vocab = lib, int(vocab)
+        h = _vp()
+        lib._check(lib.c.bitnet_hip_sampler_create(vocab, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.c.bitnet_hip_sampler_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def configure(self, temperature: float, top_k: int, top_p: float, repetition_penalty: float, seed: int | None = None) -> None:
+        cfg = SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed)
+        self.lib._check(self.lib.c.bitnet_hip_sampler_configure(self.h, C.byref(cfg)))
+
+    def reset(self) -> None:
+        self.lib._check(self.lib.c.bitnet_hip_sampler_reset(self.h))
+
+    def draws(self) -> int:
+        d = C.c_uint64(0)
+        self.lib._check(self.lib.c.bitnet_hip_sampler_draws(self.h, C.byref(d)))
+        return int(d.value)
+
+    def sample_host(self, logits, generated=()) -> int:
+        """Sampler::sample(&logits, &generated_tokens): the whole generated list on every call."""
+        x = _np(logits, np.float32)
+        g = _np(np.asarray(generated, dtype=np.uint32), np.uint32)
+        tok = C.c_uint32(0)
+        self.lib._check(self.lib.c.bitnet_hip_sample_host(self.h, x.ctypes.data_as(_f32p), x.size, g.ctypes.data_as(C.POINTER(C.c_uint32)), g.size,
+                                                          C.byref(tok)))
+        return int(tok.value)
+
+    def sample_dev(self, logits, token, pos=None, history=None, n_forced=None, stream: int = 0) -> None:
+        """One step on device tensors (torch); counts the tokens it chose since the last reset."""
+        self.lib._check(self.lib.c.bitnet_hip_sample_dev(self.h, _ptr(logits), logits.numel(), _optr(token), _optr(pos), _optr(history), _optr(n_forced),
+                                                         _vp(stream)))
 
 
 _lib = None
@@ -713,6 +785,8 @@ class HostDecoder:
         L.bitnet_host_probe_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]
         L.bitnet_host_weight_bytes.argtypes = [C.c_void_p]
         L.bitnet_host_weight_bytes.restype = C.c_uint64
+        L.bitnet_host_set_sampling.argtypes = [C.c_void_p, C.POINTER(SamplingConfig)]
+        L.bitnet_host_sampling_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         self.cfg = cfg
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
         self.h = L.bitnet_host_create(C.byref(hc))
@@ -759,6 +833,23 @@ class HostDecoder:
 
     def reset(self) -> None:
         self._check(self.c.bitnet_host_reset(self.h))
+
+    def set_sampling(self, temperature: float | None, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                     seed: int | None = None) -> None:
+        """The reference's Sampler::new(temperature, top_k, top_p, repetition_penalty, seed) behind every with-logits step, on the
+        device and inside the captured graphs.  set_sampling(None): greedy argmax, as a decoder that never called this.
+        seed None: from os.urandom, as the reference seeds from entropy."""
+        if temperature is None:
+            self._check(self.c.bitnet_host_set_sampling(self.h, None))
+            return
+        cfg = SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed)
+        self._check(self.c.bitnet_host_set_sampling(self.h, C.byref(cfg)))
+
+    def sampling_draws(self) -> int:
+        """ChaCha20 words the decoder's sampler has consumed since its last reset / set_sampling (one per non-greedy token)."""
+        d = C.c_uint64(0)
+        self._check(self.c.bitnet_host_sampling_draws(self.h, C.byref(d)))
+        return int(d.value)
 
     def feed(self, tokens) -> None:
         t = _np(tokens, np.int32)

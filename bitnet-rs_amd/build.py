@@ -31,9 +31,9 @@ COMMON_FLAGS = [
     f"-I{INCLUDE}",
     f"-I{CSRC}",
 ]
-# Per-file extra flags.  kernels_exact.hip restates the reference's scalar loops
-# bit for bit, and Rust never contracts a*b+c.
-EXTRA = {"kernels_exact.hip": ["-ffp-contract=off"]}
+# Per-file extra flags.  kernels_exact.hip and kernels_sample.hip restate the reference's
+# scalar loops bit for bit, and Rust never contracts a*b+c.
+EXTRA = {"kernels_exact.hip": ["-ffp-contract=off"], "kernels_sample.hip": ["-ffp-contract=off"]}
 
 
 # The hand-counted `s_waitcnt vmcnt(N)` around the LDS-DMA of k_prefill_attn (and the register / scratch figures DESIGN.md

@@ -165,6 +165,7 @@ Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n
 
 Decoder::~Decoder() {
     drop_graphs();
+    if (sampler_) bitnet_hip_sampler_destroy(sampler_);
     for (auto &L : layers_) {
         for (bitnet_hip_weights_t h : {L.qkv, L.o, L.gateup, L.down})
             if (h) bitnet_hip_weights_free(h);
@@ -205,6 +206,47 @@ void Decoder::drop_graphs() {
         if (graph_[i]) hipGraphDestroy((hipGraph_t)graph_[i]);
         graph_exec_[i] = graph_[i] = nullptr;
     }
+}
+
+int Decoder::pick_token(void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t H = c_.hidden;
+    if (!sampling_) {
+        // greedy token (T:1589, T:1599-1630, sampling.rs:189-202)
+        BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, token_, pos_,
+                                       history_, n_forced_, s));
+        return 0;
+    }
+    BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, nullptr, nullptr,
+                                   nullptr, nullptr, s));
+    BCHK(bitnet_hip_sample_dev(sampler_, logits_, (size_t)c_.vocab, token_, pos_, history_, n_forced_, s));
+    return 0;
+}
+
+int Decoder::set_sampling(const bitnet_hip_sampling_config *cfg) {
+    if (!cfg) {
+        if (sampling_) drop_graphs();
+        sampling_ = false;
+        return 0;
+    }
+    if (!sampler_) {
+        BCHK(bitnet_hip_sampler_create((size_t)c_.vocab, cfg, &sampler_));
+    } else {
+        BCHK(bitnet_hip_sampler_configure(sampler_, cfg));
+    }
+    if (!sampling_) drop_graphs();
+    sampling_ = true;
+    return 0;
+}
+
+int Decoder::sampling_draws(uint64_t *out) {
+    if (!out) {
+        err_ = "sampling_draws: null pointer";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    *out = 0;
+    if (sampler_) BCHK(bitnet_hip_sampler_draws(sampler_, out));
+    return 0;
 }
 
 // the four fused handles of a layer from its seven uploaded projections; frees the seven on every path
@@ -338,6 +380,7 @@ int Decoder::set_globals(const uint16_t *embed_f16, const float *final_norm) {
 
 int Decoder::reset() {
     host_forced_ = 0;
+    if (sampler_) BCHK(bitnet_hip_sampler_reset(sampler_));
     HCHK(hipMemset(pos_, 0, 4));
     HCHK(hipMemset(n_forced_, 0, 4));
     HCHK(hipMemset(history_, 0, ((size_t)c_.max_pos + 2) * 4));
@@ -482,8 +525,7 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
         }
         if (tr) TRACE("t" + std::to_string(tr->seq) + "_all_layers_out", "all_layers_out", -1, x_, H);
         if (with_logits) {
-            BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, token_, pos_,
-                                           history_, n_forced_, s));
+            if (int rc = pick_token(s)) return rc;
             TRACE(tp + "logits", "logits", -1, logits_, (size_t)c_.vocab);
         } else {
             BCHK(bitnet_hip_advance_pos_dev(pos_, s));
@@ -525,8 +567,7 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
     if (tr) TRACE("t" + std::to_string(tr->seq) + "_all_layers_out", "all_layers_out", -1, x_, H);
     if (with_logits) {
         // final norm + tied logits + greedy token (T:1589, T:1599-1630, sampling.rs:189-202)
-        BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_,
-                                       (size_t)logits_wgs_, token_, pos_, history_, n_forced_, s));
+        if (int rc = pick_token(s)) return rc;
         TRACE(tp + "logits", "logits", -1, logits_, (size_t)c_.vocab);
     } else {
         BCHK(bitnet_hip_advance_pos_dev(pos_, s));
@@ -585,8 +626,7 @@ int Decoder::step_launches_reference(bool with_logits) {
         BCHK(bitnet_hip_add_dev(x2_, ref_t_, x_, H, s));
     }
     if (with_logits) {
-        BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, token_, pos_,
-                                       history_, n_forced_, s));
+        if (int rc = pick_token(s)) return rc;
     } else {
         BCHK(bitnet_hip_advance_pos_dev(pos_, s));
     }
@@ -1029,6 +1069,10 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
         err_ = "model globals not set";
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
     }
+    if (sampling_) {
+        err_ = "prefill_sharded: not available with sampling on (set_sampling(NULL) first)";
+        return BITNET_HIP_ERR_UNSUPPORTED;
+    }
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !gather)) {
         err_ = "prefill_sharded: bad rank / world / gather";
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -1257,8 +1301,7 @@ int Decoder::finish_prefill(int n, const float *last_row, bool with_logits) {
     HCHK(hipMemcpyAsync(pos_, &last, 4, hipMemcpyHostToDevice, s));
     HCHK(hipStreamSynchronize(s));  // `last` is a stack variable
     if (with_logits && last_row) {
-        BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, token_,
-                                       pos_, history_, n_forced_, s));
+        if (int rc = pick_token(s)) return rc;
     } else {
         BCHK(bitnet_hip_advance_pos_dev(pos_, s));
     }
@@ -1460,6 +1503,8 @@ int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *fin
     return D->set_globals(embed_f16, final_norm);
 }
 int bitnet_host_reset(void *d) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->reset(); }
+int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_sampling(cfg); }
+int bitnet_host_sampling_draws(void *d, uint64_t *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->sampling_draws(out); }
 int bitnet_host_feed(void *d, const int32_t *tokens, int n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->feed(tokens, n); }
 int bitnet_host_set_kv_f16(void *d, int on) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_kv_f16(on != 0); }
 int bitnet_host_set_act_mode(void *d, int mode) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_act_mode(mode); }

@@ -78,8 +78,13 @@ class Decoder {
     int set_layer_specs(int layer, const float *attn_norm, const float *ffn_norm, const ProjSpec p[7]);
     int set_globals(const uint16_t *embed_f16, const float *final_norm);
 
-    // KVCache::clear (T:1251-1255) + token history
+    // KVCache::clear (T:1251-1255) + token history (+ the sampler's counts and word counter)
     int reset();
+    // The reference's Sampler (crates/bitnet-cli/src/sampling.rs) on the device, behind every with-logits step:
+    // cfg == NULL = greedy argmax as before (same kernels, same tokens).  Switching on / off drops the captured graphs,
+    // a new config on an existing sampler does not (the graphs read it from device memory).
+    int set_sampling(const bitnet_hip_sampling_config *cfg);
+    int sampling_draws(uint64_t *out);
     // Put `n` forced tokens at positions [pos, pos+n) of the history (the prompt).
     int feed(const int32_t *tokens, int n);
     // Run `n` single-token steps (T:1482-1504 body each).  with_logits=false skips the
@@ -182,6 +187,7 @@ class Decoder {
     int attn_launch(Layer &L, int form, float *out, void *qout);
     void release_layer(Layer &L);  // frees the layer's handles, subtracts their bytes, drops the captured graphs
     void drop_graphs();
+    int pick_token(void *stream);  // final norm + tied logits + the next token (greedy argmax or the sampler)
     int adopt_projections(Layer &L, bitnet_hip_weights_t h[7]);
     std::vector<Layer> layers_;
     void *embed_ = nullptr;
@@ -197,6 +203,8 @@ class Decoder {
     void *scratch_ = nullptr;
     float *attn_scratch_ = nullptr;
     int32_t *pos_ = nullptr, *n_forced_ = nullptr, *history_ = nullptr, *token_ = nullptr;
+    bitnet_hip_sampler *sampler_ = nullptr;
+    bool sampling_ = false;
     int host_forced_ = 0;
     // sharded prefill buffers (grown on demand)
     int sp_cap_ = 0, sp_ctx_ = 0;
@@ -251,6 +259,8 @@ int bitnet_host_set_layer_i2s(void *d, int layer, const float *attn_norm, const 
                               const uint8_t *const *w7, const float *const *scales7, size_t block_size);
 int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *final_norm);
 int bitnet_host_reset(void *d);
+int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg);  // NULL = greedy
+int bitnet_host_sampling_draws(void *d, uint64_t *out);
 int bitnet_host_feed(void *d, const int32_t *tokens, int n);
 int bitnet_host_run(void *d, int n, int with_logits, int use_graph, float *elapsed_ms);
 int bitnet_host_run_reference(void *d, int n, int with_logits);

@@ -551,6 +551,54 @@ int bitnet_hip_logits_f16_dev(const void *table_f16_dev, const float *x_dev, con
 int bitnet_hip_argmax_dev(const float *v_dev, size_t n, void *scratch_dev, size_t n_workgroups,
                           int32_t *token_dev, void *stream);
 
+/* ---- sampling on the device: crates/bitnet-cli/src/sampling.rs `Sampler` ---------------------------------------
+ * The reference's `Sampler::sample(&logits, &generated_tokens)` in its order: count every entry of the list, repetition
+ * penalty (rp^count by compiler-builtins' __powisf2 loop; logit > 0 ? logit / p : logit * p), NaN -> -inf, greedy shortcut
+ * (temperature 0, or temperature 1 && top_k 0 && top_p 1: argmax, lowest index on ties, no RNG word), temperature
+ * (division), stable top-k, top-p over the stable descending order, softmax draw with u = (next_u32 >> 8) * 2^-24 from
+ * ChaCha20Rng::seed_from_u64(seed).  Three paths, one launch each:
+ *   greedy (+- penalty): bit-exact;
+ *   1 <= top_k <= BITNET_HIP_SAMPLE_SMALL_K (< vocab): top-p and the draw over the k survivors in the reference's order
+ *   (equal up to device expf against the host's in the last ulp);
+ *   otherwise (top_k 0 or larger, full-vocabulary temperature / top-p): parallel sums, equal except where a deciding
+ *   comparison lies within ~2^-12 of its threshold.
+ * The state (config, ChaCha20 key, words drawn, per-token counts) lives in device memory: a graph that captured
+ * bitnet_hip_sample_dev follows bitnet_hip_sampler_configure.  A sampler serves one stream at a time.
+ * Invalid configs: temperature NaN, negative or infinite; top_k < 0; top_p NaN; repetition_penalty <= 0 or NaN.  top_p <= 0
+ * keeps the top entry alone, as the reference does. */
+#define BITNET_HIP_SAMPLE_SMALL_K 64
+typedef struct bitnet_hip_sampling_config {
+    float temperature;        /* --temperature (reference default 1.0) */
+    int32_t top_k;            /* --top-k (0 = off) */
+    float top_p;              /* --top-p (1.0 = off) */
+    float repetition_penalty; /* --repetition-penalty (1.0 = off) */
+    uint64_t seed;            /* --seed */
+} bitnet_hip_sampling_config;
+typedef struct bitnet_hip_sampler bitnet_hip_sampler;
+/* vocab in 1..2^20.  Allocates device memory (~5 * 4 * vocab bytes); not capture-safe. */
+int bitnet_hip_sampler_create(size_t vocab, const bitnet_hip_sampling_config *cfg, bitnet_hip_sampler **out);
+void bitnet_hip_sampler_destroy(bitnet_hip_sampler *sampler);
+/* New config and seed: the key is re-derived and the word counter restarts at 0; the counts stay.  Synchronous copy:
+ * not capture-safe, but graphs captured before it stay valid and follow it. */
+int bitnet_hip_sampler_configure(bitnet_hip_sampler *sampler, const bitnet_hip_sampling_config *cfg);
+/* Clears the counts (a new generation) and the word counter, and re-arms the launch hand-over (a launch cut short leaves it
+ * unbalanced).  Synchronous; call it with no sample_dev / sample_host in flight.  Not capture-safe. */
+int bitnet_hip_sampler_reset(bitnet_hip_sampler *sampler);
+/* ChaCha20 words consumed since create / configure / reset (one per non-greedy call).  Synchronous; not capture-safe. */
+int bitnet_hip_sampler_draws(bitnet_hip_sampler *sampler, uint64_t *draws);
+/* One sampling step on the device, capture-safe (one kernel, no host work).  "Generated" = the tokens this sampler
+ * chose since the last reset: the exponent of token t at call c is sum_{i<c, g_i = t} (c - i), the reference's count when
+ * its caller passes the growing list each step.  token_dev (nullable) receives the token; pos / history / n_forced as
+ * bitnet_hip_logits_f16_dev: with p = *pos_dev, history_dev[p+1] = token, then *pos_dev = p+1.  At a forced position
+ * (p+1 < *n_forced_dev: a prompt token sits there) nothing is sampled or counted, token_dev receives the prompt token. */
+int bitnet_hip_sample_dev(bitnet_hip_sampler *sampler, const float *logits_dev, size_t vocab, int32_t *token_dev,
+                          int32_t *pos_dev, int32_t *history_dev, const int32_t *n_forced_dev, void *stream);
+/* Drop-in of Sampler::sample(&logits, &generated_tokens) with host pointers: the whole generated list on every call,
+ * counted as the reference counts it (ids >= vocab are skipped).  Synchronous; not capture-safe.  Keeps its counts
+ * apart from those of bitnet_hip_sample_dev; both share the RNG stream. */
+int bitnet_hip_sample_host(bitnet_hip_sampler *sampler, const float *logits, size_t vocab, const uint32_t *generated,
+                           size_t n_generated, uint32_t *token);
+
 /* ---- measurement aid -------------------------------------------------------
  * Measured HBM read ceiling of the device (quote the roofline fraction against the vendor
  * figure AND a measured stream ceiling): a read-only streaming kernel (non-temporal 16-byte loads, one

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Prints the Rust `extern "C"` declaration of every entry point include/bitnet_hip.h declares (one line each), or with --missing only those
-INTEGRATION.md section 2 does not spell out yet.  A mechanical map of the C prototypes (size_t -> usize, const T * -> *const T, ...); the two
-by-value / by-pointer structs are referred to by the names INTEGRATION.md gives them.   python tools/gen_rust_extern.py [--missing]"""
+INTEGRATION.md section 2 does not spell out yet.  A mechanical map of the C prototypes (size_t -> usize, const T * -> *const T, ...); the
+by-value / by-pointer structs and the opaque sampler are referred to by the names INTEGRATION.md gives them.   python tools/gen_rust_extern.py [--missing]"""
 import os
 import re
 import sys
@@ -9,7 +9,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BASE = {"size_t": "usize", "int": "c_int", "float": "c_float", "double": "f64", "void": "c_void", "char": "c_char", "uint8_t": "u8", "int8_t": "i8",
         "uint16_t": "u16", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "int64_t": "i64", "unsigned long long": "u64", "unsigned": "u32",
-        "bitnet_hip_weights_t": "Weights", "bitnet_hip_device_info": "DeviceInfo", "bitnet_hip_gemv_item": "GemvItem", "_Float16": "u16"}
+        "bitnet_hip_weights_t": "Weights", "bitnet_hip_device_info": "DeviceInfo", "bitnet_hip_gemv_item": "GemvItem", "_Float16": "u16",
+        "bitnet_hip_sampling_config": "SamplingConfig", "bitnet_hip_sampler": "Sampler"}
 
 
 def rust_type(c: str) -> str:

@@ -10,6 +10,7 @@ The directory name carries a hyphen (as the project is named), so import it with
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import importlib.util
 import os
@@ -174,6 +175,9 @@ class HipLib:
         L.bitnet_hip_sampler_draws.argtypes = [_vp, C.POINTER(C.c_uint64)]
         L.bitnet_hip_sample_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_sample_host.argtypes = [_vp, _f32p, _sz, C.POINTER(C.c_uint32), _sz, C.POINTER(C.c_uint32)]
+        L.bitnet_hip_score_workspace_bytes.argtypes = [_sz, _sz, _sz]
+        L.bitnet_hip_score_workspace_bytes.restype = _sz
+        L.bitnet_hip_score_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -533,6 +537,17 @@ class HipLib:
         opt = lambda t: _ptr(t) if t is not None else None
         self._check(self.c.bitnet_hip_logits_f16_dev(_ptr(table), _ptr(x), opt(gamma), eps, hidden, vocab, _ptr(logits), _ptr(scratch), n_wg, opt(token), opt(pos), opt(history), opt(n_forced), _vp(stream)))
 
+    def score_workspace_bytes(self, n_rows: int, hidden: int, vocab: int) -> int:
+        """Workspace of score_f16_dev; 0 for sizes the library refuses."""
+        return int(self.c.bitnet_hip_score_workspace_bytes(n_rows, hidden, vocab))
+
+    def score_f16_dev(self, table, x, gamma, eps: float, hidden: int, vocab: int, n_rows: int, targets, nll, argmax=None, logits=None,
+                      logits_rows: int = 0, workspace=None, workspace_bytes: int = 0, stream: int = 0) -> None:
+        """Teacher-forced scoring of n_rows residual rows against the tied f16 table (include/bitnet_hip.h bitnet_hip_score_f16_dev):
+        nll[r] = logsumexp(l_r) - l_r[targets[r]], argmax[r], and the raw logits of rows < logits_rows.  Device pointers / tensors."""
+        self._check(self.c.bitnet_hip_score_f16_dev(_optr(table), _optr(x), _optr(gamma), eps, hidden, vocab, n_rows, _optr(targets), _optr(nll),
+                                                    _optr(argmax), _optr(logits), logits_rows, _optr(workspace), workspace_bytes, _vp(stream)))
+
     def argmax_dev(self, v, n: int, scratch, n_wg: int, token, stream: int = 0) -> None:
         self._check(self.c.bitnet_hip_argmax_dev(_ptr(v), n, _ptr(scratch), n_wg, _ptr(token), _vp(stream)))
 
@@ -750,6 +765,9 @@ class GgufFile:
         return bool(self.c.bitnet_host_gguf_loader_is_qk256(sh, len(shape), available))
 
 
+ScoreResult = collections.namedtuple("ScoreResult", "nll argmax logits ms")
+
+
 class HostDecoder:
     """ctypes view of the C++ Decoder (mirror of the reference's Rust-side
     TransformerModel / KVCache / greedy loop).  No arithmetic here."""
@@ -787,7 +805,9 @@ class HostDecoder:
         L.bitnet_host_weight_bytes.restype = C.c_uint64
         L.bitnet_host_set_sampling.argtypes = [C.c_void_p, C.POINTER(SamplingConfig)]
         L.bitnet_host_sampling_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bitnet_host_score.argtypes = [C.c_void_p, C.c_int, C.c_int, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.POINTER(C.c_float)]
         self.cfg = cfg
+        self._fed = 0  # tokens fed since the last reset (the default n of score)
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
         self.h = L.bitnet_host_create(C.byref(hc))
         if not self.h:
@@ -833,6 +853,7 @@ class HostDecoder:
 
     def reset(self) -> None:
         self._check(self.c.bitnet_host_reset(self.h))
+        self._fed = 0
 
     def set_sampling(self, temperature: float | None, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
                      seed: int | None = None) -> None:
@@ -854,6 +875,7 @@ class HostDecoder:
     def feed(self, tokens) -> None:
         t = _np(tokens, np.int32)
         self._check(self.c.bitnet_host_feed(self.h, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size))
+        self._fed += int(t.size)
 
     def run(self, n: int, with_logits: bool = True, use_graph: bool = True) -> float:
         ms = C.c_float(0)
@@ -931,6 +953,21 @@ class HostDecoder:
         ms = C.c_float(0)
         self._check(self.c.bitnet_host_prefill(self.h, n, int(with_logits), digits, C.byref(ms)))
         return ms.value
+
+    def score(self, n: int | None = None, digits: int = 2, logits_rows: int = 0) -> "ScoreResult":
+        """Teacher-forced scoring of the first n fed tokens (default: all of them) in one prompt forward: prefill(n, True, digits) as
+        it stands -- the decoder ends exactly where that call leaves it -- then the tied head over every row.  nll[r] (f32, n - 1) is
+        -log p(token r + 1 | tokens 0..r); argmax (i32, n) the f16 head's greedy token per row (entry n - 1 may differ from the token
+        prefill picked in a near-tie); logits: f32 [logits_rows, vocab] or None; ms: prefill + head.  digits = 2 is the prompt forward
+        bench.py times."""
+        n = self._fed if n is None else int(n)
+        nll = np.zeros(max(n - 1, 0), np.float32)
+        am = np.zeros(max(n, 0), np.int32)
+        lg = np.zeros((logits_rows, self.cfg.vocab), np.float32) if logits_rows > 0 else None
+        ms = C.c_float(0)
+        self._check(self.c.bitnet_host_score(self.h, n, digits, nll.ctypes.data_as(_f32p), am.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             lg.ctypes.data_as(_f32p) if lg is not None else None, logits_rows, C.byref(ms)))
+        return ScoreResult(nll, am, lg, ms.value)
 
     def last_prefill_path(self) -> int:
         """What the last prefill() ran: 0 digit planes (+ f16 hand-over / hybrid o / down), 1 the f16 chain, 2 the QB32 chain."""

@@ -177,7 +177,8 @@ Decoder::~Decoder() {
                     (void *)history_, (void *)token_})
         if (p) hipFree(p);
     for (void *p : {(void *)pf_x_, (void *)pf_qkv_, (void *)pf_att_, (void *)pf_h_, pf_gemm_ws_, pf_attn_ws_, sp_kv_send_, sp_kv_all_,
-                    (void *)sp_block_pos_, (void *)sp_tokens_, pf_xh_, pf_atth_, pf_hh_, (void *)pf_stats_, pf_qb_})
+                    (void *)sp_block_pos_, (void *)sp_tokens_, pf_xh_, pf_atth_, pf_hh_, (void *)pf_stats_, pf_qb_, (void *)sc_tgt_, (void *)sc_am_,
+                    (void *)sc_nll_, (void *)sc_logits_, sc_ws_})
         if (p) hipFree(p);
     for (void *e : sp_tev_)
         if (e) hipEventDestroy((hipEvent_t)e);
@@ -1288,6 +1289,81 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
     return 0;
 }
 
+int Decoder::score(int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms) {
+    if (!embed_) {
+        err_ = "model globals not set";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (!nll_out || (logits_rows > 0 && !logits_out)) {
+        err_ = "score: null pointer";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (n > host_forced_) {
+        err_ = "prefill: feed() the prompt tokens first";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (n > c_.max_pos - 1) {
+        err_ = "KV cache overflow";  // T:1190-1194
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (n < 2) {
+        err_ = "score: n must be >= 2 (row r is scored against token r + 1)";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (logits_rows < 0 || logits_rows > n) {
+        err_ = "score: logits_rows must be in [0, n]";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    const size_t H = c_.hidden, V = (size_t)c_.vocab, N = (size_t)n;
+    const size_t need = bitnet_hip_score_workspace_bytes(N, H, V);
+    if (need == 0) {
+        err_ = "score: dimensions too large";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (n > sc_cap_ || need > sc_ws_bytes_) {
+        for (void *q : {(void *)sc_tgt_, (void *)sc_am_, (void *)sc_nll_, sc_ws_})
+            if (q) hipFree(q);
+        sc_tgt_ = sc_am_ = nullptr;
+        sc_nll_ = nullptr;
+        sc_ws_ = nullptr;
+        sc_cap_ = 0;
+        sc_ws_bytes_ = 0;
+        HCHK(dalloc(&sc_tgt_, N));
+        HCHK(dalloc(&sc_am_, N));
+        HCHK(dalloc(&sc_nll_, N));
+        HCHK(hipMalloc(&sc_ws_, need));
+        sc_cap_ = n;
+        sc_ws_bytes_ = need;
+    }
+    if (logits_rows > sc_logits_cap_) {
+        if (sc_logits_) hipFree(sc_logits_);
+        sc_logits_ = nullptr;
+        sc_logits_cap_ = 0;
+        HCHK(dalloc(&sc_logits_, (size_t)logits_rows * V));
+        sc_logits_cap_ = logits_rows;
+    }
+    hipStream_t s = (hipStream_t)stream_;
+    Event ev0, ev1;
+    HCHK(hipEventCreate(&ev0.e));
+    HCHK(hipEventCreate(&ev1.e));
+    HCHK(hipEventRecord(ev0.e, s));
+    if (int rc = prefill(n, true, digits, nullptr)) return rc;
+    // row r predicts token r + 1 of the history (the prompt); the last row has no target
+    HCHK(hipMemcpyAsync(sc_tgt_, history_ + 1, (N - 1) * 4, hipMemcpyDeviceToDevice, s));
+    HCHK(hipMemsetAsync(sc_tgt_ + (N - 1), 0xff, 4, s));
+    BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, N, sc_tgt_, sc_nll_, argmax_out ? sc_am_ : nullptr,
+                                  logits_rows > 0 ? sc_logits_ : nullptr, (size_t)logits_rows, sc_ws_, sc_ws_bytes_, s));
+    HCHK(hipEventRecord(ev1.e, s));
+    HCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
+    if (elapsed_ms) *elapsed_ms = ms;
+    HCHK(hipMemcpy(nll_out, sc_nll_, (N - 1) * 4, hipMemcpyDeviceToHost));
+    if (argmax_out) HCHK(hipMemcpy(argmax_out, sc_am_, N * 4, hipMemcpyDeviceToHost));
+    if (logits_rows > 0) HCHK(hipMemcpy(logits_out, sc_logits_, (size_t)logits_rows * V * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int Decoder::finish_prefill(int n, const float *last_row, bool with_logits) {
     // hand over to the single-token state: residual stream of the last position, position counter
     if (n <= 0 || n > c_.max_pos - 1) {
@@ -1549,6 +1625,10 @@ int bitnet_host_phase_times(void *d, float out[4]) {
 int bitnet_host_finish_prefill(void *d, int n, const float *last_row, int with_logits) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
     return D->finish_prefill(n, last_row, with_logits != 0);
+}
+int bitnet_host_score(void *d, int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->score(n, digits, nll_out, argmax_out, logits_out, logits_rows, elapsed_ms);
 }
 void bitnet_host_layer_objects(void *d, int layer, uint64_t *handles4, void **ptrs4) {
     for (int i = 0; i < 4; ++i) handles4[i] = 0, ptrs4[i] = nullptr;

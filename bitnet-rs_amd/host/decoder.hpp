@@ -119,6 +119,13 @@ class Decoder {
     // the KV cache already holds positions 0..n-1; last_row (device, [hidden]) is the residual stream
     // of position n-1 or null on ranks that do not own it (then only the position counter moves).
     int finish_prefill(int n, const float *last_row, bool with_logits);
+    // Teacher-forced scoring of the first n fed tokens (score.rs / eval.rs teacher forcing, parity::eval_logits_all_positions): runs
+    // prefill(n, with_logits = true, digits) unchanged -- the decoder ends exactly as that call leaves it (KV cache, position, history,
+    // picked token; run() can go on) -- then the tied head over ALL n rows the prompt forward left (bitnet_hip_score_f16_dev, final norm).
+    // Host outputs: nll_out[n - 1] (row r against token r + 1), argmax_out[n] (nullable; entry n - 1 is the f16 head's greedy next token,
+    // which can differ from the one prefill picked with the decode head in a near-tie), logits_out[logits_rows * vocab] (nullable).
+    // 2 <= n <= fed tokens, n <= max_pos - 1.  Buffers grow on demand (none before the first call); elapsed_ms: prefill + head.
+    int score(int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms);
     bool chain_applies(int digits) const;
     bool handover16_applies(int digits) const;
     bool hybrid_applies(size_t n_rows) const;
@@ -229,6 +236,12 @@ class Decoder {
     int pf_qb_cap_ = 0;
     bool force_scaled_ = false;   // the prompt is being repeated on the row-scaled forms after an f16 hand-over value was clamped (prefill)
     int saturation_fallbacks_ = 0;
+    // score buffers (grown on demand): targets, nll, argmax, dumped logits, workspace of bitnet_hip_score_f16_dev
+    int sc_cap_ = 0, sc_logits_cap_ = 0;
+    int32_t *sc_tgt_ = nullptr, *sc_am_ = nullptr;
+    float *sc_nll_ = nullptr, *sc_logits_ = nullptr;
+    void *sc_ws_ = nullptr;
+    size_t sc_ws_bytes_ = 0;
     int last_prefill_path_ = 0;  // what the last prefill() ran: 0 digit planes (+ f16 hand-over / hybrid), 1 the f16 chain, 2 the QB32 chain
     int prefill_qb32_ = -1;   // BITNET_HOST_PREFILL_QB32: -1 not read yet; 1 = the QB32 chain where it applies (opt-in), 0 (default) = quantiser launches
     int prefill_fp6_ = -1;    // BITNET_HOST_PREFILL_FP6: -1 not yet decided, 0 int8 digit planes, 1 the fp6 x fp4 form on resident fp4 images (fp6_flag)
@@ -270,6 +283,7 @@ int bitnet_host_set_kv_f16(void *d, int on);
 int bitnet_host_act_mode(void *d);
 int bitnet_host_prefill(void *d, int n, int with_logits, int digits, float *elapsed_ms);
 int bitnet_host_finish_prefill(void *d, int n, const float *last_row, int with_logits);
+int bitnet_host_score(void *d, int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms);
 // per-phase medians of the NEXT bitnet_host_prefill_sharded calls (off by default: 8 event records per layer); out[4] = projections,
 // attention, exposed all-gather wait, all-gather on its own stream -- microseconds per layer, medians over the layers of the last call
 int bitnet_host_set_phase_timing(void *d, int on);

@@ -551,6 +551,18 @@ int bitnet_hip_logits_f16_dev(const void *table_f16_dev, const float *x_dev, con
 int bitnet_hip_argmax_dev(const float *v_dev, size_t n, void *scratch_dev, size_t n_workgroups,
                           int32_t *token_dev, void *stream);
 
+/* Teacher-forced scoring of prompt rows (score.rs / eval.rs NLL, parity::eval_logits_all_positions).  Row r of x_dev ([n_rows, hidden] f32, the
+ * residual stream after the last block): l_r = f16(LN(x_r) * gamma) . E^T, E the f16 table [vocab, hidden], f32 accumulate; non-finite l -> -inf;
+ * nll_dev[r] = logsumexp(l_r) - l_r[targets_dev[r]]  (0 where target < 0, NaN where target >= vocab, +inf where the target logit is non-finite,
+ * NaN where every logit of the row is);  argmax_dev[r] (nullable): lowest index on ties;  logits_dev (nullable): raw logits of rows [0, logits_rows),
+ * f32 [logits_rows, vocab].  Deterministic.  hidden % 64 == 0.
+ * gamma_dev == NULL: no norm (l_r = f16(x_r) . E^T).  The workspace holds the f16 rows and one 16-byte partial per (row, 128-entry vocabulary
+ * block); bitnet_hip_score_workspace_bytes returns 0 for sizes this library refuses. */
+size_t bitnet_hip_score_workspace_bytes(size_t n_rows, size_t hidden, size_t vocab);
+int bitnet_hip_score_f16_dev(const void *table_f16_dev, const float *x_dev, const float *gamma_dev, float eps, size_t hidden, size_t vocab,
+                             size_t n_rows, const int32_t *targets_dev, float *nll_dev, int32_t *argmax_dev, float *logits_dev,
+                             size_t logits_rows, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- sampling on the device: crates/bitnet-cli/src/sampling.rs `Sampler` ---------------------------------------
  * The reference's `Sampler::sample(&logits, &generated_tokens)` in its order: count every entry of the list, repetition
  * penalty (rp^count by compiler-builtins' __powisf2 loop; logit > 0 ? logit / p : logit * p), NaN -> -inf, greedy shortcut

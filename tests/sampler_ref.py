@@ -6,8 +6,10 @@ order), the sorts are stable and compare -0.0 equal to +0.0 as `partial_cmp` doe
 `rng.random::<f32>()` = (next_u32 >> 8) * 2^-24 (rand 0.9).  The keystream is pinned by a published test vector; the seed
 expansion and the f32 conversion are restated from the crates' sources and have not been run against a Rust build.
 
-`RefSampler.sample` also reports how close the deciding comparisons came to flipping (`last_margin`), so that tests of the
-device's parallel-sum paths can tell a real mismatch from a rounding tie."""
+`RefSampler.sample` also reports how close the deciding comparisons came to flipping (`last_margin`), and keeps what the call
+decided in `last` (the tempered logits, the kept set after top-k, the top-p cut and its f32 sums, `u`, the f32 sums of the draw),
+so that tests of the device's parallel-sum paths can tell a real mismatch from a rounding tie: tests/sampler_accept.py derives a
+per-draw acceptance rule from that record."""
 from __future__ import annotations
 
 import numpy as np
@@ -75,13 +77,14 @@ def powi(a: np.float32, b: int) -> np.float32:
     """compiler-builtins `__powisf2` (what `f32::powi` with a run-time exponent lowers to), b >= 0."""
     a = np.float32(a)
     r = np.float32(1.0)
-    while True:
-        if b & 1:
-            r = np.float32(r * a)
-        b //= 2
-        if b == 0:
-            break
-        a = np.float32(a * a)
+    with np.errstate(over="ignore", under="ignore"):
+        while True:
+            if b & 1:
+                r = np.float32(r * a)
+            b //= 2
+            if b == 0:
+                break
+            a = np.float32(a * a)
     return r
 
 
@@ -127,6 +130,7 @@ class RefSampler:
         self.counts: dict[int, int] = {}
         self.last_margin = np.inf  # smallest |cumsum - threshold| among the deciding comparisons of the last call
         self.last_path = ""
+        self.last: dict = {}  # what the last call decided (see sample)
 
     def is_greedy(self) -> bool:
         return self.t == 0 or (self.t == 1 and self.k == 0 and self.p == 1)
@@ -135,7 +139,7 @@ class RefSampler:
         x = np.array(logits, np.float32)
         if self.rp == 1:
             return x
-        with np.errstate(invalid="ignore", over="ignore"):
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
             for tok, cnt in self.counts.items():
                 if tok < x.size and cnt > 0:
                     pen = powi(self.rp, cnt)
@@ -148,24 +152,33 @@ class RefSampler:
         x = self.penalise(logits)
         x[np.isnan(x)] = -np.inf
         self.last_margin = np.inf
+        # `last`: vocab, want; and past the greedy shortcut: xt (tempered logits after penalty and NaN handling), xk (after top-k:
+        # removed entries are -inf), order / cum_sorted / cut (top-p: stable descending order of xk, the f32 sums over it, entries
+        # kept; None when top_p >= 1), xf (the logits the final softmax saw), u, probs and cum (f32, index order)
+        self.last = rec = {"vocab": x.size}
         if self.is_greedy():
             self.last_path = "G"
-            return argmax(x)
+            rec["want"] = argmax(x)
+            return rec["want"]
         self.last_path = "S" if 0 < self.k <= SMALL_K and self.k < x.size else "F"
         with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
             if self.t != 1:
                 x = (x / self.t).astype(np.float32)
+            rec["xt"] = x
             if 0 < self.k < x.size:
                 order = stable_desc(np.where(np.isnan(x), -np.inf, x))
                 f = np.full_like(x, -np.inf)
                 f[order[: self.k]] = x[order[: self.k]]
                 x = f
+            rec["xk"] = x
+            rec["order"] = rec["cum_sorted"] = rec["cut"] = None
             if self.p < 1:
                 x = np.where(np.isnan(x), np.float32(-np.inf), x).astype(np.float32)
                 order = stable_desc(x)
                 cum = np.add.accumulate(softmax(x)[order], dtype=np.float32)
                 over = np.flatnonzero(cum > self.p)
                 cut = int(over[0]) + 1 if over.size else x.size
+                rec["order"], rec["cum_sorted"], rec["cut"] = order, cum, cut
                 if over.size:
                     i = int(over[0])
                     lo = cum[i - 1] if i > 0 else np.float32(0)
@@ -176,14 +189,17 @@ class RefSampler:
             probs = softmax(x)
             u = self.rng.random_f32()
             cum = np.add.accumulate(probs, dtype=np.float32)
+            rec["xf"], rec["u"], rec["probs"], rec["cum"] = x, u, probs, cum
             over = np.flatnonzero(cum > u)
             if not over.size:
                 if np.isfinite(cum[-1]):
                     self.last_margin = min(self.last_margin, float(u) - float(cum[-1]))
+                rec["want"] = x.size - 1
                 return x.size - 1
             i = int(over[0])
             lo = cum[i - 1] if i > 0 else np.float32(0)
             self.last_margin = min(self.last_margin, float(cum[i]) - float(u), float(u) - float(lo))
+            rec["want"] = i
             return i
 
 

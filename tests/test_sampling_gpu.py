@@ -1,12 +1,20 @@
 """The device sampler (bitnet_hip_sampler_* / bitnet_hip_sample_*, csrc/kernels_sample.hip) against the numpy restatement of the
 reference's Sampler (tests/sampler_ref.py), at the kernel level and behind the decoder's captured graphs.
 
-Agreement rules: the greedy shortcut and top_k = 1 must match on every case (only comparisons decide them).  Otherwise a case may
-differ only where the restatement's deciding comparison (|cumsum - u| of the draw, |cumsum - top_p| of the cutoff) lay within
-2^-20 (S path: top_k <= SMALL_K, the reference's summation order) or 2^-12 (F path: parallel sums over the vocabulary); such
-near-boundary cases are counted and reported.  A high-entropy row puts nearly every draw within 2^-12 of a boundary (one entry's
-probability is ~1/vocab), so what is bounded is the mismatches, every one of them near a boundary, per path: at most 1 % of the
-S cases and F_RATE of the F cases."""
+Agreement rules.  The greedy shortcut and top_k = 1 must match on every case (only comparisons decide them).  Every other result
+that differs from the restatement's token is judged on its own by `sampler_accept.accepts` (its docstring derives the rule): on
+the S path (top_k <= SMALL_K, the reference's summation order) the restatement's deciding comparison must have lain within 2^-20
+of flipping; on the F path (parallel sums over the vocabulary) the device's token must belong to the largest kept set the
+reference's own rounding admits, and u must lie within the case's tolerance -- the reference's measured f32 drift on that row
+plus the derived allowance for the device's arithmetic -- of that token's float64 interval.  So a mismatch is checked for where
+it landed: a neighbour in cumulative mass passes, a token from another chunk, a filtered entry or a stray last index does not.
+
+On the rows of the original grid (peaked: sigma 1, 4, 12) two older conditions hold in addition, unchanged: a differing case must
+also have had its deciding comparison within 2^-20 (S) or 2^-12 (F) of flipping, and the mismatches per path are capped: at most
+1 % of the S cases and F_RATE of the F cases.  The case lists of tests/sampler_cases.py (vocabulary sweep, adversarial rows,
+penalty edges, ends of the draw) are judged by `accepts` alone: on a flat row the reference's f32 total drifts by up to 1e-3, a
+device that sums exactly lands a hundred entries away and legitimately differs on most draws, so neither the 2^-12 margin nor a
+mismatch rate says anything there.  tests/test_sampler_accept.py holds the rule itself to account on the CPU, over the same lists."""
 import importlib
 import os
 import sys
@@ -15,6 +23,8 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sampler_accept as sa  # noqa: E402
+import sampler_cases as sc  # noqa: E402
 import sampler_ref as sr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -51,29 +61,47 @@ def planted_logits(rng, vocab, sigma, k):
 
 
 class Tally:
-    def __init__(self):
+    """grid=True (the original grid's rows): the margin rule and the rate caps, and `accepts` on every mismatch in addition.
+    grid=False (the lists of sampler_cases.py): `accepts` alone."""
+
+    def __init__(self, grid=True):
+        self.grid = grid
         self.cases, self.flagged, self.mismatch = {"G": 0, "S": 0, "F": 0}, {"S": 0, "F": 0}, []
+        self.exact = {"G": 0, "S": 0, "F": 0}
+        self.worst, self.far = (0.0, None), (0, None)  # largest dist / T and largest index distance among the accepted mismatches
 
     def check(self, ref: sr.RefSampler, got: int, want: int, what):
         path = ref.last_path
         self.cases[path] += 1
+        self.exact[path] += got == want
         if path == "G" or ref.k == 1:
             assert got == want, (what, path, got, want)
             return
         near = ref.last_margin < MARGIN[path]
         self.flagged[path] += near
         if got != want:
-            assert near, (what, path, got, want, ref.last_margin)
+            if self.grid:
+                assert near, (what, path, got, want, ref.last_margin)
+            ok, reason = sa.accepts(ref, got)
+            print(f"  mismatch {what} want {want} got {got}: {reason}")
+            assert ok, (what, path, reason)
             self.mismatch.append((path,) + tuple(what))
+            v = ref.last["verdict"]
+            if v["T"] > 0 and v["dist"] / v["T"] > self.worst[0]:
+                self.worst = (v["dist"] / v["T"], what)
+            if v["idx"] > self.far[0]:
+                self.far = (v["idx"], what)
 
-    def report(self):
+    def report(self, name=""):
         per = {p: sum(1 for m in self.mismatch if m[0] == p) for p in ("S", "F")}
-        msg = f"cases {self.cases}, near-boundary {self.flagged}, mismatches {per}"
+        msg = (f"{name}: cases {self.cases}, exact {self.exact}, accepted mismatches {per}, near-boundary {self.flagged}, "
+               f"worst dist/T {self.worst[0]:.3f} {self.worst[1]}, largest index distance {self.far[0]} {self.far[1]}")
         print(msg)
-        # each path on its own count: S sums in the reference's order (only expf can differ); F's parallel sums differ from
-        # the reference's sequential f32 sum by its own drift, which moves a high-entropy draw to a neighbour now and then
-        assert per["S"] <= max(1, 0.01 * self.cases["S"]), msg
-        assert per["F"] <= max(1, F_RATE * self.cases["F"]), msg
+        if self.grid:
+            # each path on its own count: S sums in the reference's order (only expf can differ); F's parallel sums differ from
+            # the reference's sequential f32 sum by its own drift, which moves a high-entropy draw to a neighbour now and then
+            assert per["S"] <= max(1, 0.01 * self.cases["S"]), msg
+            assert per["F"] <= max(1, F_RATE * self.cases["F"]), msg
         return msg
 
 
@@ -103,7 +131,7 @@ def test_sample_host_grid_matches_the_restatement(hip, vocab):
         got = smp.sample_host(x, gen)
         tally.check(ref, got, want, ("host", vocab, t, k, p, rp, sigma, n_gen))
         assert smp.draws() == (0 if ref.last_path == "G" else 1)
-    tally.report()
+    tally.report("grid")
     smp.close()
 
 
@@ -134,7 +162,7 @@ def test_sample_dev_sequences_match_the_restatement(hip, torch_, vocab):
             tally.check(ref, got, want, ("dev", vocab, t, k, p, rp, step))
             gen.append(got)  # the device's own choice is what it counts next
         assert smp.draws() == ref.rng.draws
-    tally.report()
+    tally.report("grid")
     smp.close()
 
 
@@ -154,6 +182,183 @@ def test_sample_dev_writes_history_and_skips_forced_positions(hip, torch_):
     smp.sample_dev(x, tok, pos, hist, nf)
     torch.cuda.synchronize()
     assert int(pos.item()) == 5 and int(hist[5].item()) == int(tok.item()) and smp.draws() == 1
+
+
+# ---- the case lists of tests/sampler_cases.py: judged by sampler_accept.accepts alone ---------------------------------------
+LISTS = {"sweep": sc.SWEEP, "adversarial": sc.ADVERSARIAL, "penalty": sc.PENALTY, "ends": sc.ENDS}
+
+
+class Samplers:
+    """one device sampler per vocabulary, made on first use"""
+
+    def __init__(self, hip):
+        self.hip, self.by_vocab = hip, {}
+
+    def get(self, vocab):
+        if vocab not in self.by_vocab:
+            self.by_vocab[vocab] = self.hip.sampler(vocab, 1.0, 0, 1.0, 1.0, seed=0)
+        return self.by_vocab[vocab]
+
+    def close(self):
+        for s in self.by_vocab.values():
+            s.close()
+
+
+def run_case(smp, torch, case, mode, tally):
+    """host: every call passes the growing list (the case's own list first) to sample_host.  dev: sample_dev counts the tokens it
+    chose itself, so the case's list is left out and the restatement is fed the device's tokens."""
+    x = sc.row(case)
+    smp.configure(*case["cfg"], case["seed"])
+    smp.reset()
+    ref = sr.RefSampler(*case["cfg"], seed=case["seed"])
+    hist = sc.gen(case) if mode == "host" else []
+    if mode == "dev":
+        xd = torch.from_numpy(x).cuda()
+        tok = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for step in range(case["steps"]):
+        if mode == "host":
+            got = smp.sample_host(x, hist)
+        else:
+            smp.sample_dev(xd, tok)
+            torch.cuda.synchronize()
+            got = int(tok.item())
+        want = ref.sample(x, hist)
+        tally.check(ref, got, want, (mode, case["id"], step))
+        hist = hist + [got]
+    assert smp.draws() == ref.rng.draws, case["id"]
+
+
+@pytest.mark.parametrize("mode", ["host", "dev"])
+@pytest.mark.parametrize("name", list(LISTS))
+def test_case_lists_are_defensible_draw_by_draw(hip, torch_, name, mode):
+    tally = Tally(grid=False)
+    pool = Samplers(hip)
+    for case in LISTS[name]:
+        run_case(pool.get(case["vocab"]), torch_, case, mode, tally)
+    pool.close()
+    tally.report(f"{name}/{mode}")
+    assert sum(tally.cases.values()) == sum(c["steps"] for c in LISTS[name])
+
+
+def test_ends_of_the_draw_seeds():
+    lo, hi = sr.ChaCha20Rng(sc.SEED_U_LOW).random_f32(), sr.ChaCha20Rng(sc.SEED_U_HIGH).random_f32()
+    assert 0 <= lo < 2.0 ** -16 and 1 - 2.0 ** -16 <= hi < 1
+
+
+def test_sample_dev_512_calls_with_a_compounding_penalty(hip, torch_):
+    """512 calls at vocab 128256 with rp 1.3: the exponents reach the hundreds of thousands, powi(1.3, e) is inf from e = 339 on, so
+    positive favourites go to +0, negative ones to -inf, and the draw moves on to fresh tokens.  The restatement is fed the
+    device's own tokens."""
+    torch = torch_
+    vocab, cfg, seed = 128256, (0.7, 0, 0.95, 1.3), 77
+    base = (4.0 * np.random.default_rng(5).standard_normal(vocab)).astype(np.float32)
+    smp = hip.sampler(vocab, *cfg, seed=seed)
+    ref = sr.RefSampler(*cfg, seed=seed)
+    tally = Tally(grid=False)
+    tok = torch.zeros(1, dtype=torch.int32, device="cuda")
+    bd = torch.from_numpy(base).cuda()
+    hist: list[int] = []
+    for step in range(512):
+        sh = (step * 9973) % vocab
+        smp.sample_dev(torch.roll(bd, sh), tok)
+        torch.cuda.synchronize()
+        got = int(tok.item())
+        want = ref.sample(np.roll(base, sh), hist)
+        tally.check(ref, got, want, ("dev512", step))
+        hist.append(got)
+    assert smp.draws() == ref.rng.draws == 512
+    tally.report("dev 512 calls")
+    smp.close()
+
+
+def test_configure_mid_sequence_keeps_the_counts(hip, torch_):
+    """A new config and seed without reset(): the stream restarts, the counts stay (what a new reference Sampler would not do, so
+    the restatement's counts are carried over by hand)."""
+    torch = torch_
+    vocab = 128256
+    x = (12.0 * np.random.default_rng(11).standard_normal(vocab)).astype(np.float32)
+    xd = torch.from_numpy(x).cuda()
+    tok = torch.zeros(1, dtype=torch.int32, device="cuda")
+    tally = Tally(grid=False)
+    a, b = (0.7, 0, 0.9, 1.5), (1.0, 0, 1.0, 1.5)  # F, then the penalised argmax, then S
+    smp = hip.sampler(vocab, *a, seed=1)
+    ref = sr.RefSampler(*a, seed=1)
+    hist: list[int] = []
+    for ci, cfg in enumerate([a, b, (0.9, 40, 0.95, 1.5)]):
+        if ci:
+            smp.configure(*cfg, 100 + ci)
+            counts = ref.counts
+            ref = sr.RefSampler(*cfg, seed=100 + ci)
+            ref.counts = counts
+        for step in range(4):
+            smp.sample_dev(xd, tok)
+            torch.cuda.synchronize()
+            got = int(tok.item())
+            want = ref.sample(x, hist)
+            tally.check(ref, got, want, ("configure", ci, step))
+            hist.append(got)
+        assert smp.draws() == ref.rng.draws
+    assert len(set(hist)) > 1  # the penalty moved the favourite: the counts mattered
+    tally.report("configure mid-sequence")
+    smp.close()
+
+
+def test_two_samplers_of_different_vocabulary_alternate_on_one_stream(hip, torch_):
+    """2^20 first, then 1000: the kernel's dynamic-LDS attribute only ever grows, so the later, smaller sampler leaves it alone."""
+    torch = torch_
+    tally = Tally(grid=False)
+    big, small = 1 << 20, 1000
+    cb, cs = (0.7, 0, 0.9, 1.1), (1.3, 0, 0.5, 1.1)
+    sb = hip.sampler(big, *cb, seed=3)
+    ss = hip.sampler(small, *cs, seed=4)
+    rb, rs = sr.RefSampler(*cb, seed=3), sr.RefSampler(*cs, seed=4)
+    xb = (4.0 * np.random.default_rng(1).standard_normal(big)).astype(np.float32)
+    xs = np.random.default_rng(2).standard_normal(small).astype(np.float32)
+    xbd, xsd = torch.from_numpy(xb).cuda(), torch.from_numpy(xs).cuda()
+    tb = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ts = torch.zeros(1, dtype=torch.int32, device="cuda")
+    hb, hs = [], []
+    for step in range(4):
+        sb.sample_dev(xbd, tb)
+        ss.sample_dev(xsd, ts)
+        torch.cuda.synchronize()
+        gb, gs = int(tb.item()), int(ts.item())
+        tally.check(rb, gb, rb.sample(xb, hb), ("alternate", big, step))
+        tally.check(rs, gs, rs.sample(xs, hs), ("alternate", small, step))
+        hb.append(gb)
+        hs.append(gs)
+    assert sb.draws() == 4 and ss.draws() == 4
+    tally.report("two samplers")
+    sb.close()
+    ss.close()
+
+
+def test_greedy_then_full_then_greedy_on_one_sampler(hip):
+    vocab = 128256
+    x = (4.0 * np.random.default_rng(21).standard_normal(vocab)).astype(np.float32)
+    tally = Tally(grid=False)
+    smp = hip.sampler(vocab, 1.0, 0, 1.0, 1.1, seed=8)
+    for ci, cfg in enumerate([(1.0, 0, 1.0, 1.1), (0.7, 0, 0.95, 1.1), (0.0, 50, 0.5, 1.1)]):
+        smp.configure(*cfg, 8)
+        ref = sr.RefSampler(*cfg, seed=8)
+        got = smp.sample_host(x, [int(np.argmax(x))] * 3)
+        tally.check(ref, got, ref.sample(x, [int(np.argmax(x))] * 3), ("G-F-G", ci))
+        assert ref.last_path == "GFG"[ci] and smp.draws() == ref.rng.draws == (1 if ci == 1 else 0)
+    smp.close()
+
+
+def test_sampler_refuses_vocabularies_it_was_not_made_for(hip, pkg, torch_):
+    for vocab in (0, (1 << 20) + 1):
+        with pytest.raises(pkg.BitNetHipError, match=r"sampler_create: vocab must be in 1\.\.1048576"):
+            hip.sampler(vocab, 1.0, 0, 1.0, 1.0, seed=0)
+    smp = hip.sampler(1000, 0.7, 0, 0.9, 1.0, seed=0)
+    tok = torch_.zeros(1, dtype=torch_.int32, device="cuda")
+    with pytest.raises(pkg.BitNetHipError, match="sample_dev: vocab 999, the sampler was made for 1000"):
+        smp.sample_dev(torch_.zeros(999, device="cuda"), tok)
+    with pytest.raises(pkg.BitNetHipError, match="sample_host: vocab 1001, the sampler was made for 1000"):
+        smp.sample_host(np.zeros(1001, np.float32), [])
+    assert smp.draws() == 0
+    smp.close()
 
 
 # ---- decoder level ---------------------------------------------------------------------------------------------------------
@@ -210,7 +415,7 @@ def test_decoder_sampling_matches_the_restatement(hip, pkg, synth, cfgd, fmt):
         dec.set_sampling(0.8, 40, 0.9, 1.1, seed=9)
         ref = sr.RefSampler(0.8, 40, 0.9, 1.1, seed=9)
         sampled_run(dec, prompt, 24, use_graph, ref, tally)
-    tally.report()
+    tally.report("grid")
     assert len(set(toks)) > 1
     dec.close()
 
@@ -258,6 +463,7 @@ def test_first_token_after_prefill_is_sampled(hip, pkg, synth):
     want = ref.sample(dec.last_logits(), [])
     got = int(dec.history(65)[64])
     assert got == want or ref.last_margin < MARGIN["F"]
+    assert sa.accepts(ref, got)[0], sa.accepts(ref, got)[1]
     with pytest.raises(pkg.BitNetHipError, match="sampling"):
         dec.reset()
         dec.feed(prompt)

@@ -158,6 +158,9 @@ class HipLib:
         L.bitnet_hip_attention_prefill_workspace_bytes.argtypes = [_sz, _sz, _sz]
         L.bitnet_hip_attention_prefill_workspace_bytes.restype = _sz
         L.bitnet_hip_attention_prefill_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp]
+        L.bitnet_hip_attention_extend_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz]
+        L.bitnet_hip_attention_extend_workspace_bytes.restype = _sz
+        L.bitnet_hip_attention_extend_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, C.c_int, _vp]
         L.bitnet_hip_attention_prefill_sharded_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz]
         L.bitnet_hip_attention_prefill_sharded_workspace_bytes.restype = _sz
         L.bitnet_hip_attention_prefill_sharded_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp]
@@ -406,6 +409,18 @@ class HipLib:
                               workspace_bytes, out, stream: int = 0) -> None:
         self._check(self.c.bitnet_hip_attention_prefill_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kcache), _ptr(vcache), n_heads, n_kv,
                                                             head_dim, max_pos, seq_len, _ptr(workspace), workspace_bytes, _ptr(out), _vp(stream)))
+
+    def attention_extend_workspace_bytes(self, n_heads: int, n_kv: int, past_len: int, seq_len: int) -> int:
+        """Workspace of attention_extend_dev; 0 for sizes it refuses, non-decreasing in both lengths."""
+        return int(self.c.bitnet_hip_attention_extend_workspace_bytes(n_heads, n_kv, past_len, seq_len))
+
+    def attention_extend_dev(self, qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv, head_dim, max_pos, past_len, seq_len, workspace,
+                             workspace_bytes, out, flags: int = 0, stream: int = 0) -> None:
+        """seq_len new tokens at positions past_len .. past_len + seq_len - 1 over caches that hold 0 .. past_len - 1: RoPE, cache append,
+        causal GQA attention over keys 0 .. own position.  flags: ATTN_CACHE_F16 (1) | ATTN_OUT_F16 (2)."""
+        self._check(self.c.bitnet_hip_attention_extend_dev(_optr(qkv), _optr(rope_sin), _optr(rope_cos), _optr(kcache), _optr(vcache), n_heads, n_kv,
+                                                           head_dim, max_pos, past_len, seq_len, _optr(workspace), workspace_bytes, _optr(out), flags,
+                                                           _vp(stream)))
 
     def attention_prefill_sharded_workspace_bytes(self, n_heads: int, n_kv: int, n_q: int, n_ctx: int) -> int:
         return int(self.c.bitnet_hip_attention_prefill_sharded_workspace_bytes(n_heads, n_kv, n_q, n_ctx))
@@ -806,6 +821,10 @@ class HostDecoder:
         L.bitnet_host_set_sampling.argtypes = [C.c_void_p, C.POINTER(SamplingConfig)]
         L.bitnet_host_sampling_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.bitnet_host_score.argtypes = [C.c_void_p, C.c_int, C.c_int, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.POINTER(C.c_float)]
+        L.bitnet_host_extend.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.bitnet_host_extend.restype = C.c_int
+        L.bitnet_host_rewind.argtypes = [C.c_void_p, C.c_int]
+        L.bitnet_host_rewind.restype = C.c_int
         self.cfg = cfg
         self._fed = 0  # tokens fed since the last reset (the default n of score)
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
@@ -953,6 +972,20 @@ class HostDecoder:
         ms = C.c_float(0)
         self._check(self.c.bitnet_host_prefill(self.h, n, int(with_logits), digits, C.byref(ms)))
         return ms.value
+
+    def extend(self, n: int, with_logits: bool = True, digits: int = 2) -> float:
+        """Prompt forward on a LIVE sequence: history tokens [position, position + n) as [n, *] matrices over the cached positions, at
+        prefill speed; ends as prefill ends (position + n, with_logits picks the next token).  At position 0 it is prefill.  After a
+        with-logits step the picked token sits unconsumed at history[position()] and feed() writes onto that slot: feed it again in
+        front of the new tokens to keep it in the context."""
+        ms = C.c_float(0)
+        self._check(self.c.bitnet_host_extend(self.h, n, int(with_logits), digits, C.byref(ms)))
+        return ms.value
+
+    def rewind(self, n: int) -> None:
+        """Keep the first n positions (0 <= n <= position()): the next feed() writes at n.  The cache bytes and the sampler state stay."""
+        self._check(self.c.bitnet_host_rewind(self.h, n))
+        self._fed = min(self._fed, int(n))
 
     def score(self, n: int | None = None, digits: int = 2, logits_rows: int = 0) -> "ScoreResult":
         """Teacher-forced scoring of the first n fed tokens (default: all of them) in one prompt forward: prefill(n, True, digits) as

@@ -1203,6 +1203,32 @@ int bitnet_hip_attention_prefill_flags_dev(const float *qkv, const float *rope_s
     BH_GUARD_END
 }
 
+size_t bitnet_hip_attention_extend_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t past_len, size_t seq_len) {
+    const size_t lim = (size_t)1 << 30;
+    if (n_heads == 0 || n_kv_heads == 0 || n_heads % n_kv_heads != 0 || seq_len == 0 || n_heads >= lim || past_len >= lim || seq_len >= lim || past_len + seq_len >= lim)
+        return 0;
+    return attn_extend_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)past_len, (int)seq_len);
+}
+
+int bitnet_hip_attention_extend_dev(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, size_t n_heads,
+                                    size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t past_len, size_t seq_len, void *workspace,
+                                    size_t workspace_bytes, void *out, int flags, void *stream) {
+    BH_GUARD_BEGIN
+    if (past_len > max_pos) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: past_len %zu, max_pos %zu", past_len, max_pos);
+    int rc = check_prefill_args(qkv, qkv, rope_sin, rope_cos, kcache, vcache, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, past_len + seq_len);
+    if (rc) return rc;
+    if (seq_len == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_extend_dev: seq_len must be at least 1");
+    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_extend_dev: unknown flag bits 0x%x", flags);
+    const size_t need = bitnet_hip_attention_extend_workspace_bytes(n_heads, n_kv_heads, past_len, seq_len);
+    if (need == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_extend_dev: sizes out of range");
+    if (workspace_bytes < need)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
+    BH_HIP_TRY(launch_attn_extend(qkv, rope_sin, rope_cos, kcache, vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, (int)past_len,
+                                  (int)seq_len, workspace, workspace_bytes, out, flags, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 int bitnet_hip_attention_prefill_gathered_dev(const float *q, size_t ld_q, const int32_t *q_block_pos, size_t n_q, const void *kv_gathered,
                                               size_t n_ctx, size_t world, int kv_is_f16, const float *rope_sin, const float *rope_cos,
                                               void *kcache, void *vcache, int cache_f16, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,

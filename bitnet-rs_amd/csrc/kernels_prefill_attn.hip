@@ -19,6 +19,9 @@
 //                   already in B-operand form for the second product once the V^T operand
 //                   uses the same key -> k-slot map.
 //   k_prefill_merge combines the key-split partials of launches too small to fill the chip.
+// A LIVE sequence (seq_len new tokens at positions past_len .. over a cache holding 0 .. past_len - 1: the reference's seq_len queries
+// over past_len + seq_len keys, T:455-470, T:704-719, append T:1171-1202) runs the same attention kernel behind
+//   k_extend_prep   which builds the k / v images from the decode cache (past) and the new rows (appended); see launch_attn_extend.
 // q, k, v and the probabilities are rounded to f16 for the matrix cores (relative 2^-11);
 // the f32 KV cache the decode steps read afterwards holds the exact f32 values.
 #include <cstdlib>
@@ -737,6 +740,260 @@ hipError_t launch_attn_prefill(const float *q, int ld_q, const int *q_block_pos,
     } else {
         hipLaunchKernelGGL(k_prefill_prep, dim3(nbq > nbk ? nbq : nbk, (unsigned)(n_heads + 2 * n_kv)), dim3(256), 0, stream, p);
     }
+    return launch_attn_kernel(p, stream);
+}
+
+// ---- continuing a LIVE sequence: seq new tokens at positions past .. past + seq - 1 over a cache that holds 0 .. past - 1 ----
+// The reference's attention takes seq_len queries over past_len + seq_len keys from the cache, its causal mask hiding the keys
+// beyond past_len + i from query i (T:455-470, T:704-719; cache append T:1171-1202).  k_prefill_attn already separates queries
+// (64-row blocks at q_block_pos[b], here past + 64 b: its mask and RoPE only use block position + row) from keys (the f16 images
+// kh / vt over T = past + seq positions), so what a continuation needs is the producer of those images:
+//
+//   k_extend_prep  grid (Tpad / 64, 2 kv): one 64-position tile of k or v through LDS.  Positions < past come from the decode
+//                  cache (any of its four layouts), positions in [past, T) from the new q|k|v rows (k with RoPE at the absolute
+//                  position) and go INTO the cache at their unaligned offset, positions >= T are zeros; the whole tile is then
+//                  written to kh / vt exactly as k_prefill_prep writes it.  A workgroup reads only past slots and writes only
+//                  new ones.  Slots >= past are never read: they may hold what a longer, rewound sequence left there.
+//
+// A past key goes cache -> f16: the bits k_prefill_prep's f16 of the exact value has, so the attention operands of a continued
+// prompt are those of the one-shot prompt.  The re-preparation reads the whole past on every call: O(past) bytes per layer.
+struct ExtendPrepArgs {
+    const float *k_new, *v_new;  // element (kv head h, new row r, dim d) at base + r * ld + h * 128 + d
+    int ld;
+    const float *rope_sin, *rope_cos;
+    void *kcache, *vcache;
+    int n_kv, max_pos, past, T, Tpad, cache_f16;
+    _Float16 *kh, *vt;   // [kv][Tpad][128], [kv][128][Tpad]
+    int *q_block_pos;    // [n_qblocks]: past + 64 b, filled here so that the call stays asynchronous on its stream
+    int n_qblocks;
+};
+
+__global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
+    // every global access is 16 bytes wide (8 for f16) and contiguous along the fastest index of its tensor, as in k_prefill_prep;
+    // only the 4-position (f16: 2-position) groups that straddle `past` or T fall back to single elements
+    __shared__ __attribute__((aligned(16))) float tile[kQB][kPD + 4];
+    const int tid = threadIdx.x, t0 = blockIdx.x * kQB;
+    const bool is_k = (int)blockIdx.y < p.n_kv;
+    const int kvh = is_k ? (int)blockIdx.y : (int)blockIdx.y - p.n_kv;
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int b = tid; b < p.n_qblocks; b += 256) p.q_block_pos[b] = p.past + kQB * b;
+    const int dp = p.past - t0, dl = p.T - t0;
+    const int n_past = dp < 0 ? 0 : dp > kQB ? kQB : dp;  // tile rows [0, n_past) come from the cache,
+    const int n_live = dl > kQB ? kQB : dl;               // [n_past, n_live) from the new rows, [n_live, 64) are zeros
+    const size_t head_elems = (size_t)((p.max_pos + 63) / 64) * 64 * kPD;
+    float *c32 = static_cast<float *>(is_k ? p.kcache : p.vcache) + (size_t)kvh * head_elems;
+    _Float16 *c16 = static_cast<_Float16 *>(is_k ? p.kcache : p.vcache) + (size_t)kvh * head_elems;
+    if (n_past < kQB) {
+        const float *src = (is_k ? p.k_new : p.v_new) + (size_t)kvh * kPD;
+        const bool vec_ok = (p.ld & 3) == 0 && ((uintptr_t)src & 15) == 0;
+        for (int i = 0; i < 8; ++i) {
+            const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
+            if (tok < n_past) continue;
+            float4 v = {0.f, 0.f, 0.f, 0.f};
+            if (tok < n_live) {
+                const float *e = src + (size_t)(t0 + tok - p.past) * p.ld + d;
+                v = vec_ok ? *reinterpret_cast<const float4 *>(e) : float4{e[0], e[1], e[2], e[3]};
+            }
+            *reinterpret_cast<float4 *>(&tile[tok][d]) = v;
+        }
+    }
+    if (n_past > 0) {
+        if (is_k && !p.cache_f16) {  // [chunk][128][64]: 4 adjacent positions of one dim
+            const float *kt = c32 + (size_t)(t0 >> 6) * kPD * 64;
+            for (int i = 0; i < 8; ++i) {
+                const int idx = tid + 256 * i, d = idx >> 4, tok = (idx & 15) * 4;
+                if (tok >= n_past) continue;
+                const float4 v = *reinterpret_cast<const float4 *>(kt + (size_t)d * 64 + tok);  // the tile is inside the (chunk-padded) allocation
+                const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (tok + j < n_past) tile[tok + j][d] = e[j];
+            }
+        } else if (is_k) {  // [chunk][D / 2][64][2]: a dim pair of 2 adjacent positions
+            const _Float16 *k16 = c16 + (size_t)(t0 >> 6) * kPD * 64;
+            for (int i = 0; i < 8; ++i) {
+                const int idx = tid + 256 * i, d2 = idx >> 5, tok = (idx & 31) * 2;
+                if (tok >= n_past) continue;
+                const v4h h = *reinterpret_cast<const v4h *>(k16 + ((size_t)d2 * 64 + tok) * 2);
+                tile[tok][2 * d2] = (float)h[0];
+                tile[tok][2 * d2 + 1] = (float)h[1];
+                if (tok + 1 < n_past) {
+                    tile[tok + 1][2 * d2] = (float)h[2];
+                    tile[tok + 1][2 * d2 + 1] = (float)h[3];
+                }
+            }
+        } else {  // [pos][128]
+            for (int i = 0; i < 8; ++i) {
+                const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
+                if (tok >= n_past) continue;
+                float4 v;
+                if (p.cache_f16) {
+                    const v4h h = *reinterpret_cast<const v4h *>(c16 + (size_t)(t0 + tok) * kPD + d);
+                    v = float4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+                } else {
+                    v = *reinterpret_cast<const float4 *>(c32 + (size_t)(t0 + tok) * kPD + d);
+                }
+                *reinterpret_cast<float4 *>(&tile[tok][d]) = v;
+            }
+        }
+    }
+    __syncthreads();
+    if (is_k && n_past < n_live) {
+        // split-half RoPE of the NEW keys at their absolute positions: the arithmetic of k_prefill_prep (cached keys are rotated already)
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + 256 * i, tok = idx >> 4, j = (idx & 15) * 4;
+            if (tok < n_past || tok >= n_live) continue;
+            const int pos = t0 + tok;
+            const float4 s = *reinterpret_cast<const float4 *>(p.rope_sin + (size_t)pos * 64 + j), c = *reinterpret_cast<const float4 *>(p.rope_cos + (size_t)pos * 64 + j);
+            const float4 x0 = *reinterpret_cast<const float4 *>(&tile[tok][j]), x1 = *reinterpret_cast<const float4 *>(&tile[tok][64 + j]);
+            *reinterpret_cast<float4 *>(&tile[tok][j]) = float4{x0.x * c.x - x1.x * s.x, x0.y * c.y - x1.y * s.y, x0.z * c.z - x1.z * s.z, x0.w * c.w - x1.w * s.w};
+            *reinterpret_cast<float4 *>(&tile[tok][64 + j]) = float4{x0.x * s.x + x1.x * c.x, x0.y * s.y + x1.y * c.y, x0.z * s.z + x1.z * c.z, x0.w * s.w + x1.w * c.w};
+        }
+        __syncthreads();
+    }
+    // ---- append the new positions to the decode cache ----
+    if (n_past < n_live) {
+        if (is_k && !p.cache_f16) {
+            float *kt = c32 + (size_t)(t0 >> 6) * kPD * 64;
+            for (int i = 0; i < 8; ++i) {
+                const int idx = tid + 256 * i, d = idx >> 4, tok = (idx & 15) * 4;
+                if (tok >= n_past && tok + 3 < n_live) {
+                    *reinterpret_cast<float4 *>(kt + (size_t)d * 64 + tok) = float4{tile[tok][d], tile[tok + 1][d], tile[tok + 2][d], tile[tok + 3][d]};
+                } else {
+                    for (int e = 0; e < 4; ++e)
+                        if (tok + e >= n_past && tok + e < n_live) kt[(size_t)d * 64 + tok + e] = tile[tok + e][d];
+                }
+            }
+        } else if (is_k) {
+            typedef _Float16 v2h __attribute__((ext_vector_type(2)));
+            _Float16 *k16 = c16 + (size_t)(t0 >> 6) * kPD * 64;
+            for (int i = 0; i < 8; ++i) {
+                const int idx = tid + 256 * i, d2 = idx >> 5, tok = (idx & 31) * 2;
+                const bool lo = tok >= n_past && tok < n_live, hi = tok + 1 >= n_past && tok + 1 < n_live;
+                _Float16 *dst = k16 + ((size_t)d2 * 64 + tok) * 2;
+                const v2h a = {(_Float16)tile[tok][2 * d2], (_Float16)tile[tok][2 * d2 + 1]}, b = {(_Float16)tile[tok + 1][2 * d2], (_Float16)tile[tok + 1][2 * d2 + 1]};
+                if (lo && hi)
+                    *reinterpret_cast<v4h *>(dst) = (v4h){a[0], a[1], b[0], b[1]};
+                else if (lo)
+                    *reinterpret_cast<v2h *>(dst) = a;
+                else if (hi)
+                    *reinterpret_cast<v2h *>(dst + 2) = b;
+            }
+        } else {
+            for (int i = 0; i < 8; ++i) {
+                const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
+                if (tok < n_past || tok >= n_live) continue;
+                const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
+                if (p.cache_f16)
+                    *reinterpret_cast<v4h *>(c16 + (size_t)(t0 + tok) * kPD + d) = (v4h){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+                else
+                    *reinterpret_cast<float4 *>(c32 + (size_t)(t0 + tok) * kPD + d) = v;
+            }
+        }
+    }
+    // ---- the f16 images of the whole tile, in k_prefill_prep's order ----
+    if (is_k) {
+        _Float16 *dst = p.kh + ((size_t)kvh * p.Tpad + t0) * kPD;
+        for (int i = 0; i < 8; ++i) {
+            const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
+            const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
+            *reinterpret_cast<v4h *>(dst + (size_t)tok * kPD + d) = (v4h){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+        }
+    } else {
+        // the V^T key permutation inside each group of 32 (k_prefill_prep): key 4 a + 16 b + j at slot 8 a + 4 b + j
+        _Float16 *vt = p.vt + (size_t)kvh * kPD * p.Tpad;
+        for (int i = 0; i < 8; ++i) {
+            const int idx = tid + 256 * i, d = idx >> 4, t4 = idx & 15, tok = t4 * 4;
+            const int slot = 32 * (t4 >> 3) + 8 * (t4 & 3) + 4 * ((t4 >> 2) & 1);
+            const v4h h = {(_Float16)tile[tok][d], (_Float16)tile[tok + 1][d], (_Float16)tile[tok + 2][d], (_Float16)tile[tok + 3][d]};
+            *reinterpret_cast<v4h *>(vt + (size_t)d * p.Tpad + t0 + slot) = h;
+        }
+    }
+}
+
+// A bound on attn_prefill_workspace_bytes(n_heads, n_kv, nq', T') over all nq' <= nq, T' <= T (the key split's partials vanish once the
+// query blocks alone fill the chip, so the exact size is not monotone), plus the q_block_pos array: non-decreasing in both lengths.
+static size_t extend_partial_bytes(int n_heads, int n_kv, size_t qpad, int T) {
+    const int group = n_heads / n_kv, hw = group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 1, qg = 16 * (4 / hw) * 2;
+    const size_t q_split_max = (size_t)(511 / (n_heads / hw)) * qg;  // the most query rows a split launch has (attn_ksplit: n_wg < 512)
+    const int tiles = (T + kQB - 1) / kQB;
+    int ks = (tiles + attn_split_tiles() - 1) / attn_split_tiles();
+    ks = ks < 1 ? 1 : ks > 8 ? 8 : ks;
+    return ks > 1 ? (size_t)ks * (qpad < q_split_max ? qpad : q_split_max) * n_heads * (kPD + 2) * sizeof(float) : 0;
+}
+size_t attn_extend_workspace_bytes(int n_heads, int n_kv, int past, int seq) {
+    if (n_heads <= 0 || n_kv <= 0 || n_heads % n_kv != 0 || past < 0 || seq <= 0) return 0;
+    const size_t qpad = div_ceil((size_t)seq, kQPad) * kQPad, tpad = div_ceil((size_t)past + seq, kQB) * kQB;
+    return attn_f16_bytes(n_heads, n_kv, qpad, tpad) + extend_partial_bytes(n_heads, n_kv, qpad, past + seq) + div_ceil(qpad / kQB * sizeof(int), 256) * 256 + 256;
+}
+
+hipError_t launch_attn_extend(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, int n_heads, int n_kv,
+                              int D, int max_pos, int past, int seq, void *workspace, size_t workspace_bytes, void *out, int flags, hipStream_t stream) {
+    if (D != kPD || past < 0 || seq <= 0 || n_kv <= 0 || n_heads % n_kv != 0 || (size_t)past + seq > (size_t)max_pos) return hipErrorInvalidValue;
+    if (!workspace || workspace_bytes < attn_extend_workspace_bytes(n_heads, n_kv, past, seq)) return hipErrorInvalidValue;
+    const int ld = (n_heads + 2 * n_kv) * kPD, T = past + seq;
+    PrefillArgs p;
+    p.q = qkv;
+    p.k = qkv + (size_t)n_heads * kPD;
+    p.v = p.k + (size_t)n_kv * kPD;
+    p.zz_world = p.zz_chunk = p.kv_f16 = 0;
+    p.cache_f16 = flags & 1;
+    p.out_f16 = (flags >> 1) & 1;
+    p.ld_q = p.ld_kv = ld;
+    p.hs_q = p.hs_kv = kPD;
+    p.out_hs = kPD;
+    p.out_ld = n_heads * kPD;
+    p.rope = 1;
+    p.causal = 1;
+    p.scale = 1.0f / sqrtf((float)kPD);
+    p.nq = seq;
+    p.nq_pad = (int)(div_ceil((size_t)seq, kQPad) * kQPad);
+    p.rope_sin = rope_sin;
+    p.rope_cos = rope_cos;
+    p.kcache = static_cast<float *>(kcache);
+    p.vcache = static_cast<float *>(vcache);
+    p.n_heads = n_heads;
+    p.n_kv = n_kv;
+    p.max_pos = max_pos;
+    p.T = T;
+    p.Tpad = (int)(div_ceil((size_t)T, kQB) * kQB);
+    uint8_t *ws = reinterpret_cast<uint8_t *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    p.qh = reinterpret_cast<_Float16 *>(ws);
+    p.kh = p.qh + (size_t)n_heads * p.nq_pad * kPD;
+    p.vt = p.kh + (size_t)n_kv * p.Tpad * kPD;
+    p.out = static_cast<float *>(out);
+    p.ksplit = attn_ksplit(n_heads, n_kv, p.nq_pad, T);
+    p.split_tiles = attn_split_tiles();
+    const size_t f16b = attn_f16_bytes(n_heads, n_kv, (size_t)p.nq_pad, (size_t)p.Tpad);
+    p.part_o = reinterpret_cast<float *>(ws + f16b);
+    p.part_ml = p.part_o + (size_t)p.ksplit * p.nq_pad * n_heads * kPD;
+    int *qbp = reinterpret_cast<int *>(ws + f16b + extend_partial_bytes(n_heads, n_kv, (size_t)p.nq_pad, T));
+    p.q_block_pos = qbp;
+    p.phase = 1;
+    p.slot0 = 0;
+    static const bool q_in_kernel = !(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL") && atoi(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL")) == 0);
+    p.q_in_kernel = q_in_kernel && ((uintptr_t)qkv & 15) == 0 ? 1 : 0;
+    ExtendPrepArgs e;
+    e.k_new = p.k;
+    e.v_new = p.v;
+    e.ld = ld;
+    e.rope_sin = rope_sin;
+    e.rope_cos = rope_cos;
+    e.kcache = kcache;
+    e.vcache = vcache;
+    e.n_kv = n_kv;
+    e.max_pos = max_pos;
+    e.past = past;
+    e.T = T;
+    e.Tpad = p.Tpad;
+    e.cache_f16 = p.cache_f16;
+    e.kh = p.kh;
+    e.vt = p.vt;
+    e.q_block_pos = qbp;
+    e.n_qblocks = p.nq_pad / kQB;
+    hipLaunchKernelGGL(k_extend_prep, dim3((unsigned)(p.Tpad / kQB), (unsigned)(2 * n_kv)), dim3(256), 0, stream, e);
+    // misaligned query rows: the f16 query image of k_prefill_prep (its query slabs alone), positions from the array filled above
+    if (!p.q_in_kernel) hipLaunchKernelGGL(k_prefill_prep, dim3((unsigned)(p.nq_pad / kQB), (unsigned)n_heads), dim3(256), 0, stream, p);
     return launch_attn_kernel(p, stream);
 }
 

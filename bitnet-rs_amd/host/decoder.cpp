@@ -854,6 +854,23 @@ int Decoder::ensure_chain_buffers(size_t N) {
     return 0;
 }
 
+// The attention of one layer of a prompt forward over the N rows in pf_qkv_ (all three forms of the layer loop come here): on a fresh
+// sequence the whole-prompt operator, on a live one (pf_past_ cached positions: Decoder::extend) the continuation operator, which reads the
+// past keys from the cache and takes every slot at or beyond pf_past_ from the new rows.
+int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16) {
+    const size_t NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, D = (size_t)c_.head_dim, MP = (size_t)c_.max_pos;
+    const int flags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
+    if (pf_past_ > 0)
+        BCHK(bitnet_hip_attention_extend_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, pf_past_, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
+    else if (out_f16)
+        BCHK(bitnet_hip_attention_prefill_flags_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
+    else if (kv_f16_)
+        BCHK(bitnet_hip_attention_prefill_kv16_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, static_cast<float *>(out), stream_));
+    else
+        BCHK(bitnet_hip_attention_prefill_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, static_cast<float *>(out), stream_));
+    return 0;
+}
+
 int Decoder::prefill_chain_layers(size_t N) {
     const size_t H = c_.hidden, nst = H / 64;
     hipStream_t s = (hipStream_t)stream_;
@@ -863,12 +880,10 @@ int Decoder::prefill_chain_layers(size_t N) {
     }
     BCHK(bitnet_hip_rows_to_f16_dev(pf_x_, layers_[0].attn_norm, N, H, pf_xh_, pf_stats_, s));
     size_t n_stats = 1;
-    const int aflags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | BITNET_HIP_ATTN_OUT_F16;
     for (size_t l = 0; l < layers_.size(); ++l) {
         auto &L = layers_[l];
         BCHK(bitnet_hip_matmul_f16_dev(L.qkv, pf_xh_, N, pf_stats_, n_stats, L.attn_norm, c_.eps, pf_qkv_, nullptr, 0, nullptr, nullptr, nullptr, s));
-        BCHK(bitnet_hip_attention_prefill_flags_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, (size_t)c_.n_heads, (size_t)c_.n_kv_heads,
-                                                    (size_t)c_.head_dim, (size_t)c_.max_pos, N, pf_attn_ws_, pf_attn_ws_bytes_, pf_atth_, aflags, s));
+        if (int rc = prompt_attention(L, N, pf_atth_, true)) return rc;
         BCHK(bitnet_hip_matmul_f16_dev(L.o, pf_atth_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, pf_xh_, L.ffn_norm, pf_stats_, s));
         n_stats = nst;
         BCHK(bitnet_hip_matmul_f16_dev(L.gateup, pf_xh_, N, pf_stats_, n_stats, L.ffn_norm, c_.eps, nullptr, nullptr, BITNET_HIP_FUSE_SILU_MUL, pf_hh_, nullptr,
@@ -918,12 +933,10 @@ int Decoder::prefill_qb32_layers(size_t N) {
     }
     BCHK(bitnet_hip_rows_to_qb32_dev(pf_x_, layers_[0].attn_norm, N, H, pf_qb_, pf_stats_, s));
     size_t n_stats = 1;
-    const int aflags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | BITNET_HIP_ATTN_OUT_F16;
     for (size_t l = 0; l < layers_.size(); ++l) {
         auto &L = layers_[l];
         BCHK(bitnet_hip_matmul_qb32_dev(L.qkv, pf_qb_, N, pf_stats_, n_stats, L.attn_norm, c_.eps, pf_qkv_, nullptr, 0, nullptr, nullptr, nullptr, s));
-        BCHK(bitnet_hip_attention_prefill_flags_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, (size_t)c_.n_heads, (size_t)c_.n_kv_heads,
-                                                    (size_t)c_.head_dim, (size_t)c_.max_pos, N, pf_attn_ws_, pf_attn_ws_bytes_, pf_atth_, aflags, s));
+        if (int rc = prompt_attention(L, N, pf_atth_, true)) return rc;
         BCHK(bitnet_hip_matmul_f16_dev(L.o, pf_atth_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, BITNET_HIP_FUSE_YH_QB32, pf_qb_, L.ffn_norm, pf_stats_, s));
         n_stats = nst;
         BCHK(bitnet_hip_matmul_qb32_dev(L.gateup, pf_qb_, N, pf_stats_, n_stats, L.ffn_norm, c_.eps, nullptr, nullptr, BITNET_HIP_FUSE_SILU_MUL, pf_hh_, nullptr,
@@ -957,24 +970,69 @@ int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
         err_ = "KV cache overflow";  // T:1190-1194
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
     }
+    return prompt_forward(0, n, with_logits, digits, elapsed_ms);
+}
+
+int Decoder::extend(int n, bool with_logits, int digits, float *elapsed_ms) {
+    if (!embed_) {
+        err_ = "model globals not set";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    const int p = position();
+    if (p < 0) return BITNET_HIP_ERR_GPU;
+    if (n <= 0 || p + n > host_forced_) {
+        err_ = "prefill: feed() the prompt tokens first";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (p + n > c_.max_pos - 1) {
+        err_ = "KV cache overflow";  // T:1190-1194
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    if (p == 0) return prefill(n, with_logits, digits, elapsed_ms);
+    return prompt_forward(p, n, with_logits, digits, elapsed_ms);
+}
+
+int Decoder::rewind(int n) {
+    const int p = position();
+    if (p < 0) return BITNET_HIP_ERR_GPU;
+    if (n < 0 || n > p) {
+        err_ = "rewind: n must be in [0, position()]";
+        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    }
+    // the cache bytes stay: the decode attention gives slots beyond the position zero weight, and the continuation operator takes every slot at
+    // or beyond its past length from the new rows
+    const int32_t np = n;
+    HCHK(hipMemcpy(pos_, &np, 4, hipMemcpyHostToDevice));
+    if (host_forced_ > n) host_forced_ = n;
+    HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// History tokens [p, p + n) through every layer as [n, *] matrices; p = the position (0: a fresh sequence and the whole-prompt attention;
+// otherwise the continuation operator over the p cached positions).  The callers hold the guards.
+int Decoder::prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms) {
     const size_t H = c_.hidden, QD = (size_t)c_.n_heads * c_.head_dim, KD = (size_t)c_.n_kv_heads * c_.head_dim, F = c_.ffn;
-    if (n > pf_cap_ || bitnet_hip_attention_prefill_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)n) > pf_attn_ws_bytes_) {
+    pf_past_ = (size_t)p;
+    const size_t attn_need = p == 0 ? bitnet_hip_attention_prefill_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)n)
+                                    : bitnet_hip_attention_extend_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)p, (size_t)n);
+    if (n > pf_cap_ || attn_need > pf_attn_ws_bytes_) {
+        const size_t N = (size_t)(n > pf_cap_ ? n : pf_cap_);  // the row buffers never shrink: a short turn at a long context keeps the prompt's
+        const size_t attn_bytes = attn_need > pf_attn_ws_bytes_ ? attn_need : pf_attn_ws_bytes_;
         for (void *q : {(void *)pf_x_, (void *)pf_qkv_, (void *)pf_att_, (void *)pf_h_, pf_gemm_ws_, pf_attn_ws_})
             if (q) hipFree(q);
         pf_x_ = pf_qkv_ = pf_att_ = pf_h_ = nullptr;
         pf_gemm_ws_ = pf_attn_ws_ = nullptr;
         pf_cap_ = 0;
         pf_attn_ws_bytes_ = 0;
-        const size_t N = (size_t)n;
         pf_gemm_ws_bytes_ = bitnet_hip_matmul_workspace_bytes(N, H > F ? H : F, 4);
-        pf_attn_ws_bytes_ = bitnet_hip_attention_prefill_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, N);
+        pf_attn_ws_bytes_ = attn_bytes;
         HCHK(dalloc(&pf_x_, N * H));
         HCHK(dalloc(&pf_qkv_, N * (QD + 2 * KD)));
         HCHK(dalloc(&pf_att_, N * QD));
         HCHK(dalloc(&pf_h_, N * F));
         HCHK(hipMalloc(&pf_gemm_ws_, pf_gemm_ws_bytes_));
         HCHK(hipMalloc(&pf_attn_ws_, pf_attn_ws_bytes_));
-        pf_cap_ = n;
+        pf_cap_ = (int)N;
     }
     hipStream_t s = (hipStream_t)stream_;
     Event ev0, ev1;
@@ -984,7 +1042,7 @@ int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
     if (!force_scaled_) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this prompt
     HCHK(hipEventRecord(e0, s));
     const size_t N = (size_t)n;
-    BCHK(bitnet_hip_embed_f16_dev(embed_, history_, pos_, N, H, (size_t)c_.vocab, pf_x_, s));  // *pos_ == 0
+    BCHK(bitnet_hip_embed_f16_dev(embed_, history_, pos_, N, H, (size_t)c_.vocab, pf_x_, s));  // rows history[*pos_ + i], *pos_ == p
     const bool chain = chain_applies(digits);
     if (chain) {
         const int rc = prefill_chain_layers(N);
@@ -1012,9 +1070,7 @@ int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
         if (chain || qb) break;
         BCHK(bitnet_hip_matmul_fused_dev(L.qkv, pf_x_, pf_qkv_, N, L.attn_norm, c_.eps, nullptr, f6, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
         if (h16) {
-            BCHK(bitnet_hip_attention_prefill_flags_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, (size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)c_.head_dim,
-                                                        (size_t)c_.max_pos, N, pf_attn_ws_, pf_attn_ws_bytes_, pf_atth_,
-                                                        (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | BITNET_HIP_ATTN_OUT_F16, s));
+            if (int rc = prompt_attention(L, N, pf_atth_, true)) return rc;
             if (hybrid)
                 BCHK(bitnet_hip_matmul_f16_dev(L.o, pf_atth_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, nullptr, nullptr, nullptr, s));
             else
@@ -1027,12 +1083,7 @@ int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
                 BCHK(bitnet_hip_matmul_fused_dev(L.down, (const float *)pf_hh_, pf_x_, N, nullptr, 0.f, pf_x_, BITNET_HIP_FUSE_X_F16 | f6od, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
             continue;
         }
-        if (kv_f16_)
-            BCHK(bitnet_hip_attention_prefill_kv16_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, (size_t)c_.n_heads, (size_t)c_.n_kv_heads,
-                                                       (size_t)c_.head_dim, (size_t)c_.max_pos, N, pf_attn_ws_, pf_attn_ws_bytes_, pf_att_, s));
-        else
-            BCHK(bitnet_hip_attention_prefill_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, (size_t)c_.n_heads, (size_t)c_.n_kv_heads,
-                                                  (size_t)c_.head_dim, (size_t)c_.max_pos, N, pf_attn_ws_, pf_attn_ws_bytes_, pf_att_, s));
+        if (int rc = prompt_attention(L, N, pf_att_, false)) return rc;
         BCHK(bitnet_hip_matmul_fused_dev(L.o, pf_att_, pf_x_, N, nullptr, 0.f, pf_x_, 0, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
         BCHK(bitnet_hip_matmul_fused_dev(L.gateup, pf_x_, pf_h_, N, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL | f6, digits, pf_gemm_ws_,
                                          pf_gemm_ws_bytes_, s));
@@ -1047,13 +1098,13 @@ int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
         if (bitnet_hip_f16_saturations(1) > 0) {
             force_scaled_ = true;
             ++saturation_fallbacks_;
-            const int rc = prefill(n, with_logits, 4, elapsed_ms);
+            const int rc = prompt_forward(p, n, with_logits, 4, elapsed_ms);  // (a continuation rewrites only the new positions)
             force_scaled_ = false;
             return rc;
         }
     }
     {
-        const int rc = finish_prefill(n, pf_x_ + (N - 1) * H, with_logits);
+        const int rc = finish_prefill(p + n, pf_x_ + (N - 1) * H, with_logits);
         if (rc) return rc;
     }
     HCHK(hipEventRecord(e1, s));
@@ -1594,6 +1645,14 @@ int bitnet_host_run(void *d, int n, int with_logits, int use_graph, float *elaps
 int bitnet_host_prefill(void *d, int n, int with_logits, int digits, float *elapsed_ms) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
     return D->prefill(n, with_logits != 0, digits, elapsed_ms);
+}
+int bitnet_host_extend(void *d, int n, int with_logits, int digits, float *elapsed_ms) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->extend(n, with_logits != 0, digits, elapsed_ms);
+}
+int bitnet_host_rewind(void *d, int n) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->rewind(n);
 }
 int bitnet_host_prefill_sharded(void *d, int n, int rank, int world, bitnet_host_allgather_fn gather, void *gather_ctx, int with_logits,
                                 int digits, int wire_f16, float *elapsed_ms) {

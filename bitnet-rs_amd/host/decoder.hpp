@@ -108,6 +108,22 @@ class Decoder {
     // with_logits samples the token after the prompt exactly as run() does for the last
     // prompt position.  digits: fixed-point digits per activation in the matmuls (2..4).
     int prefill(int n, bool with_logits, int digits, float *elapsed_ms);
+    // The same forward on a LIVE sequence: with p = position(), history tokens [p, p + n) go through every layer as [n, *] matrices
+    // over the p positions the KV cache already holds (the reference's forward with seq_len n over a cache of past_len p: T:455-470,
+    // T:704-719), on the matmul chain prefill would choose for n rows (last_prefill_path()) and with the continuation attention
+    // (bitnet_hip_attention_extend_dev) in place of the whole-prompt one; it ends as prefill ends: position p + n, with_logits picks
+    // the next token (argmax or the sampler) into history[p + n], run() can go on.  At p == 0 it IS prefill (same logits bit for bit).
+    // n >= 1, p + n <= fed tokens, p + n <= max_pos - 1.  Both storage formats, both cache types, sampling on or off.
+    // Carry-on rule: after a with-logits step the picked token sits UNCONSUMED at history[position()], and feed() writes at
+    // max(position, fed) -- onto that slot.  A host that wants the picked token in the context therefore feeds it again in front of
+    // the new tokens (feed([picked] + new), extend(1 + len(new))); one that does not (an end-of-turn marker it replaces) just feeds
+    // the new tokens.
+    int extend(int n, bool with_logits, int digits, float *elapsed_ms);
+    // Keep the first n positions of the sequence, 0 <= n <= position(): the position becomes n and the forced count min(forced, n), on
+    // host and device.  The cache bytes stay as they are (the decode attention gives slots beyond the position zero weight, the
+    // continuation attention never reads a slot at or beyond its past length), and so do the sampler's counts and word counter:
+    // reset() remains the full clear.
+    int rewind(int n);
     // Token-parallel prefill of ONE long prompt over `world` GPUs, one process per GPU (BASELINE configs[4]):
     // this rank runs the first n fed tokens' zigzag chunks rank and 2 world - 1 - rank through every layer (weights are
     // replicated: all seven projections are collective-free); per layer ONE all-gather of the raw k|v rows through
@@ -192,6 +208,9 @@ class Decoder {
         bool q_ok = false;  // all four matrices take QAct inputs (bitnet_hip_gemv_q_supported)
     };
     int attn_launch(Layer &L, int form, float *out, void *qout);
+    int prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms);  // the body of prefill (p == 0) and extend
+    int prompt_attention(Layer &L, size_t N, void *out, bool out_f16);                   // one layer's attention of a prompt forward
+    size_t pf_past_ = 0;  // cached positions under the prompt forward in flight (0: fresh sequence)
     void release_layer(Layer &L);  // frees the layer's handles, subtracts their bytes, drops the captured graphs
     void drop_graphs();
     int pick_token(void *stream);  // final norm + tied logits + the next token (greedy argmax or the sampler)
@@ -283,6 +302,8 @@ int bitnet_host_set_kv_f16(void *d, int on);
 int bitnet_host_act_mode(void *d);
 int bitnet_host_prefill(void *d, int n, int with_logits, int digits, float *elapsed_ms);
 int bitnet_host_finish_prefill(void *d, int n, const float *last_row, int with_logits);
+int bitnet_host_extend(void *d, int n, int with_logits, int digits, float *elapsed_ms);  // Decoder::extend
+int bitnet_host_rewind(void *d, int n);                                                    // Decoder::rewind
 int bitnet_host_score(void *d, int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms);
 // per-phase medians of the NEXT bitnet_host_prefill_sharded calls (off by default: 8 event records per layer); out[4] = projections,
 // attention, exposed all-gather wait, all-gather on its own stream -- microseconds per layer, medians over the layers of the last call

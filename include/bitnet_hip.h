@@ -476,6 +476,22 @@ int bitnet_hip_attention_prefill_kv16_dev(const float *qkv_dev, const float *rop
 int bitnet_hip_attention_prefill_flags_dev(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, size_t n_heads,
                                            size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t seq_len, void *workspace, size_t workspace_bytes,
                                            void *out, int flags, void *stream);
+/* Continuing a LIVE sequence: seq_len new tokens at absolute positions past_len .. past_len + seq_len - 1 over caches that already hold
+ * positions 0 .. past_len - 1 (filled by any mix of bitnet_hip_attention_prefill*_dev, the decode attention and earlier calls of this
+ * operator).  The reference's attention takes seq_len queries over past_len + seq_len keys from its cache, create_causal_mask(q_len,
+ * k_len) hiding the keys beyond past_len + i from query i (T:455-470, T:704-719; cache append T:1171-1202).  qkv_dev: [seq_len,
+ * n_heads*D + 2*n_kv*D], the raw projections of the NEW tokens.  The call applies RoPE to q and k at the absolute positions, appends
+ * the new k, v to the caches (exact f32, or rounded once to f16) and computes causal GQA attention of each new query over keys 0 .. its
+ * own position; out_dev: [seq_len, n_heads*D].  flags: BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16 as above.  past_len may be
+ * ANY value in [0, max_pos - seq_len] (not only a multiple of 64), seq_len >= 1, head_dim 128; past_len + seq_len > max_pos fails with
+ * "KV cache overflow".  Cache slots at positions >= past_len are never read as keys (they may hold what a longer, rewound sequence left
+ * there) and slots < past_len are not written.  Every call re-reads the past from the cache: O(past_len) bytes on top of the attention.
+ * The workspace size is 0 for invalid sizes and non-decreasing in both lengths; the call is asynchronous on `stream`. */
+size_t bitnet_hip_attention_extend_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t past_len, size_t seq_len);
+int bitnet_hip_attention_extend_dev(const float *qkv_dev, const float *rope_sin_dev, const float *rope_cos_dev,
+                                    void *kcache_dev, void *vcache_dev, size_t n_heads, size_t n_kv_heads, size_t head_dim,
+                                    size_t max_pos, size_t past_len, size_t seq_len, void *workspace_dev, size_t workspace_bytes,
+                                    void *out_dev, int flags, void *stream);
 /* bitnet_hip_gemv_attn_merge_dev (short contexts) with the QAct outputs of gemv_q_dev */
 int bitnet_hip_gemv_attn_merge_q_dev(bitnet_hip_weights_t w, const float *attn_scratch_dev, size_t n_heads,
                                      size_t n_kv_heads, size_t max_pos, const int32_t *pos_dev, float *y_dev,

@@ -277,11 +277,16 @@ def test_prefill_extend_then_decode_matches_oracle(pkg, oracle, synth, cfgd, fmt
     for a, b in AB:
         prompt = synth.prompt(a + b, cfg.vocab)
         seq, o_logits, _ = oracle_walk(oracle, om, prompt, 4)  # the token behind the prompt + 3 greedy steps
-        # digits = 4 once, for the layer loop without the f16 hand-over (f32 attention rows): QK256 only -- the block-scaled format's row-by-row
-        # fallback at 3 / 4 digits leaves a KV cache the decode steps disagree with from about 100 prompt rows on, with prefill() alone as well
-        for digits in ((2, 4) if (a, b) == (70, 37) and fmt == "qk256" else (2,)):
+        # digits = 4 once, for the layer loop without the f16 hand-over (f32 attention rows)
+        for digits in ((2, 4) if (a, b) == (70, 37) else (2,)):
             dec.reset()
-            dec.feed(prompt)
+            # the block-scaled format at 4 digits: where the oracle's two best logits behind the prompt lie closer than one f16 rounding of their
+            # value (2^-11: the tied head multiplies f16 operands), the pick is not decidable and that ONE pick is forced to the oracle's, so that
+            # the steps compare one sequence.  SMALL at 107 rows: 73.09796 / 73.09398, 5.4e-5 apart; the 2-digit chain picks the oracle's token,
+            # the 3- / 4-digit planes the other one, on caches that agree with float64 slot by slot (EXPERIMENTS 12.3)
+            top = np.sort(o_logits[0])[-2:]
+            tie = fmt == "i2s" and digits == 4 and top[1] - top[0] <= 2.0 ** -11 * abs(top[1])
+            dec.feed(seq[:a + b + 1] if tie else prompt)
             if a:
                 dec.prefill(a, with_logits=False, digits=digits)
                 assert dec.position() == a

@@ -468,3 +468,71 @@ def test_wave_per_row_quantiser_carries_the_documented_integer(hip, torch_, K):
         outs.append(got)
     assert np.array_equal(outs[0], outs[1])  # the two digit forms carry the same integer
     hip.weights_free(h)
+
+
+GUARD = 64  # NaN rows behind the m output rows: beyond every token tile the launch pads m to (32 / 64-token workgroups)
+
+
+@pytest.mark.parametrize("f16_scales", [True, False], ids=["f16-exact scales", "f32 scales"])
+@pytest.mark.parametrize("k", [512, 1024])
+def test_block32_scaled_gemm_fusions_beyond_100_rows(hip, oracle, torch_, k, f16_scales):
+    """32-element block scales at 3 and 4 digits as the decoder launches them and test_ternary_scaled_gemm (m <= 70, no fusion) does not:
+    m in {96, 107, 128, 130, 256} (several 16- / 32-token wave tiles, ragged last workgroups), the LayerNorm prologue, the in-place
+    residual, a weights_concat handle, plain (q | k | v) and interleave16 with FUSE_SILU_MUL (gate | up).  f16-exact scales run
+    k_gemm_mfma<NDIG, TT32, 3, 2, 1> (the K = 32 form: scale_mode 3), others the masked K = 64 form on row-major f32 scales (scale_mode 2).
+    Against oracle.i2s_matmul on the oracle's LayerNorm-ed rows, 2e-5 * max|want| + 1e-6 (this file's tolerance for the format); the output
+    buffers carry NaN guard rows behind row m, which must stay NaN."""
+    rng = np.random.default_rng(32 + k + (1 if f16_scales else 0))
+    n, M, block = 384, 256, 32
+
+    def matrix():
+        codes = rng.choice(np.array([0, 1, 3], np.uint8), size=(n, k), p=[0.5, 0.25, 0.25])
+        packed = (codes[:, 0::4] | codes[:, 1::4] << 2 | codes[:, 2::4] << 4 | codes[:, 3::4] << 6).astype(np.uint8)
+        scales = (2.0 / ((rng.permutation(n * (k // block)) % 100) + 1)).astype(np.float32)
+        if f16_scales:
+            scales = scales.astype(np.float16).astype(np.float32)
+        return packed.reshape(-1), scales, hip.weights_upload_i2s(packed.reshape(-1), scales, n, k, block)
+
+    pa, sa, ha = matrix()
+    pb, sb, hb = matrix()
+    hc, hg = hip.weights_concat([ha, hb]), hip.weights_concat([ha, hb], interleave16=True)
+    x = (rng.normal(0.2, 1.0, (M, k)) * np.exp(rng.uniform(-2, 2, (M, 1)))).astype(np.float32)  # rows of very different magnitude
+    g = (rng.uniform(0.5, 1.5, k) / (0.181 * np.sqrt(k))).astype(np.float32)                      # synth.make_layer's gamma for this format
+    res = rng.normal(0, 1, (M, n)).astype(np.float32)
+    xn = np.stack([oracle.layernorm(x[i], g, 1e-5) for i in range(M)])
+    ya = oracle.i2s_matmul(xn.reshape(-1), pa, sa, M, n, k, block).reshape(M, n)
+    yb = oracle.i2s_matmul(xn.reshape(-1), pb, sb, M, n, k, block).reshape(M, n)
+    gd, xd = torch_.from_numpy(g).cuda(), torch_.from_numpy(x).cuda()
+    mode = 3 if f16_scales else 2
+
+    def launch(h, m, out_cols, digits, init=None, **kw):
+        wsb = hip.matmul_workspace_bytes(m, k, digits)
+        ws = torch_.empty(wsb, dtype=torch_.uint8, device="cuda")
+        y = torch_.full((m + GUARD, out_cols), float("nan"), device="cuda")
+        if init is not None:
+            y[:m] = torch_.from_numpy(init[:m]).cuda()
+        if kw.pop("in_place", False):
+            kw["residual"] = y
+        hip.matmul_fused_dev(h, xd[:m].contiguous(), y, m, ws, wsb, digits=digits, ln_gamma=gd, ln_eps=1e-5, **kw)
+        torch_.cuda.synchronize()
+        t = hip.matmul_last_tile()
+        assert t["digits"] == digits and t["scale_mode"] == mode and t["wave_tokens"] == (32 if digits == 3 else 16), t
+        out = y.cpu().numpy()
+        assert np.isnan(out[m:]).all(), ("a guard row behind the output was written", m, digits, sorted(kw))
+        return out[:m]
+
+    def close(got, want, what):
+        d = float(np.max(np.abs(got - want)))
+        tol = 2e-5 * float(np.max(np.abs(want))) + 1e-6
+        print(f"block32 k={k} f16_scales={f16_scales} {what}: max|diff| {d:.3e} of tol {tol:.3e}")
+        assert not np.isnan(got).any() and d <= tol, (what, d, tol)
+
+    for m in (96, 107, 128, 130, 256):
+        for digits in (3, 4):
+            close(launch(ha, m, n, digits), ya[:m], (m, digits, "LayerNorm"))
+            close(launch(ha, m, n, digits, init=res, in_place=True), ya[:m] + res[:m], (m, digits, "LayerNorm + in-place residual"))
+            close(launch(hc, m, 2 * n, digits), np.concatenate([ya[:m], yb[:m]], axis=1), (m, digits, "LayerNorm, concatenated handle"))
+            want = (ya[:m] / (1 + np.exp(-ya[:m].astype(np.float64)))).astype(np.float32) * yb[:m]
+            close(launch(hg, m, n, digits, flags=1), want, (m, digits, "LayerNorm, interleave16 + silu * mul"))
+    for h in (hc, hg, ha, hb):
+        hip.weights_free(h)

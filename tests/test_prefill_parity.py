@@ -126,7 +126,7 @@ def test_prefill_then_decode_matches_oracle(pkg, oracle, synth, cfgd, n_prompt, 
     if fmt == "qk256":
         layers = [synth.make_layer(cfg, l) for l in range(cfg.n_layers)]
         olayers = layers
-    else:  # ternary codes + 32-element block scales: the matmuls fall back to the row-by-row GEMV inside the same entry point
+    else:  # ternary codes + 32-element block scales (f16 values, cols % 256 == 0): the tiled matmul's K = 32 form, k_gemm_mfma<NDIG, TT32, 3, 2, 1>
         layers = [synth.make_layer(cfg, l, fmt="i2s", block=32) for l in range(cfg.n_layers)]
         tmap = np.array([0, 1, 0, -1], np.float32)
         olayers = []

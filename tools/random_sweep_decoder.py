@@ -1,11 +1,16 @@
 """Developer tool (GPU box): the whole host decoder (embedding -> layers -> logits -> greedy token) on random small model
 configurations, both storage formats, random prompt lengths, prefill or step-by-step prompt, f32 / f16 KV cache, against the oracle's
-restated reference transformer (teacher-forced on the oracle's greedy tokens): logits cosine and greedy tokens.
+restated reference transformer (teacher-forced on the oracle's greedy tokens): logits cosine and greedy tokens; and the KV cache the case
+leaves, read back (tests/kv_read.py) against the float64 forward (tests/model_ref.py): every row within 4 u_l (+ 2^-11 with an f16 cache)
+of the f64 K / V row, u_l the f16-activation class model's distance in that layer; every slot beyond the sequence finite
+(tests/test_decoder_state_gpu.py, checks (a) and (b)).
 python tools/random_sweep_decoder.py [n] [seed]"""
 import importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import kv_read, model_ref  # noqa: E402
 pkg = importlib.import_module("bitnet-rs_amd")
 synth = importlib.import_module("bitnet-rs_amd.synth")
 from oracle import oracle  # noqa: E402
@@ -13,7 +18,7 @@ hip = pkg.load(); hip.init(0)
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 12
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 4)
 cos = lambda a, b: float(np.dot(a.astype(np.float64), b.astype(np.float64)) / (np.linalg.norm(a.astype(np.float64)) * np.linalg.norm(b.astype(np.float64)) + 1e-300))
-bad = 0
+bad, worst_ratio, worst_cos = 0, 0.0, 1.0
 for case in range(n_cases):
     hidden = int(rng.choice([512, 1024, 1536]))
     n_heads = hidden // 128
@@ -77,14 +82,28 @@ for case in range(n_cases):
                 gap_note = f"oracle top-2 gap {float(top[1] - top[0]):.3g} of max |logit| {float(np.max(np.abs(o_logits[p]))):.3g}; max |device - oracle| {float(np.max(np.abs(lg - o_logits[p]))):.3g}"
         floor = 0.9995 if kv16 or use_prefill else 0.9999
         same = picks_equal
-        if worst < floor:
+        # the cache the case leaves: positions [0, filled) against float64, everything beyond finite (a fresh decoder)
+        filled = n_prompt + n_new - 1
+        dense = [model_ref.dense_weights(cfg, w, fmt) for w in layers]
+        rope = oracle.rope_tables(cfg.head_dim, cfg.max_pos, cfg.rope_theta)
+        ref = model_ref.forward(cfg, dense, glob, seq[:filled], *rope)
+        u = model_ref.yardstick(ref, model_ref.forward(cfg, dense, glob, seq[:filled], *rope, rnd=model_ref.f16))
+        ratio, cache_ok = 0.0, dec.position() == filled
+        for l in range(cfg.n_layers):
+            k, v = kv_read.caches(dec, cfg, l, kv16)
+            rel = max(float(model_ref.kv_rel(k[:filled], ref.K[l]).max()), float(model_ref.kv_rel(v[:filled], ref.V[l]).max()))
+            ratio = max(ratio, rel / u[l])
+            cache_ok = cache_ok and rel <= 4.0 * u[l] + (2.0 ** -11 if kv16 else 0.0)
+            cache_ok = cache_ok and bool(np.isfinite(k[filled:].astype(np.float64)).all() and np.isfinite(v[filled:].astype(np.float64)).all())
+        worst_ratio, worst_cos = max(worst_ratio, ratio), min(worst_cos, worst)
+        if worst < floor or not cache_ok:
             bad += 1
-            print("FAIL", tag, "worst cosine", worst, "tokens equal" if same else "tokens differ", flush=True)
+            print("FAIL", tag, "worst cosine", worst, "worst rel / u_l", round(ratio, 3), "cache ok" if cache_ok else "CACHE off", "tokens equal" if same else "tokens differ", flush=True)
         elif not same:
             print("note ", tag, "worst cosine", round(worst, 7), "greedy pick differs from the oracle's:", gap_note, flush=True)
     except pkg.BitNetHipError as e:
         bad += 1
         print("FAIL", tag, repr(e), flush=True)
     dec.close()
-print(f"{n_cases - bad}/{n_cases} configurations agree", flush=True)
+print(f"{n_cases - bad}/{n_cases} configurations agree; worst logits cosine {worst_cos:.7f}, worst cache rel / u_l {worst_ratio:.3f} (gate 4)", flush=True)
 sys.exit(1 if bad else 0)

@@ -477,6 +477,13 @@ int bitnet_hip_matmul_kernel_dev(bitnet_hip_weights_t h, const float *x_dev, flo
     return matmul_dev_kernel(h, x_dev, y_dev, m, kernel, stream);
 }
 
+// FUSE_SILU_MUL of every fused matmul / GEMV entry: the rows must be (gate tile, up tile) pairs, and there is no residual to add
+static int check_silu_pairing(const Weights &w, bool silu_mul, const float *residual_dev) {
+    if (silu_mul && (!w.paired || residual_dev))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
+    return BITNET_HIP_OK;
+}
+
 size_t bitnet_hip_matmul_workspace_bytes(size_t m, size_t k, int digits) {
     return gemm_workspace_bytes(m, k, digits >= 2 && digits <= 4 ? digits : 4);
 }
@@ -502,9 +509,7 @@ int bitnet_hip_matmul_fused_dev(bitnet_hip_weights_t h, const float *x_dev, floa
     fu.fp6_expand = (flags & BITNET_HIP_FUSE_FP6_EXPAND) != 0;
     if (fu.fp6_form && (fu.int8_form || digits != 2 || !gemm_fp6_supported(*w)))
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_FP6_DIGITS needs digits = 2, an unscaled matrix with a code map in -2..2, and no FUSE_INT8_DIGITS");
-    if (fu.silu_mul && (!w->paired || residual_dev))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT,
-                         "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
+    if (int rc = check_silu_pairing(*w, fu.silu_mul, residual_dev)) return rc;
     if ((fu.x_f16 || fu.y_f16) && (!gemm_supported(*w) || (fu.y_f16 && (!fu.silu_mul || (w->rows / 2) % 4 != 0)) || (fu.x_f16 && ln_gamma_dev)))
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_X_F16 (no LayerNorm) / FUSE_Y_F16 (with FUSE_SILU_MUL) need a matrix the tiled matmul takes");
     if (!gemm_supported(*w)) return run_gemv(*w, x_dev, y_dev, m, fu, (hipStream_t)stream);  // 32-element block scales: row by row
@@ -561,20 +566,20 @@ int bitnet_hip_rows_to_f16_dev(const float *x_dev, const float *gamma_dev, size_
     BH_GUARD_END
 }
 
-int bitnet_hip_matmul_f16_dev(bitnet_hip_weights_t h, const void *xh_dev, size_t m, const float *stats_in_dev, size_t n_stats,
-                              const float *ln_gamma_dev, float ln_eps, float *y_dev, const float *residual_dev, int flags, void *yh_dev,
-                              const float *gamma_out_dev, float *stats_out_dev, void *stream) {
-    BH_GUARD_BEGIN
-    const WeightsRef w = lookup(h);
+// The front that bitnet_hip_matmul_f16_dev and bitnet_hip_matmul_qb32_dev share: the handle, the pointers, whether the matrix takes the form
+// (`supported`; `takes` words the refusal), the LayerNorm binding; then `io` filled from the arguments.  `entry` names the caller in the messages.
+// Each entry handles its own flag bits next, then check_silu_pairing: the checks fire in the order they always did.
+static int matmul_chain_front(const char *entry, bool (*supported)(const Weights &), const char *takes, bitnet_hip_weights_t h, const void *x_dev, size_t m,
+                              const float *stats_in_dev, size_t n_stats, const float *ln_gamma_dev, float ln_eps, float *y_dev, const float *residual_dev,
+                              int flags, void *yh_dev, const float *gamma_out_dev, float *stats_out_dev, WeightsRef &w, GemmF16Io &io) {
+    w = lookup(h);
     if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
-    if (!xh_dev || (!y_dev && !yh_dev)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to matmul_f16_dev");
+    if (!x_dev || (!y_dev && !yh_dev)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to %s", entry);
     if (m == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions must be > 0: m=0");
-    if (!gemm_f16_chain_supported(*w))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "matmul_f16_dev: this matrix does not take the f16 chain (rows %% 256, cols %% 256, code map in -2..2, f16 block scales)");
+    if (!supported(*w)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: %s", entry, takes);
     if ((ln_gamma_dev != nullptr) != (stats_in_dev != nullptr) || (ln_gamma_dev && (!w->ln_g || w->ln_gamma_bound != ln_gamma_dev || n_stats == 0)))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "matmul_f16_dev: LayerNorm needs the bound gamma (bitnet_hip_weights_bind_ln) and its statistics partials");
-    GemmF16Io io;
-    io.xh = xh_dev;
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: LayerNorm needs the bound gamma (bitnet_hip_weights_bind_ln) and its statistics partials", entry);
+    io.xh = x_dev;
     io.stats_in = stats_in_dev;
     io.n_stats = (int)n_stats;
     io.ln_eps = ln_eps;
@@ -584,14 +589,25 @@ int bitnet_hip_matmul_f16_dev(bitnet_hip_weights_t h, const void *xh_dev, size_t
     io.yh = yh_dev;
     io.gamma_out = gamma_out_dev;
     io.stats_out = stats_out_dev;
+    return BITNET_HIP_OK;
+}
+
+int bitnet_hip_matmul_f16_dev(bitnet_hip_weights_t h, const void *xh_dev, size_t m, const float *stats_in_dev, size_t n_stats,
+                              const float *ln_gamma_dev, float ln_eps, float *y_dev, const float *residual_dev, int flags, void *yh_dev,
+                              const float *gamma_out_dev, float *stats_out_dev, void *stream) {
+    BH_GUARD_BEGIN
+    WeightsRef w;
+    GemmF16Io io;
+    int rc = matmul_chain_front("matmul_f16_dev", gemm_f16_chain_supported, "this matrix does not take the f16 chain (rows % 256, cols % 256, code map in -2..2, f16 block scales)",
+                                h, xh_dev, m, stats_in_dev, n_stats, ln_gamma_dev, ln_eps, y_dev, residual_dev, flags, yh_dev, gamma_out_dev, stats_out_dev, w, io);
+    if (rc) return rc;
     if (flags & BITNET_HIP_FUSE_YH_QB32) {  // yh_dev is a QB32 buffer (bitnet_hip_qb32_bytes(m, rows)): the next fp6-form matmul's input
         if (!yh_dev || io.silu_mul || w->rows % 256 != 0)
             return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_YH_QB32 needs a QB32 buffer in yh_dev, rows %% 256 == 0 and no FUSE_SILU_MUL");
         io.qb_out = yh_dev;
         io.yh = nullptr;
     }
-    if (io.silu_mul && (!w->paired || residual_dev))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
+    if ((rc = check_silu_pairing(*w, io.silu_mul, residual_dev)) != BITNET_HIP_OK) return rc;
     hipError_t e = launch_gemm_f16_chain(*w, io, m, (hipStream_t)stream);
     if (e == hipErrorInvalidValue && io.qb_out)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_YH_QB32: this launch does not run 64-token tiles (too few rows for the QB32 hand-over)");
@@ -623,28 +639,13 @@ int bitnet_hip_matmul_qb32_dev(bitnet_hip_weights_t h, const void *qb_dev, size_
                                const float *ln_gamma_dev, float ln_eps, float *y_dev, const float *residual_dev, int flags, void *yh_dev,
                                const float *gamma_out_dev, float *stats_out_dev, void *stream) {
     BH_GUARD_BEGIN
-    const WeightsRef w = lookup(h);
-    if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
-    if (!qb_dev || (!y_dev && !yh_dev)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to matmul_qb32_dev");
-    if (m == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions must be > 0: m=0");
-    if (!gemm_qb32_supported(*w))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "matmul_qb32_dev: needs an unscaled matrix with a code map in -2..2, rows %% 256 == 0, cols %% 256 == 0");
-    if ((ln_gamma_dev != nullptr) != (stats_in_dev != nullptr) || (ln_gamma_dev && (!w->ln_g || w->ln_gamma_bound != ln_gamma_dev || n_stats == 0)))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "matmul_qb32_dev: LayerNorm needs the bound gamma (bitnet_hip_weights_bind_ln) and its statistics partials");
-    if (flags & ~BITNET_HIP_FUSE_SILU_MUL) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "matmul_qb32_dev: unknown flag bits 0x%x", flags);
+    WeightsRef w;
     GemmF16Io io;
-    io.xh = qb_dev;
-    io.stats_in = stats_in_dev;
-    io.n_stats = (int)n_stats;
-    io.ln_eps = ln_eps;
-    io.y = y_dev;
-    io.residual = residual_dev;
-    io.silu_mul = (flags & BITNET_HIP_FUSE_SILU_MUL) != 0;
-    io.yh = yh_dev;
-    io.gamma_out = gamma_out_dev;
-    io.stats_out = stats_out_dev;
-    if (io.silu_mul && (!w->paired || residual_dev))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
+    int rc = matmul_chain_front("matmul_qb32_dev", gemm_qb32_supported, "needs an unscaled matrix with a code map in -2..2, rows % 256 == 0, cols % 256 == 0",
+                                h, qb_dev, m, stats_in_dev, n_stats, ln_gamma_dev, ln_eps, y_dev, residual_dev, flags, yh_dev, gamma_out_dev, stats_out_dev, w, io);
+    if (rc) return rc;
+    if (flags & ~BITNET_HIP_FUSE_SILU_MUL) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "matmul_qb32_dev: unknown flag bits 0x%x", flags);
+    if ((rc = check_silu_pairing(*w, io.silu_mul, residual_dev)) != BITNET_HIP_OK) return rc;
     if (gemm_fp4_resident_enabled() && !w->tiles4) {
         const hipError_t ei = ensure_fp4_image(*w, (hipStream_t)stream);
         if (ei != hipSuccess) return set_error(BITNET_HIP_ERR_GPU, "building the resident fp4 weight image failed: %s", hipGetErrorString(ei));
@@ -681,9 +682,7 @@ int bitnet_hip_gemv_fused_dev(bitnet_hip_weights_t h, const float *x_dev, float 
     fu.ln_eps = ln_eps;
     fu.residual = residual_dev;
     fu.silu_mul = (flags & BITNET_HIP_FUSE_SILU_MUL) != 0;
-    if (fu.silu_mul && (!w->paired || residual_dev))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT,
-                         "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
+    if (int rc = check_silu_pairing(*w, fu.silu_mul, residual_dev)) return rc;
     return run_gemv(*w, x_dev, y_dev, m, fu, (hipStream_t)stream);
     BH_GUARD_END
 }
@@ -1131,76 +1130,67 @@ static int check_prefill_args(const void *a, const void *b, const void *rs, cons
     return BITNET_HIP_OK;
 }
 
+// One body for the four whole-prompt attention entries.  q: n_q query rows (stride ld_q) whose 64-row blocks sit at q_block_pos (null: the prompt's own
+// rows in order), kv: the n_ctx context rows (stride ld_kv).  `sharded`: the caller chose rows and strides itself, so they are checked.  flags:
+// BITNET_HIP_ATTN_CACHE_F16 | _OUT_F16; only attention_prefill_flags_dev takes the word from its caller and has unknown bits refused (check_flags).
+static int attention_prefill_body(const float *q, size_t ld_q, const int32_t *q_block_pos, size_t n_q, const float *kv, size_t ld_kv, size_t n_ctx,
+                                  const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, size_t n_heads, size_t n_kv_heads, size_t head_dim,
+                                  size_t max_pos, void *workspace, size_t workspace_bytes, void *out, int flags, bool check_flags, bool sharded, void *stream) {
+    BH_GUARD_BEGIN
+    int rc = check_prefill_args(q, kv, rope_sin, rope_cos, kcache, vcache, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, n_ctx);
+    if (rc) return rc;
+    if (sharded) {
+        if (n_q == 0 || !q_block_pos) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_sharded: n_q and q_block_pos must be given");
+        if (ld_q < n_heads * head_dim || ld_kv < 2 * n_kv_heads * head_dim)
+            return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_sharded: row strides too small (ld_q %zu, ld_kv %zu)", ld_q, ld_kv);
+    }
+    if (check_flags && (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_flags_dev: unknown flag bits 0x%x", flags);
+    const size_t need = attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_q, (int)n_ctx);
+    if (workspace_bytes < need)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
+    BH_HIP_TRY(launch_attn_prefill(q, (int)ld_q, q_block_pos, (int)n_q, kv, (int)ld_kv, (int)n_ctx, rope_sin, rope_cos, static_cast<float *>(kcache),
+                                   static_cast<float *>(vcache), (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, workspace, workspace_bytes,
+                                   static_cast<float *>(out), (hipStream_t)stream, 0, 0, flags));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+// ... on a prompt's own q|k|v rows [seq_len][(n_heads + 2 n_kv_heads) head_dim]
+static int attention_prefill_whole(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, size_t n_heads, size_t n_kv_heads,
+                                   size_t head_dim, size_t max_pos, size_t seq_len, void *workspace, size_t workspace_bytes, void *out, int flags, bool check_flags,
+                                   void *stream) {
+    const size_t ld = (n_heads + 2 * n_kv_heads) * head_dim;
+    return attention_prefill_body(qkv, ld, nullptr, seq_len, qkv ? qkv + n_heads * head_dim : nullptr, ld, seq_len, rope_sin, rope_cos, kcache, vcache, n_heads,
+                                  n_kv_heads, head_dim, max_pos, workspace, workspace_bytes, out, flags, check_flags, false, stream);
+}
+
 int bitnet_hip_attention_prefill_dev(const float *qkv, const float *rope_sin, const float *rope_cos, float *kcache,
                                      float *vcache, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,
                                      size_t seq_len, void *workspace, size_t workspace_bytes, float *out, void *stream) {
-    BH_GUARD_BEGIN
-    int rc = check_prefill_args(qkv, qkv, rope_sin, rope_cos, kcache, vcache, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, seq_len);
-    if (rc) return rc;
-    const size_t need = attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)seq_len, (int)seq_len);
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
-    const int ld = (int)((n_heads + 2 * n_kv_heads) * head_dim);
-    BH_HIP_TRY(launch_attn_prefill(qkv, ld, nullptr, (int)seq_len, qkv + n_heads * head_dim, ld, (int)seq_len, rope_sin, rope_cos, kcache,
-                                   vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, workspace, workspace_bytes, out,
-                                   (hipStream_t)stream));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    return attention_prefill_whole(qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv_heads, head_dim, max_pos, seq_len, workspace, workspace_bytes, out, 0, false,
+                                   stream);
 }
 
 int bitnet_hip_attention_prefill_sharded_dev(const float *q, size_t ld_q, const int32_t *q_block_pos, size_t n_q, const float *kv,
                                              size_t ld_kv, size_t n_ctx, const float *rope_sin, const float *rope_cos, float *kcache,
                                              float *vcache, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,
                                              void *workspace, size_t workspace_bytes, float *out, void *stream) {
-    BH_GUARD_BEGIN
-    int rc = check_prefill_args(q, kv, rope_sin, rope_cos, kcache, vcache, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, n_ctx);
-    if (rc) return rc;
-    if (n_q == 0 || !q_block_pos) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_sharded: n_q and q_block_pos must be given");
-    if (ld_q < n_heads * head_dim || ld_kv < 2 * n_kv_heads * head_dim)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_sharded: row strides too small (ld_q %zu, ld_kv %zu)", ld_q, ld_kv);
-    const size_t need = attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_q, (int)n_ctx);
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
-    BH_HIP_TRY(launch_attn_prefill(q, (int)ld_q, q_block_pos, (int)n_q, kv, (int)ld_kv, (int)n_ctx, rope_sin, rope_cos, kcache, vcache,
-                                   (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, workspace, workspace_bytes, out,
-                                   (hipStream_t)stream));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    return attention_prefill_body(q, ld_q, q_block_pos, n_q, kv, ld_kv, n_ctx, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv_heads, head_dim, max_pos, workspace,
+                                  workspace_bytes, out, 0, false, true, stream);
 }
 
 int bitnet_hip_attention_prefill_kv16_dev(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache_f16, void *vcache_f16,
                                           size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t seq_len, void *workspace,
                                           size_t workspace_bytes, float *out, void *stream) {
-    BH_GUARD_BEGIN
-    int rc = check_prefill_args(qkv, qkv, rope_sin, rope_cos, kcache_f16, vcache_f16, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, seq_len);
-    if (rc) return rc;
-    const size_t need = attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)seq_len, (int)seq_len);
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
-    const int ld = (int)((n_heads + 2 * n_kv_heads) * head_dim);
-    BH_HIP_TRY(launch_attn_prefill(qkv, ld, nullptr, (int)seq_len, qkv + n_heads * head_dim, ld, (int)seq_len, rope_sin, rope_cos, static_cast<float *>(kcache_f16),
-                                   static_cast<float *>(vcache_f16), (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, workspace, workspace_bytes, out,
-                                   (hipStream_t)stream, 0, 0, 1));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    return attention_prefill_whole(qkv, rope_sin, rope_cos, kcache_f16, vcache_f16, n_heads, n_kv_heads, head_dim, max_pos, seq_len, workspace, workspace_bytes, out,
+                                   BITNET_HIP_ATTN_CACHE_F16, false, stream);
 }
 
 int bitnet_hip_attention_prefill_flags_dev(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, size_t n_heads,
                                            size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t seq_len, void *workspace, size_t workspace_bytes,
                                            void *out, int flags, void *stream) {
-    BH_GUARD_BEGIN
-    int rc = check_prefill_args(qkv, qkv, rope_sin, rope_cos, kcache, vcache, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, seq_len);
-    if (rc) return rc;
-    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_flags_dev: unknown flag bits 0x%x", flags);
-    const size_t need = attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)seq_len, (int)seq_len);
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
-    const int ld = (int)((n_heads + 2 * n_kv_heads) * head_dim);
-    BH_HIP_TRY(launch_attn_prefill(qkv, ld, nullptr, (int)seq_len, qkv + n_heads * head_dim, ld, (int)seq_len, rope_sin, rope_cos, static_cast<float *>(kcache),
-                                   static_cast<float *>(vcache), (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, workspace, workspace_bytes,
-                                   static_cast<float *>(out), (hipStream_t)stream, 0, 0, flags));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    return attention_prefill_whole(qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv_heads, head_dim, max_pos, seq_len, workspace, workspace_bytes, out, flags, true,
+                                   stream);
 }
 
 size_t bitnet_hip_attention_extend_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t past_len, size_t seq_len) {

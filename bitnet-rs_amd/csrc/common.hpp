@@ -42,6 +42,12 @@ inline int set_error(int code, const char *fmt, ...) {
 
 inline size_t div_ceil(size_t a, size_t b) { return (a + b - 1) / b; }
 
+// Raises hipFuncAttributeMaxDynamicSharedMemorySize of `kernel` to `bytes`, once per kernel (kernels_mfma.hip).  Launchers call it before the launch that
+// needs more than the default 64 KiB; entry points may run concurrently (Send + Sync), so the record of raised kernels is guarded.
+hipError_t raise_dynamic_lds(const void *kernel, int bytes);
+template <class... A>
+inline hipError_t raise_dynamic_lds(void (*kernel)(A...), int bytes) { return raise_dynamic_lds(reinterpret_cast<const void *>(kernel), bytes); }
+
 // Code -> value maps used by the reference (SURVEY.md 8a "code-map summary"),
 // packed as four int8 in one u32 (byte c = value of code c).
 constexpr uint32_t pack_lut(int v0, int v1, int v2, int v3) {

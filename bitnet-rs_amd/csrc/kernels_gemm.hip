@@ -29,9 +29,6 @@
 //                               int8 planes); resident fp4 image (k_retile_fp4); fp6w = 2 x 2 wave arrangement, LDS-DMA staging, buffer-loaded weights
 //   k_quant_rows_w              the 2-digit quantiser with one wave per row (long launches of rows <= 2560 columns)
 //   QB32 (k_rows_to_qb32, qb32_pack_unit, k_gemm_fp6<.., EPI = 1>)   producer-quantised block-scaled rows: no quantiser launch (opt-in)
-#include <mutex>
-#include <unordered_set>
-
 #include "common.hpp"
 
 namespace bitnet_hip {
@@ -2037,6 +2034,7 @@ __global__ __launch_bounds__(256) void k_rows_to_f16(const float *__restrict__ x
 // ---- host side ---------------------------------------------------------------------------------
 constexpr size_t kGemmCUs = 256;
 thread_local GemmTileChoice g_last_gemm_tile;  // what the last launch on this thread ran (bitnet_hip_matmul_last_tile)
+static size_t gemm_row_blocks(const Weights &w) { return div_ceil(div_ceil(w.rows, 16), 16); }  // 256-row workgroups over the 16-row tiles
 // Token tiles (of 16) per wave of the 4-wave 2-digit / f16 forms: 4 (64 tokens) unless
 //  (a) the grid would not cover the chip twice (a short prompt, or one rank's share of a token-parallel prefill: 1024 rows x 2560
 //      output rows are 160 such tiles for 512 slots): narrower tiles until it does;
@@ -2108,6 +2106,35 @@ size_t gemm_workspace_bytes(size_t m, size_t cols, int ndig) {
     return m_pad * plane_bytes + div_ceil(m_pad * sizeof(float), 256) * 256 + 256;
 }
 
+// ---- what the launchers below share: the argument fill, the row quantiser, the kernel tables, the launch itself ----
+// What every form takes from the matrix; every other field starts out null / zero and each launcher states its own.
+static GemmArgs gemm_args(const Weights &w) {
+    GemmArgs a{};
+    a.tiles = w.tiles;
+    a.rows = (int)w.rows;
+    a.cols = (int)w.cols;
+    a.nblk = (int)div_ceil(w.cols, 256);
+    a.lut = w.lut;
+    return a;
+}
+// ... and what the chain's forms (launch_gemm_f16_chain, launch_gemm_qb32) take from their GemmF16Io: the producer's rows in `planes`, LayerNorm after
+// the product from the partials, the f32 / f16 outputs and the next partials
+static void gemm_args_chain(GemmArgs &a, const Weights &w, const GemmF16Io &io, size_t m, size_t m_pad) {
+    a.planes = static_cast<const int8_t *>(io.xh);
+    a.y = io.y;
+    a.m = (int)m;
+    a.residual = io.residual;
+    a.silu_mul = io.silu_mul ? 1 : 0;
+    a.stats_in = io.stats_in;
+    a.n_stats = io.n_stats;
+    a.stats_stride = (int)m_pad;
+    a.ln_eps = io.ln_eps;
+    a.ln_g = w.ln_g;
+    a.yh = static_cast<_Float16 *>(io.yh);
+    a.gamma_out = io.gamma_out;
+    a.stats_out = io.stats_out;
+}
+
 // 2 digits, rows of up to 2560 columns: the wave-per-row quantiser (both digit forms: the int8 planes and the fp6 form stay bit-identical)
 static bool quant_rows_w_applies(const QuantArgs &q) {
     static const int mode = [] { const char *e = getenv("BITNET_HIP_QUANT_W"); return e ? atoi(e) : 1; }();
@@ -2115,20 +2142,69 @@ static bool quant_rows_w_applies(const QuantArgs &q) {
     // (4096-token prompt 18.6 -> 18.4 ms with it, 512-token prompt 4.94 -> 5.08 ms: one box each)
     return mode != 0 && q.kp <= 2560 && q.m_pad % 4 == 0 && q.m_pad >= 2048;
 }
-static void launch_quant_rows_w(const QuantArgs &q, bool fp6, hipStream_t stream) {
-    if (fp6) {
-        hipLaunchKernelGGL(k_quant_rows_w<1>, dim3(q.m_pad / 4), dim3(256), (size_t)4 * (size_t)(q.kp / 32) * 80, stream, q);
-    } else {
-        hipLaunchKernelGGL(k_quant_rows_w<0>, dim3(q.m_pad / 4), dim3(256), 0, stream, q);
+// The row quantiser of the digit forms (fp6: the 2-digit integer as three base-32 fp6 digits): wave-per-row where that applies, else one workgroup
+// per row with 3 or 8 float4 per thread.
+static void launch_quant_rows(const QuantArgs &q, int ndig, bool fp6, hipStream_t stream) {
+    if (ndig == 2 && quant_rows_w_applies(q)) {
+        if (fp6) hipLaunchKernelGGL(k_quant_rows_w<1>, dim3(q.m_pad / 4), dim3(256), (size_t)4 * (size_t)(q.kp / 32) * 80, stream, q);
+        else hipLaunchKernelGGL(k_quant_rows_w<0>, dim3(q.m_pad / 4), dim3(256), 0, stream, q);
+        return;
     }
+    const bool nv3 = div_ceil((size_t)q.kp / 4, 256) <= 3;
+    void (*qk)(QuantArgs) = fp6         ? (nv3 ? k_quant_rows<2, 3, 1> : k_quant_rows<2, 8, 1>)
+                            : ndig == 2 ? (nv3 ? k_quant_rows<2, 3> : k_quant_rows<2, 8>)
+                            : ndig == 3 ? (nv3 ? k_quant_rows<3, 3> : k_quant_rows<3, 8>)
+                                        : (nv3 ? k_quant_rows<4, 3> : k_quant_rows<4, 8>);
+    // fp6, LDS: the row's integers (144 bytes per 32 columns) + its packed image
+    hipLaunchKernelGGL(qk, dim3(q.m_pad), dim3(256), fp6 ? (size_t)(q.kp / 32) * 144 + (size_t)(q.kp / 256) * 576 : 0, stream, q);
+}
+
+// Every instance of k_gemm_f16a<FMT, TTW, EPI, RT> the library holds, and no other (tests/test_isa_guard.py pins their registers by name).
+// FMT 1: f16 32-block scale tiles, 0: unscaled; EPI 0: behind the f16 row quantiser, 1: the chain's epilogue, 2: ... + QB32 rows out (64-token tiles
+// only); RT 5: the 320-row workgroup (64-token tiles of the chain only).  A combination that is not here does not exist: null.
+typedef void (*GemmKernelL)(GemmArgs, uint32_t);
+static GemmKernelL pick_f16a(int fmt, int ttw, int epi, bool rt5) {
+    static const struct { int fmt, ttw, epi, rt; GemmKernelL k; } table[] = {
+        {0, 1, 0, 4, k_gemm_f16a<0, 1, 0, 4>}, {0, 2, 0, 4, k_gemm_f16a<0, 2, 0, 4>}, {0, 4, 0, 4, k_gemm_f16a<0, 4, 0, 4>},
+        {1, 1, 0, 4, k_gemm_f16a<1, 1, 0, 4>}, {1, 2, 0, 4, k_gemm_f16a<1, 2, 0, 4>}, {1, 4, 0, 4, k_gemm_f16a<1, 4, 0, 4>},
+        {0, 1, 1, 4, k_gemm_f16a<0, 1, 1, 4>}, {0, 2, 1, 4, k_gemm_f16a<0, 2, 1, 4>}, {0, 4, 1, 4, k_gemm_f16a<0, 4, 1, 4>}, {0, 4, 1, 5, k_gemm_f16a<0, 4, 1, 5>},
+        {1, 1, 1, 4, k_gemm_f16a<1, 1, 1, 4>}, {1, 2, 1, 4, k_gemm_f16a<1, 2, 1, 4>}, {1, 4, 1, 4, k_gemm_f16a<1, 4, 1, 4>}, {1, 4, 1, 5, k_gemm_f16a<1, 4, 1, 5>},
+        {0, 4, 2, 4, k_gemm_f16a<0, 4, 2, 4>}, {0, 4, 2, 5, k_gemm_f16a<0, 4, 2, 5>},
+        {1, 4, 2, 4, k_gemm_f16a<1, 4, 2, 4>}, {1, 4, 2, 5, k_gemm_f16a<1, 4, 2, 5>},
+    };
+    for (const auto &r : table)
+        if (r.fmt == fmt && r.ttw == ttw && r.epi == epi && r.rt == (rt5 ? 5 : 4)) return r.k;
+    return nullptr;
+}
+// ... and of k_gemm_fp6<TTW, RT, RES, EPI>.  RES 1: the resident fp4 image, 0: the 2-bit tiles expanded in the K loop; EPI 1: QB32 rows in, the chain's
+// epilogue -- its 320-row form does not fit 256 registers (hipcc spills 80 bytes) and is not built.
+static GemmKernelL pick_fp6(int ttw, bool rt5, bool resident, int epi) {
+    static const struct { int ttw, rt, res, epi; GemmKernelL k; } table[] = {
+        {1, 4, 0, 0, k_gemm_fp6<1, 4, 0, 0>}, {2, 4, 0, 0, k_gemm_fp6<2, 4, 0, 0>}, {4, 4, 0, 0, k_gemm_fp6<4, 4, 0, 0>}, {4, 5, 0, 0, k_gemm_fp6<4, 5, 0, 0>},
+        {1, 4, 1, 0, k_gemm_fp6<1, 4, 1, 0>}, {2, 4, 1, 0, k_gemm_fp6<2, 4, 1, 0>}, {4, 4, 1, 0, k_gemm_fp6<4, 4, 1, 0>}, {4, 5, 1, 0, k_gemm_fp6<4, 5, 1, 0>},
+        {1, 4, 0, 1, k_gemm_fp6<1, 4, 0, 1>}, {2, 4, 0, 1, k_gemm_fp6<2, 4, 0, 1>}, {4, 4, 0, 1, k_gemm_fp6<4, 4, 0, 1>},
+        {1, 4, 1, 1, k_gemm_fp6<1, 4, 1, 1>}, {2, 4, 1, 1, k_gemm_fp6<2, 4, 1, 1>}, {4, 4, 1, 1, k_gemm_fp6<4, 4, 1, 1>},
+    };
+    for (const auto &r : table)
+        if (r.ttw == ttw && r.rt == (rt5 ? 5 : 4) && r.res == (resident ? 1 : 0) && r.epi == epi) return r.k;
+    return nullptr;
+}
+
+// How every form ends: the kernel's dynamic-LDS limit raised (once), the choice recorded for bitnet_hip_matmul_last_tile, the launch.
+// A null kernel is a combination the tables above do not hold.
+template <class... KA>
+static hipError_t gemm_fire(void (*k)(KA...), const GemmTileChoice &tile, dim3 grid, unsigned threads, size_t lds, hipStream_t stream, KA... args) {
+    if (!k) return hipErrorInvalidValue;
+    const hipError_t e = raise_dynamic_lds(k, 160 * 1024);
+    if (e != hipSuccess) return e;
+    g_last_gemm_tile = tile;
+    hipLaunchKernelGGL(k, grid, dim3(threads), lds, stream, args...);
+    return hipGetLastError();
 }
 
 template <int NDIG, int TTW>
 static hipError_t launch_gemm_t(const Weights &w, const QuantArgs &q, const GemmArgs &a, hipStream_t stream) {
-    const int nv = (int)div_ceil((size_t)q.kp / 4, 256);
-    void (*qk)(QuantArgs) = nv <= 3 ? k_quant_rows<NDIG, 3> : k_quant_rows<NDIG, 8>;
-    if (NDIG == 2 && quant_rows_w_applies(q)) launch_quant_rows_w(q, false, stream);
-    else hipLaunchKernelGGL(qk, dim3(q.m_pad), dim3(256), 0, stream, q);
+    launch_quant_rows(q, NDIG, false, stream);
     constexpr int TTWS = 2;  // scaled variant: narrower token tile (f32 accumulators take the registers)
     const bool k32 = a.stiles_h != nullptr;
     const bool bs32 = (a.wscale && w.block_size == 32) || k32;  // 32-block scales: one token tile per wave (registers)
@@ -2147,31 +2223,17 @@ static hipError_t launch_gemm_t(const Weights &w, const QuantArgs &q, const Gemm
         if (NDIG == 2 && !scaled_variant) {
             // few activation rows (a short prompt, or one rank's share of a token-parallel prefill: 1024 rows x 2560 output rows
             // is 160 of these tiles for 512 slots): narrower token tiles until the grid covers the chip
-            const size_t gx0 = div_ceil(div_ceil(w.rows, 16), 16);
             static const size_t cover = [] { const char *e = getenv("BITNET_HIP_I8_COVER"); return e ? (size_t)atoi(e) : 3 * kGemmCUs / 2; }();  // 384: swept 512 / 384 / 256 / 128 at 256 .. 2048 tokens, QK256 prompt -1 .. -3.5 % against 512
-            ttw = gemm_token_tiles(gx0, q.m_pad, true, cover);
+            ttw = gemm_token_tiles(gemm_row_blocks(w), q.m_pad, true, cover);
             if (ttw == 2) gk = k_gemm_mfma<2, 2, 0, 2, 1>;
             if (ttw == 1) gk = k_gemm_mfma<2, 1, 0, 2, 1>;
         }
     }
     const size_t lds = (size_t)cw * NDIG * ttw * 16 * (k32 ? kColStride : 256) * (scaled_variant ? 1 : 2) + (k32 ? (size_t)4 * cw * 4096 : 0);  // unscaled: double-buffered; K = 32: + tile staging
-    {
-        // once per kernel; entry points may run concurrently (Send + Sync), so the set is guarded like its twin in kernels_mfma.hip
-        static std::mutex raised_mu;
-        static std::unordered_set<const void *> raised;
-        std::lock_guard<std::mutex> lk(raised_mu);
-        if (!raised.count((const void *)gk)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            raised.insert((const void *)gk);
-        }
-    }
-    g_last_gemm_tile = GemmTileChoice{NDIG, 16 * ttw, 4 * cw, k32 ? 3 : !a.wscale ? 0 : bs32 ? 2 : 1};
-    const unsigned gx = (unsigned)div_ceil(div_ceil(w.rows, 16), 16), gy = (unsigned)(q.m_pad / (16 * cw * ttw));
+    const unsigned gx = (unsigned)gemm_row_blocks(w), gy = (unsigned)(q.m_pad / (16 * cw * ttw));
     GemmArgs aw = a;
     if (!scaled_variant) aw.wgroup = gemm_weight_group(gx, 256, w.cols, false);
-    hipLaunchKernelGGL(gk, dim3(gx, gy), dim3(256 * cw), lds, stream, aw);
-    return hipGetLastError();
+    return gemm_fire(gk, GemmTileChoice{NDIG, 16 * ttw, 4 * cw, k32 ? 3 : !a.wscale ? 0 : bs32 ? 2 : 1}, dim3(gx, gy), 256 * cw, lds, stream, aw);
 }
 
 // k_gemm_f16a builds (code value) x (block scale) in f16: only code maps whose four values are in -2 .. 2 (every map of the
@@ -2198,28 +2260,14 @@ static uint32_t lut_f16_hi(uint32_t lut) {
 // f16 activations on the f16 matrix cores (k_gemm_f16a): BitNet32-F16 at 2 digits; QK256 only on request (BITNET_HIP_GEMM_F16A=1:
 // measured 5-13 % slower than the int8 digit form there -- twice the expansion VALU for the same MFMA count)
 static hipError_t launch_gemm_f16(const Weights &w, const QuantArgs &q, const GemmArgs &a, hipStream_t stream) {
-    const int nv = (int)div_ceil((size_t)q.kp / 4, 256);
-    void (*qk)(QuantArgs) = nv <= 3 ? k_quant_rows_f16<3> : k_quant_rows_f16<8>;
+    void (*qk)(QuantArgs) = div_ceil((size_t)q.kp / 4, 256) <= 3 ? k_quant_rows_f16<3> : k_quant_rows_f16<8>;
     hipLaunchKernelGGL(qk, dim3(q.m_pad), dim3(256), 0, stream, q);
     // token tile: 64 (TTW 4) while the grid still covers the chip twice over, else narrower (short prompts, one rank's share)
-    const size_t gx0 = div_ceil(div_ceil(w.rows, 16), 16);
+    const size_t gx0 = gemm_row_blocks(w);
     const int ttw = gemm_token_tiles(gx0, q.m_pad, false, kGemmCUs);
-    const bool fmt1 = a.stiles_h != nullptr;
-    void (*fk)(GemmArgs, uint32_t) = fmt1 ? (ttw == 4 ? k_gemm_f16a<1, 4> : ttw == 2 ? k_gemm_f16a<1, 2> : k_gemm_f16a<1, 1>)
-                                          : (ttw == 4 ? k_gemm_f16a<0, 4> : ttw == 2 ? k_gemm_f16a<0, 2> : k_gemm_f16a<0, 1>);
-    {
-        static std::mutex f_mu;
-        static std::unordered_set<const void *> f_raised;
-        std::lock_guard<std::mutex> lk(f_mu);
-        if (!f_raised.count((const void *)fk)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            f_raised.insert((const void *)fk);
-        }
-    }
-    g_last_gemm_tile = GemmTileChoice{2, 16 * ttw, 4, fmt1 ? 4 : 5};
-    hipLaunchKernelGGL(fk, dim3((unsigned)gx0, (unsigned)(q.m_pad / (16 * ttw))), dim3(256), (size_t)2 * ttw * 16 * 512, stream, a, lut_f16_hi(w.lut));
-    return hipGetLastError();
+    const int fmt = a.stiles_h ? 1 : 0;
+    return gemm_fire(pick_f16a(fmt, ttw, 0, false), GemmTileChoice{2, 16 * ttw, 4, fmt ? 4 : 5}, dim3((unsigned)gx0, (unsigned)(q.m_pad / (16 * ttw))), 256,
+                     (size_t)2 * ttw * 16 * 512, stream, a, lut_f16_hi(w.lut));
 }
 
 // the fp6 form (k_gemm_fp6) takes unscaled matrices whose code map fits fp4 (every map of the reference: values in -2 .. 2)
@@ -2268,52 +2316,42 @@ void drop_fp4_image(Weights &w) {
     if (w.tiles4) (void)hipFree(w.tiles4);
     w.tiles4 = nullptr;
 }
-// would launch_gemm_mfma send this call to k_gemm_fp6? (the ABI asks before the launch, to build the image outside it)
-bool gemm_takes_fp6(const Weights &w, const GemvFusion &fu, int ndig) {
-    if (fu.int8_form || ndig != 2 || !gemm_fp6_supported(w)) return false;
-    if (gemm_k32(w)) return false;
+
+// Which form a launch_gemm_mfma call takes -- the one place that decides it (and reads the two switches):
+//   f16 matrix cores  2 digits on 32-block scales that are f16 values (BitNet32-F16 at f16 activation precision); unscaled matrices only with
+//                     BITNET_HIP_GEMM_F16A=1
+//   fp6 x fp4         2 digits, unscaled: the same integer on the fp6 x fp4 MFMA, on request (FUSE_FP6_DIGITS) or by BITNET_HIP_GEMM_FP6=1
+//   int8 planes       everything else: 3 and 4 digits, FUSE_INT8_DIGITS, the other scale layouts, code maps outside -2 .. 2
+enum class GemmForm { Int8Planes, F16Cores, Fp6 };
+static GemmForm gemm_form(const Weights &w, const GemvFusion &fu, int ndig) {
     static const int f16a_mode = [] { const char *e = getenv("BITNET_HIP_GEMM_F16A"); return e ? atoi(e) : 0; }();
-    if (f16a_mode && w.cols % 256 == 0) return false;
-    return fu.fp6_form || gemm_fp6_mode();
+    if (fu.int8_form || ndig != 2 || !lut_fits_f16w(w.lut)) return GemmForm::Int8Planes;
+    if (gemm_k32(w)) return w.scales_f16_x2_finite ? GemmForm::F16Cores : GemmForm::Int8Planes;
+    if (w.scaled) return GemmForm::Int8Planes;
+    if (f16a_mode && w.cols % 256 == 0) return GemmForm::F16Cores;
+    return (fu.fp6_form || gemm_fp6_mode()) && gemm_supported(w) ? GemmForm::Fp6 : GemmForm::Int8Planes;
 }
+// would launch_gemm_mfma send this call to k_gemm_fp6? (the ABI asks before the launch, to build the image outside it)
+bool gemm_takes_fp6(const Weights &w, const GemvFusion &fu, int ndig) { return gemm_form(w, fu, ndig) == GemmForm::Fp6; }
 
 static hipError_t launch_gemm_fp6(const Weights &w, const QuantArgs &q, const GemmArgs &a, hipStream_t stream) {
-    const int nv = (int)div_ceil((size_t)q.kp / 4, 256);
-    void (*qk)(QuantArgs) = nv <= 3 ? k_quant_rows<2, 3, 1> : k_quant_rows<2, 8, 1>;
-    if (quant_rows_w_applies(q)) launch_quant_rows_w(q, true, stream);
-    else hipLaunchKernelGGL(qk, dim3(q.m_pad), dim3(256), (size_t)(q.kp / 32) * 144 + (size_t)(q.kp / 256) * 576, stream, q);  // LDS: the row's integers (144 bytes per 32 columns) + its packed image
-    size_t gx0 = div_ceil(div_ceil(w.rows, 16), 16);
+    launch_quant_rows(q, 2, true, stream);
+    size_t gx0 = gemm_row_blocks(w);
     static const size_t cover = [] { const char *e = getenv("BITNET_HIP_FP6_COVER"); return e ? (size_t)atoi(e) : 2 * kGemmCUs; }();  // (developer sweep of the token tile)
     int ttw = gemm_token_tiles(gx0, q.m_pad, false, cover);
     const bool rt5 = ttw == 4 && !a.silu_mul && w.rows % 4 == 0 && gemm_five_tiles(w.rows, q.m_pad);
     if (rt5) gx0 = w.rows / 320;
     else ttw = gemm_token_tiles(gx0, q.m_pad, true, cover);
     const bool res = a.tiles4 != nullptr;
-    void (*fk)(GemmArgs, uint32_t) = res ? (rt5 ? k_gemm_fp6<4, 5, 1> : ttw == 4 ? k_gemm_fp6<4, 4, 1> : ttw == 2 ? k_gemm_fp6<2, 4, 1> : k_gemm_fp6<1, 4, 1>)
-                                         : (rt5 ? k_gemm_fp6<4, 5> : ttw == 4 ? k_gemm_fp6<4> : ttw == 2 ? k_gemm_fp6<2> : k_gemm_fp6<1>);
-    {
-        static std::mutex f_mu;
-        static std::unordered_set<const void *> f_raised;
-        std::lock_guard<std::mutex> lk(f_mu);
-        if (!f_raised.count((const void *)fk)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            f_raised.insert((const void *)fk);
-        }
-    }
-    g_last_gemm_tile = GemmTileChoice{2, 16 * ttw, 4, 6, rt5 ? 80 : 64, res ? 1 : 0};
+    GemmTileChoice tile{2, 16 * ttw, 4, 6, rt5 ? 80 : 64, res ? 1 : 0};
     GemmArgs aw = a;
     aw.wgroup = gemm_weight_group(gx0, rt5 ? 320 : 256, res ? 2 * w.cols : w.cols, false, res ? kFp4GroupBudget : (size_t)3 << 19);  // (the image is twice the bytes per row block)
     static const int fp6w_mode = [] { const char *e = getenv("BITNET_HIP_GEMM_FP6W"); return e ? atoi(e) : 1; }();
     if (fp6w_mode && res && ttw == 4 && !rt5 && w.rows % 256 == 0 && (size_t)div_ceil(w.rows, 16) * (w.cols / 256) * 2048 < ((size_t)1 << 31)) {
-        static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_fp6w), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  // (72 KiB of tile buffers; once, thread-safe)
-        if (raised != hipSuccess) return raised;
-        g_last_gemm_tile.wave_rows = 128;  // the 2 x 2 arrangement: a wave owns 128 rows x 32 tokens of the 256 x 64 tile
-        hipLaunchKernelGGL(k_gemm_fp6w, dim3((unsigned)gx0, (unsigned)(q.m_pad / 64)), dim3(256), (size_t)2 * 64 * 576, stream, aw);
-        return hipGetLastError();
+        tile.wave_rows = 128;  // the 2 x 2 arrangement: a wave owns 128 rows x 32 tokens of the 256 x 64 tile (72 KiB of tile buffers)
+        return gemm_fire(k_gemm_fp6w, tile, dim3((unsigned)gx0, (unsigned)(q.m_pad / 64)), 256, (size_t)2 * 64 * 576, stream, aw);
     }
-    hipLaunchKernelGGL(fk, dim3((unsigned)gx0, (unsigned)(q.m_pad / (16 * ttw))), dim3(256), (size_t)2 * ttw * 16 * 576, stream, aw, lut_fp4(w.lut));
-    return hipGetLastError();
+    return gemm_fire(pick_fp6(ttw, rt5, res, 0), tile, dim3((unsigned)gx0, (unsigned)(q.m_pad / (16 * ttw))), 256, (size_t)2 * ttw * 16 * 576, stream, aw, lut_fp4(w.lut));
 }
 
 // ---- the f16 activation chain: every projection input is an f16 matrix its PRODUCER wrote (no quantiser kernel between the launches) ----
@@ -2337,56 +2375,23 @@ hipError_t launch_gemm_f16_chain(const Weights &w, const GemmF16Io &io, size_t m
     if (io.stats_in && !(w.ln_g && io.n_stats > 0)) return hipErrorInvalidValue;
     if (io.silu_mul && (!w.paired || io.residual)) return hipErrorInvalidValue;
     const size_t m_pad = div_ceil(m, 64) * 64;
-    GemmArgs a;
-    a.tiles = w.tiles;
+    GemmArgs a = gemm_args(w);
+    gemm_args_chain(a, w, io, m, m_pad);
     a.stiles_h = w.scaled ? w.scale_tiles_h : nullptr;
-    a.rows = (int)w.rows;
-    a.cols = (int)w.cols;
-    a.nblk = (int)(w.cols / 256);
-    a.lut = w.lut;
-    a.planes = static_cast<const int8_t *>(io.xh);
-    a.inv_scale = nullptr;
-    a.y = io.y;
-    a.m = (int)m;
-    a.residual = io.residual;
-    a.wscale = nullptr;
-    a.silu_mul = io.silu_mul ? 1 : 0;
-    a.stats_in = io.stats_in;
-    a.n_stats = io.n_stats;
-    a.stats_stride = (int)m_pad;
-    a.ln_eps = io.ln_eps;
-    a.ln_g = w.ln_g;
-    a.yh = static_cast<_Float16 *>(io.yh);
-    a.gamma_out = io.gamma_out;
-    a.stats_out = io.stats_out;
 #ifdef BH_STAMPS
     a.stamps = g_mfma_stamps;
 #endif
     size_t gx0 = w.rows / 256;
     const int ttw = gemm_token_tiles(gx0, m_pad, false, kGemmCUs);
-    const bool fmt1 = w.scaled;
+    const int fmt = w.scaled ? 1 : 0;
     const bool rt5 = ttw == 4 && !io.silu_mul && gemm_five_tiles(w.rows, m_pad);
     if (rt5) gx0 = w.rows / 320;
-    void (*fk)(GemmArgs, uint32_t) = rt5    ? (fmt1 ? k_gemm_f16a<1, 4, 1, 5> : k_gemm_f16a<0, 4, 1, 5>)
-                                     : fmt1 ? (ttw == 4 ? k_gemm_f16a<1, 4, 1> : ttw == 2 ? k_gemm_f16a<1, 2, 1> : k_gemm_f16a<1, 1, 1>)
-                                            : (ttw == 4 ? k_gemm_f16a<0, 4, 1> : ttw == 2 ? k_gemm_f16a<0, 2, 1> : k_gemm_f16a<0, 1, 1>);
     if (io.qb_out) {  // the outputs also leave as QB32 rows (the next fp6-form matmul's input): 64-token tiles only, no silu pairing, K' = rows % 256 == 0
         if (ttw != 4 || io.silu_mul || w.rows % 256 != 0) return hipErrorInvalidValue;
-        fk = rt5 ? (fmt1 ? k_gemm_f16a<1, 4, 2, 5> : k_gemm_f16a<0, 4, 2, 5>) : (fmt1 ? k_gemm_f16a<1, 4, 2> : k_gemm_f16a<0, 4, 2>);
         a.qb_nblk_out = (int)(w.rows / 256);
         a.qb_out = static_cast<uint8_t *>(io.qb_out);
     }
-    {
-        static std::mutex f_mu;
-        static std::unordered_set<const void *> f_raised;
-        std::lock_guard<std::mutex> lk(f_mu);
-        if (!f_raised.count((const void *)fk)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            f_raised.insert((const void *)fk);
-        }
-    }
-    g_last_gemm_tile = GemmTileChoice{2, 16 * ttw, 4, fmt1 ? 4 : 5, rt5 ? 80 : 64};
+    const GemmKernelL fk = pick_f16a(fmt, ttw, io.qb_out ? 2 : 1, rt5);
     const size_t lds = (size_t)2 * ttw * 16 * 512 + (size_t)ttw * 16 * 8 + 4096;  // two tile buffers + the tokens' (mean, 1 / denom) + the statistics scratch
     // Wide launches (gate|up: 54 row blocks): 128-token workgroups (k_gemm_f16h: half the code expansion per MFMA) on as many row blocks as fill WHOLE rounds
     // of the 512 slots, this kernel's 64-token workgroups on the rest -- 13824 rows x 4096 tokens: 48 x 32 = 1536 workgroups = 3 rounds, then 6 x 64 = 384
@@ -2402,31 +2407,20 @@ hipError_t launch_gemm_f16_chain(const Weights &w, const GemmF16Io &io, size_t m
         if (gx0 * t128 <= slots && 4 * gx0 * t128 >= 3 * slots) n_a = gx0;
         if (gx0 < 24 && n_a != gx0) n_a = 0;
         if (n_a >= gx0 / 2 && n_a > 0) {
-            void (*hk)(GemmArgs, uint32_t) = fmt1 ? k_gemm_f16h<1> : k_gemm_f16h<0>;
-            {
-                static std::mutex h_mu;
-                static std::unordered_set<const void *> h_raised;
-                std::lock_guard<std::mutex> lk(h_mu);
-                if (!h_raised.count((const void *)hk)) {
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(hk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (e != hipSuccess) return e;
-                    h_raised.insert((const void *)hk);
-                }
-            }
+            const GemmTileChoice tile{2, 128, 4, fmt ? 4 : 5, 64};  // what is recorded for the whole call, the 64-token rest included
             GemmArgs aa = a;
-            aa.wgroup = gemm_weight_group(n_a, 256, w.cols, fmt1);
-            hipLaunchKernelGGL(hk, dim3((unsigned)n_a, (unsigned)t128), dim3(256), (size_t)2 * 128 * 256 + 128 * 8 + 4096, stream, aa, lut_f16_hi(w.lut));
-            g_last_gemm_tile = GemmTileChoice{2, 128, 4, fmt1 ? 4 : 5, 64};
-            if (n_a == gx0) return hipGetLastError();
+            aa.wgroup = gemm_weight_group(n_a, 256, w.cols, fmt != 0);
+            const hipError_t e = gemm_fire(fmt ? k_gemm_f16h<1> : k_gemm_f16h<0>, tile, dim3((unsigned)n_a, (unsigned)t128), 256, (size_t)2 * 128 * 256 + 128 * 8 + 4096,
+                                           stream, aa, lut_f16_hi(w.lut));
+            if (e != hipSuccess || n_a == gx0) return e;
             a.bx_off = (int)n_a;
             a.wgroup = 0;
-            hipLaunchKernelGGL(fk, dim3((unsigned)(gx0 - n_a), (unsigned)(m_pad / 64)), dim3(256), lds, stream, a, lut_f16_hi(w.lut));
-            return hipGetLastError();
+            return gemm_fire(fk, tile, dim3((unsigned)(gx0 - n_a), (unsigned)(m_pad / 64)), 256, lds, stream, a, lut_f16_hi(w.lut));
         }
     }
-    a.wgroup = gemm_weight_group(gx0, rt5 ? 320 : 256, w.cols, fmt1);
-    hipLaunchKernelGGL(fk, dim3((unsigned)gx0, (unsigned)(m_pad / (16 * ttw))), dim3(256), lds, stream, a, lut_f16_hi(w.lut));
-    return hipGetLastError();
+    a.wgroup = gemm_weight_group(gx0, rt5 ? 320 : 256, w.cols, fmt != 0);
+    return gemm_fire(fk, GemmTileChoice{2, 16 * ttw, 4, fmt ? 4 : 5, rt5 ? 80 : 64}, dim3((unsigned)gx0, (unsigned)(m_pad / (16 * ttw))), 256, lds, stream, a,
+                     lut_f16_hi(w.lut));
 }
 
 size_t qb32_bytes(size_t m, size_t cols) {
@@ -2436,10 +2430,8 @@ size_t qb32_bytes(size_t m, size_t cols) {
 
 hipError_t launch_rows_to_qb32(const float *x, const float *gamma, size_t m, size_t cols, void *qb, float *stats, hipStream_t stream) {
     if (cols % 256 != 0 || m == 0 || cols > 8192) return hipErrorInvalidValue;
-    const size_t m_pad = div_ceil(m, 64) * 64, nblk = cols / 256;
-    uint8_t *planes = static_cast<uint8_t *>(qb);
-    (void)nblk;
-    hipLaunchKernelGGL(k_rows_to_qb32, dim3((unsigned)m_pad), dim3(256), (cols / 32) * 144, stream, x, gamma, (int)m, (int)cols, planes, stats);
+    const size_t m_pad = div_ceil(m, 64) * 64;
+    hipLaunchKernelGGL(k_rows_to_qb32, dim3((unsigned)m_pad), dim3(256), (cols / 32) * 144, stream, x, gamma, (int)m, (int)cols, static_cast<uint8_t *>(qb), stats);
     return hipGetLastError();
 }
 
@@ -2449,50 +2441,17 @@ hipError_t launch_gemm_qb32(const Weights &w, const GemmF16Io &io, size_t m, hip
     if (!gemm_qb32_supported(w) || m == 0 || !io.xh || io.qb_out) return hipErrorInvalidValue;
     if (io.stats_in && !(w.ln_g && io.n_stats > 0)) return hipErrorInvalidValue;
     if (io.silu_mul && (!w.paired || io.residual)) return hipErrorInvalidValue;
-    const size_t m_pad = div_ceil(m, 64) * 64, nblk = w.cols / 256;
-    GemmArgs a;
-    a.tiles = w.tiles;
+    const size_t m_pad = div_ceil(m, 64) * 64;
+    GemmArgs a = gemm_args(w);
+    gemm_args_chain(a, w, io, m, m_pad);
     a.tiles4 = gemm_fp4_resident_enabled() ? w.tiles4 : nullptr;
-    a.stiles_h = nullptr;
-    a.rows = (int)w.rows;
-    a.cols = (int)w.cols;
-    a.nblk = (int)nblk;
-    a.lut = w.lut;
-    a.planes = static_cast<const int8_t *>(io.xh);
-    a.inv_scale = nullptr;
-    a.y = io.y;
-    a.m = (int)m;
-    a.residual = io.residual;
-    a.wscale = nullptr;
-    a.silu_mul = io.silu_mul ? 1 : 0;
-    a.stats_in = io.stats_in;
-    a.n_stats = io.n_stats;
-    a.stats_stride = (int)m_pad;
-    a.ln_eps = io.ln_eps;
-    a.ln_g = w.ln_g;
-    a.yh = static_cast<_Float16 *>(io.yh);
-    a.gamma_out = io.gamma_out;
-    a.stats_out = io.stats_out;
-    size_t gx0 = w.rows / 256;
+    const size_t gx0 = w.rows / 256;
     const int ttw = gemm_token_tiles(gx0, m_pad, false);
-    const bool rt5 = false;  // (the 320-row form of this variant does not fit 256 registers: hipcc spills 80 bytes; the model's QB32 consumers -- 3840 and 13824 rows -- take four tiles anyway)
+    // no 320-row form here: it does not fit 256 registers (pick_fp6), and the model's QB32 consumers -- 3840 and 13824 rows -- take four tiles anyway
     const bool res = a.tiles4 != nullptr;
-    void (*fk)(GemmArgs, uint32_t) = res ? (ttw == 4 ? k_gemm_fp6<4, 4, 1, 1> : ttw == 2 ? k_gemm_fp6<2, 4, 1, 1> : k_gemm_fp6<1, 4, 1, 1>)
-                                         : (ttw == 4 ? k_gemm_fp6<4, 4, 0, 1> : ttw == 2 ? k_gemm_fp6<2, 4, 0, 1> : k_gemm_fp6<1, 4, 0, 1>);
-    {
-        static std::mutex f_mu;
-        static std::unordered_set<const void *> f_raised;
-        std::lock_guard<std::mutex> lk(f_mu);
-        if (!f_raised.count((const void *)fk)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            f_raised.insert((const void *)fk);
-        }
-    }
-    g_last_gemm_tile = GemmTileChoice{2, 16 * ttw, 4, 8, rt5 ? 80 : 64, res ? 1 : 0};  // scale_mode 8: the fp6 form on QB32 rows
-    a.wgroup = gemm_weight_group(gx0, rt5 ? 320 : 256, res ? 2 * w.cols : w.cols, false, res ? kFp4GroupBudget : (size_t)3 << 19);
-    hipLaunchKernelGGL(fk, dim3((unsigned)gx0, (unsigned)(m_pad / (16 * ttw))), dim3(256), (size_t)2 * ttw * 16 * (576 + 8) + (size_t)ttw * 16 * 8 + 4096, stream, a, lut_fp4(w.lut));
-    return hipGetLastError();
+    a.wgroup = gemm_weight_group(gx0, 256, res ? 2 * w.cols : w.cols, false, res ? kFp4GroupBudget : (size_t)3 << 19);
+    return gemm_fire(pick_fp6(ttw, false, res, 1), GemmTileChoice{2, 16 * ttw, 4, 8, 64, res ? 1 : 0},  // scale_mode 8: the fp6 form on QB32 rows
+                     dim3((unsigned)gx0, (unsigned)(m_pad / (16 * ttw))), 256, (size_t)2 * ttw * 16 * (576 + 8) + (size_t)ttw * 16 * 8 + 4096, stream, a, lut_fp4(w.lut));
 }
 
 hipError_t launch_gemm_mfma(const Weights &w, const float *x, float *y, size_t m, const GemvFusion &fu, int ndig,
@@ -2517,13 +2476,8 @@ hipError_t launch_gemm_mfma(const Weights &w, const float *x, float *y, size_t m
     ws = reinterpret_cast<uint8_t *>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     q.inv_scale = reinterpret_cast<float *>(ws);
     q.planes = reinterpret_cast<int8_t *>(ws + div_ceil(m_pad * 4, 256) * 256);
-    GemmArgs a;
-    a.tiles = w.tiles;
+    GemmArgs a = gemm_args(w);
     a.stiles_h = k32 ? w.scale_tiles_h : nullptr;
-    a.rows = (int)w.rows;
-    a.cols = (int)w.cols;
-    a.nblk = (int)div_ceil(w.cols, 256);
-    a.lut = w.lut;
     a.planes = q.planes;
     a.inv_scale = q.inv_scale;
     a.y = y;
@@ -2532,19 +2486,16 @@ hipError_t launch_gemm_mfma(const Weights &w, const float *x, float *y, size_t m
     a.wscale = k32 ? nullptr : w.scales;  // per 256-block or per 32-block (row-major [rows, cols / block])
     a.silu_mul = fu.silu_mul ? 1 : 0;
     a.tiles4 = gemm_fp4_resident_enabled() && !fu.fp6_expand ? w.tiles4 : nullptr;  // (set before the launch by the ABI: ensure_fp4_image)
-    const bool takes_f16 = !fu.int8_form && ndig == 2 && k32 && lut_fits_f16w(w.lut) && w.scales_f16_x2_finite;
+    const GemmForm form = gemm_form(w, fu, ndig);
     if (fu.x_f16 || fu.y_f16) {  // f16 hand-over: the int8 digit form's quantiser reads f16 rows; silu * up goes out as f16 rows
-        const bool f16_form = takes_f16;
+        const bool f16_form = form == GemmForm::F16Cores && k32;  // (BitNet32-F16 has bitnet_hip_matmul_f16_dev for this; the F16A=1 route of an unscaled matrix reads f16 rows)
         if (f16_form || (fu.y_f16 && (!fu.silu_mul || ((w.rows >> 1) & 3) != 0))) return hipErrorInvalidValue;
         if (fu.y_f16) a.yh = reinterpret_cast<_Float16 *>(y), a.y = nullptr;
     }
-    if (takes_f16) return launch_gemm_f16(w, q, a, stream);  // BitNet32-F16 at f16 activation precision: the f16 matrix cores
-    if (!fu.int8_form) {
-        static const int f16a_mode = [] { const char *e = getenv("BITNET_HIP_GEMM_F16A"); return e ? atoi(e) : 0; }();
-        if (f16a_mode && ndig == 2 && !w.scaled && lut_fits_f16w(w.lut) && w.cols % 256 == 0)
-            return launch_gemm_f16(w, q, a, stream);
-        // unscaled matrices at 2 digits: the same integer on the fp6 x fp4 MFMA, on request (flag) or by BITNET_HIP_GEMM_FP6=1
-        if (gemm_takes_fp6(w, fu, ndig)) return launch_gemm_fp6(w, q, a, stream);
+    switch (form) {
+    case GemmForm::F16Cores: return launch_gemm_f16(w, q, a, stream);
+    case GemmForm::Fp6: return launch_gemm_fp6(w, q, a, stream);
+    case GemmForm::Int8Planes: break;
     }
     if (ndig == 2) return launch_gemm_t<2, 4>(w, q, a, stream);
     if (ndig == 3) return launch_gemm_t<3, 2>(w, q, a, stream);

@@ -631,6 +631,16 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_mfma(MfmaArgs p) {
 
 unsigned long long *g_mfma_stamps = nullptr;  // set through bitnet_hip_debug_set_stamps (diagnostic build)
 
+hipError_t raise_dynamic_lds(const void *kernel, int bytes) {
+    static std::mutex raised_mu;                     // launches may come from several host threads (Send + Sync)
+    static std::unordered_set<const void *> raised;  // raised once per kernel, outside any capture
+    std::lock_guard<std::mutex> lk(raised_mu);
+    if (raised.count(kernel)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) raised.insert(kernel);
+    return e;
+}
+
 bool mfma_supported(const Weights &w) {
     if (w.cols == 0 || w.rows == 0) return false;
     if (w.cols > (size_t)kNVMAX * 2048) return false;                    // prologue register budget
@@ -718,14 +728,8 @@ hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m
     const size_t lds = (size_t)nw * (bs32 ? 5 : 4) * (ring_t * 256 + 16) + 2 * nw * sizeof(double) + nw * 16 * sizeof(float) +
                        ((ln && !ln2) ? w.cols * sizeof(float) : 0);
     if (lds > 64 * 1024) {
-        static std::mutex raised_mu;                     // launches may come from several host threads (Send + Sync)
-        static std::unordered_set<const void *> raised;  // raised once per kernel, outside any capture
-        std::lock_guard<std::mutex> lk(raised_mu);
-        if (!raised.count((const void *)kfn)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            raised.insert((const void *)kfn);
-        }
+        const hipError_t e = raise_dynamic_lds(kfn, 160 * 1024);
+        if (e != hipSuccess) return e;
     }
     // one activation row per workgroup row of the grid (forward_qk256's row loop, T:683-691, in one launch)
     a.out_rows = (int)out_rows;

@@ -25,8 +25,6 @@
 // q, k, v and the probabilities are rounded to f16 for the matrix cores (relative 2^-11);
 // the f32 KV cache the decode steps read afterwards holds the exact f32 values.
 #include <cstdlib>
-#include <mutex>
-#include <unordered_set>
 
 #include "common.hpp"
 
@@ -649,17 +647,8 @@ static hipError_t launch_attn_kernel(const PrefillArgs &p, hipStream_t stream) {
     PrefillArgs pa = p;
     pa.head_fast = head_fast ? 1 : 0;
     if (head_fast) grid = dim3(grid.y, grid.x, grid.z);
-    {
-        // two tile buffers = 64 KiB of dynamic LDS (+ a static word): raised once per kernel; entry points may run concurrently
-        static std::mutex raised_mu;
-        static std::unordered_set<const void *> raised;
-        std::lock_guard<std::mutex> lk(raised_mu);
-        if (!raised.count((const void *)ak)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ak), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kKVBuf);
-            if (e != hipSuccess) return e;
-            raised.insert((const void *)ak);
-        }
-    }
+    const hipError_t er = raise_dynamic_lds(ak, 2 * kKVBuf);  // two tile buffers = 64 KiB of dynamic LDS (+ a static word)
+    if (er != hipSuccess) return er;
     hipLaunchKernelGGL(ak, grid, dim3(256), 2 * kKVBuf, stream, pa);
     if (p.ksplit > 1)
         hipLaunchKernelGGL(k_prefill_merge, dim3((unsigned)div_ceil((size_t)p.nq * p.n_heads * 32, 256)), dim3(256), 0, stream, p);

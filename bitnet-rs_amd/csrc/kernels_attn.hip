@@ -17,6 +17,7 @@
 // reads dims contiguously: lane = dim).  *pos_ptr = number of cached tokens.
 #include "common.hpp"
 #include "qact.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
 
@@ -26,33 +27,10 @@ constexpr int kD = 128;
 // per (kv head, chunk) record in the scratch buffer: (m, l)[4], o[4][128]   (kAttnRecFloats, common.hpp)
 constexpr int kRec = kAttnRecFloats;
 static_assert(kRec == 2 * kMaxGroup + kMaxGroup * kD, "record layout");
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 // K cache element (dim d, position pos) of one KV head
 __device__ __forceinline__ size_t kidx(int d, int pos) { return ((size_t)(pos >> 6) * kD + d) * 64 + (pos & 63); }
 __host__ __device__ __forceinline__ size_t kv_head_floats(int max_pos) { return (size_t)((max_pos + 63) / 64) * 64 * kD; }
-
-template <int CTRL>
-__device__ __forceinline__ float adpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float arl(float v, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-__device__ __forceinline__ float awave_max(float v) {
-    v = fmaxf(v, adpp<0xB1>(v));
-    v = fmaxf(v, adpp<0x4E>(v));
-    v = fmaxf(v, adpp<0x141>(v));
-    v = fmaxf(v, adpp<0x140>(v));
-    return fmaxf(fmaxf(arl(v, 0), arl(v, 16)), fmaxf(arl(v, 32), arl(v, 48)));
-}
-__device__ __forceinline__ float awave_sum(float v) {
-    v += adpp<0xB1>(v);
-    v += adpp<0x4E>(v);
-    v += adpp<0x141>(v);
-    v += adpp<0x140>(v);
-    return (arl(v, 0) + arl(v, 16)) + (arl(v, 32) + arl(v, 48));
-}
 
 // In-kernel time stamps (s_memrealtime, 100 MHz): diagnostic build only (-DBH_STAMPS; tools/stamp_attn.py), 8 x u64 per workgroup.
 #ifdef BH_STAMPS
@@ -70,21 +48,6 @@ __device__ __forceinline__ float awave_sum(float v) {
 // run the chunk algorithm side by side and meet in LDS, so there is ONE record per 128 positions: half as many
 // records for whoever merges them (the combine kernel, or the o-projection at short contexts) and, at 4k keys, 160
 // workgroups instead of 320 (one per CU instead of 64 CUs with two).
-__device__ __forceinline__ float amix_lo(float a, uint32_t h, float c) {  // a * f16(h.lo) + c, no conversion instruction
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float amix_hi(float a, uint32_t h, float c) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
-    return r;
-}
-__device__ __forceinline__ uint32_t pack_h2(float lo, float hi) {
-    const _Float16 a = (_Float16)lo, b = (_Float16)hi;
-    return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
-}
-
 // KV16: the cache holds f16 (opt-in: half the bytes of the long-context stream; the reference's cache is f32 Tensor::cat,
 // T:1171-1202 -- values rounded ONCE, from the exact f32 k / v, when they are appended).  Layout then:
 // K [kv][chunk][D / 2][64 positions][2 dims] (a lane still reads 4 bytes per load: a dim PAIR of its position),
@@ -230,10 +193,10 @@ __global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restri
 #pragma unroll
             for (int g = 0; g < kMaxGroup; ++g) {
                 const float4 q4 = *reinterpret_cast<const float4 *>(qs + g * kD + 32 * wave + 2 * i);
-                acc[g] = amix_lo(q4.x, kh[i], acc[g]);
-                acc2[g] = amix_hi(q4.y, kh[i], acc2[g]);
-                acc[g] = amix_lo(q4.z, kh[i + 1], acc[g]);
-                acc2[g] = amix_hi(q4.w, kh[i + 1], acc2[g]);
+                acc[g] = fma_mix_lo(q4.x, kh[i], acc[g]);
+                acc2[g] = fma_mix_hi(q4.y, kh[i], acc2[g]);
+                acc[g] = fma_mix_lo(q4.z, kh[i + 1], acc[g]);
+                acc2[g] = fma_mix_hi(q4.w, kh[i + 1], acc2[g]);
             }
         }
 #pragma unroll
@@ -276,9 +239,9 @@ __global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restri
         const int g = wave, j = j0 + lane;
         float s = ((partial[half][0][lane][g] + partial[half][1][lane][g]) + partial[half][2][lane][g]) + partial[half][3][lane][g];
         s = j < t_k ? s * scale : -INFINITY;
-        m_c = awave_max(s);
+        m_c = wave64_max_f_rows_readlane(s);
         const float e = j < t_k ? expf(s - m_c) : 0.0f;
-        l_c = awave_sum(e);
+        l_c = wave64_sum_f_rows_readlane(e);
         // the new token's value is not in the cache registers: its weight goes aside (enew) and its slot gets 0
         if (KV16)
             sc[half][g][lane & 3][lane >> 2] = j == pos ? 0.0f : e;
@@ -302,14 +265,14 @@ __global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restri
 #pragma unroll
             for (int g = 0; g < kMaxGroup; ++g) {
                 const float4 w = *reinterpret_cast<const float4 *>(&sc[half][g][pq][i]);
-                a0[g] = amix_lo(w.x, vh[i], a0[g]);
-                a1[g] = amix_hi(w.x, vh[i], a1[g]);
-                a0[g] = amix_lo(w.y, vh[i + 1], a0[g]);
-                a1[g] = amix_hi(w.y, vh[i + 1], a1[g]);
-                a0[g] = amix_lo(w.z, vh[i + 2], a0[g]);
-                a1[g] = amix_hi(w.z, vh[i + 2], a1[g]);
-                a0[g] = amix_lo(w.w, vh[i + 3], a0[g]);
-                a1[g] = amix_hi(w.w, vh[i + 3], a1[g]);
+                a0[g] = fma_mix_lo(w.x, vh[i], a0[g]);
+                a1[g] = fma_mix_hi(w.x, vh[i], a1[g]);
+                a0[g] = fma_mix_lo(w.y, vh[i + 1], a0[g]);
+                a1[g] = fma_mix_hi(w.y, vh[i + 1], a1[g]);
+                a0[g] = fma_mix_lo(w.z, vh[i + 2], a0[g]);
+                a1[g] = fma_mix_hi(w.z, vh[i + 2], a1[g]);
+                a0[g] = fma_mix_lo(w.w, vh[i + 3], a0[g]);
+                a1[g] = fma_mix_hi(w.w, vh[i + 3], a1[g]);
             }
         }
         if (last && pq == 0) {  // the new token: value from LDS (rounded as the cache holds it), weight from enew

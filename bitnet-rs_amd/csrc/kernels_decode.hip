@@ -9,36 +9,9 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-// 256-thread block reductions; slot = 4 floats of LDS.
-__device__ __forceinline__ float bsum(float v, float *slot) {
-    v = wsum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
-}
-__device__ __forceinline__ float bmax(float v, float *slot) {
-    v = wmax(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(slot[0], slot[1]), fmaxf(slot[2], slot[3]));
-}
 
 // ---- embedding: row gather from the f16 table (T:1415-1424) -------------------------
 __global__ void k_embed_f16(const _Float16 *__restrict__ table, const int *__restrict__ tokens,
@@ -50,7 +23,7 @@ __global__ void k_embed_f16(const _Float16 *__restrict__ table, const int *__res
     const int t = gid / per_row, c = gid % per_row;
     int tok = tokens[t + (offset_ptr ? *offset_ptr : 0)];
     tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
-    const half8 h = *reinterpret_cast<const half8 *>(table + (size_t)tok * hidden + 8 * c);
+    const h8 h = *reinterpret_cast<const h8 *>(table + (size_t)tok * hidden + 8 * c);
     float *o = out + (size_t)t * hidden + 8 * c;
 #pragma unroll
     for (int i = 0; i < 8; ++i) o[i] = (float)h[i];
@@ -76,14 +49,14 @@ __global__ __launch_bounds__(256) void k_norm_rows(const float *__restrict__ x, 
     if (!RMS) {
         float s = 0.0f;
         for (int i = threadIdx.x; i < hidden; i += 256) s += xr[i];
-        mean = bsum(s, slot) / (float)hidden;
+        mean = block256_sum_f(s, slot) / (float)hidden;
     }
     float ss = 0.0f;
     for (int i = threadIdx.x; i < hidden; i += 256) {
         const float d = xr[i] - mean;
         ss += d * d;
     }
-    const float denom = sqrtf(bsum(ss, slot) / (float)hidden + eps);
+    const float denom = sqrtf(block256_sum_f(ss, slot) / (float)hidden + eps);
     for (int i = threadIdx.x; i < hidden; i += 256) orow[i] = (xr[i] - mean) / denom * gamma[i];
 }
 
@@ -119,13 +92,13 @@ __global__ __launch_bounds__(256) void k_logits_f16(const _Float16 *__restrict__
     // final norm (T:1589), recomputed per workgroup: 10 KB from L2
     float s = 0.0f;
     for (int i = tid; i < hidden; i += 256) s += x[i];
-    const float mean = gamma ? bsum(s, slot) / (float)hidden : 0.0f;
+    const float mean = gamma ? block256_sum_f(s, slot) / (float)hidden : 0.0f;
     float ss = 0.0f;
     for (int i = tid; i < hidden; i += 256) {
         const float d = x[i] - mean;
         ss += d * d;
     }
-    const float denom = gamma ? sqrtf(bsum(ss, slot) / (float)hidden + eps) : 1.0f;
+    const float denom = gamma ? sqrtf(block256_sum_f(ss, slot) / (float)hidden + eps) : 1.0f;
     for (int i = tid; i < hidden; i += 256) xs[i] = gamma ? (x[i] - mean) / denom * gamma[i] : x[i];
     __syncthreads();
     const int nchunks = hidden >> 9;
@@ -138,7 +111,7 @@ __global__ __launch_bounds__(256) void k_logits_f16(const _Float16 *__restrict__
     int bi = 0x7fffffff;
     const int total_waves = gridDim.x * 4;
     for (int row = (blockIdx.x * 4 + wave) * R; row < vocab; row += total_waves * R) {
-        half8 w[R][NCH];
+        h8 w[R][NCH];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             // the table is read once per token by one wave: non-temporal (MI355X_MICROARCH.md, nt-weights);
@@ -146,7 +119,7 @@ __global__ __launch_bounds__(256) void k_logits_f16(const _Float16 *__restrict__
             const _Float16 *e = table + (size_t)(row + r < vocab ? row + r : vocab - 1) * hidden + 8 * lane;
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
-                w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const half8 *>(e + 512 * ((!GUARD || c < nchunks) ? c : 0)));
+                w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const h8 *>(e + 512 * ((!GUARD || c < nchunks) ? c : 0)));
         }
         float acc[R];
 #pragma unroll

@@ -30,10 +30,9 @@
 //   k_quant_rows_w              the 2-digit quantiser with one wave per row (long launches of rows <= 2560 columns)
 //   QB32 (k_rows_to_qb32, qb32_pack_unit, k_gemm_fp6<.., EPI = 1>)   producer-quantised block-scaled rows: no quantiser launch (opt-in)
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 // LDS image of an activation column (256 bytes = sixteen 16-byte units; unit 4 g + m is what lane group g reads for MFMA m):
 // the K = 32 form (WS == 3) pads the column to 272 bytes; every other form keeps 256 bytes and stores unit u of column c at
@@ -84,24 +83,6 @@ struct QuantArgs {
     float *inv_scale;
 };
 
-template <int CTRL>
-__device__ __forceinline__ float qdpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float qwave_max(float v) {
-    v = fmaxf(v, qdpp_f<0xB1>(v));
-    v = fmaxf(v, qdpp_f<0x4E>(v));
-    v = fmaxf(v, qdpp_f<0x141>(v));
-    v = fmaxf(v, qdpp_f<0x140>(v));
-    v = fmaxf(v, __shfl_xor(v, 16));
-    v = fmaxf(v, __shfl_xor(v, 32));
-    return v;
-}
-__device__ __forceinline__ double qwave_sum_d(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ---- activation rows -> digit planes --------------------------------------------------------
 // 256 threads per row, NV float4 per thread (cols <= 1024 * NV).
 // FP6 = 1 (NDIG = 2 only): the SAME 15-bit integer q = rint(x 2^(13 - E)) written as three balanced base-32 digits in fp6 (e2m3)
@@ -124,8 +105,7 @@ __global__ __launch_bounds__(256) void k_quant_rows(QuantArgs p) {
     for (int i = 0; i < NV; ++i) {
         const int idx = tid + 256 * i, ci = idx < nvec ? idx : nvec - 1;
         if (p.x_f16) {  // (wave-uniform)
-            typedef _Float16 qh4 __attribute__((ext_vector_type(4)));
-            const qh4 hv = *reinterpret_cast<const qh4 *>(reinterpret_cast<const _Float16 *>(p.x) + (size_t)rr * p.cols + 4 * ci);
+            const h4 hv = *reinterpret_cast<const h4 *>(reinterpret_cast<const _Float16 *>(p.x) + (size_t)rr * p.cols + 4 * ci);
             v[i] = float4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
         } else {
             v[i] = *reinterpret_cast<const float4 *>(p.x + (size_t)rr * p.cols + 4 * ci);
@@ -141,8 +121,8 @@ __global__ __launch_bounds__(256) void k_quant_rows(QuantArgs p) {
             s1 += (a + b) + (c + d);
             s2 += (a * a + b * b) + (c * c + d * d);
         }
-        s1 = qwave_sum_d(s1);
-        s2 = qwave_sum_d(s2);
+        s1 = wave64_sum_d_xor(s1);
+        s2 = wave64_sum_d_xor(s2);
         if (lane == 0) {
             stat[2 * wave] = s1;
             stat[2 * wave + 1] = s2;
@@ -167,7 +147,7 @@ __global__ __launch_bounds__(256) void k_quant_rows(QuantArgs p) {
     float am = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) am = fmaxf(fmaxf(am, fmaxf(fabsf(v[i].x), fabsf(v[i].y))), fmaxf(fabsf(v[i].z), fabsf(v[i].w)));
-    am = qwave_max(am);
+    am = wave64_max_f_rows_xor(am);
     if (lane == 0) smax[wave] = am;
     __syncthreads();
     am = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
@@ -251,33 +231,6 @@ __global__ __launch_bounds__(256) void k_quant_rows(QuantArgs p) {
     }
 }
 
-// f64 sum over the wave on the VALU: DPP steps inside a row of 16 lanes (quad_perm, row_half_mirror, row_mirror: each lane adds a partner
-// that holds the other half of its group), v_permlane16_swap / v_permlane32_swap across rows -- no ds_bpermute round trips.  Every
-// lane ends with the same value (a fixed order of additions).
-template <int CTRL>
-__device__ __forceinline__ double qdpp_d(double v) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, true);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double qswap_d(double v, bool rows32) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t l = (uint32_t)u, h = (uint32_t)(u >> 32);
-    // with both operands the same register the swap leaves (own, partner) in some order in the two results: their sum is what is wanted
-    const auto a = rows32 ? __builtin_amdgcn_permlane32_swap(l, l, false, false) : __builtin_amdgcn_permlane16_swap(l, l, false, false);
-    const auto b = rows32 ? __builtin_amdgcn_permlane32_swap(h, h, false, false) : __builtin_amdgcn_permlane16_swap(h, h, false, false);
-    return __builtin_bit_cast(double, ((uint64_t)b[0] << 32) | a[0]) + __builtin_bit_cast(double, ((uint64_t)b[1] << 32) | a[1]);
-}
-__device__ __forceinline__ double qwave_sum_d_valu(double v) {
-    v += qdpp_d<0xB1>(v);
-    v += qdpp_d<0x4E>(v);
-    v += qdpp_d<0x141>(v);
-    v += qdpp_d<0x140>(v);
-    v = qswap_d(v, false);
-    return qswap_d(v, true);
-}
-
 // ---- the 2-digit quantiser for rows of up to 2560 columns (round 5): ONE WAVE PER ROW ----------------
 // k_quant_rows<2, 3, FP6> is instruction bound, not memory bound (ISA count: ~2,600 wave-instructions per 2560-column row -- an IEEE
 // division per element for the LayerNorm, f64 butterflies over ds_bpermute, four workgroup barriers, the fp6 packing on 80 of 256
@@ -299,8 +252,7 @@ __global__ __launch_bounds__(256, 4) void k_quant_rows_w(QuantArgs p) {
     for (int i = 0; i < NV; ++i) {
         const int idx = lane + 64 * i, ci = idx < nvec ? idx : nvec - 1;
         if (p.x_f16) {  // (uniform)
-            typedef _Float16 qh4 __attribute__((ext_vector_type(4)));
-            const qh4 hv = *reinterpret_cast<const qh4 *>(reinterpret_cast<const _Float16 *>(p.x) + (size_t)rr * p.cols + 4 * ci);
+            const h4 hv = *reinterpret_cast<const h4 *>(reinterpret_cast<const _Float16 *>(p.x) + (size_t)rr * p.cols + 4 * ci);
             v[i] = float4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
         } else {
             v[i] = *reinterpret_cast<const float4 *>(p.x + (size_t)rr * p.cols + 4 * ci);
@@ -321,8 +273,8 @@ __global__ __launch_bounds__(256, 4) void k_quant_rows_w(QuantArgs p) {
             s1a += a, s1b += b, s1a += c, s1b += d;
             s2a = __builtin_fma(a, a, s2a), s2b = __builtin_fma(b, b, s2b), s2a = __builtin_fma(c, c, s2a), s2b = __builtin_fma(d, d, s2b);
         }
-        double s1 = qwave_sum_d_valu(s1a + s1b);
-        double s2 = qwave_sum_d_valu(s2a + s2b);
+        double s1 = wave64_sum_d_rows_permlane(s1a + s1b);
+        double s2 = wave64_sum_d_rows_permlane(s2a + s2b);
         const double mean_d = s1 / (double)p.cols, var_d = s2 / (double)p.cols - mean_d * mean_d;
         const float mean = (float)mean_d;
         denom = sqrtf((float)(var_d > 0.0 ? var_d : 0.0) + p.ln_eps);
@@ -337,7 +289,7 @@ __global__ __launch_bounds__(256, 4) void k_quant_rows_w(QuantArgs p) {
     float am = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) am = fmaxf(fmaxf(am, fmaxf(fabsf(v[i].x), fabsf(v[i].y))), fmaxf(fabsf(v[i].z), fabsf(v[i].w)));
-    am = qwave_max(am) / denom;
+    am = wave64_max_f_rows_xor(am) / denom;
     int be = (int)((__float_as_uint(am) >> 23) & 0xffu);
     be = be < 32 ? 32 : be;
     const float sc = __uint_as_float((uint32_t)(254 + S - be) << 23) / denom;  // 2^(S - E) / denom
@@ -405,15 +357,6 @@ __global__ __launch_bounds__(256, 4) void k_quant_rows_w(QuantArgs p) {
     }
 }
 
-__device__ __forceinline__ v4i gdecode16(uint32_t w, uint32_t lut) {
-    v4i a;
-    a[0] = (int)__builtin_amdgcn_perm(0u, lut, w & 0x03030303u);
-    a[1] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 2) & 0x03030303u);
-    a[2] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 4) & 0x03030303u);
-    a[3] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 6) & 0x03030303u);
-    return a;
-}
-
 // the same value from ONE conversion where the integer fits (a 32-block's digit sums are < 2^14 each): exact integer
 // d0 + 256 d1 (+ 65536 d2), rounded once by the conversion -- what the f32 additions of exact terms give too
 template <int NDIG>
@@ -421,16 +364,6 @@ __device__ __forceinline__ float combine_digits_i(const v4i *acc, int j) {
     if (NDIG == 2) return (float)(int)(((uint32_t)acc[1][j] << 8) + (uint32_t)acc[0][j]);
     if (NDIG == 3) return (float)(int)(((((uint32_t)acc[2][j] << 8) + (uint32_t)acc[1][j]) << 8) + (uint32_t)acc[0][j]);
     return (float)(int)(((uint32_t)acc[1][j] << 8) + (uint32_t)acc[0][j]) + (65536.0f * (float)acc[2][j] + 16777216.0f * (float)acc[3][j]);
-}
-__device__ __forceinline__ float gfma_mix_lo(float a, uint32_t h, float c) {  // a * f16(h[15:0]) + c
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float gfma_mix_hi(float a, uint32_t h, float c) {  // a * f16(h[31:16]) + c
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
-    return r;
 }
 
 template <int NDIG>
@@ -452,15 +385,13 @@ __device__ __forceinline__ float combine_digits(const v4i *acc, int j) {
 // memory instead cost 40 % of the prefill: 32 load instructions per K step).  Scales come as f16 tiles.
 // MINW = 4 waves per SIMD = two workgroups per CU (<= 128 registers): the narrow-token-tile form for launches whose wide-tile grid would
 // leave most CUs idle in its last round (a 2560-row matrix x 4096 tokens = 320 wide workgroups on 256 CUs).
-typedef unsigned gv4u __attribute__((ext_vector_type(4)));
-typedef float gv4f __attribute__((ext_vector_type(4)));
 
 // Output rows are written once and read by the NEXT kernel: stored non-temporal, they stop evicting the activation tiles and
 // weight slabs the K loops of the other workgroups are re-reading from L2 (4096 x 13824 outputs = 226 MB through 8 x 4 MB of L2).
 // Measured (tools/perf_gemm_ksweep.py): the launch's time over K is a line whose intercept is the stores' -- 80 -> 59 us at 13824
 // rows, 15.5 -> 10.3 at 2560 -- gate|up 299 -> 275 us, q|k|v 98 -> 93, o 78 -> 73, down 177 -> 172 (quantiser included).
 __device__ __forceinline__ void store_out4(float *dst, float a, float b, float c, float d) {
-    __builtin_nontemporal_store((gv4f){a, b, c, d}, reinterpret_cast<gv4f *>(dst));
+    __builtin_nontemporal_store((v4f){a, b, c, d}, reinterpret_cast<v4f *>(dst));
 }
 
 // f16 hand-over rows are clamped to +-65504 (an f16 element carries its own exponent: no row scale).  A clamp is COUNTED, not silent: the
@@ -547,16 +478,15 @@ __device__ __forceinline__ void store_wave_tiles(const GemmArgs &p, float (&val)
             }
         const int ra = 16 * (tile0 >> 1) + 4 * g;  // tile0 / 2 = the wave's first tile of the [m, rows / 2] output
         if (p.yh) {  // f16 rows for the down-projection's quantiser: half the bytes written here and read there (half_rows % 4 == 0 checked by the launcher)
-            typedef _Float16 sh4 __attribute__((ext_vector_type(4)));
             if (token < p.m) {
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
-                    sh4 o;
+                    h4 o;
                     bool sat = false;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = gclamp_f16(r[pr][j], sat);
                     gflush_sat(sat);
-                    *reinterpret_cast<sh4 *>(p.yh + (size_t)token * half_rows + ra + 16 * pr) = o;  // (non-temporal: no gain, 257-275 vs 261-291 us same box)
+                    *reinterpret_cast<h4 *>(p.yh + (size_t)token * half_rows + ra + 16 * pr) = o;  // (non-temporal: no gain, 257-275 vs 261-291 us same box)
                 }
             }
         } else if ((half_rows & 3) == 0) {
@@ -620,18 +550,18 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
         bdst[i] = col * CSTR + (WS == 3 ? seg : seg ^ col_swz(col & 15)) * 16;
     }
     constexpr int kBuf = WG_COLS * CSTR;  // one activation tile in LDS; the unscaled variant keeps two
-    gv4u wn[4], bn[NB];  // native vectors: arrays of HIP's uint4 struct are kept in scratch memory by this compiler
+    v4u wn[4], bn[NB];  // native vectors: arrays of HIP's uint4 struct are kept in scratch memory by this compiler
     if (!WS) {
         // prologue: activation tile 0 -> LDS buffer 0, tile 1's loads in flight; weights of step 0 in flight
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) wn[rt] = *reinterpret_cast<const gv4u *>(wptr[rt]);
+        for (int rt = 0; rt < 4; ++rt) wn[rt] = *reinterpret_cast<const v4u *>(wptr[rt]);
 #pragma unroll
-        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(bsrc[i]);
+        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(bsrc[i]);
 #pragma unroll
-        for (int i = 0; i < NB; ++i) *reinterpret_cast<gv4u *>(lds + bdst[i]) = bn[i];
+        for (int i = 0; i < NB; ++i) *reinterpret_cast<v4u *>(lds + bdst[i]) = bn[i];
         const int n1 = p.nblk > 1 ? 1 : 0;
 #pragma unroll
-        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(bsrc[i] + (size_t)n1 * 256);
+        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(bsrc[i] + (size_t)n1 * 256);
         __syncthreads();
     }
     v4i acc[4][CT];
@@ -671,7 +601,7 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
 
     // K = 32 form: this lane's f16 scale tiles, one 16-byte load per (row tile, 64 columns)
     const uint16_t *sptr[WS == 3 ? 4 : 1];
-    gv4u scn[WS == 3 ? 4 : 1];
+    v4u scn[WS == 3 ? 4 : 1];
     const int sh3 = 4 * (g & 1);  // this lane's columns are the low (g even) or high nibble half of each source byte
     uint8_t *wst = lds + kBuf + wave * 4096;                                       // WS == 3: this wave's tile staging area
     const uint8_t *wrd = wst + c * 16 + 4 * (g >> 1);                              //          and where this lane reads it back
@@ -681,7 +611,7 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
             int t = bx * 16 + rw * 4 + rt;
             t = t < n_tiles ? t : n_tiles - 1;
             sptr[rt] = p.stiles_h + (size_t)t * p.nblk * 128 + 8 * g;
-            scn[rt] = *reinterpret_cast<const gv4u *>(sptr[rt]);
+            scn[rt] = *reinterpret_cast<const v4u *>(sptr[rt]);
         }
     }
 
@@ -689,18 +619,18 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
         const uint8_t *bcur = bread;
         if (WS) {  // scaled variant: registers go to the f32 accumulators: single buffer, no prefetch
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt) wn[rt] = *reinterpret_cast<const gv4u *>(wptr[rt] + (size_t)blk * 1024);
+            for (int rt = 0; rt < 4; ++rt) wn[rt] = *reinterpret_cast<const v4u *>(wptr[rt] + (size_t)blk * 1024);
 #pragma unroll
-            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(bsrc[i] + (size_t)blk * 256);
+            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(bsrc[i] + (size_t)blk * 256);
             __syncthreads();  // the previous step's LDS reads are done
 #pragma unroll
-            for (int i = 0; i < NB; ++i) *reinterpret_cast<gv4u *>(lds + bdst[i]) = bn[i];
+            for (int i = 0; i < NB; ++i) *reinterpret_cast<v4u *>(lds + bdst[i]) = bn[i];
             if (WS == 3) {
                 // the K = 32 operand of lane (r, g) is eight 2-bit fields of ONE dword of lane (r, i)'s 16 bytes (blocks 2 i,
                 // 2 i + 1): the wave's four 1-KiB tiles pass through a wave-private LDS area and are read back in that deal
                 // (the barrier below also orders these stores before the reads)
 #pragma unroll
-                for (int rt = 0; rt < 4; ++rt) *reinterpret_cast<gv4u *>(wst + rt * 1024 + lane * 16) = wn[rt];
+                for (int rt = 0; rt < 4; ++rt) *reinterpret_cast<v4u *>(wst + rt * 1024 + lane * 16) = wn[rt];
             }
             __syncthreads();
         } else {
@@ -714,21 +644,21 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
             if (blk + 1 < p.nblk) {
 #endif
 #pragma unroll
-                for (int i = 0; i < NB; ++i) *reinterpret_cast<gv4u *>(nxt + bdst[i]) = bn[i];
+                for (int i = 0; i < NB; ++i) *reinterpret_cast<v4u *>(nxt + bdst[i]) = bn[i];
             }
         }
-        gv4u wc[4];
+        v4u wc[4];
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) wc[rt] = wn[rt];
         if (!WS) {
             const int n1 = blk + 1 < p.nblk ? blk + 1 : p.nblk - 1, n2 = blk + 2 < p.nblk ? blk + 2 : p.nblk - 1;
 #if !(defined(BH_ABLATE) && (BH_ABLATE & 32))  // developer build: no weight loads in the loop
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt) wn[rt] = *reinterpret_cast<const gv4u *>(wptr[rt] + (size_t)n1 * 1024);  // next step's weights
+            for (int rt = 0; rt < 4; ++rt) wn[rt] = *reinterpret_cast<const v4u *>(wptr[rt] + (size_t)n1 * 1024);  // next step's weights
 #endif
 #if !(defined(BH_ABLATE) && (BH_ABLATE & 8))  // developer build: no activation tile loads
 #pragma unroll
-            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(bsrc[i] + (size_t)n2 * 256);
+            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(bsrc[i] + (size_t)n2 * 256);
 #endif
         }
         if (WS == 3) {
@@ -736,14 +666,14 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
             for (int i = 0; i < 4; ++i) {  // dword i of the lane = 32-blocks 2 i, 2 i + 1 of this 256-block
                 // scales of step (blk, i): 16 bytes per row tile = rows 4 g .. 4 g + 3 x (block 2 i, 2 i + 1); the next step's
                 // are requested now and used one iteration later
-                gv4u scc[4];
+                v4u scc[4];
 #pragma unroll
                 for (int rt = 0; rt < 4; ++rt) scc[rt] = scn[rt];
                 {
                     int nx = blk * 4 + i + 1;
                     nx = nx < p.nblk * 4 ? nx : p.nblk * 4 - 1;
 #pragma unroll
-                    for (int rt = 0; rt < 4; ++rt) scn[rt] = *reinterpret_cast<const gv4u *>(sptr[rt] + 32 * nx);
+                    for (int rt = 0; rt < 4; ++rt) scn[rt] = *reinterpret_cast<const v4u *>(sptr[rt] + 32 * nx);
                 }
                 v4i a[4];
 #pragma unroll
@@ -778,7 +708,7 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
 #pragma unroll
                             for (int tt = 0; tt < TTW; ++tt) {
                                 const float cv = combine_digits_i<NDIG>(&acc[rt][tt * NDIG], j);
-                                facc[rt][tt][j] = hb ? gfma_mix_hi(cv, sw[j], facc[rt][tt][j]) : gfma_mix_lo(cv, sw[j], facc[rt][tt][j]);
+                                facc[rt][tt][j] = hb ? fma_mix_hi(cv, sw[j], facc[rt][tt][j]) : fma_mix_lo(cv, sw[j], facc[rt][tt][j]);
                             }
                         }
                     }
@@ -794,7 +724,7 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
 #if defined(BH_ABLATE) && (BH_ABLATE & 2)  // developer build: no code expansion
                     a[rt] = (v4i){(int)wd, (int)(wd >> 1), (int)(wd >> 2), (int)(wd >> 3)};
 #else
-                    a[rt] = gdecode16(wd, p.lut);
+                    a[rt] = decode16(wd, p.lut);
 #endif
                 }
 #pragma unroll
@@ -822,7 +752,7 @@ __global__ __launch_bounds__(256 * CW, MINW) void k_gemm_mfma(GemmArgs p) {
 #pragma unroll
                         for (int rt = 0; rt < 4; ++rt) {
                             const uint32_t lo = mm == 0 ? wc[rt].x : wc[rt].y, hi = mm == 0 ? wc[rt].z : wc[rt].w;
-                            a[rt] = gdecode16(mp == 0 ? lo : hi, p.lut);  // dword m = 2 mp + mm
+                            a[rt] = decode16(mp == 0 ? lo : hi, p.lut);  // dword m = 2 mp + mm
                         }
 #pragma unroll
                         for (int ct = 0; ct < CT; ++ct) {
@@ -909,8 +839,7 @@ __global__ __launch_bounds__(256) void k_quant_rows_f16(QuantArgs p) {
         const int idx = tid + 256 * i, ci = idx < nvec ? idx : nvec - 1;
         if (p.x_f16) {  // (wave-uniform) f16 rows from the producing kernel (BITNET_HIP_FUSE_X_F16), as k_quant_rows reads them:
                         // without this branch the QK256 route of BITNET_HIP_GEMM_F16A=1 read the f16 buffer as f32 rows
-            typedef _Float16 qh4 __attribute__((ext_vector_type(4)));
-            const qh4 hv = *reinterpret_cast<const qh4 *>(reinterpret_cast<const _Float16 *>(p.x) + (size_t)rr * p.cols + 4 * ci);
+            const h4 hv = *reinterpret_cast<const h4 *>(reinterpret_cast<const _Float16 *>(p.x) + (size_t)rr * p.cols + 4 * ci);
             v[i] = float4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
         } else {
             v[i] = *reinterpret_cast<const float4 *>(p.x + (size_t)rr * p.cols + 4 * ci);
@@ -925,8 +854,8 @@ __global__ __launch_bounds__(256) void k_quant_rows_f16(QuantArgs p) {
             s1 += (a + b) + (c + d);
             s2 += (a * a + b * b) + (c * c + d * d);
         }
-        s1 = qwave_sum_d(s1);
-        s2 = qwave_sum_d(s2);
+        s1 = wave64_sum_d_xor(s1);
+        s2 = wave64_sum_d_xor(s2);
         if (lane == 0) {
             stat[2 * wave] = s1;
             stat[2 * wave + 1] = s2;
@@ -951,7 +880,7 @@ __global__ __launch_bounds__(256) void k_quant_rows_f16(QuantArgs p) {
     float am = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) am = fmaxf(fmaxf(am, fmaxf(fabsf(v[i].x), fabsf(v[i].y))), fmaxf(fabsf(v[i].z), fabsf(v[i].w)));
-    am = qwave_max(am);
+    am = wave64_max_f_rows_xor(am);
     if (lane == 0) smax[wave] = am;
     __syncthreads();
     am = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
@@ -965,14 +894,10 @@ __global__ __launch_bounds__(256) void k_quant_rows_f16(QuantArgs p) {
     for (int i = 0; i < NV; ++i) {
         const int idx = tid + 256 * i;
         if (idx >= kvec) continue;
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         const h4 o = {(_Float16)(v[i].x * sc), (_Float16)(v[i].y * sc), (_Float16)(v[i].z * sc), (_Float16)(v[i].w * sc)};
         *reinterpret_cast<h4 *>(base + 4 * idx) = o;
     }
 }
-
-typedef _Float16 gh2 __attribute__((ext_vector_type(2)));
-typedef _Float16 gh8 __attribute__((ext_vector_type(8)));
 
 // ================================================================================================================================
 // k_gemm_f16a: both storage formats on the f16 matrix cores.  Round 3's form (k_gemm_f16w) made one MFMA = one 32-block, for which each
@@ -992,17 +917,17 @@ typedef _Float16 gh8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ int fswz(int c) { return (c & 3) | ((c & 8) >> 1); }
 
 template <int FMT>
-__device__ __forceinline__ gh8 expand8_f16(uint32_t w, int h, uint32_t lut_hi, gh2 s2) {
+__device__ __forceinline__ h8 expand8_f16(uint32_t w, int h, uint32_t lut_hi, h2 s2) {
     const uint32_t ca = (w >> (4 * h)) & 0x03030303u, cb = (w >> (4 * h + 2)) & 0x03030303u;
     uint32_t t[4];
     t[0] = __builtin_amdgcn_perm(0u, lut_hi, __builtin_amdgcn_perm(0x0C0C0C0Cu, ca, 0x01040004u));
     t[1] = __builtin_amdgcn_perm(0u, lut_hi, __builtin_amdgcn_perm(0x0C0C0C0Cu, ca, 0x03040204u));
     t[2] = __builtin_amdgcn_perm(0u, lut_hi, __builtin_amdgcn_perm(0x0C0C0C0Cu, cb, 0x01040004u));
     t[3] = __builtin_amdgcn_perm(0u, lut_hi, __builtin_amdgcn_perm(0x0C0C0C0Cu, cb, 0x03040204u));
-    gh2 w2[4];
+    h2 w2[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) w2[q] = FMT == 1 ? __builtin_bit_cast(gh2, t[q]) * s2 : __builtin_bit_cast(gh2, t[q]);
-    return (gh8){w2[0][0], w2[0][1], w2[1][0], w2[1][1], w2[2][0], w2[2][1], w2[3][0], w2[3][1]};
+    for (int q = 0; q < 4; ++q) w2[q] = FMT == 1 ? __builtin_bit_cast(h2, t[q]) * s2 : __builtin_bit_cast(h2, t[q]);
+    return (h8){w2[0][0], w2[0][1], w2[1][0], w2[1][1], w2[2][0], w2[2][1], w2[3][0], w2[3][1]};
 }
 
 // ================================================================================================================================
@@ -1082,7 +1007,7 @@ __global__ __launch_bounds__(256) void k_rows_to_qb32(const float *__restrict__ 
         }
         *reinterpret_cast<float4 *>(qb_row + ((i >> 3) * 9 + (i & 7)) * 4) = v;
     }
-    s1 = qwave_sum_d(s1), s2 = qwave_sum_d(s2);
+    s1 = wave64_sum_d_xor(s1), s2 = wave64_sum_d_xor(s2);
     if (lane == 0) red[2 * wave] = s1, red[2 * wave + 1] = s2;
     __syncthreads();
     if (tid == 0 && stats) {
@@ -1158,7 +1083,7 @@ struct ChainLnStats {
 // QB = true (TTW = 4 only): the outputs also leave as QB32 of gamma_out * y for the next fp6-form matmul (GemmArgs::qb_out): a token's NW RT / 2 units of
 // 32 output rows are staged in LDS half a token tile (32 tokens) at a time and packed one unit per work item (qb32_pack_unit).
 template <int RT, int TTW, int NW, bool QB = false>
-__device__ __forceinline__ void f16_chain_epilogue(const GemmArgs &p, gv4f (&acc)[RT][TTW], uint8_t *lds, const float2 *mu_rs, int bx, int by, int rw, int c, int g, int tid) {
+__device__ __forceinline__ void f16_chain_epilogue(const GemmArgs &p, v4f (&acc)[RT][TTW], uint8_t *lds, const float2 *mu_rs, int bx, int by, int rw, int c, int g, int tid) {
     static_assert(!QB || TTW == 4, "the QB32 hand-over is staged in two halves of a 64-token tile");
     constexpr int WG_TOK = TTW * 16;
     const int tile0 = bx * (NW * RT) + rw * RT;
@@ -1172,7 +1097,6 @@ __device__ __forceinline__ void f16_chain_epilogue(const GemmArgs &p, gv4f (&acc
         lng[rt][0] = lg.x, lng[rt][1] = lg.y, lng[rt][2] = lg.z, lng[rt][3] = lg.w;
         gout[rt][0] = go.x, gout[rt][1] = go.y, gout[rt][2] = go.z, gout[rt][3] = go.w;
     }
-    typedef _Float16 gh4 __attribute__((ext_vector_type(4)));
     bool sat = false;  // an f16 hand-over value of a live token was clamped (counted once per lane at the end)
 #pragma unroll
     for (int tt = 0; tt < TTW; ++tt) {
@@ -1199,10 +1123,10 @@ __device__ __forceinline__ void f16_chain_epilogue(const GemmArgs &p, gv4f (&acc
                 }
                 if (live) {
                     if (p.yh) {
-                        gh4 o;
+                        h4 o;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) o[j] = gclamp_f16(r[j], sat);
-                        *reinterpret_cast<gh4 *>(p.yh + (size_t)token * half_rows + ra + 16 * pr) = o;
+                        *reinterpret_cast<h4 *>(p.yh + (size_t)token * half_rows + ra + 16 * pr) = o;
                     }
                     if (p.y) store_out4(p.y + (size_t)token * half_rows + ra + 16 * pr, r[0], r[1], r[2], r[3]);
                 }
@@ -1223,10 +1147,10 @@ __device__ __forceinline__ void f16_chain_epilogue(const GemmArgs &p, gv4f (&acc
             if (live) {
                 if (p.y) *reinterpret_cast<float4 *>(p.y + off) = float4{val[rt][0], val[rt][1], val[rt][2], val[rt][3]};
                 if (p.yh) {
-                    gh4 o;
+                    h4 o;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = gclamp_f16(val[rt][j] * gout[rt][j], sat);
-                    *reinterpret_cast<gh4 *>(p.yh + off) = o;
+                    *reinterpret_cast<h4 *>(p.yh + off) = o;
                 }
             }
             if (QB) {  // stage gamma_out * y: token (tt & 1) 16 + c of this half, columns 16 (rw RT + rt) + 4 g .. + 3 of the workgroup's NW RT 16
@@ -1308,30 +1232,30 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16a(GemmArgs p, uint32_t lut_h
     int boff[8];  // this lane's unit of MFMA (m, h): 8 g + ((2 m + h) ^ fswz(c))
 #pragma unroll
     for (int u = 0; u < 8; ++u) boff[u] = c * ROWB + 128 * g + ((u ^ fswz(c)) * 16);
-    gv4f acc[RT][TTW];
+    v4f acc[RT][TTW];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (gv4f){0.f, 0.f, 0.f, 0.f};
+        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (v4f){0.f, 0.f, 0.f, 0.f};
     ChainLnStats<WG_TOK, 4> lnst;
     const bool ln_in = EPI && p.stats_in;
     if (ln_in) lnst.issue(p, by, tid);
-    gv4u wn[RT], bn[NB];
+    v4u wn[RT], bn[NB];
     uint32_t sn[RT];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) wn[rt] = *reinterpret_cast<const gv4u *>(wptr[rt]), sn[rt] = 0;
+    for (int rt = 0; rt < RT; ++rt) wn[rt] = *reinterpret_cast<const v4u *>(wptr[rt]), sn[rt] = 0;
     if (FMT == 1) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) sn[rt] = sptr[rt][0];
     }
 #pragma unroll
-    for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(bsrc[i]);
+    for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(bsrc[i]);
 #pragma unroll
-    for (int i = 0; i < NB; ++i) *reinterpret_cast<gv4u *>(lds + bdst[i]) = bn[i];
+    for (int i = 0; i < NB; ++i) *reinterpret_cast<v4u *>(lds + bdst[i]) = bn[i];
     {
         const int n1 = p.nblk > 1 ? 1 : 0;
 #pragma unroll
-        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(bsrc[i] + (size_t)n1 * 512);
+        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(bsrc[i] + (size_t)n1 * 512);
     }
     // the input LayerNorm's (mean, 1 / denom) per token and the reduction's scratch, behind the tile buffers
     float2 *mu_rs = reinterpret_cast<float2 *>(lds + 2 * kBuf);
@@ -1366,17 +1290,17 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16a(GemmArgs p, uint32_t lut_h
         uint8_t *nxt = lds + ((blk + 1) & 1) * kBuf;
         if (blk + 1 < p.nblk) {
 #pragma unroll
-            for (int i = 0; i < NB; ++i) *reinterpret_cast<gv4u *>(nxt + bdst[i]) = bn[i];
+            for (int i = 0; i < NB; ++i) *reinterpret_cast<v4u *>(nxt + bdst[i]) = bn[i];
         }
         F16A_PHASE(0);
-        gv4u wc[RT];
+        v4u wc[RT];
         uint32_t sc[RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) wc[rt] = wn[rt], sc[rt] = sn[rt];
         {
             const int n1 = blk + 1 < p.nblk ? blk + 1 : p.nblk - 1, n2 = blk + 2 < p.nblk ? blk + 2 : p.nblk - 1;
 #pragma unroll
-            for (int rt = 0; rt < RT; ++rt) wn[rt] = *reinterpret_cast<const gv4u *>(wptr[rt] + (size_t)n1 * 1024);
+            for (int rt = 0; rt < RT; ++rt) wn[rt] = *reinterpret_cast<const v4u *>(wptr[rt] + (size_t)n1 * 1024);
             if (FMT == 1) {
 #pragma unroll
 #if defined(BH_ABLATE) && (BH_ABLATE & 4)  // developer build: no scale loads in the loop
@@ -1386,7 +1310,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16a(GemmArgs p, uint32_t lut_h
 #endif
             }
 #pragma unroll
-            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(bsrc[i] + (size_t)n2 * 512);
+            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(bsrc[i] + (size_t)n2 * 512);
         }
         F16A_PHASE(1);
 #ifdef BH_IGLP
@@ -1396,14 +1320,14 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16a(GemmArgs p, uint32_t lut_h
         for (int m = 0; m < 4; ++m) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                gh8 a[RT];
+                h8 a[RT];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     const uint32_t wd = m == 0 ? wc[rt].x : m == 1 ? wc[rt].y : m == 2 ? wc[rt].z : wc[rt].w;
                     // (s, s) of this lane's 32-block 2 g + (m >> 1): low / high half of its scale dword
-                    const gh2 s2 = __builtin_bit_cast(gh2, __builtin_amdgcn_perm(0u, sc[rt], (m >> 1) ? 0x03020302u : 0x01000100u));
+                    const h2 s2 = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0u, sc[rt], (m >> 1) ? 0x03020302u : 0x01000100u));
 #if defined(BH_ABLATE) && (BH_ABLATE & 2)  // developer build: no code expansion
-                    a[rt] = __builtin_bit_cast(gh8, (gv4u){wd, wd >> (h + 1), sc[rt], wd ^ lut_hi});
+                    a[rt] = __builtin_bit_cast(h8, (v4u){wd, wd >> (h + 1), sc[rt], wd ^ lut_hi});
 #else
                     a[rt] = expand8_f16<FMT>(wd, h, lut_hi, s2);
 #endif
@@ -1411,9 +1335,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16a(GemmArgs p, uint32_t lut_h
 #pragma unroll
                 for (int ct = 0; ct < TTW; ++ct) {
 #if defined(BH_ABLATE) && (BH_ABLATE & 1)  // developer build: no LDS operand reads
-                    const gh8 b = __builtin_bit_cast(gh8, (gv4u){(unsigned)(ct + blk), (unsigned)m, (unsigned)h, 1u});
+                    const h8 b = __builtin_bit_cast(h8, (v4u){(unsigned)(ct + blk), (unsigned)m, (unsigned)h, 1u});
 #else
-                    const gh8 b = *reinterpret_cast<const gh8 *>(bcur + ct * 16 * ROWB + boff[2 * m + h]);
+                    const h8 b = *reinterpret_cast<const h8 *>(bcur + ct * 16 * ROWB + boff[2 * m + h]);
 #endif
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rt], b, acc[rt][ct], 0, 0, 0);
@@ -1461,16 +1385,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16a(GemmArgs p, uint32_t lut_h
 // q ^ ((c & 3) | (c & 8)) -- conflict-free for the four 16-lane service groups of ds_read_b128 (brute-forced).  Chain epilogue only (EPI = 1 of
 // k_gemm_f16a), four row tiles per wave.  The launcher pairs it with k_gemm_f16a: 128-token workgroups on as many row blocks as fill whole rounds of
 // the 512 slots, 64-token workgroups on the rest (13824 rows x 4096 tokens: 48 x 32 = 1536 = 3 rounds, then 6 x 64 = 384 half-length ones).
-// LDS-DMA: 64 lanes x 16 B from (scalar base + per-lane byte offset) to LDS bytes [lds_dst, lds_dst + 1024) -- no VGPR staging (kernels_prefill_attn.hip
-// uses the same form).  Invisible to hipcc's vmcnt bookkeeping: the kernel waits for its pieces with an explicit s_waitcnt vmcnt(0) ahead of the barrier
-// that publishes the tile; hipcc's own waits for the weight loads only ever over-wait (loads return in order).
-__device__ __forceinline__ void gdma1k(unsigned lane_off, const void *sbase, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(lane_off), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
+// The activation tile is staged by LDS-DMA (lds_dma_1k, wave.hpp).
 
 // Register loads as BUFFER loads (SGPR resource descriptor + scalar offset + one 32-bit lane offset): written as pointer arithmetic hipcc folds base + offset
 // into eight 64-bit VGPR pointers and spills them around k_gemm_f16h's 128 accumulators; as buffer loads they cost one VGPR and stay visible to hipcc's
@@ -1531,7 +1446,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16h(GemmArgs p, uint32_t lut_h
         const uint8_t *src = abase + (size_t)(s >> 1) * 512 + (size_t)(s & 1) * 64;
         const unsigned dst = lds0 + (unsigned)buf * kBuf + (unsigned)(8 * wave) * 1024u;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) gdma1k(dsrc[i & 3], src + (size_t)(i >> 2) * 16 * row_b, dst + 1024u * i);
+        for (int i = 0; i < 8; ++i) lds_dma_1k(dsrc[i & 3], src + (size_t)(i >> 2) * 16 * row_b, dst + 1024u * i);
     };
     int boff[4];  // this lane's unit of MFMA k = 2 (m - 2 hs) + h
 #pragma unroll
@@ -1539,10 +1454,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16h(GemmArgs p, uint32_t lut_h
     ChainLnStats<WG_TOK, 4> lnst;
     const bool ln_in = p.stats_in != nullptr;
     if (ln_in) lnst.issue(p, by, tid);
-    gv4u wn[RT];
+    v4u wn[RT];
     uint32_t sn[RT];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) wn[rt] = __builtin_bit_cast(gv4u, __builtin_amdgcn_raw_buffer_load_b128(rs_w, woff, wptr[rt], 0)), sn[rt] = 0;
+    for (int rt = 0; rt < RT; ++rt) wn[rt] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs_w, woff, wptr[rt], 0)), sn[rt] = 0;
     if (FMT == 1) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) sn[rt] = __builtin_amdgcn_raw_buffer_load_b32(rs_s, soff, sptr[rt], 0);
@@ -1555,21 +1470,21 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16h(GemmArgs p, uint32_t lut_h
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (ln_in) lnst.final(p, ln_red, mu_rs, tid);
-    gv4f acc[RT][TTW];  // (declared behind the statistics' twenty registers: with both live the prologue spilled)
+    v4f acc[RT][TTW];  // (declared behind the statistics' twenty registers: with both live the prologue spilled)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (gv4f){0.f, 0.f, 0.f, 0.f};
+        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (v4f){0.f, 0.f, 0.f, 0.f};
     for (int blk = 0; blk < p.nblk; ++blk) {
         // this block's weights / scales become current; the next block's are requested
-        gv4u wc[RT];
+        v4u wc[RT];
         uint32_t sc[RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) wc[rt] = wn[rt], sc[rt] = sn[rt];
         {
             const int n1 = blk + 1 < p.nblk ? blk + 1 : p.nblk - 1;
 #pragma unroll
-            for (int rt = 0; rt < RT; ++rt) wn[rt] = __builtin_bit_cast(gv4u, __builtin_amdgcn_raw_buffer_load_b128(rs_w, woff, wptr[rt] + n1 * 1024, 0));
+            for (int rt = 0; rt < RT; ++rt) wn[rt] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs_w, woff, wptr[rt] + n1 * 1024, 0));
             if (FMT == 1) {
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) sn[rt] = __builtin_amdgcn_raw_buffer_load_b32(rs_s, soff, sptr[rt] + n1 * 256, 0);
@@ -1584,17 +1499,17 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16h(GemmArgs p, uint32_t lut_h
             for (int mm = 0; mm < 2; ++mm) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    gh8 a[RT];
+                    h8 a[RT];
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
                         // dword m = 2 hs + mm of the lane's 16 bytes; (s, s) of its 32-block 2 g + hs: low / high half of the scale dword
                         const uint32_t wd = hs == 0 ? (mm == 0 ? wc[rt].x : wc[rt].y) : (mm == 0 ? wc[rt].z : wc[rt].w);
-                        const gh2 s2v = __builtin_bit_cast(gh2, __builtin_amdgcn_perm(0u, sc[rt], hs ? 0x03020302u : 0x01000100u));
+                        const h2 s2v = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0u, sc[rt], hs ? 0x03020302u : 0x01000100u));
                         a[rt] = expand8_f16<FMT>(wd, h, lut_hi, s2v);
                     }
 #pragma unroll
                     for (int ct = 0; ct < TTW; ++ct) {
-                        const gh8 b = *reinterpret_cast<const gh8 *>(bcur + ct * 16 * ROWB + boff[2 * mm + h]);
+                        const h8 b = *reinterpret_cast<const h8 *>(bcur + ct * 16 * ROWB + boff[2 * mm + h]);
 #pragma unroll
                         for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rt], b, acc[rt][ct], 0, 0, 0);
                     }
@@ -1623,8 +1538,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16h(GemmArgs p, uint32_t lut_h
 // Activation tile in LDS: [g 4][token 16 TTW][144 bytes = digit 3 x m 2 x 24]: a lane's nine 16-byte units are contiguous, and the
 // sixteen lanes of every ds_read_b128 service group (MI355X_MICROARCH.md, LDS: all 16 tokens, mixed g) touch units 9 c + const
 // (mod 16): sixteen different ones, since 9 is odd and a group's slab is a multiple of 16 units -- conflict-free without padding.
-typedef int gv8i __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ void expand16_fp4(uint32_t w, uint32_t lut4, int &o0, int &o1) {
     const uint32_t p0 = __builtin_amdgcn_perm(0u, lut4, w & 0x03030303u), p1 = __builtin_amdgcn_perm(0u, lut4, (w >> 2) & 0x03030303u);
     const uint32_t p2 = __builtin_amdgcn_perm(0u, lut4, (w >> 4) & 0x03030303u), p3 = __builtin_amdgcn_perm(0u, lut4, (w >> 6) & 0x03030303u);
@@ -1638,7 +1551,7 @@ __device__ __forceinline__ void expand16_fp4(uint32_t w, uint32_t lut4, int &o0,
 __global__ void k_retile_fp4(const uint8_t *__restrict__ tiles, uint8_t *__restrict__ tiles4, uint32_t lut4, size_t total16) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // one 16-byte lane segment of the streaming tiles each
     if (i >= total16) return;
-    const gv4u w = *reinterpret_cast<const gv4u *>(tiles + i * 16);
+    const v4u w = *reinterpret_cast<const v4u *>(tiles + i * 16);
     int e[8];
     expand16_fp4(w.x, lut4, e[0], e[1]);
     expand16_fp4(w.y, lut4, e[2], e[3]);
@@ -1709,26 +1622,26 @@ __global__ __launch_bounds__(256, (TTW >= 4 || EPI) ? 2 : TTW == 2 ? 3 : 4) void
     ChainLnStats<T, 4> lnst;
     const bool ln_in = EPI && p.stats_in;
     if (ln_in) lnst.issue(p, by, tid);
-    gv4f acc[RT][TTW];
+    v4f acc[RT][TTW];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (gv4f){0.f, 0.f, 0.f, 0.f};
-    gv4u wn[NM][RT], bn[NB];
+        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (v4f){0.f, 0.f, 0.f, 0.f};
+    v4u wn[NM][RT], bn[NB];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int m = 0; m < NM; ++m) wn[m][rt] = *reinterpret_cast<const gv4u *>(wptr[rt] + m * 1024 + woff);
+        for (int m = 0; m < NM; ++m) wn[m][rt] = *reinterpret_cast<const v4u *>(wptr[rt] + m * 1024 + woff);
 #pragma unroll
-    for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(abase + bsrc[i]);
+    for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(abase + bsrc[i]);
     if (e_thr) exn = *reinterpret_cast<const gv2u *>(abase + esrc);
 #pragma unroll
-    for (int i = 0; i < NB; ++i) *reinterpret_cast<gv4u *>(lds + bdst[i]) = bn[i];
+    for (int i = 0; i < NB; ++i) *reinterpret_cast<v4u *>(lds + bdst[i]) = bn[i];
     if (e_thr) *reinterpret_cast<gv2u *>(lds + kDig + tid * 8) = exn;
     {
         const int n1 = p.nblk > 1 ? 1 : 0;
 #pragma unroll
-        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(abase + (size_t)n1 * REC + bsrc[i]);
+        for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(abase + (size_t)n1 * REC + bsrc[i]);
         if (e_thr) exn = *reinterpret_cast<const gv2u *>(abase + (size_t)n1 * REC + esrc);
     }
     // (EPI) the input LayerNorm's (mean, 1 / denom) per token and the reduction's scratch, behind the tile buffers
@@ -1749,10 +1662,10 @@ __global__ __launch_bounds__(256, (TTW >= 4 || EPI) ? 2 : TTW == 2 ? 3 : 4) void
         uint8_t *nxt = lds + ((blk + 1) & 1) * kBuf;
         if (blk + 1 < p.nblk) {
 #pragma unroll
-            for (int i = 0; i < NB; ++i) *reinterpret_cast<gv4u *>(nxt + bdst[i]) = bn[i];
+            for (int i = 0; i < NB; ++i) *reinterpret_cast<v4u *>(nxt + bdst[i]) = bn[i];
             if (e_thr) *reinterpret_cast<gv2u *>(nxt + kDig + tid * 8) = exn;
         }
-        gv4u wc[NM][RT];
+        v4u wc[NM][RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -1762,9 +1675,9 @@ __global__ __launch_bounds__(256, (TTW >= 4 || EPI) ? 2 : TTW == 2 ? 3 : 4) void
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-                for (int m = 0; m < NM; ++m) wn[m][rt] = *reinterpret_cast<const gv4u *>(wptr[rt] + (size_t)n1 * WSTEP + m * 1024 + woff);
+                for (int m = 0; m < NM; ++m) wn[m][rt] = *reinterpret_cast<const v4u *>(wptr[rt] + (size_t)n1 * WSTEP + m * 1024 + woff);
 #pragma unroll
-            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const gv4u *>(abase + (size_t)n2 * REC + bsrc[i]);
+            for (int i = 0; i < NB; ++i) bn[i] = *reinterpret_cast<const v4u *>(abase + (size_t)n2 * REC + bsrc[i]);
             if (e_thr) exn = *reinterpret_cast<const gv2u *>(abase + (size_t)n2 * REC + esrc);
         }
         if (EPI) {
@@ -1811,8 +1724,8 @@ __global__ __launch_bounds__(256, (TTW >= 4 || EPI) ? 2 : TTW == 2 ? 3 : 4) void
             }
             if (PIPE) __builtin_amdgcn_sched_barrier(0);
             const v4i r0 = rr[grp & 1][0], r1 = rr[grp & 1][1], r2 = rr[grp & 1][2];
-            const gv8i b0 = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, -1, -1);
-            const gv8i b1 = __builtin_shufflevector(r1, r2, 2, 3, 4, 5, 6, 7, -1, -1);
+            const v8i b0 = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, -1, -1);
+            const v8i b1 = __builtin_shufflevector(r1, r2, 2, 3, 4, 5, 6, 7, -1, -1);
             // B scale byte (byte 0 of the operand): the digit's weight 2^(3 + 5 d) -- times the unit's own 2^(E_u - 13) on QB32 rows (s_u + 5 d)
             const int sb0 = EPI ? (int)(ec[ct] & 0xffu) + 5 * d : 130 + 5 * d, sb1 = EPI ? (int)(ec[ct] >> 8) + 5 * d : 130 + 5 * d;
 #pragma unroll
@@ -1906,13 +1819,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_fp6w(GemmArgs p) {
         const uint8_t *src = abase + (size_t)blk * 576;
         const unsigned dst = lds0 + (unsigned)buf * kBuf + (unsigned)wave * 9216u;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) gdma1k(dsrc[i], src, dst + 1024u * i);
+        for (int i = 0; i < 9; ++i) lds_dma_1k(dsrc[i], src, dst + 1024u * i);
     };
-    gv4f acc[RT][TTW];
+    v4f acc[RT][TTW];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (gv4f){0.f, 0.f, 0.f, 0.f};
+        for (int ct = 0; ct < TTW; ++ct) acc[rt][ct] = (v4f){0.f, 0.f, 0.f, 0.f};
     v4i wn[2][RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
@@ -1961,8 +1874,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_fp6w(GemmArgs p) {
             }
             __builtin_amdgcn_sched_barrier(0);
             const v4i r0 = rr[grp & 1][0], r1 = rr[grp & 1][1], r2 = rr[grp & 1][2];
-            const gv8i b0 = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, -1, -1);
-            const gv8i b1 = __builtin_shufflevector(r1, r2, 2, 3, 4, 5, 6, 7, -1, -1);
+            const v8i b0 = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, -1, -1);
+            const v8i b1 = __builtin_shufflevector(r1, r2, 2, 3, 4, 5, 6, 7, -1, -1);
             const int sb = 130 + 5 * d;  // B scale: the digit's weight 2^(3 + 5 d)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
@@ -2015,13 +1928,12 @@ __global__ __launch_bounds__(256) void k_rows_to_f16(const float *__restrict__ x
             const float4 gm = *reinterpret_cast<const float4 *>(gamma + 4 * i);
             v.x *= gm.x, v.y *= gm.y, v.z *= gm.z, v.w *= gm.w;
         }
-        typedef _Float16 gh4 __attribute__((ext_vector_type(4)));
         bool sat = false;
-        const gh4 o = {gclamp_f16(v.x, sat), gclamp_f16(v.y, sat), gclamp_f16(v.z, sat), gclamp_f16(v.w, sat)};
+        const h4 o = {gclamp_f16(v.x, sat), gclamp_f16(v.y, sat), gclamp_f16(v.z, sat), gclamp_f16(v.w, sat)};
         gflush_sat(sat && live);
-        *reinterpret_cast<gh4 *>(xh + (size_t)row * cols + 4 * i) = o;
+        *reinterpret_cast<h4 *>(xh + (size_t)row * cols + 4 * i) = o;
     }
-    s1 = qwave_sum_d(s1), s2 = qwave_sum_d(s2);
+    s1 = wave64_sum_d_xor(s1), s2 = wave64_sum_d_xor(s2);
     if (lane == 0) red[2 * wave] = s1, red[2 * wave + 1] = s2;
     __syncthreads();
     if (tid == 0 && stats) {

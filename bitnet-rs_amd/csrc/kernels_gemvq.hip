@@ -27,58 +27,13 @@
 
 #include "common.hpp"
 #include "qact.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
 
 namespace {
 
 constexpr int kMaxGroupQ = 4;  // query heads per KV head in an attention chunk record (kAttnRecFloats = 2 * 4 + 4 * 128)
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t umin32q(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ v4u ldq_nt16(const void *p) { return __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p)); }
-__device__ __forceinline__ v4i decode16q(uint32_t w, uint32_t lut) {
-    v4i a;
-    a[0] = (int)__builtin_amdgcn_perm(0u, lut, w & 0x03030303u);
-    a[1] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 2) & 0x03030303u);
-    a[2] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 4) & 0x03030303u);
-    a[3] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 6) & 0x03030303u);
-    return a;
-}
-__device__ __forceinline__ float fmix_lo(float a, uint32_t h, float c) {  // a * f16(h.lo) + c
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float fmix_hi(float a, uint32_t h, float c) {  // a * f16(h.hi) + c
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
-    return r;
-}
-template <int CTRL>
-__device__ __forceinline__ double wdpp_d(double v) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double wave_sum_dq(double v) {
-    v += wdpp_d<0xB1>(v);
-    v += wdpp_d<0x4E>(v);
-    v += wdpp_d<0x141>(v);
-    v += wdpp_d<0x140>(v);
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    double r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, 16 * i);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 16 * i);
-        r[i] = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-    }
-    return (r[0] + r[1]) + (r[2] + r[3]);
-}
-
 // In-kernel time stamps (s_memrealtime, 100 MHz): diagnostic build only (-DBH_STAMPS), 16 x u64 per workgroup.
 #ifdef BH_STAMPS
 #define BH_QSTAMP(i)                                                                                           \
@@ -170,7 +125,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
     float2 mml[MRG ? NE : 1][4];  //      and their heads' (m, l)
     if (!MRG) {
 #pragma unroll
-        for (int i = 0; i < NCP; ++i) qa[i] = *reinterpret_cast<const v4u *>(p.qin + umin32q(16u * (uint32_t)(tid + NT * i), q_last));
+        for (int i = 0; i < NCP; ++i) qa[i] = *reinterpret_cast<const v4u *>(p.qin + umin32(16u * (uint32_t)(tid + NT * i), q_last));
     } else {
         // chunks 0..3 are requested before the position (hence the live chunk count) is known; dead records hold zeros or
         // an earlier token's finite values: only their m is masked below.  A thread takes 4 consecutive elements (one
@@ -226,7 +181,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
 #pragma unroll
     for (int j = 0; j < RING; ++j) {
         const int blk = b0 + j < b1 ? b0 + j : b1 - 1;  // clamped: a short range re-reads its last tile
-        wt[j] = ldq_nt16(wbase + (size_t)blk * 1024);
+        wt[j] = load_nt16v(wbase + (size_t)blk * 1024);
         if (SC == 2) sh[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p.stiles) + (tb0 + blk) * 64 + lane);
         if (SC == 1) {
             const float *sp = reinterpret_cast<const float *>(p.stiles) + ((tb0 + blk) * 64 + lane) * 2;
@@ -265,8 +220,8 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
             // qact_emit's arithmetic (qact.hpp) with the 16-element group spread over 4 lanes x 4 elements; destination = the
             // LDS image instead of a global record
             uint32_t u = __float_as_uint(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])))), o;
-            o = qdpp_u<0xB1>(u), u = o > u ? o : u;  // quad_perm [1,0,3,2]
-            o = qdpp_u<0x4E>(u), u = o > u ? o : u;  // quad_perm [2,3,0,1]: the maximum over the quad = the 16 elements
+            o = dpp_u<0xB1>(u), u = o > u ? o : u;  // quad_perm [1,0,3,2]
+            o = dpp_u<0x4E>(u), u = o > u ? o : u;  // quad_perm [2,3,0,1]: the maximum over the quad = the 16 elements
             int be = (int)(u >> 23);
             be = be < 32 ? 32 : be;
             be = be > 254 ? 254 : be;
@@ -312,15 +267,15 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
         for (int pp = 0; pp < 2; ++pp) {  // the lane group's two 32-weight blocks
             v4i acc = {0, 0, 0, 0};
             acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i *>(ba0 + kQRec * j + 32 * pp),
-                                                        decode16q(wd[2 * pp], p.lut), acc, 0, 0, 0);
+                                                        decode16(wd[2 * pp], p.lut), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i *>(ba1 + kQRec * j + 32 * pp + 16),
-                                                        decode16q(wd[2 * pp + 1], p.lut), acc, 0, 0, 0);
+                                                        decode16(wd[2 * pp + 1], p.lut), acc, 0, 0, 0);
             // acc[2 d + h]: exact sums over the 16 weights of half h with digit plane d; |.| <= 16 * 2 * 128
             const int i0 = (int)(((uint32_t)acc[2] << 8) + (uint32_t)acc[0]), i1 = (int)(((uint32_t)acc[3] << 8) + (uint32_t)acc[1]);
             float t = (float)i0 * (pp ? as.y : as.x);
             t = fmaf((float)i1, pp ? as.w : as.z, t);
             if (SC == 2)
-                facc = pp ? fmix_hi(t, sh[j], facc) : fmix_lo(t, sh[j], facc);
+                facc = pp ? fma_mix_hi(t, sh[j], facc) : fma_mix_lo(t, sh[j], facc);
             else if (SC == 1)
                 facc = fmaf(t, pp ? sf[j].y : sf[j].x, facc);
             else
@@ -353,8 +308,8 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
             s1 += pr.x;
             s2 += pr.y;
         }
-        s1 = wave_sum_dq(s1);
-        s2 = wave_sum_dq(s2);
+        s1 = wave64_sum_d_rows_readlane(s1);
+        s2 = wave64_sum_d_rows_readlane(s2);
         const double mean_d = s1 * p.inv_cols;
         const double var_d = s2 * p.inv_cols - mean_d * mean_d;
         ln_mean = (double)(float)mean_d;  // the f32 mean the reference subtracts

@@ -36,24 +36,9 @@
 
 #include "common.hpp"
 #include "qact.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef float v4fl __attribute__((ext_vector_type(4)));
-
-// Weight bytes are read ONCE per launch by ONE CU: non-temporal loads keep them from displacing
-// the activation vectors in L2 / Infinity Cache and land sooner (MI355X_MICROARCH.md, nt-weights).
-__device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint4 load_nt16(const void *p) {
-    const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p));
-    return uint4{v[0], v[1], v[2], v[3]};
-}
-__device__ __forceinline__ float4 load_nt16f(const float *p) {
-    const v4fl v = __builtin_nontemporal_load(reinterpret_cast<const v4fl *>(p));
-    return float4{v[0], v[1], v[2], v[3]};
-}
 
 // In-kernel time stamps (s_memrealtime, 100 MHz) for the diagnostic build only; the
 // production library is compiled without BH_STAMPS and carries none of this.
@@ -104,66 +89,6 @@ struct MfmaArgs {
     unsigned long long *stamps;  // diagnostic builds only
 };
 
-// ---- wave-64 reductions on DPP (no LDS crossbar): 4 row steps + 4 readlanes -------------
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ float readlane_f(float v, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-// quad_perm [1,0,3,2] = 0xB1, [2,3,0,1] = 0x4E, row_half_mirror = 0x141, row_mirror = 0x140
-// maximum of a NON-NEGATIVE float over the wave: on the bit patterns as unsigned integers (same order, no NaN
-// canonicalisation instructions), four DPP steps inside the rows of 16, row_bcast 15 / 31 across them, lane 63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_max_u(uint32_t v) {
-    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
-    return o > v ? o : v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-    uint32_t u = __float_as_uint(v);
-    u = dpp_max_u<0xB1, 0xf>(u);
-    u = dpp_max_u<0x4E, 0xf>(u);
-    u = dpp_max_u<0x141, 0xf>(u);
-    u = dpp_max_u<0x140, 0xf>(u);
-    u = dpp_max_u<0x142, 0xa>(u);  // row_bcast:15 into rows 1 and 3
-    u = dpp_max_u<0x143, 0xc>(u);  // row_bcast:31 into rows 2 and 3
-    return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)u, 63));
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-    v += dpp_d<0xB1>(v);
-    v += dpp_d<0x4E>(v);
-    v += dpp_d<0x141>(v);
-    v += dpp_d<0x140>(v);
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    double r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, 16 * i);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 16 * i);
-        r[i] = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-    }
-    return (r[0] + r[1]) + (r[2] + r[3]);
-}
-
-// One dword = 16 codes (already field-transposed) -> the A operand of one MFMA:
-// register i, byte b <- LUT[code of element 4i+b].
-__device__ __forceinline__ v4i decode16(uint32_t w, uint32_t lut) {
-    v4i a;
-    a[0] = (int)__builtin_amdgcn_perm(0u, lut, w & 0x03030303u);
-    a[1] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 2) & 0x03030303u);
-    a[2] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 4) & 0x03030303u);
-    a[3] = (int)__builtin_amdgcn_perm(0u, lut, (w >> 6) & 0x03030303u);
-    return a;
-}
-
 // 30-bit fixed point -> four balanced base-256 digits d0..d3 in [-128, 127], q = sum d_i 256^i.
 // Adding 0x808080 turns the three low digits into the UNSIGNED bytes of the sum (d_i + 128, the carries are the
 // adder's own), the top byte is already d3; flipping the three added bits back gives the signed digits:
@@ -179,17 +104,6 @@ __device__ __forceinline__ int cvt_rpi(float x) {
 __device__ __forceinline__ float max3_abs(float a, float b, float m) {
     float r;
     asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "v"(m));
-    return r;
-}
-// a * (f16 half of h) + c in f32
-__device__ __forceinline__ float fma_mix_lo(float a, uint32_t h, float c) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float fma_mix_hi(float a, uint32_t h, float c) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(h), "v"(c));
     return r;
 }
 __device__ __forceinline__ uint32_t digits4(float v, float sc) {
@@ -394,8 +308,8 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_mfma(MfmaArgs p) {
             s1 += (a + b) + (c + d);
             s2 += (a * a + b * b) + (c * c + d * d);
         }
-        s1 = wave_sum_d(s1);
-        s2 = wave_sum_d(s2);
+        s1 = wave64_sum_d_rows_readlane(s1);
+        s2 = wave64_sum_d_rows_readlane(s2);
         if (lane == 0) {
             stat[2 * wave] = s1;
             stat[2 * wave + 1] = s2;
@@ -441,7 +355,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_mfma(MfmaArgs p) {
     }
 #pragma unroll
     for (int j = 0; j < RING; ++j) am = max3_abs(xr[j].z, xr[j].w, max3_abs(xr[j].x, xr[j].y, am));
-    am = wave_max_f(am);  // this wave's K range only: the scale is per wave
+    am = wave64_max_bits_rows_bcast(am);  // this wave's K range only: the scale is per wave
     BH_STAMP(2);
     // scale = 2^(29 - E), E = unbiased exponent of the maximum (clamped so the scale stays a
     // normal float); |x * scale| < 2^30
@@ -545,8 +459,8 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_mfma(MfmaArgs p) {
             s1 += (a + b) + (c + d);
             s2 += (a * a + b * b) + (c * c + d * d);
         }
-        s1 = wave_sum_d(s1);
-        s2 = wave_sum_d(s2);
+        s1 = wave64_sum_d_rows_readlane(s1);
+        s2 = wave64_sum_d_rows_readlane(s2);
         if (lane == 0) {
             stat[2 * wave] = s1;
             stat[2 * wave + 1] = s2;

@@ -27,12 +27,9 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
-
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef _Float16 v4h __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kPD = 128;       // head dim
 constexpr int kQB = 64;        // keys per tile; query rows come in 64-row blocks (q_block_pos)
@@ -147,8 +144,8 @@ __global__ __launch_bounds__(256) void k_prefill_prep(PrefillArgs p) {
         for (int i = 0; i < 8; ++i) {
             const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
             const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
-            const v4h h = {(_Float16)(v.x * qmul), (_Float16)(v.y * qmul), (_Float16)(v.z * qmul), (_Float16)(v.w * qmul)};
-            *reinterpret_cast<v4h *>(dst + (size_t)tok * kPD + d) = h;
+            const h4 h = {(_Float16)(v.x * qmul), (_Float16)(v.y * qmul), (_Float16)(v.z * qmul), (_Float16)(v.w * qmul)};
+            *reinterpret_cast<h4 *>(dst + (size_t)tok * kPD + d) = h;
         }
     };
     if (is_q) {
@@ -198,8 +195,8 @@ __global__ __launch_bounds__(256) void k_prefill_prep(PrefillArgs p) {
         for (int i = 0; i < 8; ++i) {
             const int idx = tid + 256 * i, d = idx >> 4, t4 = idx & 15, tok = t4 * 4;
             const int slot = 32 * (t4 >> 3) + 8 * (t4 & 3) + 4 * ((t4 >> 2) & 1);
-            const v4h h = {(_Float16)tile[tok][d], (_Float16)tile[tok + 1][d], (_Float16)tile[tok + 2][d], (_Float16)tile[tok + 3][d]};
-            *reinterpret_cast<v4h *>(vt + (size_t)d * p.Tpad + t0 + slot) = h;
+            const h4 h = {(_Float16)tile[tok][d], (_Float16)tile[tok + 1][d], (_Float16)tile[tok + 2][d], (_Float16)tile[tok + 3][d]};
+            *reinterpret_cast<h4 *>(vt + (size_t)d * p.Tpad + t0 + slot) = h;
         }
     }
 }
@@ -213,7 +210,6 @@ __global__ __launch_bounds__(256) void k_prefill_prep(PrefillArgs p) {
 // queries) with a launch bound of two waves per SIMD: TWO workgroups per CU with independent barriers (one in its softmax
 // while the other multiplies).  The next key tile is requested into registers one iteration ahead and the LDS operand reads
 // are pinned one chunk ahead of their MFMAs (hipcc's own schedule waited for every read right before its MFMAs).
-typedef unsigned pv4u __attribute__((ext_vector_type(4)));
 
 // max of three without the v_max(x, x) canonicalisation hipcc puts in front of every fmaxf of an MFMA result (no NaNs here)
 __device__ __forceinline__ float max3_raw(float a, float b, float c) {
@@ -233,17 +229,6 @@ __device__ __forceinline__ float max_over_g(float v) {
     const unsigned w = __float_as_uint(m1);
     const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
     return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
-// LDS-DMA: 64 lanes x 16 B from (scalar base + per-lane byte offset) to LDS bytes [lds_dst, lds_dst + 1024).  Invisible to hipcc's
-// vmcnt bookkeeping (cdna_hip_programming.md 5.7): the kernel waits with explicit s_waitcnt vmcnt(0) and issues no other vector
-// memory loads while these are in flight.
-__device__ __forceinline__ void gdma1k_s(unsigned lane_off, const void *sbase, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(lane_off), "s"(sbase), "s"(lds_dst)
-                 : "memory");
 }
 
 template <int HW, int NW, int NQ>
@@ -293,7 +278,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
 #pragma unroll
     for (int q = 0; q < NQ; ++q) qlim[q] = p.causal ? bpos + 16 * q + c : p.T - 1;
     // Q^T operands: 8 consecutive dims per k-slot group, kept in registers for the whole block (filled below, behind the first tile requests)
-    v8h qreg[NQ][4];
+    h8 qreg[NQ][4];
     v4f o[NQ][8];
     float m_run[NQ], l_run[NQ];
 #pragma unroll
@@ -322,13 +307,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
         const uint8_t *src = kbase + (size_t)kt * kKTile;
         const unsigned dst = lds0 + (unsigned)buf * kKVBuf + (unsigned)(4 * wave) * 1024u;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) gdma1k_s(ksrc[i], src, dst + 1024u * i);
+        for (int i = 0; i < 4; ++i) lds_dma_1k(ksrc[i], src, dst + 1024u * i);
     };
     auto stage_v = [&](int kt, int buf) {
         const uint8_t *src = vbase + (size_t)kt * (kQB * 2);
         const unsigned dst = lds0 + (unsigned)buf * kKVBuf + kKTile + (unsigned)(4 * wave) * 1024u;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) gdma1k_s(vsrc[i], src, dst + 1024u * i);
+        for (int i = 0; i < 4; ++i) lds_dma_1k(vsrc[i], src, dst + 1024u * i);
     };
     // operand read offsets inside a tile (+ 4096 i per key tile of 16, + 2048 dt per dim tile of 16: immediates)
     const unsigned kro = (unsigned)(c * 256 + ((g ^ c) * 16));                               // ^ (64 ch): unit 4 ch + g of key c
@@ -337,16 +322,16 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
     // (32-63, 0-63), (32-63, 64-127)), 4 operands of 1 KiB per wave each; chunk j's LDS reads are issued TWO chunks ahead of its
     // MFMAs, across the softmax and across the tile boundary (hipcc's own schedule waited for every read right before its MFMAs;
     // one chunk ahead still left the waves waiting: the reads' latency, not LDS bandwidth, was what the kernel stood on).
-    v8h ring[4][4];
+    h8 ring[4][4];
     auto kread = [&](int slot, int ch, const uint8_t *ks) {
         const uint8_t *kp = ks + (kro ^ (unsigned)(64 * ch));
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ring[slot][i] = *reinterpret_cast<const v8h *>(kp + 4096 * i);
+        for (int i = 0; i < 4; ++i) ring[slot][i] = *reinterpret_cast<const h8 *>(kp + 4096 * i);
     };
     auto vread = [&](int slot, int st, const uint8_t *vs) {
         const uint8_t *vp = vs + (vro ^ (unsigned)(64 * (st >> 1))) + 2048 * 4 * (st & 1);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ring[slot][i] = *reinterpret_cast<const v8h *>(vp + 2048 * i);
+        for (int i = 0; i < 4; ++i) ring[slot][i] = *reinterpret_cast<const h8 *>(vp + 2048 * i);
     };
     // Staging: K and V^T tiles have separate double buffers and separate schedules, each requested a whole tile ahead of its first
     // read.  Two barriers per tile: B1 (before the K chunk 2 MFMAs = before the first V read of this tile is issued) waits for
@@ -401,7 +386,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
         for (int q = 0; q < NQ; ++q) {
             const _Float16 *qp = p.qh + ((size_t)h * p.nq_pad + qbase + 16 * q + c) * kPD + 8 * g;
 #pragma unroll
-            for (int ch = 0; ch < 4; ++ch) qreg[q][ch] = *reinterpret_cast<const v8h *>(qp + 32 * ch);
+            for (int ch = 0; ch < 4; ++ch) qreg[q][ch] = *reinterpret_cast<const h8 *>(qp + 32 * ch);
         }
     }
     // the builtin form, so that hipcc's own bookkeeping sees its q loads retired here: left to itself it re-waits for them with
@@ -450,7 +435,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
         // ---- online softmax for query column c of each group (keys of this lane: 16 i + 4 g + j) ----
         // Only tiles that reach past some query's limit are masked (the diagonal ones, and the context's last): wave-uniform.
         const bool need_mask = kt * kQB + kQB - 1 > qmin;
-        v8h pb[NQ][2];
+        h8 pb[NQ][2];
         // The query groups' softmax chains are independent: each stage below handles ALL groups in one basic block (one branch per
         // stage, not per group), so hipcc interleaves their dependent chains -- maximum, exponentials, sum -- instead of running
         // them one after the other.
@@ -563,7 +548,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
             const float inv = 1.0f / l;
             const size_t oo = (size_t)qrow * p.out_ld + (size_t)h * p.out_hs + 4 * g;
             if (p.out_f16) {
-                typedef _Float16 h4 __attribute__((ext_vector_type(4)));
                 _Float16 *oh = reinterpret_cast<_Float16 *>(p.out) + oo;
 #pragma unroll
                 for (int dt = 0; dt < 8; ++dt)
@@ -602,7 +586,6 @@ __global__ __launch_bounds__(256) void k_prefill_merge(PrefillArgs p) {
     }
     const float inv = 1.0f / L;
     if (p.out_f16) {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(p.out) + row * p.out_ld + h * p.out_hs + 4 * d4) = (h4){(_Float16)(a.x * inv), (_Float16)(a.y * inv), (_Float16)(a.z * inv), (_Float16)(a.w * inv)};
         return;
     }
@@ -803,7 +786,7 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
             for (int i = 0; i < 8; ++i) {
                 const int idx = tid + 256 * i, d2 = idx >> 5, tok = (idx & 31) * 2;
                 if (tok >= n_past) continue;
-                const v4h h = *reinterpret_cast<const v4h *>(k16 + ((size_t)d2 * 64 + tok) * 2);
+                const h4 h = *reinterpret_cast<const h4 *>(k16 + ((size_t)d2 * 64 + tok) * 2);
                 tile[tok][2 * d2] = (float)h[0];
                 tile[tok][2 * d2 + 1] = (float)h[1];
                 if (tok + 1 < n_past) {
@@ -817,7 +800,7 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
                 if (tok >= n_past) continue;
                 float4 v;
                 if (p.cache_f16) {
-                    const v4h h = *reinterpret_cast<const v4h *>(c16 + (size_t)(t0 + tok) * kPD + d);
+                    const h4 h = *reinterpret_cast<const h4 *>(c16 + (size_t)(t0 + tok) * kPD + d);
                     v = float4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
                 } else {
                     v = *reinterpret_cast<const float4 *>(c32 + (size_t)(t0 + tok) * kPD + d);
@@ -854,19 +837,18 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
                 }
             }
         } else if (is_k) {
-            typedef _Float16 v2h __attribute__((ext_vector_type(2)));
             _Float16 *k16 = c16 + (size_t)(t0 >> 6) * kPD * 64;
             for (int i = 0; i < 8; ++i) {
                 const int idx = tid + 256 * i, d2 = idx >> 5, tok = (idx & 31) * 2;
                 const bool lo = tok >= n_past && tok < n_live, hi = tok + 1 >= n_past && tok + 1 < n_live;
                 _Float16 *dst = k16 + ((size_t)d2 * 64 + tok) * 2;
-                const v2h a = {(_Float16)tile[tok][2 * d2], (_Float16)tile[tok][2 * d2 + 1]}, b = {(_Float16)tile[tok + 1][2 * d2], (_Float16)tile[tok + 1][2 * d2 + 1]};
+                const h2 a = {(_Float16)tile[tok][2 * d2], (_Float16)tile[tok][2 * d2 + 1]}, b = {(_Float16)tile[tok + 1][2 * d2], (_Float16)tile[tok + 1][2 * d2 + 1]};
                 if (lo && hi)
-                    *reinterpret_cast<v4h *>(dst) = (v4h){a[0], a[1], b[0], b[1]};
+                    *reinterpret_cast<h4 *>(dst) = (h4){a[0], a[1], b[0], b[1]};
                 else if (lo)
-                    *reinterpret_cast<v2h *>(dst) = a;
+                    *reinterpret_cast<h2 *>(dst) = a;
                 else if (hi)
-                    *reinterpret_cast<v2h *>(dst + 2) = b;
+                    *reinterpret_cast<h2 *>(dst + 2) = b;
             }
         } else {
             for (int i = 0; i < 8; ++i) {
@@ -874,7 +856,7 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
                 if (tok < n_past || tok >= n_live) continue;
                 const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
                 if (p.cache_f16)
-                    *reinterpret_cast<v4h *>(c16 + (size_t)(t0 + tok) * kPD + d) = (v4h){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+                    *reinterpret_cast<h4 *>(c16 + (size_t)(t0 + tok) * kPD + d) = (h4){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
                 else
                     *reinterpret_cast<float4 *>(c32 + (size_t)(t0 + tok) * kPD + d) = v;
             }
@@ -886,7 +868,7 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
         for (int i = 0; i < 8; ++i) {
             const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
             const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
-            *reinterpret_cast<v4h *>(dst + (size_t)tok * kPD + d) = (v4h){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+            *reinterpret_cast<h4 *>(dst + (size_t)tok * kPD + d) = (h4){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
         }
     } else {
         // the V^T key permutation inside each group of 32 (k_prefill_prep): key 4 a + 16 b + j at slot 8 a + 4 b + j
@@ -894,8 +876,8 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
         for (int i = 0; i < 8; ++i) {
             const int idx = tid + 256 * i, d = idx >> 4, t4 = idx & 15, tok = t4 * 4;
             const int slot = 32 * (t4 >> 3) + 8 * (t4 & 3) + 4 * ((t4 >> 2) & 1);
-            const v4h h = {(_Float16)tile[tok][d], (_Float16)tile[tok + 1][d], (_Float16)tile[tok + 2][d], (_Float16)tile[tok + 3][d]};
-            *reinterpret_cast<v4h *>(vt + (size_t)d * p.Tpad + t0 + slot) = h;
+            const h4 h = {(_Float16)tile[tok][d], (_Float16)tile[tok + 1][d], (_Float16)tile[tok + 2][d], (_Float16)tile[tok + 3][d]};
+            *reinterpret_cast<h4 *>(vt + (size_t)d * p.Tpad + t0 + slot) = h;
         }
     }
 }

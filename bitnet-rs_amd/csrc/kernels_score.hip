@@ -22,12 +22,11 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
 namespace {
 
-typedef _Float16 sc_h8 __attribute__((ext_vector_type(8)));
-typedef float sc_f4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void glb_void_t;
 
@@ -36,20 +35,6 @@ constexpr int kST = 128;                // tokens per workgroup
 constexpr int kSK = 64;                 // columns per K step (128 bytes of a row)
 constexpr int kSTile = kSV * kSK * 2;   // bytes of one staged operand tile (16 KiB; kSV == kST)
 constexpr int kSLds = 4 * kSTile;       // two buffers x two operands
-
-__device__ __forceinline__ float sc_wsum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-// 256-thread sum in the order of kernels_decode.hip's bsum (the final norm of k_logits_f16)
-__device__ __forceinline__ float sc_bsum(float v, float *slot) {
-    v = sc_wsum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
-}
 
 // (v, i) beats (bv, bi): larger value, or equal value and lower index
 __device__ __forceinline__ bool sc_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -75,13 +60,13 @@ __global__ __launch_bounds__(256) void k_score_rows_f16(const float *__restrict_
     const float *xr = x + (size_t)blockIdx.x * hidden;
     float s = 0.0f;
     for (int i = tid; i < hidden; i += 256) s += xr[i];
-    const float mean = gamma ? sc_bsum(s, slot) / (float)hidden : 0.0f;
+    const float mean = gamma ? block256_sum_f(s, slot) / (float)hidden : 0.0f;
     float ss = 0.0f;
     for (int i = tid; i < hidden; i += 256) {
         const float d = xr[i] - mean;
         ss += d * d;
     }
-    const float denom = gamma ? sqrtf(sc_bsum(ss, slot) / (float)hidden + eps) : 1.0f;
+    const float denom = gamma ? sqrtf(block256_sum_f(ss, slot) / (float)hidden + eps) : 1.0f;
     for (int i = tid; i < hidden; i += 256) ar[i] = (_Float16)(gamma ? (xr[i] - mean) / denom * gamma[i] : xr[i]);
 }
 
@@ -90,7 +75,7 @@ struct ScoreArgs {
     const _Float16 *a;      // [n_pad, hidden]
     const int32_t *targets;
     float *logits;          // [logits_rows, vocab] or null
-    sc_f4 *part;            // [n_pad][vb_count]: (max, sum, best value, best index as bits)
+    v4f *part;            // [n_pad][vb_count]: (max, sum, best value, best index as bits)
     float *tlog;            // [n_pad]: raw logit of the row's target
     int hidden, vocab, n_rows, logits_rows, vb_count, tb_count;
 };
@@ -137,11 +122,11 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
         off_e[kk] = (wv * 64 + c) * 128 + u;
         off_a[kk] = (wt * 64 + c) * 128 + u;
     }
-    sc_f4 acc[4][4];
+    v4f acc[4][4];
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = (sc_f4){0.f, 0.f, 0.f, 0.f};
+        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = (v4f){0.f, 0.f, 0.f, 0.f};
     const int nk = p.hidden / kSK;
     stage(0, 0);
     for (int ks = 0; ks < nk; ++ks) {
@@ -151,11 +136,11 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
         const uint8_t *eb = lds + (ks & 1) * 2 * kSTile, *ab = eb + kSTile;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            sc_h8 af[4], bf[4];
+            h8 af[4], bf[4];
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt) af[rt] = *reinterpret_cast<const sc_h8 *>(eb + off_e[kk] + rt * 16 * 128);
+            for (int rt = 0; rt < 4; ++rt) af[rt] = *reinterpret_cast<const h8 *>(eb + off_e[kk] + rt * 16 * 128);
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) bf[ct] = *reinterpret_cast<const sc_h8 *>(ab + off_a[kk] + ct * 16 * 128);
+            for (int ct = 0; ct < 4; ++ct) bf[ct] = *reinterpret_cast<const h8 *>(ab + off_a[kk] + ct * 16 * 128);
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
@@ -212,10 +197,10 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
     }
     // merge the two vocabulary halves of the block (wave column wv = 0 holds the lower indices) and write one partial per token
     __syncthreads();  // every wave is done with the staged tiles
-    sc_f4 *xch = reinterpret_cast<sc_f4 *>(lds);  // [wt][64 tokens]
+    v4f *xch = reinterpret_cast<v4f *>(lds);  // [wt][64 tokens]
     if (wv == 1 && g == 0) {
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) xch[wt * 64 + ct * 16 + c] = (sc_f4){pm[ct], ps[ct], pv[ct], __int_as_float(pi[ct])};
+        for (int ct = 0; ct < 4; ++ct) xch[wt * 64 + ct * 16 + c] = (v4f){pm[ct], ps[ct], pv[ct], __int_as_float(pi[ct])};
     }
     __syncthreads();
     if (wv == 0 && g == 0) {
@@ -223,27 +208,27 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
         for (int ct = 0; ct < 4; ++ct) {
             const int token = t0 + wt * 64 + ct * 16 + c;
             if (token >= p.n_rows) continue;
-            const sc_f4 o = xch[wt * 64 + ct * 16 + c];
+            const v4f o = xch[wt * 64 + ct * 16 + c];
             float m = pm[ct], s = ps[ct], bv = pv[ct];
             int bi = pi[ct];
             sc_merge(m, s, o.x, o.y);
             if (sc_better(o.z, __float_as_int(o.w), bv, bi)) bv = o.z, bi = __float_as_int(o.w);
-            p.part[(size_t)token * p.vb_count + vb] = (sc_f4){m, s, bv, __int_as_float(bi)};
+            p.part[(size_t)token * p.vb_count + vb] = (v4f){m, s, bv, __int_as_float(bi)};
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_score_combine(const sc_f4 *__restrict__ part, const float *__restrict__ tlog,
+__global__ __launch_bounds__(256) void k_score_combine(const v4f *__restrict__ part, const float *__restrict__ tlog,
                                                        const int32_t *__restrict__ targets, int vb_count, int vocab, float *__restrict__ nll,
                                                        int32_t *__restrict__ argmax) {
     __shared__ float sm[256], ss[256], sv[256];
     __shared__ int si[256];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const sc_f4 *pr = part + (size_t)row * vb_count;
+    const v4f *pr = part + (size_t)row * vb_count;
     float m = -INFINITY, s = 0.0f, bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int b = tid; b < vb_count; b += 256) {
-        const sc_f4 q = pr[b];
+        const v4f q = pr[b];
         sc_merge(m, s, q.x, q.y);
         if (sc_better(q.z, __float_as_int(q.w), bv, bi)) bv = q.z, bi = __float_as_int(q.w);
     }
@@ -323,7 +308,7 @@ int bitnet_hip_score_f16_dev(const void *table_f16_dev, const float *x_dev, cons
     a.table = static_cast<const _Float16 *>(table_f16_dev);
     a.a = reinterpret_cast<const _Float16 *>(ws);
     a.tlog = reinterpret_cast<float *>(ws + align256(n_pad * hidden * 2));
-    a.part = reinterpret_cast<sc_f4 *>(ws + align256(n_pad * hidden * 2) + align256(n_pad * 4));
+    a.part = reinterpret_cast<v4f *>(ws + align256(n_pad * hidden * 2) + align256(n_pad * 4));
     a.targets = targets_dev;
     a.logits = logits_rows ? logits_dev : nullptr;
     a.hidden = (int)hidden, a.vocab = (int)vocab, a.n_rows = (int)n_rows, a.logits_rows = (int)logits_rows;

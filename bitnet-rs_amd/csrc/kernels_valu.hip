@@ -9,6 +9,7 @@
 // budget of this formulation is ~2.75 vector ops per weight, which puts it above
 // the HBM roofline time on MI355X; see profiles/).
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace bitnet_hip {
 
@@ -35,12 +36,6 @@ __device__ __forceinline__ float dot16(uint32_t w, const float *xs, uint32_t lut
     return acc;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <bool HAS_SCALE>
 __global__ __launch_bounds__(256) void k_gemv_valu(const uint32_t *__restrict__ codes, int stride_dw,
                                                    const float *__restrict__ scales, int nblk,
@@ -60,7 +55,7 @@ __global__ __launch_bounds__(256) void k_gemv_valu(const uint32_t *__restrict__ 
             if (HAS_SCALE) part *= scales[(size_t)row * nblk + d / bs_dw];
             acc += part;
         }
-        acc = wave_sum(acc);
+        acc = wave64_sum_f_xor(acc);
         if (lane == 0) y[row] = acc;
     }
 }

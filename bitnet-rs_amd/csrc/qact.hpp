@@ -30,51 +30,13 @@
 
 #include <cstdint>
 
+#include "wave.hpp"
+
 namespace bitnet_hip {
 
 constexpr int kQRec = 576;  // bytes per 256-column record
 
 __host__ __device__ inline size_t qact_bytes(size_t cols) { return ((cols + 255) / 256) * (size_t)kQRec; }
-
-// ---- reductions inside the 16-lane DPP rows (lanes 16 t .. 16 t + 15 of a wave) ----------------------------
-template <int CTRL>
-__device__ __forceinline__ uint32_t qdpp_u(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-// maximum of NON-NEGATIVE floats over the row of 16 (bit patterns order like unsigned integers)
-__device__ __forceinline__ float row16_max_abs(float v) {
-    uint32_t u = __float_as_uint(v) & 0x7fffffffu, o;
-    o = qdpp_u<0xB1>(u), u = o > u ? o : u;   // quad_perm [1,0,3,2]
-    o = qdpp_u<0x4E>(u), u = o > u ? o : u;   // quad_perm [2,3,0,1]
-    o = qdpp_u<0x141>(u), u = o > u ? o : u;  // row_half_mirror
-    o = qdpp_u<0x140>(u), u = o > u ? o : u;  // row_mirror
-    return __uint_as_float(u);
-}
-template <int CTRL>
-__device__ __forceinline__ double qdpp_d(double v) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = qdpp_u<CTRL>((unsigned)u), hi = qdpp_u<CTRL>((unsigned)(u >> 32));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double row16_sum_d(double v) {
-    v += qdpp_d<0xB1>(v);
-    v += qdpp_d<0x4E>(v);
-    v += qdpp_d<0x141>(v);
-    v += qdpp_d<0x140>(v);
-    return v;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float qdpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row16_sum_f(float v) {  // four v_add_f32 with a DPP operand
-    v += qdpp_f<0xB1>(v);
-    v += qdpp_f<0x4E>(v);
-    v += qdpp_f<0x141>(v);
-    v += qdpp_f<0x140>(v);
-    return v;
-}
 
 __device__ __forceinline__ int qcvt_rpi(float x) {  // floor(x + 1/2), one instruction
     int r;

@@ -139,6 +139,9 @@ class HipLib:
         L.bitnet_hip_gemv_q_dev.argtypes = [C.c_uint64, _vp, _vp, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_attention_decode_q_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_int, _vp, _vp, _vp]
         L.bitnet_hip_gemv_attn_merge_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_gemv_attn_merge_rec_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        L.bitnet_hip_attention_merge_q_max_keys.restype = _sz
+        L.bitnet_hip_attention_merge_q_max_keys.argtypes = []
         L.bitnet_hip_matmul_workspace_bytes.argtypes = [_sz, _sz, C.c_int]
         L.bitnet_hip_matmul_workspace_bytes.restype = _sz
         L.bitnet_hip_matmul_fused_dev.argtypes = [C.c_uint64, _vp, _vp, _sz, _vp, C.c_float, _vp, C.c_int, C.c_int, _vp, _sz, _vp]
@@ -506,6 +509,15 @@ class HipLib:
         self._check(self.c.bitnet_hip_attention_decode_q_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kcache), _ptr(vcache), n_heads, n_kv,
                                                              head_dim, max_pos, _ptr(pos), _ptr(scratch), flags, _optr(out), _optr(qact_out), _vp(stream)))
 
+    def attention_merge_q_max_keys(self) -> int:
+        return int(self.c.bitnet_hip_attention_merge_q_max_keys())
+
+    def gemv_attn_merge_rec_q_dev(self, h: int, scratch, n_heads, n_kv, max_pos, pos, y, qact_out, max_records: int, residual=None, gamma_out=None,
+                                  stats_out=None, stream: int = 0) -> None:
+        """gemv_attn_merge_q_dev with the record bound chosen by the caller (4 or 8 records of 64 positions)"""
+        self._check(self.c.bitnet_hip_gemv_attn_merge_rec_q_dev(h, _ptr(scratch), n_heads, n_kv, max_pos, _ptr(pos), _ptr(y), _optr(residual),
+                                                                _ptr(qact_out), _optr(gamma_out), _optr(stats_out), max_records, _vp(stream)))
+
     def gemv_attn_merge_q_dev(self, h: int, scratch, n_heads, n_kv, max_pos, pos, y, qact_out, residual=None, gamma_out=None, stats_out=None,
                               stream: int = 0) -> None:
         self._check(self.c.bitnet_hip_gemv_attn_merge_q_dev(h, _ptr(scratch), n_heads, n_kv, max_pos, _ptr(pos), _ptr(y), _optr(residual),
@@ -809,6 +821,7 @@ class HostDecoder:
         L.bitnet_host_set_act_mode.argtypes = [C.c_void_p, C.c_int]
         L.bitnet_host_act_mode.argtypes = [C.c_void_p]
         L.bitnet_host_position.argtypes = [C.c_void_p]
+        L.bitnet_host_form_at.argtypes = [C.c_void_p, C.c_int]
         L.bitnet_host_last_prefill_path.argtypes = [C.c_void_p]
         L.bitnet_host_saturation_fallbacks.argtypes = [C.c_void_p]
         L.bitnet_host_history.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
@@ -1012,6 +1025,10 @@ class HostDecoder:
 
     def position(self) -> int:
         return int(self.c.bitnet_host_position(self.h))
+
+    def form_at(self, pos: int) -> int:
+        """attention form of a step at `pos`: 0 records + combine, 1 / 3 the o-projection merges 4 / 8 records, 2 128-position records"""
+        return int(self.c.bitnet_host_form_at(self.h, pos))
 
     def history(self, n: int) -> np.ndarray:
         out = np.zeros(n, np.int32)

@@ -970,10 +970,11 @@ int bitnet_hip_attention_decode_partial_dev(const float *qkv, const float *rope_
 }
 
 size_t bitnet_hip_attention_merge_max_keys(void) { return (size_t)4 * 64; }
+size_t bitnet_hip_attention_merge_q_max_keys(void) { return (size_t)8 * 64; }
 
 static int gemv_attn_merge(bitnet_hip_weights_t h, const float *attn_scratch_dev, size_t n_heads, size_t n_kv_heads, size_t max_pos,
                            const int32_t *pos_dev, float *y_dev, const float *residual_dev, void *qact_out, const float *gamma_out_dev,
-                           double *stats_out, void *stream, int chunk_log2 = 6) {
+                           double *stats_out, void *stream, int chunk_log2 = 6, int records = 4) {
     BH_GUARD_BEGIN
     const WeightsRef w = lookup(h);
     if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
@@ -986,6 +987,9 @@ static int gemv_attn_merge(bitnet_hip_weights_t h, const float *attn_scratch_dev
         return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_attn_merge_dev: matrix shape %zux%zu not supported", w->rows, w->cols);
     if (qact_out && w->rows % 16 != 0)
         return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_attn_merge_q_dev: rows %zu must be a multiple of 16 for a QAct output", w->rows);
+    if (records != 4 && !(qact_out && gemvq_supported(*w) && w->cols <= 2560))
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_attn_merge_rec_q_dev: %d records need a QAct matrix of at most 2560 columns (got %zux%zu)", records,
+                         w->rows, w->cols);
     if (qact_out && gemvq_supported(*w) && w->cols <= 4096) {
         // QAct consumer form: the workgroup merges the records and quantises them once, into its LDS image (kernels_gemvq.hip MRG)
         GemvQIo io;
@@ -999,6 +1003,7 @@ static int gemv_attn_merge(bitnet_hip_weights_t h, const float *attn_scratch_dev
         io.attn_chunk_log2 = chunk_log2;
         io.attn_chunks_max = (int)div_ceil(max_pos, (size_t)1 << chunk_log2);
         io.attn_group_log2 = group == 4 ? 2 : group == 2 ? 1 : 0;
+        io.attn_records = records;
         hipError_t e = launch_gemv_q(*w, io, (hipStream_t)stream);
         if (e != hipSuccess) return set_error(BITNET_HIP_ERR_GPU, "kernel launch failed: %s", hipGetErrorString(e));
         return BITNET_HIP_OK;
@@ -1027,6 +1032,16 @@ int bitnet_hip_gemv_attn_merge_q_dev(bitnet_hip_weights_t h, const float *attn_s
                                      const float *gamma_out_dev, double *stats_out, void *stream) {
     if (!qact_out) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_attn_merge_q_dev");
     return gemv_attn_merge(h, attn_scratch_dev, n_heads, n_kv_heads, max_pos, pos_dev, y_dev, residual_dev, qact_out, gamma_out_dev, stats_out, stream);
+}
+
+int bitnet_hip_gemv_attn_merge_rec_q_dev(bitnet_hip_weights_t h, const float *attn_scratch_dev, size_t n_heads, size_t n_kv_heads,
+                                         size_t max_pos, const int32_t *pos_dev, float *y_dev, const float *residual_dev, void *qact_out,
+                                         const float *gamma_out_dev, double *stats_out, size_t max_records, void *stream) {
+    if (!qact_out) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_attn_merge_rec_q_dev");
+    if (max_records != 4 && max_records != 8)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "gemv_attn_merge_rec_q_dev: max_records must be 4 or 8 (got %zu)", max_records);
+    return gemv_attn_merge(h, attn_scratch_dev, n_heads, n_kv_heads, max_pos, pos_dev, y_dev, residual_dev, qact_out, gamma_out_dev, stats_out, stream, 6,
+                           (int)max_records);
 }
 
 /* ---- QAct: activations quantised by their producer (csrc/qact.hpp) ---- */

@@ -135,6 +135,7 @@ struct GemvQIo {
     const float *attn_rec = nullptr;
     const int *attn_pos = nullptr;
     int attn_chunks_max = 0, attn_group_log2 = 0, attn_chunk_log2 = 6;  // positions per record = 1 << attn_chunk_log2
+    int attn_records = 4;              // records the merge requests up front (4 or 8): *attn_pos + 1 <= attn_records << attn_chunk_log2
 };
 
 // ---- kernel launchers (kernels_*.hip) -------------------------------------

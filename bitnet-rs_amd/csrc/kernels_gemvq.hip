@@ -47,6 +47,15 @@ constexpr int kMaxGroupQ = 4;  // query heads per KV head in an attention chunk 
     } while (0)
 #endif
 
+// Two floats at a WAVE-UNIFORM address that no launch in flight writes (another kernel's finished output): read through the
+// constant address space, i.e. the scalar cache -- one s_load_dwordx2 into SGPRs instead of a 64-lane request for 8 bytes.
+__device__ __forceinline__ v2f load_uniform2(const void *p) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) v2f *>(reinterpret_cast<uintptr_t>(p));
+}
+__device__ __forceinline__ int load_uniform_i(const int *p) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) int *>(reinterpret_cast<uintptr_t>(p));
+}
+
 struct GemvQArgs {
     const uint8_t *tiles;    // [n_tiles][nblk][64 lanes][16 B] code tiles (k_retile)
     const void *stiles;      // [n_tiles][nblk][64 lanes] x {f16 x 2 | f32 x 2}: 32-block scales (k_retile_scales[_h]) or null
@@ -84,12 +93,16 @@ struct GemvQArgs {
 // (g_r, residual, the next LayerNorm's gamma) are requested up front too -- behind the barrier they were dependent
 // L2 / HBM round trips (0.7-0.8 us of a 2.5 us kernel).
 // Every global load is unconditional and sits ahead of a scheduling fence (kernels_mfma.hip explains why).
-// MRG = NE > 0: short contexts (<= 4 chunk records): instead of copying QAct records the workgroup merges the attention's
-// chunk records itself -- thread t the elements t, t + NT, ... (NE of them) of the attention output: softmax merge of up to
-// 4 records, then the 16-lane group quantisation of qact.hpp straight into the LDS image.  One launch (k_attn_combine) and
-// one global round trip of the vector less per layer; every workgroup reads every live record (n_chunks x 10 KB), which
-// is why the decoder takes this form up to 256 keys only.
-template <int NW, int RING, int SC, int LN, int NCP, int NE = 0>
+// MRG = NE > 0: contexts of at most NR chunk records (NR = 4 or 8): instead of copying QAct records the workgroup merges the
+// attention's chunk records itself: softmax merge of the NR records, then the 16-element group quantisation of qact.hpp straight
+// into the LDS image.  One launch (k_attn_combine) and one global round trip of the vector less per layer.  Every workgroup reads
+// all NR records, so the fetch asks for each o value ONCE and for nothing else (the rule above): thread t takes NE float4 slots
+// (elements 4 (t + NT i) .. + 3: a quad of lanes = one 16-element group) and, for the columns past 4 NT NE, NE1 single floats
+// (element 4 NT NE + t: a DPP row of 16 lanes = one group), so 2560 columns are 2048 + 512 with no clamped duplicate; a wave's
+// slot lies in two heads (float4) or one (tail), wave-uniform, whose (m, l) pairs come by scalar loads -- no vector request.
+// 4 records x 2560 columns: 41 KB per workgroup (the clamped two-slot mapping with per-lane (m, l) loads asked for 98 KB);
+// 8 records: 82 KB, which is why the decoder takes the 8-record form up to Decoder::form_at's bound only.
+template <int NW, int RING, int SC, int LN, int NCP, int NE = 0, int NE1 = 0, int NR = 4>
 __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
     constexpr int NT = NW * 64;
     constexpr bool MRG = NE > 0;
@@ -121,27 +134,60 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
     // ---- 1. the activation vector (L2-resident, every workgroup reads it), statistics pairs, epilogue operands ----
     const uint32_t q_last = (uint32_t)kQRec * (uint32_t)p.nblk - 16u;
     v4u qa[NCP];  // native vectors: arrays of HIP's uint4 struct went through scratch memory at the scheduling fence
-    float4 mo[MRG ? NE : 1][4];   // MRG: un-normalised P.V values of this thread's NE 4-element slots, chunks 0..3
-    float2 mml[MRG ? NE : 1][4];  //      and their heads' (m, l)
+    float4 mo[MRG ? NE : 1][NR];      // MRG: un-normalised P.V values of this thread's NE float4 slots, records 0..NR-1,
+    float mt[NE1 ? NE1 : 1][NR];      //      of its NE1 tail elements,
+    v2f sml[MRG ? NE : 1][2][NR];     //      and the (m, l) pairs of a wave's two heads per float4 slot / one head per tail slot:
+    v2f smt[NE1 ? NE1 : 1][NR];       //      wave-uniform addresses -> scalar loads (load_uniform2)
+    int mpos = 0;                     //      and the position, likewise
     if (!MRG) {
 #pragma unroll
         for (int i = 0; i < NCP; ++i) qa[i] = *reinterpret_cast<const v4u *>(p.qin + umin32(16u * (uint32_t)(tid + NT * i), q_last));
     } else {
-        // chunks 0..3 are requested before the position (hence the live chunk count) is known; dead records hold zeros or
-        // an earlier token's finite values: only their m is masked below.  A thread takes 4 consecutive elements (one
-        // 16-byte load per chunk); a wave's 256 elements lie in at most two heads, whose (m, l) pairs every lane fetches.
+        // records 0..NR-1 are requested before the position (hence the live record count) is known; dead records hold zeros or
+        // an earlier token's finite values: only their m is masked below.
+        // Byte offsets in 32 bits from the one uniform base (the launcher bounds the buffer): one add per request.
+        const int gl = p.attn_group_log2, gm = (1 << gl) - 1, h_last = (p.cols >> 7) - 1;
+        const uint32_t kv_stride = (uint32_t)p.attn_chunks_max * (kAttnRecFloats * 4u);
+        const char *rbase = reinterpret_cast<const char *>(p.attn_rec);
+        uint32_t ro[NR];
+#pragma unroll
+        for (int c = 0; c < NR; ++c) ro[c] = (uint32_t)(c < p.attn_chunks_max ? c : p.attn_chunks_max - 1) * (kAttnRecFloats * 4u);
+        mpos = load_uniform_i(p.attn_pos);
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
             int e = 4 * (tid + NT * i);
             e = e < p.cols ? e : p.cols - 4;
-            const int h = e >> 7, d = e & 127, kvh = h >> p.attn_group_log2, hg = h & ((1 << p.attn_group_log2) - 1);
-            const float *rb = p.attn_rec + (size_t)kvh * p.attn_chunks_max * kAttnRecFloats;
+            const int h = e >> 7, d = e & 127;
+            const uint32_t vo = (uint32_t)(h >> gl) * kv_stride + 4u * (uint32_t)(2 * kMaxGroupQ + (h & gm) * 128 + d);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float *rec = rb + (size_t)(c < p.attn_chunks_max ? c : p.attn_chunks_max - 1) * kAttnRecFloats;
-                mml[i][c] = *reinterpret_cast<const float2 *>(rec + 2 * hg);
-                mo[i][c] = *reinterpret_cast<const float4 *>(rec + 2 * kMaxGroupQ + hg * 128 + d);
+            for (int c = 0; c < NR; ++c) mo[i][c] = *reinterpret_cast<const float4 *>(rbase + (vo + ro[c]));
+        }
+#pragma unroll
+        for (int i = 0; i < NE1; ++i) {
+            int e = 4 * NT * NE + tid + NT * i;
+            e = e < p.cols ? e : p.cols - 1;
+            const int h = e >> 7, d = e & 127;
+            const uint32_t vo = (uint32_t)(h >> gl) * kv_stride + 4u * (uint32_t)(2 * kMaxGroupQ + (h & gm) * 128 + d);
+#pragma unroll
+            for (int c = 0; c < NR; ++c) mt[i][c] = *reinterpret_cast<const float *>(rbase + (vo + ro[c]));
+        }
+#pragma unroll
+        for (int i = 0; i < NE; ++i)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {  // lanes 0..31 / 32..63 of this wave's slot
+                int hs = 2 * (wave + NW * i) + s;
+                hs = hs < h_last ? hs : h_last;
+                const uint32_t so = (uint32_t)(hs >> gl) * kv_stride + 8u * (uint32_t)(hs & gm);
+#pragma unroll
+                for (int c = 0; c < NR; ++c) sml[i][s][c] = load_uniform2(rbase + (so + ro[c]));
             }
+#pragma unroll
+        for (int i = 0; i < NE1; ++i) {
+            int hs = ((4 * NT * NE + NT * i) >> 7) + (wave >> 1);
+            hs = hs < h_last ? hs : h_last;
+            const uint32_t so = (uint32_t)(hs >> gl) * kv_stride + 8u * (uint32_t)(hs & gm);
+#pragma unroll
+            for (int c = 0; c < NR; ++c) smt[i][c] = load_uniform2(rbase + (so + ro[c]));
         }
     }
     v4u st = {0u, 0u, 0u, 0u};
@@ -196,27 +242,66 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
 #pragma unroll
         for (int i = 0; i < NCP; ++i) *reinterpret_cast<v4u *>(cq + 16 * (tid + NT * i)) = qa[i];
     } else {
-        const int m_chunks = (*p.attn_pos + (1 << p.attn_chunk_log2)) >> p.attn_chunk_log2;  // live records, 1..4 (the caller switches to the combine kernel beyond that)
+        const int m_chunks = (mpos + (1 << p.attn_chunk_log2)) >> p.attn_chunk_log2;  // live records, 1..NR (the caller switches form beyond that)
+        // softmax merge: out = sum_c e^(m_c - M) o_c / sum_c e^(m_c - M) l_c   (k_attn_combine's value); records in ascending order.
+        // Every record count gives the bits the two-launch form gives there.  Up to 4 live records that is the 4-record merge
+        // (v_exp_f32, one reciprocal).  From 5 records the decoder used to run k_attn_combine, which for at most 8 records is this
+        // same two-pass sum -- each of its 8 thread groups holds one record, (m, l, o) unchanged -- with expf and a division per
+        // element: the 8-record instance takes those two from 5 live records on (wave-uniform), so a step's numbers do not depend
+        // on whether the combine kernel or this prologue merged the records.
+        const bool as_combine = NR > 4 && m_chunks > 4;
+        constexpr int NS = MRG ? NE + NE1 : 1;
+        float ml[NS][NR], xl[NS][NR], wl[NS][NR];  // per slot (float4 slots, then tail slots): l_c, m_c - M, the weights e^(m_c - M)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            float mc[NR], M = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < NR; ++c) {
+                const float mv = k < NE ? (lane < 32 ? sml[k < NE ? k : 0][0][c].x : sml[k < NE ? k : 0][1][c].x) : smt[k < NE ? 0 : k - NE][c].x;
+                ml[k][c] = k < NE ? (lane < 32 ? sml[k < NE ? k : 0][0][c].y : sml[k < NE ? k : 0][1][c].y) : smt[k < NE ? 0 : k - NE][c].y;
+                mc[c] = c < m_chunks ? mv : -INFINITY;
+                M = fmaxf(M, mc[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < NR; ++c) xl[k][c] = mc[c] - M;
+        }
+        if constexpr (NR <= 4) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k)
+#pragma unroll
+                for (int c = 0; c < NR; ++c) wl[k][c] = __expf(xl[k][c]);
+        } else {
+            // The weights are wave-uniform per head, and expf is ~12 instructions: lane 8 k + c (32 + 8 k + c for the upper half's
+            // head) evaluates the exponential of record c of slot k ONCE and readlane hands the results round -- one evaluation per
+            // wave instead of NR per slot and lane (the same function of the same argument: the same bits).
+            float tx = 0.0f;
+#pragma unroll
+            for (int k = 0; k < NS; ++k)
+#pragma unroll
+                for (int c = 0; c < NR; ++c) tx = (lane & 31) == 8 * k + c ? xl[k][c] : tx;
+            const float ex = as_combine ? expf(tx) : __expf(tx);
+#pragma unroll
+            for (int k = 0; k < NS; ++k)
+#pragma unroll
+                for (int c = 0; c < NR; ++c) {
+                    const float lo = readlane_f(ex, 8 * k + c);
+                    wl[k][c] = k < NE ? (lane < 32 ? lo : readlane_f(ex, 32 + 8 * k + c)) : lo;
+                }
+        }
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
             const int e = 4 * (tid + NT * i);
-            // softmax merge: out = sum_c e^(m_c - M) o_c / sum_c e^(m_c - M) l_c   (k_attn_combine's value)
-            float M = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                mml[i][c].x = c < m_chunks ? mml[i][c].x : -INFINITY;
-                M = fmaxf(M, mml[i][c].x);
-            }
             float L = 0.0f;
             float4 a = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float w = __expf(mml[i][c].x - M);
-                L += w * mml[i][c].y;
-                a.x += w * mo[i][c].x, a.y += w * mo[i][c].y, a.z += w * mo[i][c].z, a.w += w * mo[i][c].w;
+            for (int c = 0; c < NR; ++c) {
+                const float w = wl[i][c];  // explicit fused multiply-adds: what the contraction made of `L += w * l` in the 4-record
+                L = fmaf(w, ml[i][c], L);  // form and in k_attn_combine, and no packed multiply + add may take their place
+                a.x = fmaf(w, mo[i][c].x, a.x), a.y = fmaf(w, mo[i][c].y, a.y), a.z = fmaf(w, mo[i][c].z, a.z), a.w = fmaf(w, mo[i][c].w, a.w);
             }
             const float rl = e < p.cols ? 1.0f / L : 0.0f;
-            const float v[4] = {a.x * rl, a.y * rl, a.z * rl, a.w * rl};
+            float v[4] = {a.x * rl, a.y * rl, a.z * rl, a.w * rl};
+            if (as_combine && e < p.cols) v[0] = a.x / L, v[1] = a.y / L, v[2] = a.z / L, v[3] = a.w / L;
             // qact_emit's arithmetic (qact.hpp) with the 16-element group spread over 4 lanes x 4 elements; destination = the
             // LDS image instead of a global record
             uint32_t u = __float_as_uint(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])))), o;
@@ -239,6 +324,32 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
                 *reinterpret_cast<uint32_t *>(qb + 16 * tp + (e & 15)) = d0;
                 *reinterpret_cast<uint32_t *>(qb + 256 + 16 * tp + (e & 15)) = d1;
                 if ((e & 15) == 0) reinterpret_cast<float *>(qb + 512)[4 * (tp >> 2) + 2 * (tp & 1) + ((tp & 3) >> 1)] = as;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NE1; ++i) {
+            const int e = 4 * NT * NE + tid + NT * i;  // whole 16-lane rows are live or dead together (cols % 16 == 0)
+            float L = 0.0f, a = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NR; ++c) {
+                const float w = wl[NE + i][c];
+                L = fmaf(w, ml[NE + i][c], L);
+                a = fmaf(w, mt[i][c], a);
+            }
+            float v = a * (e < p.cols ? 1.0f / L : 0.0f);
+            if (as_combine && e < p.cols) v = a / L;
+            // qact_emit's arithmetic with its own layout: one element per lane, the group = a DPP row
+            int be = (int)(__float_as_uint(row16_max_abs(v)) >> 23);
+            be = be < 32 ? 32 : be;
+            be = be > 254 ? 254 : be;
+            const float sc = __uint_as_float((uint32_t)(267 - be) << 23), as = __uint_as_float((uint32_t)(be - 13) << 23);
+            const uint32_t t = ((uint32_t)qcvt_rpi(v * sc) + 0x80u) ^ 0x80u;
+            if (e < p.cols) {
+                const int grp = e >> 4, rec = grp >> 4, tp = grp & 15, r = e & 15;
+                uint8_t *qb = cq + kQRec * rec;
+                qb[16 * tp + r] = (uint8_t)t;
+                qb[256 + 16 * tp + r] = (uint8_t)(t >> 8);
+                if (r == 0) reinterpret_cast<float *>(qb + 512)[4 * (tp >> 2) + 2 * (tp & 1) + ((tp & 3) >> 1)] = as;
             }
         }
     }
@@ -467,13 +578,20 @@ hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream
     BH_QPICK(2) BH_QPICK(3) BH_QPICK(4) BH_QPICK(5)
 #undef BH_QPICK
 #undef BH_QPICK2
-    if (io.attn_rec) {  // merging form: the o-projection shape (K = heads * 128 <= 4096: 8 elements per thread at most, ring <= 2)
-        const int ne = (int)div_ceil(w.cols / 4, (size_t)512);  // 4-element slots per thread
-        if (ln || nw != 8 || ring > 2 || ncp != 1 || w.cols % 128 != 0 || ne > 2 || !io.attn_pos || io.attn_chunks_max < 1) return hipErrorInvalidValue;
-#define BH_QMRG(NEv)                                                                                                                   \
-    if (ne <= NEv && !kfn) kfn = sc == 2 ? k_gemv_q<8, 2, 2, 0, 1, NEv> : sc == 1 ? k_gemv_q<8, 2, 1, 0, 1, NEv> : k_gemv_q<8, 2, 0, 0, 1, NEv>;
+    if (io.attn_rec) {  // merging form: the o-projection shape (K = heads * 128: ring <= 2, one copy pass)
+        // slots per thread: one float4 (K <= 2048), one float4 + one float (K <= 2560), two float4 (beyond; 4 records only)
+        const int nr = io.attn_records;
+        const int ne = w.cols <= 2560 ? 1 : 2, ne1 = w.cols > 2048 && w.cols <= 2560 ? 1 : 0;
+        if (ln || nw != 8 || ring > 2 || ncp != 1 || w.cols % 128 != 0 || w.cols > 4096 || !io.attn_pos || io.attn_chunks_max < 1 || (nr != 4 && nr != 8) ||
+            (nr == 8 && ne == 2))
+            return hipErrorInvalidValue;
+        // the kernel addresses the records with 32-bit byte offsets
+        if (((uint64_t)(w.cols / 128) >> io.attn_group_log2) * (uint64_t)io.attn_chunks_max * kAttnRecFloats * 4u >= (1ull << 32)) return hipErrorInvalidValue;
+#define BH_QMRG(NEv, NE1v, NRv)                     \
+    if (ne == NEv && ne1 == NE1v && nr == NRv)      \
+        kfn = sc == 2 ? k_gemv_q<8, 2, 2, 0, 1, NEv, NE1v, NRv> : sc == 1 ? k_gemv_q<8, 2, 1, 0, 1, NEv, NE1v, NRv> : k_gemv_q<8, 2, 0, 0, 1, NEv, NE1v, NRv>;
         kfn = nullptr;
-        BH_QMRG(1) BH_QMRG(2)
+        BH_QMRG(1, 0, 4) BH_QMRG(1, 1, 4) BH_QMRG(2, 0, 4) BH_QMRG(1, 0, 8) BH_QMRG(1, 1, 8)
 #undef BH_QMRG
     }
     if (!kfn) return hipErrorInvalidValue;

@@ -104,6 +104,7 @@ Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n
         const int group = c_.n_kv_heads > 0 ? c_.n_heads / c_.n_kv_heads : 0;
         merge_ok_ = c_.head_dim == 128 && (group == 1 || group == 2 || group == 4) && c_.n_heads % c_.n_kv_heads == 0 &&
                     (size_t)c_.n_heads * 128 <= 4096;
+        merge8_ok_ = merge_ok_ && (size_t)c_.n_heads * 128 <= 2560;  // bitnet_hip_gemv_attn_merge_rec_q_dev with 8 records
     }
     bool ok = true;
     ok &= dalloc(&x_, H) == hipSuccess && dalloc(&x2_, H) == hipSuccess;
@@ -422,12 +423,12 @@ int Decoder::position() {
     return p;
 }
 
-// The decode attention in the form and cache type this decoder runs: form 0 two kernels (64-position records), 1 records only
+// The decode attention in the form and cache type this decoder runs: form 0 two kernels (64-position records), 1 and 3 records only
 // (the o-projection merges them), 2 two kernels with 128-position records; out / qout: f32 output and / or its QAct.
 int Decoder::attn_launch(Layer &L, int form, float *out, void *qout) {
     // forms (form_at): 0 = 64-position records + combine, 1 = 64-position records merged by the o-projection (<= 256 keys),
-    //                  2 = 128-position records + combine
-    const int flags = (form >= 2 ? BITNET_HIP_ATTN_WIDE : 0) | ((form & 1) ? BITNET_HIP_ATTN_PARTIAL : 0) | (kv_f16_ ? BITNET_HIP_ATTN_KV_F16 : 0);
+    //                  2 = 128-position records + combine, 3 = as 1 with the 8-record merge (257..kMerge8MaxKeys keys, QAct path)
+    const int flags = (form == 2 ? BITNET_HIP_ATTN_WIDE : 0) | ((form & 1) ? BITNET_HIP_ATTN_PARTIAL : 0) | (kv_f16_ ? BITNET_HIP_ATTN_KV_F16 : 0);
     BCHK(bitnet_hip_attention_decode_q_dev(qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, (size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)c_.head_dim,
                                            (size_t)c_.max_pos, pos_, attn_scratch_, flags, out, qout, stream_));
     return 0;
@@ -494,7 +495,8 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
     const size_t H = c_.hidden;
     const size_t tQD = (size_t)c_.n_heads * c_.head_dim, tKD = (size_t)c_.n_kv_heads * c_.head_dim;
     const std::string tp = tr ? "t" + std::to_string(tr->seq) + "/" : "";
-    if (tr && (form & 1)) form -= 1;  // the merging o-projection never materialises the attention output
+    if (tr && (form & 1)) form = 0;  // the merging o-projection never materialises the attention output
+    if (form == 3 && !qact_path()) form = 0;  // the 8-record merge exists on the QAct path only
     if (qact_path()) {
         // Every vector that travels between two GEMVs goes as a QAct written by its producer's epilogue (x: embedding /
         // down-projection, attention output: combine kernel or merging o-projection, x2: o-projection, h: gate|up).
@@ -508,9 +510,9 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
             TRACE(bp + "q_proj", "q_proj", (int)l, qkv_, tQD);
             TRACE(bp + "k_proj", "k_proj", (int)l, qkv_ + tQD, tKD);
             TRACE(bp + "v_proj", "v_proj", (int)l, qkv_ + tQD + tKD, tKD);
-            if (form == 1) {
-                if (int rc = attn_launch(L, 1, nullptr, nullptr)) return rc;
-                BCHK(bitnet_hip_gemv_attn_merge_q_dev(L.o, attn_scratch_, NH, NK, MP, pos_, x2_, x_, qa_x2_, L.ffn_norm, st_x2_, s));
+            if (form & 1) {
+                if (int rc = attn_launch(L, form, nullptr, nullptr)) return rc;
+                BCHK(bitnet_hip_gemv_attn_merge_rec_q_dev(L.o, attn_scratch_, NH, NK, MP, pos_, x2_, x_, qa_x2_, L.ffn_norm, st_x2_, form == 3 ? 8 : 4, s));
             } else {
                 if (int rc = attn_launch(L, form, tr ? att_ : nullptr, qa_att_)) return rc;
                 TRACE(bp + "attn_out", "attn_out", (int)l, att_, tQD);
@@ -663,12 +665,16 @@ int Decoder::run_reference(int n, bool with_logits) {
 
 // Which attention form a step at `pos` (pos + 1 keys) takes; the host knows every step's position.
 int Decoder::form_at(int pos) const {
-    static const bool merge_env = !(getenv("BITNET_HOST_ATTN_MERGE") && atoi(getenv("BITNET_HOST_ATTN_MERGE")) == 0);
+    // BITNET_HOST_ATTN_MERGE = the largest record count the o-projection merges: 0 none (also negative values and text that is no number: atoi), 1..7 four (<= 256 keys), unset or >= 8 eight
+    static const int merge_env = getenv("BITNET_HOST_ATTN_MERGE") ? atoi(getenv("BITNET_HOST_ATTN_MERGE")) : 8;
     static const bool wide_env = !(getenv("BITNET_HOST_ATTN_WIDE") && atoi(getenv("BITNET_HOST_ATTN_WIDE")) == 0);
     const int keys = pos + 1;
-    if (merge_env && merge_ok_ && keys <= (int)bitnet_hip_attention_merge_max_keys()) return 1;
+    if (merge_env > 0 && merge_ok_ && keys <= (int)bitnet_hip_attention_merge_max_keys()) return 1;
+    // 257..kMerge8MaxKeys keys: the same 64-position records, merged eight at a time by a prologue that asks for each value once
+    // (EXPERIMENTS 15; the QAct path only: k_gemv_mfma's merge stays at 4 records).
     // (257..512 keys as four 128-position records merged by the o-projection measured SLOWER than 64-position records + combine --
-    // c2 1201-1214 vs 1224 tok/s, round 2 -- and was removed in round 3)
+    // c2 1201-1214 vs 1224 tok/s, round 2 -- and was removed in round 3: the wide attention kernel is +1.5 us at these lengths)
+    if (merge_env >= 8 && merge8_ok_ && qact_path() && keys <= kMerge8MaxKeys && keys <= (int)bitnet_hip_attention_merge_q_max_keys()) return 3;
     if (wide_env && c_.n_kv_heads * ((keys + 63) / 64) > 256) return 2;  // more 64-position chunks than CUs
     return 0;
 }
@@ -1698,6 +1704,7 @@ void bitnet_host_global_objects(void *d, void **ptrs7) {
     if (Decoder *D = live(d)) D->global_objects(ptrs7);
 }
 int bitnet_host_position(void *d) { LIVE(-1); return D->position(); }
+int bitnet_host_form_at(void *d, int pos) { LIVE(-1); return pos < 0 ? -1 : D->form_at(pos); }
 int bitnet_host_last_prefill_path(void *d) { LIVE(-1); return D->last_prefill_path(); }
 int bitnet_host_saturation_fallbacks(void *d) { LIVE(-1); return D->saturation_fallbacks(); }
 int bitnet_host_history(void *d, int32_t *out, int n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->history(out, n); }

@@ -185,7 +185,7 @@ class Decoder {
     int fail_arg(const char *what);
     bool dead_ = false;
     // attention form of a step: 0 = two kernels, 64-position chunks; 1 = one kernel + merging o-projection (short
-    // contexts); 2 = two kernels, 128-position chunks (more chunks than CUs)
+    // contexts: 4 records); 2 = two kernels, 128-position chunks (more chunks than CUs); 3 = as 1, 8 records (QAct path)
     struct Tracer;
     int step_launches(bool with_logits, int form, Tracer *tr = nullptr);
     int step_launches_reference(bool with_logits);
@@ -194,9 +194,14 @@ class Decoder {
     // Captures and instantiates the step graph of every attention form a sequence can reach (by position: form_at) ahead of
     // time, so that no run() pays for a capture in the middle of a generation.  Nothing executes.
     int prepare_graphs(bool with_logits);
-  private:
+    // Which attention form a step at `pos` takes (0..3 above): what run() will launch there with the current weights and settings.
     int form_at(int pos) const;
-    bool merge_ok_ = false;  // the o-projection can merge the attention chunk records itself (short contexts)
+    // Largest key count of form 3, by measurement (EXPERIMENTS 15.2): the form is taken up to the largest live record count at
+    // which it beat records + combine at that count and at every smaller one.
+    static constexpr int kMerge8MaxKeys = 512;
+  private:
+    bool merge_ok_ = false;   // the o-projection can merge the attention chunk records itself (short contexts)
+    bool merge8_ok_ = false;  // ... and up to 8 of them on the QAct path
 
     Config c_;
     std::string err_;
@@ -267,8 +272,8 @@ class Decoder {
     int prefill_chain_ = -1;  // BITNET_HOST_PREFILL_CHAIN: -1 automatic (the block-scaled format, whose matmul runs on f16 activations anyway), 0 off, 1 on
     size_t pf_gemm_ws_bytes_ = 0, pf_attn_ws_bytes_ = 0;
     size_t weight_bytes_ = 0;
-    static constexpr int kGraphs = 6;
-    void *graph_exec_[kGraphs] = {};  // [2 * form + with_logits], forms 0..2 (form_at)
+    static constexpr int kGraphs = 8;
+    void *graph_exec_[kGraphs] = {};  // [2 * form + with_logits], forms 0..3 (form_at)
     void *graph_[kGraphs] = {};
     int logits_wgs_ = 512;  // two workgroups per CU: whole rounds on the 256 CUs (768 / 1280 workgroups are 15-20 % slower)
 };
@@ -317,6 +322,7 @@ int bitnet_host_rccl_allgather(void *nccl_comm, const void *send_dev, void *recv
 void bitnet_host_layer_objects(void *d, int layer, uint64_t *handles4, void **ptrs4);
 void bitnet_host_global_objects(void *d, void **ptrs7);
 int bitnet_host_position(void *d);
+int bitnet_host_form_at(void *d, int pos);  // attention form (0..3, Decoder::form_at) of a step at position pos; -1 for a dead handle
 int bitnet_host_history(void *d, int32_t *out, int n);
 int bitnet_host_last_logits(void *d, float *out);
 int bitnet_host_last_hidden(void *d, float *out);

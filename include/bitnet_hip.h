@@ -497,6 +497,15 @@ int bitnet_hip_gemv_attn_merge_q_dev(bitnet_hip_weights_t w, const float *attn_s
                                      size_t n_kv_heads, size_t max_pos, const int32_t *pos_dev, float *y_dev,
                                      const float *residual_dev, void *qact_out, const float *gamma_out_dev,
                                      double *stats_out, void *stream);
+/* The same with the record bound chosen by the caller: max_records = 4 is bitnet_hip_gemv_attn_merge_q_dev itself; 8 merges up to 8 records
+ * of 64 positions (*pos_dev + 1 <= bitnet_hip_attention_merge_q_max_keys() = 512) and gives bit-identical y / QAct / statistics while at
+ * most 4 records are live.  All max_records records are requested by every workgroup (the request is what the merge costs: 41 KB at 4, 82 KB
+ * at 8 records x 2560 columns), so pass the smallest bound that covers the context.  8 records: w takes the QAct form, cols <= 2560. */
+size_t bitnet_hip_attention_merge_q_max_keys(void);
+int bitnet_hip_gemv_attn_merge_rec_q_dev(bitnet_hip_weights_t w, const float *attn_scratch_dev, size_t n_heads,
+                                         size_t n_kv_heads, size_t max_pos, const int32_t *pos_dev, float *y_dev,
+                                         const float *residual_dev, void *qact_out, const float *gamma_out_dev,
+                                         double *stats_out, size_t max_records, void *stream);
 /* The same attention for a whole prompt of seq_len tokens on a FRESH cache (positions
  * 0..seq_len-1): RoPE, cache append, causal GQA softmax attention (T:398-543 with the causal
  * mask T:452-470).  qkv_dev: [seq_len, n_heads*D + 2*n_kv*D]; out_dev: [seq_len, n_heads*D].

@@ -5,7 +5,12 @@ The launch sits where it sits in the real step: behind the q|k|v GEMV that produ
 ahead of the merging o-projection, `layers` such triples in one hipGraph; the stamps are taken in the LAST triple.
 Never used by tests / bench.
 
-    python tools/stamp_attn.py [--keys 150] [--kv16]
+    python tools/stamp_attn.py [--keys 150] [--kv16] [--records auto|0|4|8]
+    python tools/stamp_attn.py --table [--keys-list 200,250,300,360,420,500]
+
+Which tail a triple takes follows the library (bitnet_hip_attention_merge_max_keys / _merge_q_max_keys): the o-projection merging 4
+or 8 records, or records + combine + plain o-projection; --records overrides it.  --table needs no diagnostic library: per key
+count it times the combine form and the merging form in turn (three rounds, alternating) and prints us per triple of each.
 """
 from __future__ import annotations
 
@@ -29,10 +34,15 @@ def main():
     ap.add_argument("--layers", type=int, default=30)
     ap.add_argument("--kv16", action="store_true")
     ap.add_argument("--wide", action="store_true", help="128-position workgroups")
+    ap.add_argument("--records", default="auto", help="records the o-projection merges: auto (the library's bounds), 0 (combine kernel), 4, 8")
+    ap.add_argument("--table", action="store_true", help="time combine vs merging form per key count (regular library, no stamps)")
+    ap.add_argument("--keys-list", default="200,250,300,360,420,500")
     args = ap.parse_args()
-    hip = pkg.HipLib(pkg.LIB_PATH.replace(".so", "_diag.so"))
+    hip = pkg.HipLib(pkg.LIB_PATH if args.table else pkg.LIB_PATH.replace(".so", "_diag.so"))
     hip.init(0)
-    hip.c.bitnet_hip_debug_set_stamps.argtypes = [C.c_void_p]
+    if not args.table:
+        hip.c.bitnet_hip_debug_set_stamps.argtypes = [C.c_void_p]
+    hip.c.bitnet_hip_attention_merge_max_keys.restype = C.c_size_t
     H, NH, NK, D, max_pos = 2560, 20, 5, 128, 1024
     rng = np.random.default_rng(0)
     rows = (NH + 2 * NK) * D
@@ -69,11 +79,20 @@ def main():
     qatt = torch.zeros(hip.qact_bytes(NH * D), dtype=torch.uint8, device="cuda")
     st_out = torch.zeros(H // 16 * 2, dtype=torch.float64, device="cuda")
     stamps = torch.zeros(4096 * 8, dtype=torch.int64, device="cuda")
-    merge = args.keys <= 256 and not args.wide
+
+    def records_for(keys):  # what Decoder::form_at takes on the QAct path
+        if args.wide:
+            return 0
+        if args.records != "auto":
+            return int(args.records)
+        return 4 if keys <= hip.c.bitnet_hip_attention_merge_max_keys() else 8 if keys <= hip.attention_merge_q_max_keys() else 0
+
+    state = {"records": records_for(args.keys)}
 
     stamps_q = torch.zeros(4096 * 16, dtype=torch.int64, device="cuda")
     stamps_o = torch.zeros(4096 * 16, dtype=torch.int64, device="cuda")
-    setst = lambda t: hip.c.bitnet_hip_debug_set_stamps(C.c_void_p(t.data_ptr() if t is not None else 0))  # read by a launcher when its call is captured
+    setst = (lambda t: None) if args.table else (
+        lambda t: hip.c.bitnet_hip_debug_set_stamps(C.c_void_p(t.data_ptr() if t is not None else 0)))  # read by a launcher when its call is captured
 
     def triple(i, s, stamp=False):
         setst(stamps_q if stamp else None)
@@ -87,37 +106,62 @@ def main():
             setst(None)
 
     def tail(i, s):
-        if merge:
-            hip.gemv_attn_merge_q_dev(os_[i], scratch, NH, NK, max_pos, pos_d, y, qout, residual=res, gamma_out=gamma, stats_out=st_out, stream=s)
+        if state["records"]:
+            hip.gemv_attn_merge_rec_q_dev(os_[i], scratch, NH, NK, max_pos, pos_d, y, qout, state["records"], residual=res, gamma_out=gamma, stats_out=st_out,
+                                          stream=s)
         else:
             hip.gemv_q_dev(os_[i], qatt, y=y, residual=res, qact_out=qout, gamma_out=gamma, stats_out=st_out, stream=s)
 
     def attn(i, s):
-        if merge:
+        if state["records"]:
             hip.attention_decode_q_dev(qkv, sin_d, cos_d, kc[i], vc[i], NH, NK, D, max_pos, pos_d, scratch, None, None, kv_f16=args.kv16, partial=True, stream=s)
         else:
             hip.attention_decode_q_dev(qkv, sin_d, cos_d, kc[i], vc[i], NH, NK, D, max_pos, pos_d, scratch, None, qatt, wide=args.wide, kv_f16=args.kv16, stream=s)
 
-    cs = torch.cuda.current_stream().cuda_stream
-    for i in range(args.layers):
-        triple(i, cs)
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        s = torch.cuda.current_stream().cuda_stream
+    def capture(stamp_last):
+        cs = torch.cuda.current_stream().cuda_stream
         for i in range(args.layers):
-            triple(i, s, stamp=i == args.layers - 1)
-    for _ in range(3):
-        gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    print(f"{args.keys} keys ({'merging o-projection' if merge else 'combine kernel'}{', f16 cache' if args.kv16 else ''}): "
-          f"{e0.elapsed_time(e1) * 1e3 / 20 / args.layers:.2f} us per (q|k|v, attention, o) triple (diagnostic build)")
+            triple(i, cs)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            s = torch.cuda.current_stream().cuda_stream
+            for i in range(args.layers):
+                triple(i, s, stamp=stamp_last and i == args.layers - 1)
+        for _ in range(3):
+            gr.replay()
+        torch.cuda.synchronize()
+        return gr
+
+    def timed(gr, reps=20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            gr.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps / args.layers
+
+    if args.table:
+        print("keys records | combine form, us per (q|k|v, attention[, combine], o) triple | merging form | gain per layer")
+        for keys in [int(k) for k in args.keys_list.split(",")]:
+            pos_d.fill_(keys - 1)
+            rec = (keys + 63) // 64
+            graphs = {}
+            for name, r in (("combine", 0), ("merge", 4 if rec <= 4 else 8)):
+                state["records"] = r
+                graphs[name] = capture(False)
+            t = {"combine": [], "merge": []}
+            for _ in range(3):
+                for name in ("combine", "merge"):
+                    t[name].append(timed(graphs[name], 50))
+            fm = lambda v: "/".join(f"{x:.2f}" for x in v)
+            print(f"{keys:4d} {rec} | {fm(t['combine'])} | {fm(t['merge'])} | {np.mean(t['combine']) - np.mean(t['merge']):+.2f} us", flush=True)
+        return
+    merge, nrec = bool(state["records"]), state["records"]
+    gr = capture(True)
+    what = f"o-projection merging {nrec} records" if merge else "combine kernel"
+    print(f"{args.keys} keys ({what}{', f16 cache' if args.kv16 else ''}): {timed(gr):.2f} us per (q|k|v, attention, o) triple (diagnostic build)")
     st = stamps.cpu().numpy().reshape(-1, 8)
     st = st[st[:, 0] != 0]
     t0 = st[:, 0].min()

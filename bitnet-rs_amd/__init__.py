@@ -139,6 +139,15 @@ class HipLib:
         L.bitnet_hip_gemv_q_dev.argtypes = [C.c_uint64, _vp, _vp, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_attention_decode_q_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_int, _vp, _vp, _vp]
         L.bitnet_hip_gemv_attn_merge_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        # the batched decode kernels (n_seq vectors per launch; per-sequence state through device pointer tables)
+        L.bitnet_hip_embed_q_batch_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_embed_q_batch_dev.restype = C.c_int
+        L.bitnet_hip_gemv_q_batch_dev.argtypes = [C.c_uint64, _sz, _vp, _vp, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_gemv_q_batch_dev.restype = C.c_int
+        L.bitnet_hip_attention_decode_batch_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp, _vp]
+        L.bitnet_hip_attention_decode_batch_dev.restype = C.c_int
+        L.bitnet_hip_logits_f16_batch_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_logits_f16_batch_dev.restype = C.c_int
         L.bitnet_hip_gemv_attn_merge_rec_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
         L.bitnet_hip_attention_merge_q_max_keys.restype = _sz
         L.bitnet_hip_attention_merge_q_max_keys.argtypes = []
@@ -509,6 +518,28 @@ class HipLib:
         self._check(self.c.bitnet_hip_attention_decode_q_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kcache), _ptr(vcache), n_heads, n_kv,
                                                              head_dim, max_pos, _ptr(pos), _ptr(scratch), flags, _optr(out), _optr(qact_out), _vp(stream)))
 
+    # ---- several sequences per launch: vector b at b times its batch-1 size; *_ptrs = int64 device tensors of n_seq device pointers (0 = idle) ----
+    def embed_q_batch_dev(self, table, history_ptrs, pos_ptrs, n_seq: int, hidden: int, vocab: int, x_out, gamma, qact_out, stats_out=None,
+                          stream: int = 0) -> None:
+        self._check(self.c.bitnet_hip_embed_q_batch_dev(_ptr(table), _ptr(history_ptrs), _ptr(pos_ptrs), n_seq, hidden, vocab, _ptr(x_out), _optr(gamma),
+                                                        _ptr(qact_out), _optr(stats_out), _vp(stream)))
+
+    def gemv_q_batch_dev(self, h: int, n_seq: int, qact_in, y=None, stats_in=None, ln_gamma=None, ln_eps: float = 0.0, residual=None, flags: int = 0,
+                         qact_out=None, gamma_out=None, stats_out=None, stream: int = 0) -> None:
+        self._check(self.c.bitnet_hip_gemv_q_batch_dev(h, n_seq, _ptr(qact_in), _optr(stats_in), _optr(ln_gamma), ln_eps, _optr(residual), flags, _optr(y),
+                                                       _optr(qact_out), _optr(gamma_out), _optr(stats_out), _vp(stream)))
+
+    def attention_decode_batch_dev(self, qkv, rope_sin, rope_cos, kcache_ptrs, vcache_ptrs, pos_ptrs, n_seq: int, n_heads, n_kv, head_dim, max_pos, scratch,
+                                   out, qact_out, kv_f16: bool = False, stream: int = 0) -> None:
+        self._check(self.c.bitnet_hip_attention_decode_batch_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kcache_ptrs), _ptr(vcache_ptrs),
+                                                                 _ptr(pos_ptrs), n_seq, n_heads, n_kv, head_dim, max_pos, _ptr(scratch),
+                                                                 2 if kv_f16 else 0, _optr(out), _optr(qact_out), _vp(stream)))
+
+    def logits_f16_batch_dev(self, table, x, gamma, eps, hidden, vocab, n_seq: int, logits_ptrs, scratch, n_wg, token_ptrs=None, pos_ptrs=None,
+                             history_ptrs=None, n_forced_ptrs=None, stream: int = 0) -> None:
+        self._check(self.c.bitnet_hip_logits_f16_batch_dev(_ptr(table), _ptr(x), _optr(gamma), eps, hidden, vocab, n_seq, _ptr(logits_ptrs), _ptr(scratch),
+                                                           n_wg, _optr(token_ptrs), _optr(pos_ptrs), _optr(history_ptrs), _optr(n_forced_ptrs), _vp(stream)))
+
     def attention_merge_q_max_keys(self) -> int:
         return int(self.c.bitnet_hip_attention_merge_q_max_keys())
 
@@ -799,12 +830,19 @@ class HostDecoder:
     """ctypes view of the C++ Decoder (mirror of the reference's Rust-side
     TransformerModel / KVCache / greedy loop).  No arithmetic here."""
 
-    def __init__(self, cfg, path: str = HOST_LIB_PATH):
+    def __init__(self, cfg, path: str = HOST_LIB_PATH, _owner: "HostDecoder | None" = None):
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not found: build it with __graft_entry__.build() -- there is no fallback path")
         load()  # the kernel library must be loadable first
         self.c = C.CDLL(path)
         L = self.c
+        # every binding is set here, at construction, never on first use (a lazily bound pointer argument crashed a process once)
+        L.bitnet_host_create_shared.restype = C.c_void_p
+        L.bitnet_host_create_shared.argtypes = [C.c_void_p]
+        L.bitnet_host_set_attention_form.argtypes = [C.c_void_p, C.c_int]
+        L.bitnet_host_set_attention_form.restype = C.c_int
+        L.bitnet_host_release.argtypes = [C.c_void_p]
+        L.bitnet_host_release.restype = None
         L.bitnet_host_create.restype = C.c_void_p
         L.bitnet_host_create.argtypes = [C.POINTER(HostConfig)]
         L.bitnet_host_destroy.argtypes = [C.c_void_p]
@@ -841,9 +879,9 @@ class HostDecoder:
         self.cfg = cfg
         self._fed = 0  # tokens fed since the last reset (the default n of score)
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
-        self.h = L.bitnet_host_create(C.byref(hc))
+        self.h = L.bitnet_host_create(C.byref(hc)) if _owner is None else L.bitnet_host_create_shared(_owner.h)
         if not self.h:
-            raise BitNetHipError(ERR_GPU, "bitnet_host_create failed (allocation)")
+            raise BitNetHipError(ERR_GPU, "bitnet_host_create failed (allocation)" if _owner is None else "bitnet_host_create_shared: dead or closed owner")
         err = self.error()
         if err:
             self.close()  # a dead decoder (rejected configuration, failed allocation) is destroyed before the error is raised
@@ -861,6 +899,17 @@ class HostDecoder:
         if self.h:
             self.c.bitnet_host_destroy(self.h)
             self.h = None
+
+    def shared(self) -> "HostDecoder":
+        """A decoder that BORROWS this one's weights (same handles, norm vectors, embedding table): its own KV caches, history, position,
+        sampler and stream.  It refuses set_layer_* / set_globals / load_gguf / set_act_mode, and this decoder refuses set_layer_* /
+        set_globals while borrowers live.  close() order is free: the library keeps the owner until its last borrower is gone."""
+        return HostDecoder(self.cfg, path=self.c._name, _owner=self)
+
+    def set_attention_form(self, form: int) -> None:
+        """-1: the attention form follows the position (default); 0: 64-position records + combine at every position, the form a
+        HostBatch step runs -- run() under form 0 gives the bits a batch reproduces."""
+        self._check(self.c.bitnet_host_set_attention_form(self.h, form))
 
     def load_gguf(self, gguf: "GgufFile") -> None:
         self.c.bitnet_host_load_gguf.argtypes = [C.c_void_p, C.c_void_p]
@@ -1057,3 +1106,56 @@ class HostDecoder:
 
     def weight_bytes(self) -> int:
         return int(self.c.bitnet_host_weight_bytes(self.h))
+
+
+class HostBatch:
+    """ctypes view of the C++ BatchDecoder (host/batch_decoder.hpp): up to 8 slots, each holding a HostDecoder -- an owner or decoders from
+    owner.shared() -- that take decode steps TOGETHER through one launch chain, each at its own position.  After step(n) every member is
+    where its own run(n) under set_attention_form(0) would have left it, bit for bit.  set_slot() between steps is the scheduler."""
+
+    def __init__(self, n_slots: int, path: str = HOST_LIB_PATH):
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path} not found: build it with __graft_entry__.build() -- there is no fallback path")
+        load()
+        self.c = C.CDLL(path)
+        L = self.c
+        L.bitnet_host_batch_create.restype = C.c_void_p
+        L.bitnet_host_batch_create.argtypes = [C.c_int]
+        L.bitnet_host_batch_destroy.restype = None
+        L.bitnet_host_batch_destroy.argtypes = [C.c_void_p]
+        L.bitnet_host_batch_error.restype = C.c_char_p
+        L.bitnet_host_batch_error.argtypes = [C.c_void_p]
+        L.bitnet_host_batch_set_slot.restype = C.c_int
+        L.bitnet_host_batch_set_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.bitnet_host_batch_step.restype = C.c_int
+        L.bitnet_host_batch_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        self.n_slots = n_slots
+        self.h = L.bitnet_host_batch_create(n_slots)
+        if not self.h:
+            raise BitNetHipError(ERR_GPU, "bitnet_host_batch_create failed")
+        err = self.error()
+        if err:
+            self.close()
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, err)
+
+    def error(self) -> str:
+        e = self.c.bitnet_host_batch_error(self.h)
+        return e.decode() if e else ""
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise BitNetHipError(rc, self.error() or f"bitnet_host_batch rc={rc}")
+
+    def close(self) -> None:
+        if self.h:
+            self.c.bitnet_host_batch_destroy(self.h)
+            self.h = None
+
+    def set_slot(self, b: int, decoder: "HostDecoder | None") -> None:
+        self._check(self.c.bitnet_host_batch_set_slot(self.h, b, None if decoder is None else decoder.h))
+
+    def step(self, n: int = 1, use_graph: bool = True) -> float:
+        """n with-logits decode steps for every occupied slot; returns the elapsed milliseconds (HIP events)."""
+        ms = C.c_float(0.0)
+        self._check(self.c.bitnet_host_batch_step(self.h, n, int(use_graph), C.byref(ms)))
+        return float(ms.value)

@@ -1124,6 +1124,109 @@ int bitnet_hip_attention_decode_q_dev(const float *qkv, const float *rope_sin, c
     BH_GUARD_END
 }
 
+/* ---- several sequences per launch (kernels_batch.hip; k_attn_partial_batch / k_attn_combine_batch in kernels_attn.hip) ---- */
+
+static int check_n_seq(size_t n_seq, const char *who) {
+    if (n_seq == 0 || n_seq > BITNET_HIP_BATCH_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_seq %zu must be 1..%d", who, n_seq, BITNET_HIP_BATCH_MAX);
+    return BITNET_HIP_OK;
+}
+
+int bitnet_hip_embed_q_batch_dev(const void *table, const int32_t *const *history_ptrs_dev, const int32_t *const *pos_ptrs_dev, size_t n_seq, size_t hidden,
+                                 size_t vocab, float *x_out_dev, const float *gamma_dev, void *qact_out, double *stats_out, void *stream) {
+    BH_GUARD_BEGIN
+    if (int rc = check_n_seq(n_seq, "embed_q_batch_dev")) return rc;
+    if (!table || !history_ptrs_dev || !pos_ptrs_dev || !x_out_dev || !qact_out)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to embed_q_batch_dev");
+    if (hidden == 0 || hidden % 16 != 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "embed_q_batch: hidden %zu must be a positive multiple of 16", hidden);
+    BH_HIP_TRY(launch_embed_q_batch(table, history_ptrs_dev, pos_ptrs_dev, (int)n_seq, (int)hidden, (int)vocab, x_out_dev, gamma_dev, qact_out, stats_out,
+                                    (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_gemv_q_batch_dev(bitnet_hip_weights_t h, size_t n_seq, const void *qact_in, const double *stats_in, const float *ln_gamma_dev, float ln_eps,
+                                const float *residual_dev, int flags, float *y_dev, void *qact_out, const float *gamma_out_dev, double *stats_out,
+                                void *stream) {
+    BH_GUARD_BEGIN
+    if (int rc = check_n_seq(n_seq, "gemv_q_batch_dev")) return rc;
+    if (!qact_in || (!y_dev && !qact_out)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_q_batch_dev");
+    const WeightsRef w = lookup(h);
+    if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
+    if (!gemvq_supported(*w))
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_batch_dev: matrix %zux%zu (block %zu) is not on the QAct path (cols %% 256 == 0, rows %% 16 == 0, no scales or 32-element blocks)",
+                         w->rows, w->cols, w->block_size);
+    GemvQIo io;
+    io.qin = qact_in;
+    io.stats_in = stats_in;
+    io.ln_gamma = ln_gamma_dev;
+    io.ln_eps = ln_eps;
+    io.residual = residual_dev;
+    io.silu_mul = (flags & BITNET_HIP_FUSE_SILU_MUL) != 0;
+    io.y = y_dev;
+    io.qout = qact_out;
+    io.gamma_out = gamma_out_dev;
+    io.stats_out = stats_out;
+    if (io.silu_mul && (!w->paired || residual_dev || w->rows % 32 != 0))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
+    if (ln_gamma_dev && (!stats_in || !w->ln_g || w->ln_gamma_bound != ln_gamma_dev))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "gemv_q_batch_dev: LayerNorm needs stats_in and the gamma bound with bitnet_hip_weights_bind_ln");
+    if (ln_gamma_dev && w->cols > 4096)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_batch_dev: LayerNorm input of %zu columns (<= 4096)", w->cols);
+    const size_t lds = gemv_q_batch_lds_bytes(*w, ln_gamma_dev != nullptr, io.silu_mul, (int)n_seq);
+    if (lds > 160 * 1024)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_batch_dev: %zu vectors of %zu columns need %zu bytes of LDS (160 KiB): take them in smaller groups",
+                         n_seq, w->cols, lds);
+    hipError_t e = launch_gemv_q_batch(*w, io, (int)n_seq, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(BITNET_HIP_ERR_GPU, "kernel launch failed: %s", hipGetErrorString(e));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_attention_decode_batch_dev(const float *qkv, const float *rope_sin, const float *rope_cos, void *const *kcache_ptrs_dev,
+                                          void *const *vcache_ptrs_dev, const int32_t *const *pos_ptrs_dev, size_t n_seq, size_t n_heads, size_t n_kv_heads,
+                                          size_t head_dim, size_t max_pos, float *scratch, int flags, float *out, void *qact_out, void *stream) {
+    BH_GUARD_BEGIN
+    if (int rc = check_n_seq(n_seq, "attention_decode_batch_dev")) return rc;
+    if (!qkv || !rope_sin || !rope_cos || !kcache_ptrs_dev || !vcache_ptrs_dev || !pos_ptrs_dev || !scratch || (!out && !qact_out))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_decode_batch_dev");
+    if (flags & ~BITNET_HIP_ATTN_KV_F16)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_decode_batch_dev: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16: 64-position records + combine only)", flags);
+    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
+    if (max_pos == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_decode_batch_dev: max_pos 0");
+    if (head_dim != 128 || n_heads / n_kv_heads > 4)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "attention_decode: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)", head_dim,
+                         n_heads / n_kv_heads);
+    BH_HIP_TRY(launch_attn_decode_batch(qkv, rope_sin, rope_cos, reinterpret_cast<float *const *>(kcache_ptrs_dev), reinterpret_cast<float *const *>(vcache_ptrs_dev),
+                                        reinterpret_cast<const int *const *>(pos_ptrs_dev), (int)n_seq, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos,
+                                        scratch, out, qact_out, (flags & BITNET_HIP_ATTN_KV_F16) != 0, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_logits_f16_batch_dev(const void *table, const float *x, const float *gamma, float eps, size_t hidden, size_t vocab, size_t n_seq,
+                                    float *const *logits_ptrs_dev, void *scratch, size_t n_wg, int32_t *const *token_ptrs_dev, int32_t *const *pos_ptrs_dev,
+                                    int32_t *const *history_ptrs_dev, const int32_t *const *n_forced_ptrs_dev, void *stream) {
+    BH_GUARD_BEGIN
+    if (int rc = check_n_seq(n_seq, "logits_f16_batch_dev")) return rc;
+    if (!table || !x || !logits_ptrs_dev || !scratch) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to logits_f16_batch_dev");
+    if (hidden == 0 || hidden % 512 != 0 || hidden > 8192)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits: hidden %zu must be a multiple of 512, <= 8192", hidden);
+    if (n_seq * hidden * sizeof(float) > 152 * 1024)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits_f16_batch_dev: %zu vectors of %zu columns do not fit the LDS (152 KiB): take them in smaller groups", n_seq,
+                         hidden);
+    if (n_wg == 0 || n_wg > 65535) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logits: bad workgroup count %zu", n_wg);
+    float *bv = static_cast<float *>(scratch);
+    int *bi = reinterpret_cast<int *>(bv + n_seq * n_wg);
+    BH_HIP_TRY(launch_logits_f16_batch(table, x, gamma, eps, (int)hidden, (int)vocab, (int)n_seq, logits_ptrs_dev, bv, bi, (int)n_wg,
+                                       reinterpret_cast<int *const *>(token_ptrs_dev), reinterpret_cast<int *const *>(pos_ptrs_dev),
+                                       reinterpret_cast<int *const *>(history_ptrs_dev), reinterpret_cast<const int *const *>(n_forced_ptrs_dev),
+                                       (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 size_t bitnet_hip_attention_prefill_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t seq_len) {
     return attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)seq_len, (int)seq_len);
 }

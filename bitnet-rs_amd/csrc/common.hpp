@@ -153,6 +153,19 @@ hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream
 hipError_t launch_quant_act(const float *x, const float *gamma, size_t n, void *qout, double *stats, hipStream_t stream);
 hipError_t launch_embed_q(const void *table, const int *tokens, const int *offset_ptr, int hidden, int vocab, float *x_out,
                           const float *gamma, void *qout, double *stats, hipStream_t stream);
+// ---- several sequences per launch (kernels_batch.hip, kernels_attn.hip): vector b of every batched buffer lies at b times its batch-1 size;
+//      per-sequence state (caches, positions, histories, logits rows) is reached through DEVICE pointer tables, a NULL entry = idle slot ----
+constexpr int kBatchMax = 8;  // BITNET_HIP_BATCH_MAX
+hipError_t launch_gemv_q_batch(const Weights &w, const GemvQIo &io, int n_seq, hipStream_t stream);
+size_t gemv_q_batch_lds_bytes(const Weights &w, bool ln, bool silu_mul, int n_seq);
+hipError_t launch_embed_q_batch(const void *table, const int *const *history_ptrs, const int *const *pos_ptrs, int n_seq, int hidden, int vocab,
+                                float *x_out, const float *gamma, void *qout, double *stats, hipStream_t stream);
+hipError_t launch_attn_decode_batch(const float *qkv, const float *rope_sin, const float *rope_cos, float *const *kc_ptrs, float *const *vc_ptrs,
+                                    const int *const *pos_ptrs, int n_seq, int n_heads, int n_kv, int D, int max_pos, float *scratch, float *out, void *qout,
+                                    int kv_f16, hipStream_t stream);
+hipError_t launch_logits_f16_batch(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab, int n_seq,
+                                   float *const *logits_ptrs, float *best_val, int *best_idx, int n_wg, int *const *token_ptrs, int *const *pos_ptrs,
+                                   int *const *history_ptrs, const int *const *n_forced_ptrs, hipStream_t stream);
 hipError_t build_tiles(Weights &w, hipStream_t stream);
 // codes / scales in the reference layout, rebuilt from the tiles if they were dropped (exact inverse permutation);
 // synchronises `stream` when it had to rebuild.  trim_reference drops them again when the tiles can stand in.

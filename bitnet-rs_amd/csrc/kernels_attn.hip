@@ -52,17 +52,16 @@ __host__ __device__ __forceinline__ size_t kv_head_floats(int max_pos) { return 
 // T:1171-1202 -- values rounded ONCE, from the exact f32 k / v, when they are appended).  Layout then:
 // K [kv][chunk][D / 2][64 positions][2 dims] (a lane still reads 4 bytes per load: a dim PAIR of its position),
 // V [kv][pos][D] halves (a thread takes a dim pair of every 4th position).
+// The body is shared by the batch-1 kernel and the batched one (k_attn_partial_batch: the sequence is a third grid dimension and every
+// sequence brings its own caches and position): one source, so a sequence's bits do not depend on which launch computed them.
+// kvh / pc = this workgroup's KV head and record, n_rec = records per KV head in `scratch`.
 template <int NH, bool KV16>
-__global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restrict__ qkv, const float *__restrict__ rope_sin,
-                                                           const float *__restrict__ rope_cos, float *__restrict__ kcache,
-                                                           float *__restrict__ vcache, int n_heads, int n_kv, int group, int max_pos,
-                                                           const int *__restrict__ pos_ptr, float *__restrict__ scratch,
-                                                           unsigned long long *stamps /* diagnostic builds only */) {
-    // every kernel argument is requested together with pos_ptr: left alone hipcc fetches the others only behind
-    // the early exit, a second dependent scalar-load round trip for the workgroups that stay
-    asm volatile("" ::"s"(qkv), "s"(rope_sin), "s"(rope_cos), "s"(kcache), "s"(vcache), "s"(n_heads), "s"(n_kv), "s"(group), "s"(max_pos), "s"(scratch));
+__device__ __forceinline__ void attn_partial_body(const float *__restrict__ qkv, const float *__restrict__ rope_sin,
+                                                  const float *__restrict__ rope_cos, float *__restrict__ kcache,
+                                                  float *__restrict__ vcache, int n_heads, int n_kv, int group, int max_pos,
+                                                  const int *__restrict__ pos_ptr, float *__restrict__ scratch,
+                                                  unsigned long long *stamps /* diagnostic builds only */, const int kvh, const int pc, const unsigned n_rec) {
     const int pos = *pos_ptr, t_k = pos + 1;
-    const int kvh = blockIdx.x, pc = blockIdx.y;
     if (pc * NH * kAttnChunk >= t_k) return;  // record beyond the context (the grid is sized for max_pos)
     BH_ASTAMP(0);  // the position has arrived (a dependent scalar load behind the kernel arguments)
     __shared__ __attribute__((aligned(16))) float qs[kMaxGroup * kD];
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restri
     __syncthreads();
     BH_ASTAMP(4);  // softmax weights in LDS
     // ---- un-normalised P.V: thread = (dim d, position parity hp); V already in registers ---
-    float *rec = scratch + ((size_t)kvh * gridDim.y + pc) * kRec;
+    float *rec = scratch + ((size_t)kvh * n_rec + pc) * kRec;
     if (KV16) {
         const int dp = t4 & 63, pq = t4 >> 6;
         float a0[kMaxGroup] = {0.0f, 0.0f, 0.0f, 0.0f}, a1[kMaxGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -362,6 +361,35 @@ __global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restri
     BH_ASTAMP(5);
 }
 
+template <int NH, bool KV16>
+__global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restrict__ qkv, const float *__restrict__ rope_sin,
+                                                           const float *__restrict__ rope_cos, float *__restrict__ kcache,
+                                                           float *__restrict__ vcache, int n_heads, int n_kv, int group, int max_pos,
+                                                           const int *__restrict__ pos_ptr, float *__restrict__ scratch,
+                                                           unsigned long long *stamps /* diagnostic builds only */) {
+    // every kernel argument is requested together with pos_ptr: left alone hipcc fetches the others only behind
+    // the early exit, a second dependent scalar-load round trip for the workgroups that stay
+    asm volatile("" ::"s"(qkv), "s"(rope_sin), "s"(rope_cos), "s"(kcache), "s"(vcache), "s"(n_heads), "s"(n_kv), "s"(group), "s"(max_pos), "s"(scratch));
+    attn_partial_body<NH, KV16>(qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv, group, max_pos, pos_ptr, scratch, stamps, blockIdx.x, blockIdx.y,
+                                gridDim.y);
+}
+
+// Sequence b = blockIdx.z: qkv row b, its own caches and position through the pointer tables, record area b of `scratch`.  A NULL table entry
+// is an idle slot: the workgroup leaves before it reads or writes anything.  64-position records only (the form the batched step runs).
+template <bool KV16>
+__global__ __launch_bounds__(256) void k_attn_partial_batch(const float *__restrict__ qkv, const float *__restrict__ rope_sin,
+                                                            const float *__restrict__ rope_cos, float *const *__restrict__ kc_ptrs,
+                                                            float *const *__restrict__ vc_ptrs, int n_heads, int n_kv, int group, int max_pos,
+                                                            const int *const *__restrict__ pos_ptrs, float *__restrict__ scratch, size_t qkv_stride,
+                                                            size_t scratch_stride) {
+    const int b = blockIdx.z;
+    float *kc = kc_ptrs[b], *vc = vc_ptrs[b];
+    const int *pp = pos_ptrs[b];
+    if (!kc || !vc || !pp) return;  // block-uniform
+    attn_partial_body<1, KV16>(qkv + (size_t)b * qkv_stride, rope_sin, rope_cos, kc, vc, n_heads, n_kv, group, max_pos, pp, scratch + (size_t)b * scratch_stride,
+                               nullptr, blockIdx.x, blockIdx.y, gridDim.y);
+}
+
 // One workgroup per head: 8 thread groups walk the chunk records in parallel (chunk c -> group
 // c % 8), each merging (m, l, o) online; the 8 partial states meet through LDS.  Threads of a
 // group take 4 dims each (float4: one 512-byte record row per group and step).
@@ -369,12 +397,11 @@ __global__ __launch_bounds__(256 * NH) void k_attn_partial(const float *__restri
 // records were written by other CUs' workgroups, so every dependent trip is a cross-XCD miss (~0.7-1 us); with
 // 8 * NR >= n_chunks_max the whole merge is ONE round trip.  Records past the context are valid memory (the scratch buffer
 // is sized for max_pos and zero-filled once) and are dropped by their index.
+// (body shared with k_attn_combine_batch, as attn_partial_body)
 template <int NR>
-__global__ __launch_bounds__(256) void k_attn_combine(const float *__restrict__ scratch, int n_kv, int group,
-                                                      int n_chunks_max, int chunk_log2, const int *__restrict__ pos_ptr,
-                                                      float *__restrict__ out, uint8_t *__restrict__ qout) {
-    asm volatile("" ::"s"(scratch), "s"(n_kv), "s"(group), "s"(n_chunks_max), "s"(chunk_log2), "s"(out), "s"(qout));  // all arguments in one scalar-load round
-    const int kvh = blockIdx.x, g = blockIdx.y;
+__device__ __forceinline__ void attn_combine_body(const float *__restrict__ scratch, int n_kv, int group, int n_chunks_max, int chunk_log2,
+                                                  const int *__restrict__ pos_ptr, float *__restrict__ out, uint8_t *__restrict__ qout, const int kvh,
+                                                  const int g) {
     const int tid = threadIdx.x, d4 = tid & 31, part = tid >> 5;
     __shared__ float sm[8], sl[8];
     __shared__ __attribute__((aligned(16))) float sa[8][kD];
@@ -457,6 +484,27 @@ __global__ __launch_bounds__(256) void k_attn_combine(const float *__restrict__ 
     }
 }
 
+template <int NR>
+__global__ __launch_bounds__(256) void k_attn_combine(const float *__restrict__ scratch, int n_kv, int group,
+                                                      int n_chunks_max, int chunk_log2, const int *__restrict__ pos_ptr,
+                                                      float *__restrict__ out, uint8_t *__restrict__ qout) {
+    asm volatile("" ::"s"(scratch), "s"(n_kv), "s"(group), "s"(n_chunks_max), "s"(chunk_log2), "s"(out), "s"(qout));  // all arguments in one scalar-load round
+    attn_combine_body<NR>(scratch, n_kv, group, n_chunks_max, chunk_log2, pos_ptr, out, qout, blockIdx.x, blockIdx.y);
+}
+
+// grid (n_kv, group, n_seq): sequence b's records -> row b of `out` (nullable) and QAct vector b; idle slots (NULL position) are left alone
+template <int NR>
+__global__ __launch_bounds__(256) void k_attn_combine_batch(const float *__restrict__ scratch, int n_kv, int group, int n_chunks_max,
+                                                            const int *const *__restrict__ pos_ptrs, float *const *__restrict__ kc_ptrs,
+                                                            float *const *__restrict__ vc_ptrs, float *__restrict__ out, uint8_t *__restrict__ qout,
+                                                            size_t scratch_stride, size_t out_stride, size_t qout_stride) {
+    const int b = blockIdx.z;
+    const int *pp = pos_ptrs[b];
+    if (!pp || !kc_ptrs[b] || !vc_ptrs[b]) return;  // block-uniform
+    attn_combine_body<NR>(scratch + (size_t)b * scratch_stride, n_kv, group, n_chunks_max, 6, pp, out ? out + (size_t)b * out_stride : nullptr,
+                          qout ? qout + (size_t)b * qout_stride : nullptr, blockIdx.x, blockIdx.y);
+}
+
 size_t attn_scratch_floats(int n_kv, int max_pos) {
     return (size_t)n_kv * ((max_pos + kAttnChunk - 1) / kAttnChunk) * kRec;
 }
@@ -477,6 +525,22 @@ hipError_t launch_attn_decode(const float *qkv, const float *rope_sin, const flo
         hipLaunchKernelGGL(cfn, dim3(n_kv, n_heads / n_kv), dim3(256), 0, stream, scratch, n_kv, n_heads / n_kv, n_rec, halves == 2 ? 7 : 6, pos_ptr, out,
                            static_cast<uint8_t *>(qout));
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_attn_decode_batch(const float *qkv, const float *rope_sin, const float *rope_cos, float *const *kc_ptrs, float *const *vc_ptrs,
+                                    const int *const *pos_ptrs, int n_seq, int n_heads, int n_kv, int D, int max_pos, float *scratch, float *out, void *qout,
+                                    int kv_f16, hipStream_t stream) {
+    if (D != kD || n_kv <= 0 || n_heads / n_kv > kMaxGroup || n_seq < 1 || n_seq > kBatchMax || max_pos <= 0) return hipErrorInvalidValue;
+    const int n_rec = (max_pos + kAttnChunk - 1) / kAttnChunk;
+    const size_t qkv_stride = (size_t)(n_heads + 2 * n_kv) * kD, scratch_stride = attn_scratch_floats(n_kv, max_pos);
+    auto kfn = kv_f16 ? k_attn_partial_batch<true> : k_attn_partial_batch<false>;
+    hipLaunchKernelGGL(kfn, dim3(n_kv, n_rec, n_seq), dim3(256), 0, stream, qkv, rope_sin, rope_cos, kc_ptrs, vc_ptrs, n_heads, n_kv, n_heads / n_kv, max_pos,
+                       pos_ptrs, scratch, qkv_stride, scratch_stride);
+    // the combine instance launch_attn_decode takes for this record count
+    auto cfn = n_rec <= 8 ? k_attn_combine_batch<1> : n_rec <= 16 ? k_attn_combine_batch<2> : n_rec <= 40 ? k_attn_combine_batch<5> : k_attn_combine_batch<8>;
+    hipLaunchKernelGGL(cfn, dim3(n_kv, n_heads / n_kv, n_seq), dim3(256), 0, stream, scratch, n_kv, n_heads / n_kv, n_rec, pos_ptrs, kc_ptrs, vc_ptrs, out,
+                       static_cast<uint8_t *>(qout), scratch_stride, (size_t)n_heads * kD, qact_bytes((size_t)n_heads * kD));
     return hipGetLastError();
 }
 

@@ -1,0 +1,82 @@
+// batch_decoder.hpp -- one decode step for up to 8 live sequences through ONE launch chain.
+//
+// The reference's forward takes [B, T, H] and KVCache::new(config, batch_size, ..) carries a batch dimension
+// (crates/bitnet-transformer/src/lib.rs:281, :1146-1160, :1215-1245, :1437-1478): a lock-step batch.  Here a slot holds a Decoder -- an owner
+// or decoders borrowing its weights (Decoder(owner), bitnet_host_create_shared) -- and every occupied slot takes a with-logits decode step
+// together, each at its OWN position: embed -> per layer q|k|v, attention, o, gate|up, down -> head -> pick, on the batched entry points
+// (bitnet_hip_*_batch_dev) in Decoder::step_launches' QAct order.  A batch-1 step is ~155 dependent launches whose cost is the launch
+// (EXPERIMENTS.md 4.1); the batch pays them once for all its members, and reads every weight matrix once.
+//
+// After step(n) every member is in the state its own run(n, with_logits = true) would have left under attention form 0
+// (Decoder::set_attention_form(0)): KV caches, history, position, forced count, last_logits() and sampler state, BIT FOR BIT -- the batched
+// kernels restate the batch-1 arithmetic per vector.  Forced tokens are honoured as in run(), so a feed() between steps works.  NOT
+// maintained: last_hidden() (the residual stream lives in the batch's own buffers).
+//
+// Scheduling is set_slot(): members join and leave between steps (continuous batching); prompts go through the member's own prefill / extend
+// before it joins.  The step is ONE linear chain on one stream (no forked capture branches), captured once per batch: slot changes rewrite the
+// device pointer tables the kernels read and need no re-capture.  The one exception is a change in WHICH slots sample: a sampling member gets
+// logits only from the head and its own bitnet_hip_sample_dev launch, whose arguments are per member.  Single-threaded use.
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "decoder.hpp"
+
+namespace bitnet_host {
+
+class BatchDecoder {
+  public:
+    explicit BatchDecoder(int n_slots);
+    ~BatchDecoder();
+    BatchDecoder(const BatchDecoder &) = delete;
+    BatchDecoder &operator=(const BatchDecoder &) = delete;
+    const std::string &error() const { return err_; }
+    bool dead() const { return dead_; }
+    int n_slots() const { return n_; }
+    // Puts `d` into slot b (replacing what is there) or clears it (d == nullptr).  Every member: the same owner (or the owner itself), the
+    // same KV type, on the QAct path, in no other slot.  Holds a reference on the member until the slot changes.
+    int set_slot(int b, Decoder *d);
+    // n with-logits steps for every occupied slot.  Refuses with "KV cache overflow" if any member would pass max_pos - 1 (positions are read
+    // once, before the first launch).  Synchronises before returning.
+    int step(int n, bool use_graph, float *elapsed_ms);
+
+  private:
+    int fail(const char *what);
+    int fail_arg(const std::string &what);
+    int ensure_buffers();
+    int upload_tables();
+    int launches(bool warm = false);  // warm: the pass over all-idle tables that ensure_buffers runs once
+    int clear_vectors(int b);
+    void drop_graph();
+    bool dead_ = false;
+    std::string err_;
+    int n_ = 0;
+    Decoder *slot_[BITNET_HIP_BATCH_MAX] = {};
+    Decoder *root_ = nullptr;  // whose weights the batch runs on (a reference is held from the first member on)
+    bool kv_f16_ = false;
+    void *stream_ = nullptr;
+    // device pointer tables, [row][n_] pointers each: rows 0..5 = embed/attention positions, histories, logits rows, pick tokens, pick positions,
+    // pick histories, forced counts (row 6), then per layer K caches and V caches
+    void **tables_ = nullptr;
+    std::vector<void *> host_tables_;
+    bool tables_dirty_ = true;
+    float *x_ = nullptr, *x2_ = nullptr, *qkv_ = nullptr, *attn_scratch_ = nullptr;
+    void *qa_x_ = nullptr, *qa_x2_ = nullptr, *qa_att_ = nullptr, *qa_h_ = nullptr, *scratch_ = nullptr;
+    double *st_x_ = nullptr, *st_x2_ = nullptr;
+    int logits_wgs_ = 512;
+    void *graph_ = nullptr, *graph_exec_ = nullptr;
+    std::vector<void *> tables_sig_;  // ... and the one the uploaded pick tables were built for
+    std::vector<void *> graph_sig_;  // per slot the sampler the captured chain launches for it (null: fused greedy pick)
+    std::vector<void *> sampling_sig() const;
+};
+
+}  // namespace bitnet_host
+
+extern "C" {
+void *bitnet_host_batch_create(int n_slots);
+void bitnet_host_batch_destroy(void *b);
+const char *bitnet_host_batch_error(void *b);
+int bitnet_host_batch_set_slot(void *b, int slot, void *decoder);  // decoder NULL clears the slot
+int bitnet_host_batch_step(void *b, int n, int use_graph, float *elapsed_ms);
+}

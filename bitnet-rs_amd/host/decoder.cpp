@@ -164,9 +164,59 @@ Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n
     reset();
 }
 
+// Borrowing decoder: built as any other (own buffers, caches, stream), then its norm vectors, final norm, weight handles and embedding
+// table are the OWNER's.
+Decoder::Decoder(Decoder &owner, int) : Decoder(owner.c_) {
+    if (dead_) return;
+    if (owner.dead_ || owner.owner_ || !owner.embed_) {
+        dead_ = true;
+        err_ = owner.owner_ ? "create_shared: the owner borrows its weights itself" : "create_shared: the owner holds no model (set_globals / every layer first)";
+        return;
+    }
+    for (const auto &L : owner.layers_)
+        if (!L.qkv || !L.o || !L.gateup || !L.down) {
+            dead_ = true;
+            err_ = "create_shared: the owner holds no model (set_globals / every layer first)";
+            return;
+        }
+    for (size_t l = 0; l < layers_.size(); ++l) {
+        Layer &L = layers_[l];
+        const Layer &O = owner.layers_[l];
+        hipFree(L.attn_norm), hipFree(L.ffn_norm);
+        L.attn_norm = O.attn_norm, L.ffn_norm = O.ffn_norm;
+        L.qkv = O.qkv, L.o = O.o, L.gateup = O.gateup, L.down = O.down, L.q_ok = O.q_ok;
+    }
+    hipFree(final_norm_);
+    final_norm_ = owner.final_norm_;
+    embed_ = owner.embed_;
+    weight_bytes_ = owner.weight_bytes_;
+    act_mode_ = owner.act_mode_;
+    owner_ = &owner;
+    owner.borrowers_++;
+}
+
+int Decoder::weights_locked() {
+    if (owner_) return fail_arg("this decoder borrows its weights (create_shared): set them on the owner");
+    if (borrowers_ > 0) return fail_arg("the weights are shared with live borrowers (create_shared): destroy them first");
+    return 0;
+}
+
+int Decoder::set_attention_form(int form) {
+    if (form != -1 && form != 0) return fail_arg("set_attention_form: -1 (automatic) or 0 (64-position records + combine)");
+    attn_form_ = form;
+    return 0;
+}
+
+void Decoder::batch_objects(void *ptrs[3]) const { ptrs[0] = n_forced_, ptrs[1] = logits_, ptrs[2] = sampler_; }
+
 Decoder::~Decoder() {
     drop_graphs();
     if (sampler_) bitnet_hip_sampler_destroy(sampler_);
+    if (owner_) {  // borrowed objects stay the owner's
+        for (auto &L : layers_) L.qkv = L.o = L.gateup = L.down = 0, L.attn_norm = L.ffn_norm = nullptr;
+        embed_ = nullptr, final_norm_ = nullptr;
+        owner_->borrowers_--;
+    }
     for (auto &L : layers_) {
         for (bitnet_hip_weights_t h : {L.qkv, L.o, L.gateup, L.down})
             if (h) bitnet_hip_weights_free(h);
@@ -292,6 +342,7 @@ bool Decoder::qact_path() const {
 }
 
 int Decoder::set_act_mode(int mode) {
+    if (owner_) return fail_arg("this decoder borrows its weights (create_shared): the activation mode is the owner's");
     if (mode != 0 && mode != 1) {
         err_ = "activation mode must be 0 (exact f32) or 1 (QAct)";
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -302,6 +353,7 @@ int Decoder::set_act_mode(int mode) {
 }
 
 int Decoder::set_layer_qk256(int layer, const LayerWeightsQk256 &w) {
+    if (int rc = weights_locked()) return rc;
     if (layer < 0 || (size_t)layer >= layers_.size()) return fail_arg("layer index out of range");
     Layer &L = layers_[(size_t)layer];
     release_layer(L);
@@ -323,6 +375,7 @@ int Decoder::set_layer_qk256(int layer, const LayerWeightsQk256 &w) {
 }
 
 int Decoder::set_layer_i2s(int layer, const LayerWeightsI2s &w) {
+    if (int rc = weights_locked()) return rc;
     if (layer < 0 || (size_t)layer >= layers_.size()) return fail_arg("layer index out of range");
     Layer &L = layers_[(size_t)layer];
     release_layer(L);
@@ -343,6 +396,7 @@ int Decoder::set_layer_i2s(int layer, const LayerWeightsI2s &w) {
 }
 
 int Decoder::set_layer_specs(int layer, const float *attn_norm, const float *ffn_norm, const ProjSpec p[7]) {
+    if (int rc = weights_locked()) return rc;
     if (layer < 0 || (size_t)layer >= layers_.size()) return fail_arg("layer index out of range");
     Layer &L = layers_[(size_t)layer];
     const size_t H = c_.hidden, QD = (size_t)c_.n_heads * c_.head_dim, KD = (size_t)c_.n_kv_heads * c_.head_dim, F = c_.ffn;
@@ -373,6 +427,7 @@ int Decoder::set_layer_specs(int layer, const float *attn_norm, const float *ffn
 }
 
 int Decoder::set_globals(const uint16_t *embed_f16, const float *final_norm) {
+    if (int rc = weights_locked()) return rc;
     const size_t n = (size_t)c_.vocab * c_.hidden * 2;
     if (!embed_) HCHK(hipMalloc(&embed_, n));
     HCHK(hipMemcpy(embed_, embed_f16, n, hipMemcpyHostToDevice));
@@ -669,6 +724,7 @@ int Decoder::form_at(int pos) const {
     static const int merge_env = getenv("BITNET_HOST_ATTN_MERGE") ? atoi(getenv("BITNET_HOST_ATTN_MERGE")) : 8;
     static const bool wide_env = !(getenv("BITNET_HOST_ATTN_WIDE") && atoi(getenv("BITNET_HOST_ATTN_WIDE")) == 0);
     const int keys = pos + 1;
+    if (attn_form_ >= 0) return attn_form_;  // set_attention_form
     if (merge_env > 0 && merge_ok_ && keys <= (int)bitnet_hip_attention_merge_max_keys()) return 1;
     // 257..kMerge8MaxKeys keys: the same 64-position records, merged eight at a time by a prologue that asks for each value once
     // (EXPERIMENTS 15; the QAct path only: k_gemv_mfma's merge stays at 4 records).
@@ -1609,7 +1665,28 @@ void *bitnet_host_create(const bitnet_host_config *cfg) {
         return nullptr;
     }
 }
-void bitnet_host_destroy(void *d) { delete static_cast<Decoder *>(d); }
+void *bitnet_host_create_shared(void *owner) {
+    Decoder *o = live(owner);
+    if (!o) return nullptr;
+    try {
+        Decoder *d = new Decoder(*o, 0);
+        if (d->owner()) o->refs_++;  // a live borrower keeps its owner
+        return d;
+    } catch (...) {
+        return nullptr;
+    }
+}
+// Drops one reference; the last one deletes the object and, for a borrower, lets go of its owner.
+void bitnet_host_release(void *d) {
+    Decoder *p = static_cast<Decoder *>(d);
+    while (p && --p->refs_ == 0) {
+        Decoder *o = p->owner();
+        delete p;
+        p = o;
+    }
+}
+void bitnet_host_destroy(void *d) { bitnet_host_release(d); }
+int bitnet_host_set_attention_form(void *d, int form) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_attention_form(form); }
 const char *bitnet_host_error(void *d) { return d ? static_cast<Decoder *>(d)->error().c_str() : "null decoder"; }
 int bitnet_host_set_layer_qk256(void *d, int layer, const float *attn_norm, const float *ffn_norm, const uint8_t *q,
                                 const uint8_t *k, const uint8_t *v, const uint8_t *o, const uint8_t *gate,

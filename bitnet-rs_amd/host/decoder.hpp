@@ -66,6 +66,29 @@ class Decoder {
     Decoder(const Decoder &) = delete;
     Decoder &operator=(const Decoder &) = delete;
 
+    // A decoder that BORROWS the owner's weights: the owner's configuration, its weight handles, norm vectors, embedding table and final norm
+    // (the same device pointers: bitnet_hip_weights_bind_ln binds a handle to ONE gamma pointer), and everything else its own -- KV caches,
+    // history, position, sampler, stream, graphs, prompt buffers.  Several conversations then share one copy of the weights (the reference
+    // gives its KVCache a batch dimension instead, T:1146-1160).  The owner must hold every layer and the globals already.  A borrower refuses
+    // set_layer_*, set_globals (hence load_gguf) and set_act_mode; the owner refuses set_layer_* / set_globals while borrowers exist.  The
+    // owner must outlive its borrowers: the C shim's reference count sees to that (bitnet_host_destroy defers).  SINGLE-THREADED USE: an owner,
+    // its borrowers and a batch that holds them are driven from one host thread.
+    Decoder(Decoder &owner, int);
+    Decoder *owner() const { return owner_; }
+    Decoder *root() { return owner_ ? owner_ : this; }
+    int borrowers() const { return borrowers_; }
+    // the C shim's intrusive reference count (bitnet_host_destroy, BatchDecoder slots, borrowers of an owner)
+    int refs_ = 1;
+    void *batch_ = nullptr;  // the BatchDecoder whose slot holds this decoder, or null
+    // -1 (default): the attention form follows the position (form_at); 0: 64-position records + combine at EVERY position -- the form the
+    // batched step runs, so run() under form 0 gives the numbers a batch must reproduce (the merging o-projection and the wide form round
+    // differently).  Drops nothing: graphs are kept per form.
+    int set_attention_form(int form);
+    // what a batch needs beside layer_objects / global_objects: {forced count, logits row, sampler (null until set_sampling)}
+    void batch_objects(void *ptrs[3]) const;
+    bool sampling() const { return sampling_; }
+    float eps() const { return c_.eps; }
+
     const Config &config() const { return c_; }
     const std::string &error() const { return err_; }
     bool dead() const { return dead_; }  // construction failed: only error() and the destructor may be used
@@ -200,6 +223,10 @@ class Decoder {
     // which it beat records + combine at that count and at every smaller one.
     static constexpr int kMerge8MaxKeys = 512;
   private:
+    Decoder *owner_ = nullptr;  // borrowed weights (see the borrowing constructor)
+    int borrowers_ = 0;
+    int attn_form_ = -1;        // set_attention_form
+    int weights_locked();       // refusal of set_layer_* / set_globals on a borrower or an owner with borrowers, else 0
     bool merge_ok_ = false;   // the o-projection can merge the attention chunk records itself (short contexts)
     bool merge8_ok_ = false;  // ... and up to 8 of them on the QAct path
 
@@ -287,7 +314,11 @@ typedef struct bitnet_host_config {
     float eps, rope_theta;
 } bitnet_host_config;
 void *bitnet_host_create(const bitnet_host_config *cfg);
-void bitnet_host_destroy(void *d);
+void bitnet_host_destroy(void *d);  // drops the caller's reference: the object goes when no borrower and no batch slot holds it any more
+// Decoder(owner): a decoder borrowing `owner`'s weights (own KV caches, history, position, sampler, stream).  Single-threaded use.
+void *bitnet_host_create_shared(void *owner);
+void bitnet_host_release(void *d);  // one reference less (what bitnet_host_destroy does); a batch slot lets its member go with it
+int bitnet_host_set_attention_form(void *d, int form);  // -1 automatic (form_at), 0 = 64-position records + combine everywhere
 const char *bitnet_host_error(void *d);
 int bitnet_host_set_layer_qk256(void *d, int layer, const float *attn_norm, const float *ffn_norm,
                                 const uint8_t *q, const uint8_t *k, const uint8_t *v, const uint8_t *o,

@@ -464,6 +464,46 @@ int bitnet_hip_attention_decode_q_dev(const float *qkv_dev, const float *rope_si
                                       void *kcache_dev, void *vcache_dev, size_t n_heads, size_t n_kv_heads,
                                       size_t head_dim, size_t max_pos, const int32_t *pos_dev, float *scratch_dev,
                                       int flags, float *out_dev, void *qact_out, void *stream);
+/* ---- the decode step for SEVERAL sequences per launch ------------------------------------------------------------
+ * The reference's forward takes [B, T, H] and KVCache::new(config, batch_size, ..) carries a batch dimension
+ * (crates/bitnet-transformer/src/lib.rs:281, :1146-1160, :1215-1245, :1437-1478).  These four entry points are the decode kernels above taking
+ * n_seq = 1..BITNET_HIP_BATCH_MAX vectors per launch -- the weight stream (the f16 table) is read once and used for every vector -- and
+ * generalise the reference's lock-step batch to sequences at DIFFERENT positions.  Conventions:
+ *   - vector b of every batched buffer lies at b times its batch-1 size: bitnet_hip_qact_bytes / bitnet_hip_qact_stats_bytes of the vector's
+ *     length, `rows` floats for y / residual (rows / 2 with FUSE_SILU_MUL), hidden floats, n_heads * head_dim floats, the qkv row,
+ *     bitnet_hip_attention_scratch_bytes; the head's scratch is n_seq * n_wg * 8 bytes;
+ *   - per-sequence state (KV caches, position, history, forced count, logits row) is reached through DEVICE arrays of n_seq device pointers,
+ *     so every sequence keeps buffers of its own.  A NULL entry (history for the gather, a cache or the position for the attention, the
+ *     logits row for the head) marks an IDLE slot: nothing is read or written for it.  The GEMV has no tables: it computes all n_seq
+ *     vectors, an idle slot's vector must hold finite (stale) data and its outputs are ignored;
+ *   - EVERY OUTPUT IS BIT-IDENTICAL to the batch-1 entry point called on that vector alone (same K partition, block order and sums);
+ *   - asynchronous and capture-safe: no allocation, no synchronisation; n_seq == 0, n_seq > BITNET_HIP_BATCH_MAX and NULL required pointers
+ *     return BITNET_HIP_ERR_INVALID_ARGUMENT before anything launches. */
+#define BITNET_HIP_BATCH_MAX 8
+/* bitnet_hip_embed_q_dev for n_seq tokens: token b = history_ptrs[b][*pos_ptrs[b]] (clamped to the vocabulary as in batch-1) */
+int bitnet_hip_embed_q_batch_dev(const void *table_f16_dev, const int32_t *const *history_ptrs_dev, const int32_t *const *pos_ptrs_dev,
+                                 size_t n_seq, size_t hidden, size_t vocab, float *x_out_dev, const float *gamma_dev, void *qact_out,
+                                 double *stats_out, void *stream);
+/* bitnet_hip_gemv_q_dev for n_seq vectors: the same matrices (bitnet_hip_gemv_q_supported) and fusions; ln_gamma_dev / gamma_out_dev are
+ * shared by all vectors.  n_seq whole QAct vectors stay in LDS (160 KiB): 8 vectors of up to 8704 columns; beyond: BITNET_HIP_ERR_UNSUPPORTED */
+int bitnet_hip_gemv_q_batch_dev(bitnet_hip_weights_t w, size_t n_seq, const void *qact_in, const double *stats_in,
+                                const float *ln_gamma_dev, float ln_eps, const float *residual_dev, int flags, float *y_dev,
+                                void *qact_out, const float *gamma_out_dev, double *stats_out, void *stream);
+/* bitnet_hip_attention_decode_q_dev (64-position records + combine: flags 0 or BITNET_HIP_ATTN_KV_F16) for n_seq sequences in ONE pair of
+ * launches: every sequence applies RoPE, appends and attends at its own *pos_ptrs[b] over its own caches; all caches have max_pos slots */
+int bitnet_hip_attention_decode_batch_dev(const float *qkv_dev, const float *rope_sin_dev, const float *rope_cos_dev,
+                                          void *const *kcache_ptrs_dev, void *const *vcache_ptrs_dev,
+                                          const int32_t *const *pos_ptrs_dev, size_t n_seq, size_t n_heads, size_t n_kv_heads,
+                                          size_t head_dim, size_t max_pos, float *scratch_dev, int flags, float *out_dev,
+                                          void *qact_out, void *stream);
+/* bitnet_hip_logits_f16_dev for n_seq rows of x_dev: logits row b -> logits_ptrs[b]; then per slot the greedy pick of batch-1 (lowest index
+ * on ties, NaN -> -inf): *token_ptrs[b] = token, history_ptrs[b][p + 1] = token unless p + 1 < *n_forced_ptrs[b], *pos_ptrs[b] = p + 1.
+ * token_ptrs_dev / pos_ptrs_dev / history_ptrs_dev / n_forced_ptrs_dev may be NULL as a whole or per entry; a slot with neither a token nor
+ * a position pointer gets logits only (a sequence that samples).  hidden * n_seq * 4 <= 152 KiB. */
+int bitnet_hip_logits_f16_batch_dev(const void *table_f16_dev, const float *x_dev, const float *gamma_dev, float eps, size_t hidden,
+                                    size_t vocab, size_t n_seq, float *const *logits_ptrs_dev, void *scratch_dev, size_t n_wg,
+                                    int32_t *const *token_ptrs_dev, int32_t *const *pos_ptrs_dev, int32_t *const *history_ptrs_dev,
+                                    const int32_t *const *n_forced_ptrs_dev, void *stream);
 /* bitnet_hip_attention_prefill_dev filling f16 decode caches */
 int bitnet_hip_attention_prefill_kv16_dev(const float *qkv_dev, const float *rope_sin_dev, const float *rope_cos_dev,
                                           void *kcache_f16_dev, void *vcache_f16_dev, size_t n_heads, size_t n_kv_heads,

@@ -148,6 +148,9 @@ class HipLib:
         L.bitnet_hip_attention_decode_batch_dev.restype = C.c_int
         L.bitnet_hip_logits_f16_batch_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_logits_f16_batch_dev.restype = C.c_int
+        # fork of a live sequence's KV state: source tables [n_layers], destination tables [n_dst][n_layers] of device pointers
+        L.bitnet_hip_kv_fork_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]
+        L.bitnet_hip_kv_fork_dev.restype = C.c_int
         L.bitnet_hip_gemv_attn_merge_rec_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
         L.bitnet_hip_attention_merge_q_max_keys.restype = _sz
         L.bitnet_hip_attention_merge_q_max_keys.argtypes = []
@@ -540,6 +543,13 @@ class HipLib:
         self._check(self.c.bitnet_hip_logits_f16_batch_dev(_ptr(table), _ptr(x), _optr(gamma), eps, hidden, vocab, n_seq, _ptr(logits_ptrs), _ptr(scratch),
                                                            n_wg, _optr(token_ptrs), _optr(pos_ptrs), _optr(history_ptrs), _optr(n_forced_ptrs), _vp(stream)))
 
+    def kv_fork_dev(self, src_k_ptrs, src_v_ptrs, dst_k_ptrs, dst_v_ptrs, n_layers: int, n_dst: int, n_kv: int, head_dim: int, max_pos: int,
+                    n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
+        """Cache slots [0, n_positions) of every layer's K and V of one source into n_dst destinations, bit for bit, in one launch.  *_ptrs: int64
+        device tensors of device pointers, the source's [n_layers], the destinations' [n_dst][n_layers]; buffers distinct, 16-byte aligned."""
+        self._check(self.c.bitnet_hip_kv_fork_dev(_ptr(src_k_ptrs), _ptr(src_v_ptrs), _ptr(dst_k_ptrs), _ptr(dst_v_ptrs), n_layers, n_dst, n_kv, head_dim,
+                                                  max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
+
     def attention_merge_q_max_keys(self) -> int:
         return int(self.c.bitnet_hip_attention_merge_q_max_keys())
 
@@ -876,6 +886,10 @@ class HostDecoder:
         L.bitnet_host_extend.restype = C.c_int
         L.bitnet_host_rewind.argtypes = [C.c_void_p, C.c_int]
         L.bitnet_host_rewind.restype = C.c_int
+        L.bitnet_host_fork.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]
+        L.bitnet_host_fork.restype = C.c_int
+        L.bitnet_host_cached_prefix.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
+        L.bitnet_host_cached_prefix.restype = C.c_int
         self.cfg = cfg
         self._fed = 0  # tokens fed since the last reset (the default n of score)
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
@@ -1048,6 +1062,31 @@ class HostDecoder:
         """Keep the first n positions (0 <= n <= position()): the next feed() writes at n.  The cache bytes and the sampler state stay."""
         self._check(self.c.bitnet_host_rewind(self.h, n))
         self._fed = min(self._fed, int(n))
+
+    def fork_into(self, dsts, n: int) -> None:
+        """Every decoder of `dsts` (1..8 of them: this decoder's owner or borrowers of the same weights, the same cache type, in no batch
+        slot) takes over the first n positions, 0 <= n <= position(): it ends as this decoder would after rewind(n) -- position, forced
+        count, history[0 .. n], cache slots < n (one copy launch for all destinations), sampler reset -- and this decoder is untouched.
+        Best of n: prefill(P) here, fork_into(dsts, P - 1), every destination run(1) under its own seed.  Prefix hit: fork at
+        cached_prefix(prompt), feed() the rest (it writes at slot n) and extend() over it.  A destination's last_logits() / last_hidden()
+        are unspecified until its next with-logits step."""
+        dsts = list(dsts)
+        arr = (C.c_void_p * max(len(dsts), 1))(*[d.h if d is not None else None for d in dsts])
+        self._check(self.c.bitnet_host_fork(self.h, arr, len(dsts), int(n)))
+        for d in dsts:
+            d._fed = min(self._fed, int(n))
+
+    def fork_from(self, src: "HostDecoder", n: int) -> None:
+        """src.fork_into([self], n)"""
+        src.fork_into([self], n)
+
+    def cached_prefix(self, tokens) -> int:
+        """Length of the longest common prefix of `tokens` and this sequence's consumed history (the reference's PrefixCache lookup)."""
+        t = _np(tokens, np.int32)
+        n = int(self.c.bitnet_host_cached_prefix(self.h, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size))
+        if n < 0:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, self.error() or "bitnet_host_cached_prefix failed")
+        return n
 
     def score(self, n: int | None = None, digits: int = 2, logits_rows: int = 0) -> "ScoreResult":
         """Teacher-forced scoring of the first n fed tokens (default: all of them) in one prompt forward: prefill(n, True, digits) as

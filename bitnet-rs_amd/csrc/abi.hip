@@ -1227,6 +1227,38 @@ int bitnet_hip_logits_f16_batch_dev(const void *table, const float *x, const flo
     BH_GUARD_END
 }
 
+/* ---- fork of a live sequence's KV state (kernels_kvfork.hip) ---- */
+
+int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const *src_v_ptrs_dev, void *const *dst_k_ptrs_dev, void *const *dst_v_ptrs_dev,
+                           size_t n_layers, size_t n_dst, size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t n_positions, int flags, void *stream) {
+    BH_GUARD_BEGIN
+    if (!src_k_ptrs_dev || !src_v_ptrs_dev || !dst_k_ptrs_dev || !dst_v_ptrs_dev)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_fork_dev");
+    if (n_layers == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: n_layers 0");
+    if (n_dst == 0 || n_dst > BITNET_HIP_BATCH_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: n_dst %zu must be 1..%d", n_dst, BITNET_HIP_BATCH_MAX);
+    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: head_dim %zu unsupported (128)", head_dim);
+    if (n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: num_key_value_heads 0");
+    if (flags & ~BITNET_HIP_ATTN_KV_F16)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16)", flags);
+    if (n_positions > max_pos)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: n_positions %zu, max_pos %zu", n_positions, max_pos);  // T:1190-1194
+    // words (32 bits) per position and KV head, per KV head, per cache; segments = (layer, KV head, K | V) triples the grid is cut into
+    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
+    size_t slots = 0, head_words = 0, cache_bytes = 0, segments = 0;
+    if (__builtin_add_overflow(max_pos, (size_t)63, &slots) || __builtin_mul_overflow(slots / 64 * 64, rows, &head_words) ||
+        __builtin_mul_overflow(head_words, n_kv_heads, &cache_bytes) || __builtin_mul_overflow(cache_bytes, sizeof(uint32_t), &cache_bytes) ||
+        __builtin_mul_overflow(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, (size_t)2, &segments) || segments >= ((size_t)1 << 24) ||
+        __builtin_mul_overflow(n_layers, n_dst, &slots))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (kv_fork_dev: n_layers %zu, n_kv_heads %zu, max_pos %zu)", n_layers,
+                         n_kv_heads, max_pos);
+    if (n_positions == 0) return BITNET_HIP_OK;  // valid, and nothing to launch
+    BH_HIP_TRY(launch_kv_fork(src_k_ptrs_dev, src_v_ptrs_dev, dst_k_ptrs_dev, dst_v_ptrs_dev, n_layers, n_dst, n_kv_heads, rows, head_words, n_positions,
+                              (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 size_t bitnet_hip_attention_prefill_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t seq_len) {
     return attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)seq_len, (int)seq_len);
 }

@@ -166,6 +166,10 @@ hipError_t launch_attn_decode_batch(const float *qkv, const float *rope_sin, con
 hipError_t launch_logits_f16_batch(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab, int n_seq,
                                    float *const *logits_ptrs, float *best_val, int *best_idx, int n_wg, int *const *token_ptrs, int *const *pos_ptrs,
                                    int *const *history_ptrs, const int *const *n_forced_ptrs, hipStream_t stream);
+// kernels_kvfork.hip: cache slots [0, n) of every layer's K and V of one source into n_dst destinations, one launch; rows = 32-bit words per
+// position and KV head (128 for f32 caches, 64 for f16), head_words = ceil(max_pos / 64) * 64 * rows
+hipError_t launch_kv_fork(const void *const *src_k, const void *const *src_v, void *const *dst_k, void *const *dst_v, size_t n_layers, size_t n_dst,
+                          size_t n_kv, size_t rows, size_t head_words, size_t n, hipStream_t stream);
 hipError_t build_tiles(Weights &w, hipStream_t stream);
 // codes / scales in the reference layout, rebuilt from the tiles if they were dropped (exact inverse permutation);
 // synchronises `stream` when it had to rebuild.  trim_reference drops them again when the tiles can stand in.

@@ -13,7 +13,7 @@
 // maintained: last_hidden() (the residual stream lives in the batch's own buffers).
 //
 // Scheduling is set_slot(): members join and leave between steps (continuous batching); prompts go through the member's own prefill / extend
-// before it joins.  The step is ONE linear chain on one stream (no forked capture branches), captured once per batch: slot changes rewrite the
+// before it joins, or the member takes over a live sequence's prefix (Decoder::fork: one copy launch for up to 8 members).  The step is ONE linear chain on one stream (no forked capture branches), captured once per batch: slot changes rewrite the
 // device pointer tables the kernels read and need no re-capture.  The one exception is a change in WHICH slots sample: a sampling member gets
 // logits only from the head and its own bitnet_hip_sample_dev launch, whose arguments are per member.  Single-threaded use.
 #pragma once

@@ -229,7 +229,7 @@ Decoder::~Decoder() {
         if (p) hipFree(p);
     for (void *p : {(void *)pf_x_, (void *)pf_qkv_, (void *)pf_att_, (void *)pf_h_, pf_gemm_ws_, pf_attn_ws_, sp_kv_send_, sp_kv_all_,
                     (void *)sp_block_pos_, (void *)sp_tokens_, pf_xh_, pf_atth_, pf_hh_, (void *)pf_stats_, pf_qb_, (void *)sc_tgt_, (void *)sc_am_,
-                    (void *)sc_nll_, (void *)sc_logits_, sc_ws_})
+                    (void *)sc_nll_, (void *)sc_logits_, sc_ws_, (void *)fork_tables_})
         if (p) hipFree(p);
     for (void *e : sp_tev_)
         if (e) hipEventDestroy((hipEvent_t)e);
@@ -1070,6 +1070,79 @@ int Decoder::rewind(int n) {
     return 0;
 }
 
+int Decoder::fork(Decoder &src, Decoder *const *dsts, int n_dst, int n) { return src.fork_from_this(dsts, n_dst, n); }
+
+int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
+    // every refusal comes before the first write
+    if (n_dst < 1 || n_dst > BITNET_HIP_BATCH_MAX) return fail_arg("fork: n_dst must be 1..8");
+    if (!dsts) return fail_arg("fork: null destination");
+    for (int i = 0; i < n_dst; ++i) {
+        Decoder *d = dsts[i];
+        if (!d) return fail_arg("fork: null destination");
+        if (d->dead_) return fail_arg("fork: dead destination");
+        if (d == this) return fail_arg("fork: a destination is the source itself: use rewind");
+        for (int j = 0; j < i; ++j)
+            if (dsts[j] == d) return fail_arg("fork: a destination is repeated");
+        if (d->root() != root()) return fail_arg("fork: source and destination must run on the same weights (an owner and its borrowers)");
+        if (d->kv_f16_ != kv_f16_) return fail_arg("fork: mixed KV cache types");
+        if (d->batch_) return fail_arg("fork: a destination sits in a batch slot: leave the batch first");
+    }
+    const int p = position();
+    if (p < 0) return BITNET_HIP_ERR_GPU;
+    if (n < 0 || n > p) return fail_arg("fork: n must be in [0, position()]");
+
+    // one root, hence one Config: every cache has this decoder's geometry
+    const size_t L = layers_.size(), M = BITNET_HIP_BATCH_MAX;
+    std::vector<void *> t((2 + 2 * M) * L, nullptr);
+    if (!fork_tables_) {
+        HCHK(hipMalloc((void **)&fork_tables_, t.size() * sizeof(void *)));
+        for (size_t l = 0; l < L; ++l) t[l] = layers_[l].kcache, t[L + l] = layers_[l].vcache;
+        HCHK(hipMemcpy(fork_tables_, t.data(), 2 * L * sizeof(void *), hipMemcpyHostToDevice));
+    }
+    void **dst_k = fork_tables_ + 2 * L, **dst_v = dst_k + M * L;
+    hipStream_t s = (hipStream_t)stream_;
+    if (n > 0) {
+        for (int i = 0; i < n_dst; ++i)
+            for (size_t l = 0; l < L; ++l) t[(2 + (size_t)i) * L + l] = dsts[i]->layers_[l].kcache, t[(2 + M + (size_t)i) * L + l] = dsts[i]->layers_[l].vcache;
+        HCHK(hipMemcpy(dst_k, t.data() + 2 * L, 2 * M * L * sizeof(void *), hipMemcpyHostToDevice));
+        BCHK(bitnet_hip_kv_fork_dev(fork_tables_, fork_tables_ + L, dst_k, dst_v, L, (size_t)n_dst, (size_t)c_.n_kv_heads, (size_t)c_.head_dim, (size_t)c_.max_pos,
+                                    (size_t)n, kv_f16_ ? BITNET_HIP_ATTN_KV_F16 : 0, s));
+    }
+    for (int i = 0; i < n_dst; ++i) {
+        // history[0 .. n]: entry n is the unconsumed picked or fed token, as rewind(n) leaves it; zero beyond, as after reset() + n steps
+        HCHK(hipMemcpyAsync(dsts[i]->history_, history_, ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, s));
+        HCHK(hipMemsetAsync(dsts[i]->history_ + n + 1, 0, ((size_t)c_.max_pos + 1 - (size_t)n) * 4, s));
+    }
+    HCHK(hipStreamSynchronize(s));
+    const int32_t np = n, forced = host_forced_ < n ? host_forced_ : n;
+    for (int i = 0; i < n_dst; ++i) {
+        Decoder *d = dsts[i];
+        HCHK(hipMemcpy(d->pos_, &np, 4, hipMemcpyHostToDevice));
+        d->host_forced_ = forced;
+        HCHK(hipMemcpy(d->n_forced_, &forced, 4, hipMemcpyHostToDevice));
+        if (d->sampler_) BCHK(bitnet_hip_sampler_reset(d->sampler_));
+    }
+    return 0;
+}
+
+int Decoder::cached_prefix(const int32_t *tokens, int n) {
+    if (n < 0 || (n > 0 && !tokens)) {
+        err_ = "cached_prefix: null tokens";
+        return -1;
+    }
+    const int p = position();
+    if (p < 0) return -1;
+    const int m = n < p ? n : p;
+    std::vector<int32_t> h((size_t)m);
+    if (m > 0 && hipMemcpy(h.data(), history_, (size_t)m * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        err_ = "cached_prefix: history readback failed";
+        return -1;
+    }
+    int i = 0;
+    while (i < m && h[(size_t)i] == tokens[i]) ++i;
+    return i;
+}
+
 // History tokens [p, p + n) through every layer as [n, *] matrices; p = the position (0: a fresh sequence and the whole-prompt attention;
 // otherwise the continuation operator over the p cached positions).  The callers hold the guards.
 int Decoder::prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms) {
@@ -1736,6 +1809,18 @@ int bitnet_host_extend(void *d, int n, int with_logits, int digits, float *elaps
 int bitnet_host_rewind(void *d, int n) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
     return D->rewind(n);
+}
+int bitnet_host_fork(void *src, void *const *dsts, int n_dst, int n) {
+    Decoder *S = live(src);
+    if (!S) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    Decoder *ds[BITNET_HIP_BATCH_MAX] = {};
+    if (dsts)
+        for (int i = 0; i < n_dst && i < BITNET_HIP_BATCH_MAX; ++i) ds[i] = static_cast<Decoder *>(dsts[i]);
+    return Decoder::fork(*S, dsts ? ds : nullptr, n_dst, n);
+}
+int bitnet_host_cached_prefix(void *d, const int32_t *tokens, int n) {
+    LIVE(-1);
+    return D->cached_prefix(tokens, n);
 }
 int bitnet_host_prefill_sharded(void *d, int n, int rank, int world, bitnet_host_allgather_fn gather, void *gather_ctx, int with_logits,
                                 int digits, int wire_f16, float *elapsed_ms) {

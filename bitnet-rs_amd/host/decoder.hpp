@@ -147,6 +147,26 @@ class Decoder {
     // continuation attention never reads a slot at or beyond its past length), and so do the sampler's counts and word counter:
     // reset() remains the full clear.
     int rewind(int n);
+    // FORK: every one of the n_dst (1..8) destinations takes over the first n positions of `src`, 0 <= n <= src.position() -- the reference's
+    // prefix cache (crates/bitnet-inference/src/prefix_cache.rs: lookup :173, insert :212) with the state kept on the device instead of its
+    // host-side cached_state bytes.  Afterwards every destination is what src would be after src.rewind(n), and src itself is untouched:
+    // position n and forced count min(src's forced, n) on host and device; history[0 .. n] copied (n + 1 entries: as rewind leaves entry n
+    // in place, the unconsumed picked or fed token travels) and zero beyond; cache slots < n of every layer copied by ONE
+    // bitnet_hip_kv_fork_dev launch for all destinations (slots >= n keep the destination's bytes).  A destination's sampler is reset as
+    // reset() does (counts and word counter cleared, config kept); its cache type, attention form, act mode and captured graphs stay (the
+    // graphs read the position from device memory: nothing is re-captured).  last_logits() / last_hidden() of a destination are UNSPECIFIED
+    // until its next with-logits step.  Synchronises before returning.
+    // Refused, with nothing modified: n out of range; n_dst outside 1..8; a null, dead or repeated destination; a destination that is src
+    // (use rewind); one with another root() (same weights); another kv_f16(); one sitting in a BatchDecoder slot (leave the batch first).
+    // src may sit in a slot: it is only read, and step() returns synchronised.  The error text goes on src.
+    // Best of n from ONE prompt forward: src runs prefill(P, with_logits); fork at P - 1; every destination runs run(1, with_logits) under
+    // its own seed -- one decode step in place of a prompt forward -- and goes on alone or in a BatchDecoder.
+    // Prefix hit: fork at the common length (cached_prefix), then extend's carry-on rule holds as after a rewind: feed() on a fork writes at
+    // slot n; feed the rest of the prompt and extend() over it.
+    static int fork(Decoder &src, Decoder *const *dsts, int n_dst, int n);
+    // The reference's lookup for ONE live sequence: the length of the longest common prefix of tokens[0 .. n) and history[0 .. position()),
+    // or -1 on error.  Costs the position read-back and one of min(n, position()) tokens.
+    int cached_prefix(const int32_t *tokens, int n);
     // Token-parallel prefill of ONE long prompt over `world` GPUs, one process per GPU (BASELINE configs[4]):
     // this rank runs the first n fed tokens' zigzag chunks rank and 2 world - 1 - rank through every layer (weights are
     // replicated: all seven projections are collective-free); per layer ONE all-gather of the raw k|v rows through
@@ -264,6 +284,10 @@ class Decoder {
     bitnet_hip_sampler *sampler_ = nullptr;
     bool sampling_ = false;
     int host_forced_ = 0;
+    // fork: device pointer tables, allocated at the first fork FROM this decoder: [0] its own K caches [n_layers], [1] its V caches (built once),
+    // then the destinations' K [8][n_layers] and V [8][n_layers] (uploaded per call)
+    int fork_from_this(Decoder *const *dsts, int n_dst, int n);
+    void **fork_tables_ = nullptr;
     // sharded prefill buffers (grown on demand)
     int sp_cap_ = 0, sp_ctx_ = 0;
     void *sp_kv_send_ = nullptr, *sp_kv_all_ = nullptr;
@@ -340,6 +364,8 @@ int bitnet_host_prefill(void *d, int n, int with_logits, int digits, float *elap
 int bitnet_host_finish_prefill(void *d, int n, const float *last_row, int with_logits);
 int bitnet_host_extend(void *d, int n, int with_logits, int digits, float *elapsed_ms);  // Decoder::extend
 int bitnet_host_rewind(void *d, int n);                                                    // Decoder::rewind
+int bitnet_host_fork(void *src, void *const *dsts, int n_dst, int n);                      // Decoder::fork; the error text goes on src
+int bitnet_host_cached_prefix(void *d, const int32_t *tokens, int n);                      // Decoder::cached_prefix; -1 on error
 int bitnet_host_score(void *d, int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms);
 // per-phase medians of the NEXT bitnet_host_prefill_sharded calls (off by default: 8 event records per layer); out[4] = projections,
 // attention, exposed all-gather wait, all-gather on its own stream -- microseconds per layer, medians over the layers of the last call

@@ -504,6 +504,23 @@ int bitnet_hip_logits_f16_batch_dev(const void *table_f16_dev, const float *x_de
                                     size_t vocab, size_t n_seq, float *const *logits_ptrs_dev, void *scratch_dev, size_t n_wg,
                                     int32_t *const *token_ptrs_dev, int32_t *const *pos_ptrs_dev, int32_t *const *history_ptrs_dev,
                                     const int32_t *const *n_forced_ptrs_dev, void *stream);
+/* ---- fork of a live sequence: the KV state of a prompt prefix, copied on the device ------------------------------------
+ * The reference caches prompt prefixes on the host (crates/bitnet-inference/src/prefix_cache.rs: lookup, :173, returns the longest cached
+ * prefix and its opaque `cached_state` bytes; insert, :212, stores one).  This entry replaces those host-side bytes with a device-to-device
+ * copy: in every layer, KV head and destination, cache slots 0 .. n_positions - 1 of K and V become the source's, BIT FOR BIT (integer
+ * loads and stores: NaN payloads and denormals pass through), in ONE launch that loads every source vector once and stores it n_dst times.
+ * Every other byte of every destination cache keeps its value; the source is only read.
+ *   - src_k_ptrs_dev / src_v_ptrs_dev: DEVICE arrays of n_layers cache pointers; dst_k_ptrs_dev / dst_v_ptrs_dev: DEVICE arrays
+ *     [n_dst][n_layers] (destination d, layer l at d * n_layers + l), n_dst = 1..BITNET_HIP_BATCH_MAX;
+ *   - flags: 0 (f32 caches) or BITNET_HIP_ATTN_KV_F16; every cache of one call has the same type (there is no conversion), the same
+ *     max_pos and n_kv_heads, head_dim 128, and is 16-byte aligned;
+ *   - source and destination buffers are DISTINCT: no destination cache may be (or overlap) a source cache or another destination's;
+ *   - asynchronous and capture-safe: no allocation, no synchronisation.  n_positions == 0 is valid and launches nothing.  NULL tables,
+ *     n_layers == 0, n_dst outside 1..BITNET_HIP_BATCH_MAX, head_dim != 128, n_kv_heads == 0, n_positions > max_pos ("KV cache
+ *     overflow"), unknown flag bits and sizes that overflow return BITNET_HIP_ERR_INVALID_ARGUMENT before anything launches. */
+int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const *src_v_ptrs_dev, void *const *dst_k_ptrs_dev,
+                           void *const *dst_v_ptrs_dev, size_t n_layers, size_t n_dst, size_t n_kv_heads, size_t head_dim,
+                           size_t max_pos, size_t n_positions, int flags, void *stream);
 /* bitnet_hip_attention_prefill_dev filling f16 decode caches */
 int bitnet_hip_attention_prefill_kv16_dev(const float *qkv_dev, const float *rope_sin_dev, const float *rope_cos_dev,
                                           void *kcache_f16_dev, void *vcache_f16_dev, size_t n_heads, size_t n_kv_heads,

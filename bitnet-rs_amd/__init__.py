@@ -193,6 +193,14 @@ class HipLib:
         L.bitnet_hip_sampler_draws.argtypes = [_vp, C.POINTER(C.c_uint64)]
         L.bitnet_hip_sample_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_sample_host.argtypes = [_vp, _f32p, _sz, C.POINTER(C.c_uint32), _sz, C.POINTER(C.c_uint32)]
+        L.bitnet_hip_sample_batch_create.argtypes = [_sz, _sz, C.POINTER(_vp)]
+        L.bitnet_hip_sample_batch_create.restype = C.c_int
+        L.bitnet_hip_sample_batch_destroy.argtypes = [_vp]
+        L.bitnet_hip_sample_batch_destroy.restype = None
+        L.bitnet_hip_sample_batch_set.argtypes = [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_sample_batch_set.restype = C.c_int
+        L.bitnet_hip_sample_batch_dev.argtypes = [_vp, _vp]
+        L.bitnet_hip_sample_batch_dev.restype = C.c_int
         L.bitnet_hip_score_workspace_bytes.argtypes = [_sz, _sz, _sz]
         L.bitnet_hip_score_workspace_bytes.restype = _sz
         L.bitnet_hip_score_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
@@ -624,6 +632,10 @@ class HipLib:
         """A device sampler (bitnet_hip_sampler_*): the reference's Sampler::new(temperature, top_k, top_p, repetition_penalty, seed)."""
         return Sampler(self, vocab, SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed))
 
+    def sample_batch(self, vocab: int, n_slots: int) -> "SampleBatch":
+        """A table of n_slots sampler bindings served by one launch (bitnet_hip_sample_batch_*)."""
+        return SampleBatch(self, vocab, n_slots)
+
     def hbm_read_ceiling(self, nbytes: int = 2 << 30, iters: int = 10, stream: int = 0):
         """Measured read-only stream ceiling of the device: (best, mean) GB/s."""
         best, mean = C.c_double(0.0), C.c_double(0.0)
@@ -687,6 +699,45 @@ class Sampler:
         """One step on device tensors (torch); counts the tokens it chose since the last reset."""
         self.lib._check(self.lib.c.bitnet_hip_sample_dev(self.h, _ptr(logits), logits.numel(), _optr(token), _optr(pos), _optr(history), _optr(n_forced),
                                                          _vp(stream)))
+
+
+class SampleBatch:
+    """One bitnet_hip_sample_batch: up to 8 slots, each binding a Sampler and the device tensors sample_dev would take; launch() samples for
+    every bound slot in ONE kernel launch, per slot bit for bit what Sampler.sample_dev alone would have left.  Keeps the bound samplers and
+    tensors alive."""
+
+    def __init__(self, lib: HipLib, vocab: int, n_slots: int):
+        self.lib, self.vocab, self.n_slots = lib, int(vocab), int(n_slots)
+        h = _vp()
+        lib._check(lib.c.bitnet_hip_sample_batch_create(vocab, n_slots, C.byref(h)))
+        self.h = h
+        self._keep = {}
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.c.bitnet_hip_sample_batch_destroy(self.h)
+            self.h = None
+            self._keep = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def set(self, slot: int, sampler: "Sampler | None", logits=None, token=None, pos=None, history=None, n_forced=None) -> None:
+        """Bind `sampler` and its device tensors to `slot`, or empty the slot (sampler None).  Synchronous; no launch may be in flight."""
+        if sampler is None:
+            self.lib._check(self.lib.c.bitnet_hip_sample_batch_set(self.h, slot, None, None, None, None, None, None))
+            self._keep.pop(slot, None)
+            return
+        self.lib._check(self.lib.c.bitnet_hip_sample_batch_set(self.h, slot, sampler.h, _optr(logits), _optr(token), _optr(pos), _optr(history),
+                                                               _optr(n_forced)))
+        self._keep[slot] = (sampler, logits, token, pos, history, n_forced)
+
+    def launch(self, stream: int = 0) -> None:
+        """One kernel launch for every bound slot (asynchronous, capture-safe)."""
+        self.lib._check(self.lib.c.bitnet_hip_sample_batch_dev(self.h, _vp(stream)))
 
 
 _lib = None
@@ -1168,6 +1219,10 @@ class HostBatch:
         L.bitnet_host_batch_set_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.bitnet_host_batch_step.restype = C.c_int
         L.bitnet_host_batch_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.bitnet_host_batch_captures.restype = C.c_int
+        L.bitnet_host_batch_captures.argtypes = [C.c_void_p]
+        L.bitnet_host_batch_graph_nodes.restype = C.c_int
+        L.bitnet_host_batch_graph_nodes.argtypes = [C.c_void_p]
         self.n_slots = n_slots
         self.h = L.bitnet_host_batch_create(n_slots)
         if not self.h:
@@ -1198,3 +1253,11 @@ class HostBatch:
         ms = C.c_float(0.0)
         self._check(self.c.bitnet_host_batch_step(self.h, n, int(use_graph), C.byref(ms)))
         return float(ms.value)
+
+    def captures(self) -> int:
+        """Graph captures so far: one for a batch's life, two if its first sampling member arrived after an all-greedy capture."""
+        return int(self.c.bitnet_host_batch_captures(self.h))
+
+    def graph_nodes(self) -> int:
+        """Kernel nodes of the captured chain, 0 if none is held."""
+        return int(self.c.bitnet_host_batch_graph_nodes(self.h))

@@ -76,6 +76,7 @@ void BatchDecoder::drop_graph() {
 BatchDecoder::~BatchDecoder() {
     if (stream_) hipStreamSynchronize((hipStream_t)stream_);
     drop_graph();
+    if (sample_tab_) bitnet_hip_sample_batch_destroy(sample_tab_);  // before the members (and their samplers) are released
     for (void *p : {(void *)tables_, (void *)x_, (void *)x2_, (void *)qkv_, (void *)attn_scratch_, qa_x_, qa_x2_, qa_att_, qa_h_, scratch_, (void *)st_x_,
                     (void *)st_x2_})
         if (p) hipFree(p);
@@ -108,6 +109,7 @@ int BatchDecoder::ensure_buffers() {
         HCHK(hipMemset(*w.p, 0, w.bytes));
     }
     host_tables_.assign(rows * n, nullptr);
+    BCHK(bitnet_hip_sample_batch_create((size_t)c.vocab, n, &sample_tab_));
     // One pass of the chain with every slot idle (all-NULL tables: the gather, the attention and the head touch nothing, the GEMVs run on the
     // zero-filled vectors): every kernel is loaded and its dynamic-LDS limit raised BEFORE the first capture, which must see launches only.
     if (int rc = launches(true)) return rc;
@@ -168,6 +170,7 @@ int BatchDecoder::set_slot(int b, Decoder *d) {
         }
     }
     if (slot_[b]) {
+        if (int rc = bind_sampler(b, nullptr)) return rc;  // its sampler leaves the table before the member can be destroyed
         slot_[b]->batch_ = nullptr;
         bitnet_host_release(slot_[b]);
         slot_[b] = nullptr;
@@ -180,6 +183,20 @@ int BatchDecoder::set_slot(int b, Decoder *d) {
         slot_[b] = d;
     }
     tables_dirty_ = true;
+    return 0;
+}
+
+// slot b's entry of the sampling table: member d's sampler with its logits row, position, history and forced count, or empty (d == nullptr)
+int BatchDecoder::bind_sampler(int b, Decoder *d) {
+    void *g[7] = {}, *bo[3] = {};
+    if (d) {
+        d->global_objects(g);
+        d->batch_objects(bo);
+    }
+    if (!bo[2] && !bound_[b]) return 0;
+    BCHK(bitnet_hip_sample_batch_set(sample_tab_, (size_t)b, (bitnet_hip_sampler *)bo[2], (const float *)bo[1], nullptr, (int32_t *)g[5], (int32_t *)g[4],
+                                     (const int32_t *)bo[0]));
+    bound_[b] = bo[2];
     return 0;
 }
 
@@ -198,7 +215,7 @@ int BatchDecoder::upload_tables() {
         host_tables_[kRowHist * n + b] = d ? g[4] : nullptr;
         host_tables_[kRowLogits * n + b] = d ? bo[1] : nullptr;
         host_tables_[kRowTok * n + b] = nullptr;  // the picked token goes into the history only (Decoder keeps a token word of its own for probes)
-        host_tables_[kRowPickPos * n + b] = greedy ? g[5] : nullptr;  // a sampling member gets logits only: bitnet_hip_sample_dev picks and advances
+        host_tables_[kRowPickPos * n + b] = greedy ? g[5] : nullptr;  // a sampling member gets logits only: the sampling launch picks and advances
         host_tables_[kRowPickHist * n + b] = greedy ? g[4] : nullptr;
         host_tables_[kRowForced * n + b] = greedy ? bo[0] : nullptr;
         for (int l = 0; l < c.n_layers; ++l) {
@@ -210,6 +227,16 @@ int BatchDecoder::upload_tables() {
         }
     }
     HCHK(hipMemcpy(tables_, host_tables_.data(), host_tables_.size() * sizeof(void *), hipMemcpyHostToDevice));
+    // the sampling table follows: first every entry whose sampler goes (a sampler sits in one slot at a time), then the sampling members'
+    for (int b = 0; b < n_; ++b) {
+        void *bo[3] = {};
+        if (slot_[b] && slot_[b]->sampling()) slot_[b]->batch_objects(bo);
+        if (bound_[b] && bound_[b] != bo[2])
+            if (int rc = bind_sampler(b, nullptr)) return rc;
+    }
+    for (int b = 0; b < n_; ++b)
+        if (slot_[b] && slot_[b]->sampling())
+            if (int rc = bind_sampler(b, slot_[b])) return rc;
     tables_dirty_ = false;
     return 0;
 }
@@ -246,15 +273,9 @@ int BatchDecoder::launches(bool warm) {
     BCHK(bitnet_hip_logits_f16_batch_dev(g[0], x_, (const float *)g[1], c.eps, H, (size_t)c.vocab, n, (float *const *)row(kRowLogits), scratch_,
                                          (size_t)logits_wgs_, (int32_t *const *)row(kRowTok), (int32_t *const *)row(kRowPickPos),
                                          (int32_t *const *)row(kRowPickHist), (const int32_t *const *)row(kRowForced), s));
-    for (int b = 0; b < n_ && !warm; ++b) {
-        Decoder *d = slot_[b];
-        if (!d || !d->sampling()) continue;
-        void *dg[7], *bo[3];
-        d->global_objects(dg);
-        d->batch_objects(bo);
-        BCHK(bitnet_hip_sample_dev((bitnet_hip_sampler *)bo[2], (const float *)bo[1], (size_t)c.vocab, nullptr, (int32_t *)dg[5], (int32_t *)dg[4],
-                                   (const int32_t *)bo[0], s));
-    }
+    // every sampling member in ONE launch that reads per-slot sampler state through the sampling table (an empty entry: nothing to do); in the
+    // chain from the first step at which any member samples, and in the warm pass (all entries empty) so that the kernel is loaded
+    if (warm || sample_in_chain_) BCHK(bitnet_hip_sample_batch_dev(sample_tab_, s));
     return 0;
 }
 
@@ -276,9 +297,10 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
         if (int rc = upload_tables()) return rc;
         tables_sig_ = sig;
     }
+    for (void *sp : sig) sample_in_chain_ |= sp != nullptr;
     hipStream_t s = (hipStream_t)stream_;
     if (use_graph) {
-        if (graph_exec_ && sig != graph_sig_) drop_graph();  // which slots sample is part of the captured chain
+        if (graph_exec_ && sample_in_chain_ != graph_sig_) drop_graph();  // the first sampling member ever adds the sampling launch to the chain
         if (!graph_exec_) {
             hipGraph_t gr = nullptr;
             HCHK(hipStreamBeginCapture(s, hipStreamCaptureModeGlobal));
@@ -293,7 +315,8 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
             HCHK(hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0));
             graph_ = gr;
             graph_exec_ = ex;
-            graph_sig_ = sig;
+            graph_sig_ = sample_in_chain_;
+            ++captures_;
         }
     }
     Event ev0, ev1;
@@ -313,6 +336,20 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
     HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
     if (elapsed_ms) *elapsed_ms = ms;
     return 0;
+}
+
+int BatchDecoder::graph_nodes() const {
+    if (!graph_) return 0;
+    size_t n = 0;
+    if (hipGraphGetNodes((hipGraph_t)graph_, nullptr, &n) != hipSuccess || !n) return 0;
+    std::vector<hipGraphNode_t> nodes(n);
+    if (hipGraphGetNodes((hipGraph_t)graph_, nodes.data(), &n) != hipSuccess) return 0;
+    int kernels = 0;
+    for (size_t i = 0; i < n; ++i) {
+        hipGraphNodeType t;
+        if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) ++kernels;
+    }
+    return kernels;
 }
 
 }  // namespace bitnet_host
@@ -336,4 +373,6 @@ int bitnet_host_batch_set_slot(void *b, int slot, void *decoder) {
 int bitnet_host_batch_step(void *b, int n, int use_graph, float *elapsed_ms) {
     return b ? static_cast<BatchDecoder *>(b)->step(n, use_graph != 0, elapsed_ms) : BITNET_HIP_ERR_INVALID_ARGUMENT;
 }
+int bitnet_host_batch_captures(void *b) { return b ? static_cast<BatchDecoder *>(b)->captures() : 0; }
+int bitnet_host_batch_graph_nodes(void *b) { return b ? static_cast<BatchDecoder *>(b)->graph_nodes() : 0; }
 }

@@ -14,8 +14,11 @@
 //
 // Scheduling is set_slot(): members join and leave between steps (continuous batching); prompts go through the member's own prefill / extend
 // before it joins, or the member takes over a live sequence's prefix (Decoder::fork: one copy launch for up to 8 members).  The step is ONE linear chain on one stream (no forked capture branches), captured once per batch: slot changes rewrite the
-// device pointer tables the kernels read and need no re-capture.  The one exception is a change in WHICH slots sample: a sampling member gets
-// logits only from the head and its own bitnet_hip_sample_dev launch, whose arguments are per member.  Single-threaded use.
+// device pointer tables the kernels read and need no re-capture.  Sampling goes the same way: a sampling member gets logits only from the head, and
+// ONE bitnet_hip_sample_batch_dev launch after it serves every sampling member through a device table of per-slot sampler state (an empty
+// entry: nothing to do), so a member switching its sampling on or off, a sampling member leaving or a greedy one taking its place re-captures
+// nothing.  That launch joins the chain at the first step at which any member samples -- the one re-capture sampling can cost, once in a
+// batch's life; a batch that never had a sampling member launches the chain without it.  Single-threaded use.
 #pragma once
 
 #include <string>
@@ -40,12 +43,15 @@ class BatchDecoder {
     // n with-logits steps for every occupied slot.  Refuses with "KV cache overflow" if any member would pass max_pos - 1 (positions are read
     // once, before the first launch).  Synchronises before returning.
     int step(int n, bool use_graph, float *elapsed_ms);
+    int captures() const { return captures_; }  // graph captures so far
+    int graph_nodes() const;                    // kernel nodes of the captured chain, 0 if none is held
 
   private:
     int fail(const char *what);
     int fail_arg(const std::string &what);
     int ensure_buffers();
     int upload_tables();
+    int bind_sampler(int b, Decoder *d);
     int launches(bool warm = false);  // warm: the pass over all-idle tables that ensure_buffers runs once
     int clear_vectors(int b);
     void drop_graph();
@@ -66,9 +72,13 @@ class BatchDecoder {
     double *st_x_ = nullptr, *st_x2_ = nullptr;
     int logits_wgs_ = 512;
     void *graph_ = nullptr, *graph_exec_ = nullptr;
-    std::vector<void *> tables_sig_;  // ... and the one the uploaded pick tables were built for
-    std::vector<void *> graph_sig_;  // per slot the sampler the captured chain launches for it (null: fused greedy pick)
-    std::vector<void *> sampling_sig() const;
+    std::vector<void *> sampling_sig() const;  // per slot the sampler of a sampling member (null: fused greedy pick, or empty) ...
+    std::vector<void *> tables_sig_;           // ... and the one the uploaded pick and sampling tables were built for
+    bitnet_hip_sample_batch *sample_tab_ = nullptr;  // n_ entries, one launch (bitnet_hip_sample_batch_dev)
+    void *bound_[BITNET_HIP_BATCH_MAX] = {};         // the sampler each of its entries holds
+    bool sample_in_chain_ = false;  // some member has sampled: the sampling launch is part of every step from then on
+    bool graph_sig_ = false;        // ... and whether the captured chain has it
+    int captures_ = 0;
 };
 
 }  // namespace bitnet_host
@@ -79,4 +89,6 @@ void bitnet_host_batch_destroy(void *b);
 const char *bitnet_host_batch_error(void *b);
 int bitnet_host_batch_set_slot(void *b, int slot, void *decoder);  // decoder NULL clears the slot
 int bitnet_host_batch_step(void *b, int n, int use_graph, float *elapsed_ms);
+int bitnet_host_batch_captures(void *b);     // graph captures so far
+int bitnet_host_batch_graph_nodes(void *b);  // kernel nodes of the captured chain, 0 if none
 }

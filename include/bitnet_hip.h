@@ -693,6 +693,30 @@ int bitnet_hip_sample_dev(bitnet_hip_sampler *sampler, const float *logits_dev, 
 int bitnet_hip_sample_host(bitnet_hip_sampler *sampler, const float *logits, size_t vocab, const uint32_t *generated,
                            size_t n_generated, uint32_t *token);
 
+/* ---- batched sampling: every sampling member of a batch in one launch -------------------------------------------
+ * The reference's `Sampler::sample` (crates/bitnet-cli/src/sampling.rs) called once per sequence of a `[B, T, H]` batch: here a
+ * table of n_slots = 1..BITNET_HIP_BATCH_MAX entries, each binding one bitnet_hip_sampler and the pointers bitnet_hip_sample_dev
+ * would take, and ONE kernel launch that serves every bound entry -- grid (workgroups per sampler, n_slots), the entries read from
+ * device memory, so a captured graph follows every later bitnet_hip_sample_batch_set.  Per bound slot the token, the history
+ * entry, the position, the forced-position rule, the counts, the ChaCha20 word counter and the re-armed hand-over are bit for bit
+ * what bitnet_hip_sample_dev on that sampler alone would have left (one kernel body serves both); for an empty slot nothing is read
+ * or written.  No workgroup waits for another: the slots finish side by side.
+ *   create: vocab in 1..2^20 (every sampler bound later must be made for it), n_slots in 1..BITNET_HIP_BATCH_MAX; anything else is
+ *     INVALID_ARGUMENT before the GPU is touched.  Allocates the device table, every entry empty.  Not capture-safe.
+ *   set: binds `sampler` and its pointers to `slot`; sampler == NULL empties the slot.  One synchronous copy of one entry: not
+ *     capture-safe, but graphs captured before it stay valid and follow it.  Call it with no launch on the table in flight.  Refuses,
+ *     with nothing changed: a slot out of range, a NULL logits_dev with a sampler, a sampler made for another vocabulary, a sampler
+ *     already bound to another slot of this table.  A sampler serves one table or bitnet_hip_sample_dev at a time; empty its slot
+ *     before bitnet_hip_sampler_destroy.
+ *   dev: exactly one kernel launch, asynchronous and capture-safe (no allocation, copy or synchronisation); it launches even when
+ *     every slot is empty.  A NULL table is INVALID_ARGUMENT. */
+typedef struct bitnet_hip_sample_batch bitnet_hip_sample_batch;
+int bitnet_hip_sample_batch_create(size_t vocab, size_t n_slots, bitnet_hip_sample_batch **out);
+void bitnet_hip_sample_batch_destroy(bitnet_hip_sample_batch *table);
+int bitnet_hip_sample_batch_set(bitnet_hip_sample_batch *table, size_t slot, bitnet_hip_sampler *sampler, const float *logits_dev,
+                                int32_t *token_dev, int32_t *pos_dev, int32_t *history_dev, const int32_t *n_forced_dev);
+int bitnet_hip_sample_batch_dev(bitnet_hip_sample_batch *table, void *stream);
+
 /* ---- measurement aid -------------------------------------------------------
  * Measured HBM read ceiling of the device (quote the roofline fraction against the vendor
  * figure AND a measured stream ceiling): a read-only streaming kernel (non-temporal 16-byte loads, one

@@ -201,6 +201,13 @@ class HipLib:
         L.bitnet_hip_sample_batch_set.restype = C.c_int
         L.bitnet_hip_sample_batch_dev.argtypes = [_vp, _vp]
         L.bitnet_hip_sample_batch_dev.restype = C.c_int
+        # the logits tap (per-token log-probabilities and top-N logits): bound here with the rest, never lazily
+        L.bitnet_hip_logprob_scratch_bytes.argtypes = [_sz]
+        L.bitnet_hip_logprob_scratch_bytes.restype = _sz
+        L.bitnet_hip_logprob_dev.argtypes = [C.POINTER(LogprobArgs), _sz, _vp]
+        L.bitnet_hip_logprob_dev.restype = C.c_int
+        L.bitnet_hip_logprob_batch_dev.argtypes = [_vp, _sz, _sz, _vp]
+        L.bitnet_hip_logprob_batch_dev.restype = C.c_int
         L.bitnet_hip_score_workspace_bytes.argtypes = [_sz, _sz, _sz]
         L.bitnet_hip_score_workspace_bytes.restype = _sz
         L.bitnet_hip_score_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
@@ -636,11 +643,51 @@ class HipLib:
         """A table of n_slots sampler bindings served by one launch (bitnet_hip_sample_batch_*)."""
         return SampleBatch(self, vocab, n_slots)
 
+    def logprob_scratch_bytes(self, vocab: int) -> int:
+        """Bytes of the scratch one bitnet_hip_logprob_args entry needs (zeroed once by the caller); 0 for a vocabulary the library refuses."""
+        return int(self.c.bitnet_hip_logprob_scratch_bytes(vocab))
+
+    def logprob_dev(self, args: "LogprobArgs", vocab: int, stream: int = 0) -> None:
+        """One launch after the pick: record [*pos] of the entry -- token, its raw logit, the row's log-sum-exp, the top_n (id, logit) pairs."""
+        self._check(self.c.bitnet_hip_logprob_dev(C.byref(args) if args is not None else None, vocab, _vp(stream)))
+
+    def logprob_batch_dev(self, table, n_slots: int, vocab: int, stream: int = 0) -> None:
+        """The same for n_slots entries read from a DEVICE table of LogprobArgs (a uint8 tensor holding them, or a raw pointer), one launch."""
+        self._check(self.c.bitnet_hip_logprob_batch_dev(_optr(table), n_slots, vocab, _vp(stream)))
+
     def hbm_read_ceiling(self, nbytes: int = 2 << 30, iters: int = 10, stream: int = 0):
         """Measured read-only stream ceiling of the device: (best, mean) GB/s."""
         best, mean = C.c_double(0.0), C.c_double(0.0)
         self._check(self.c.bitnet_hip_hbm_read_ceiling(nbytes, iters, C.byref(best), C.byref(mean), _vp(stream)))
         return best.value, mean.value
+
+
+LOGPROB_TOP_MAX = 20
+
+
+class LogprobRecord(C.Structure):
+    """bitnet_hip_logprob_record (176 bytes)"""
+    _fields_ = [("token", C.c_int32), ("n_top", C.c_int32), ("logit", C.c_float), ("lse", C.c_float), ("top_id", C.c_int32 * LOGPROB_TOP_MAX),
+                ("top_logit", C.c_float * LOGPROB_TOP_MAX)]
+
+
+# the same layout for numpy: records read back as one structured array
+LOGPROB_DTYPE = np.dtype([("token", "<i4"), ("n_top", "<i4"), ("logit", "<f4"), ("lse", "<f4"), ("top_id", "<i4", (LOGPROB_TOP_MAX,)),
+                          ("top_logit", "<f4", (LOGPROB_TOP_MAX,))])
+
+
+class LogprobArgs(C.Structure):
+    """bitnet_hip_logprob_args: device pointers as integers (0 = NULL; records_dev 0 = an empty entry)"""
+    _fields_ = [("logits_dev", C.c_void_p), ("pos_dev", C.c_void_p), ("history_dev", C.c_void_p), ("records_dev", C.c_void_p),
+                ("scratch_dev", C.c_void_p), ("capacity", C.c_uint32), ("top_n", C.c_uint32)]
+
+    @classmethod
+    def make(cls, logits=None, pos=None, history=None, records=None, scratch=None, capacity: int = 0, top_n: int = 0) -> "LogprobArgs":
+        p = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        return cls(p(logits), p(pos), p(history), p(records), p(scratch), int(capacity), int(top_n))
+
+
+Logprobs = collections.namedtuple("Logprobs", "token logit lse logprob top_ids top_logits")
 
 
 class SamplingConfig(C.Structure):
@@ -932,6 +979,10 @@ class HostDecoder:
         L.bitnet_host_weight_bytes.restype = C.c_uint64
         L.bitnet_host_set_sampling.argtypes = [C.c_void_p, C.POINTER(SamplingConfig)]
         L.bitnet_host_sampling_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bitnet_host_set_logprobs.argtypes = [C.c_void_p, C.c_int]
+        L.bitnet_host_set_logprobs.restype = C.c_int
+        L.bitnet_host_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.bitnet_host_logprobs.restype = C.c_int
         L.bitnet_host_score.argtypes = [C.c_void_p, C.c_int, C.c_int, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.POINTER(C.c_float)]
         L.bitnet_host_extend.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.bitnet_host_extend.restype = C.c_int
@@ -942,6 +993,7 @@ class HostDecoder:
         L.bitnet_host_cached_prefix.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
         L.bitnet_host_cached_prefix.restype = C.c_int
         self.cfg = cfg
+        self._top_n = -1  # set_logprobs
         self._fed = 0  # tokens fed since the last reset (the default n of score)
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
         self.h = L.bitnet_host_create(C.byref(hc)) if _owner is None else L.bitnet_host_create_shared(_owner.h)
@@ -1017,6 +1069,28 @@ class HostDecoder:
         d = C.c_uint64(0)
         self._check(self.c.bitnet_host_sampling_draws(self.h, C.byref(d)))
         return int(d.value)
+
+    def set_logprobs(self, top_n: int | None) -> None:
+        """The reference's logits tap (GenerationConfig::logits_cb / --dump-logit-steps) on the device, inside the captured graphs: with
+        top_n = 0..20 every with-logits step leaves one record at the position of the token it placed (chosen or forced) -- the token, its raw
+        logit, the row's log-sum-exp and the top_n (id, logit) pairs.  None (or -1): off, as a decoder that never called this."""
+        self._top_n = -1 if top_n is None else int(top_n)
+        self._check(self.c.bitnet_host_set_logprobs(self.h, self._top_n))
+
+    def logprob_records(self, first: int, n: int) -> np.ndarray:
+        """Records [first, first + n) as a structured array of LOGPROB_DTYPE (the raw bytes of bitnet_hip_logprob_record)."""
+        out = np.zeros(max(int(n), 0), LOGPROB_DTYPE)
+        self._check(self.c.bitnet_host_logprobs(self.h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def logprobs(self, first: int, n: int) -> "Logprobs":
+        """Records [first, first + n): token [n] (-1: never written), logit [n], lse [n], logprob [n] (= logit - lse in f32), top_ids and
+        top_logits [n, top] with top = the current top_n (finite logits first by descending value, then ascending id)."""
+        r = self.logprob_records(first, n)
+        top = max(getattr(self, "_top_n", -1), 0)
+        with np.errstate(invalid="ignore"):
+            lp = (r["logit"] - r["lse"]).astype(np.float32)
+        return Logprobs(r["token"].copy(), r["logit"].copy(), r["lse"].copy(), lp, r["top_id"][:, :top].copy(), r["top_logit"][:, :top].copy())
 
     def feed(self, tokens) -> None:
         t = _np(tokens, np.int32)
@@ -1118,7 +1192,8 @@ class HostDecoder:
         """Every decoder of `dsts` (1..8 of them: this decoder's owner or borrowers of the same weights, the same cache type, in no batch
         slot) takes over the first n positions, 0 <= n <= position(): it ends as this decoder would after rewind(n) -- position, forced
         count, history[0 .. n], cache slots < n (one copy launch for all destinations), sampler reset -- and this decoder is untouched.
-        Best of n: prefill(P) here, fork_into(dsts, P - 1), every destination run(1) under its own seed.  Prefix hit: fork at
+        Best of n: prefill(P) here, fork_into(dsts, P - 1), every destination run(1) under its own seed; with set_logprobs on, best of n
+        ranks the candidates by logprobs(P, k).logprob.sum().  Prefix hit: fork at
         cached_prefix(prompt), feed() the rest (it writes at slot n) and extend() over it.  A destination's last_logits() / last_hidden()
         are unspecified until its next with-logits step."""
         dsts = list(dsts)

@@ -1259,6 +1259,35 @@ int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const 
     BH_GUARD_END
 }
 
+// ---- the generation path's logits tap (kernels_logprob.hip) ----
+size_t bitnet_hip_logprob_scratch_bytes(size_t vocab) { return vocab == 0 || vocab > ((size_t)1 << 20) ? 0 : logprob_scratch_bytes(); }
+
+int bitnet_hip_logprob_dev(const bitnet_hip_logprob_args *args_host, size_t vocab, void *stream) {
+    BH_GUARD_BEGIN
+    if (!args_host) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to logprob_dev");
+    if (vocab == 0 || vocab > ((size_t)1 << 20))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logprob_dev: vocab must be in 1..%d, got %zu", 1 << 20, vocab);
+    if (args_host->top_n > BITNET_HIP_LOGPROB_TOP_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logprob_dev: top_n %u, at most %d", args_host->top_n, BITNET_HIP_LOGPROB_TOP_MAX);
+    if (args_host->records_dev && (!args_host->logits_dev || !args_host->pos_dev || !args_host->history_dev || !args_host->scratch_dev))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to logprob_dev (logits, position, history or scratch of a bound entry)");
+    BH_HIP_TRY(launch_logprob(*args_host, vocab, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_logprob_batch_dev(const bitnet_hip_logprob_args *table_dev, size_t n_slots, size_t vocab, void *stream) {
+    BH_GUARD_BEGIN
+    if (!table_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null table passed to logprob_batch_dev");
+    if (vocab == 0 || vocab > ((size_t)1 << 20))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logprob_batch_dev: vocab must be in 1..%d, got %zu", 1 << 20, vocab);
+    if (n_slots == 0 || n_slots > (size_t)BITNET_HIP_BATCH_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logprob_batch_dev: n_slots must be in 1..%d, got %zu", BITNET_HIP_BATCH_MAX, n_slots);
+    BH_HIP_TRY(launch_logprob_batch(table_dev, n_slots, vocab, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 size_t bitnet_hip_attention_prefill_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t seq_len) {
     return attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)seq_len, (int)seq_len);
 }

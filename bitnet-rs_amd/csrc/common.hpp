@@ -170,6 +170,10 @@ hipError_t launch_logits_f16_batch(const void *table, const float *x, const floa
 // position and KV head (128 for f32 caches, 64 for f16), head_words = ceil(max_pos / 64) * 64 * rows
 hipError_t launch_kv_fork(const void *const *src_k, const void *const *src_v, void *const *dst_k, void *const *dst_v, size_t n_layers, size_t n_dst,
                           size_t n_kv, size_t rows, size_t head_words, size_t n, hipStream_t stream);
+// kernels_logprob.hip: the logits tap after the pick -- one entry (args by value) or a device table of n_slots entries, one launch each
+size_t logprob_scratch_bytes();
+hipError_t launch_logprob(const bitnet_hip_logprob_args &a, size_t vocab, hipStream_t stream);
+hipError_t launch_logprob_batch(const bitnet_hip_logprob_args *table, size_t n_slots, size_t vocab, hipStream_t stream);
 hipError_t build_tiles(Weights &w, hipStream_t stream);
 // codes / scales in the reference layout, rebuilt from the tiles if they were dropped (exact inverse permutation);
 // synchronises `stream` when it had to rebuild.  trim_reference drops them again when the tiles can stand in.

@@ -5,6 +5,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 namespace bitnet_host {
 
@@ -78,7 +79,7 @@ BatchDecoder::~BatchDecoder() {
     drop_graph();
     if (sample_tab_) bitnet_hip_sample_batch_destroy(sample_tab_);  // before the members (and their samplers) are released
     for (void *p : {(void *)tables_, (void *)x_, (void *)x2_, (void *)qkv_, (void *)attn_scratch_, qa_x_, qa_x2_, qa_att_, qa_h_, scratch_, (void *)st_x_,
-                    (void *)st_x2_})
+                    (void *)st_x2_, (void *)lp_table_})
         if (p) hipFree(p);
     if (stream_) hipStreamDestroy((hipStream_t)stream_);
     for (int b = 0; b < n_; ++b)
@@ -103,7 +104,8 @@ int BatchDecoder::ensure_buffers() {
         size_t bytes;
     } want[] = {{(void **)&x_, n * H * 4}, {(void **)&x2_, n * H * 4}, {(void **)&qkv_, n * (QD + 2 * KD) * 4}, {(void **)&attn_scratch_, n * as},
                 {&qa_x_, n * qh},          {&qa_x2_, n * qh},          {&qa_att_, n * qq},                       {&qa_h_, n * qf},
-                {(void **)&st_x_, n * sb}, {(void **)&st_x2_, n * sb}, {&scratch_, n * 8 * (size_t)logits_wgs_}, {(void **)&tables_, rows * n * sizeof(void *)}};
+                {(void **)&st_x_, n * sb}, {(void **)&st_x2_, n * sb}, {&scratch_, n * 8 * (size_t)logits_wgs_}, {(void **)&tables_, rows * n * sizeof(void *)},
+                {(void **)&lp_table_, n * sizeof(bitnet_hip_logprob_args)}};  // zero-filled: every entry empty
     for (auto &w : want) {
         HCHK(hipMalloc(w.p, w.bytes));
         HCHK(hipMemset(*w.p, 0, w.bytes));
@@ -276,6 +278,8 @@ int BatchDecoder::launches(bool warm) {
     // every sampling member in ONE launch that reads per-slot sampler state through the sampling table (an empty entry: nothing to do); in the
     // chain from the first step at which any member samples, and in the warm pass (all entries empty) so that the kernel is loaded
     if (warm || sample_in_chain_) BCHK(bitnet_hip_sample_batch_dev(sample_tab_, s));
+    // the logits tap of every member that has it on, after the pick; in the chain from the first step at which any member has, and in the warm pass
+    if (warm || lp_in_chain_) BCHK(bitnet_hip_logprob_batch_dev(lp_table_, n, (size_t)c.vocab, s));
     return 0;
 }
 
@@ -298,9 +302,21 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
         tables_sig_ = sig;
     }
     for (void *sp : sig) sample_in_chain_ |= sp != nullptr;
+    {
+        // the logprob table follows its members: records, scratch and top_n of each, an empty entry for a member without and for an empty slot
+        bitnet_hip_logprob_args lp[BITNET_HIP_BATCH_MAX] = {};
+        for (int b = 0; b < n_; ++b)
+            if (slot_[b]) slot_[b]->logprob_entry(&lp[b]);
+        if (memcmp(lp, lp_host_, sizeof(lp)) != 0) {
+            HCHK(hipMemcpy(lp_table_, lp, (size_t)n_ * sizeof(lp[0]), hipMemcpyHostToDevice));
+            memcpy(lp_host_, lp, sizeof(lp));
+        }
+        for (int b = 0; b < n_; ++b) lp_in_chain_ |= lp[b].records_dev != nullptr;
+    }
     hipStream_t s = (hipStream_t)stream_;
     if (use_graph) {
-        if (graph_exec_ && sample_in_chain_ != graph_sig_) drop_graph();  // the first sampling member ever adds the sampling launch to the chain
+        // the first sampling member ever adds the sampling launch to the chain, the first with logprobs on the logprob launch
+        if (graph_exec_ && (sample_in_chain_ != graph_sig_ || lp_in_chain_ != graph_lp_sig_)) drop_graph();
         if (!graph_exec_) {
             hipGraph_t gr = nullptr;
             HCHK(hipStreamBeginCapture(s, hipStreamCaptureModeGlobal));
@@ -316,6 +332,7 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
             graph_ = gr;
             graph_exec_ = ex;
             graph_sig_ = sample_in_chain_;
+            graph_lp_sig_ = lp_in_chain_;
             ++captures_;
         }
     }

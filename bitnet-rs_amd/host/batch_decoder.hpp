@@ -18,7 +18,12 @@
 // ONE bitnet_hip_sample_batch_dev launch after it serves every sampling member through a device table of per-slot sampler state (an empty
 // entry: nothing to do), so a member switching its sampling on or off, a sampling member leaving or a greedy one taking its place re-captures
 // nothing.  That launch joins the chain at the first step at which any member samples -- the one re-capture sampling can cost, once in a
-// batch's life; a batch that never had a sampling member launches the chain without it.  Single-threaded use.
+// batch's life; a batch that never had a sampling member launches the chain without it.  The logits tap (Decoder::set_logprobs) goes the same
+// way again: the members' bitnet_hip_logprob_args form one more device table (a member with logprobs off, or an empty slot: an empty entry),
+// ONE bitnet_hip_logprob_batch_dev launch follows the head and the sampling launch, and it joins the chain at the first step at which any
+// member has logprobs on -- one re-capture, once; from then on members switching, joining or leaving re-capture nothing, and a batch that never
+// had such a member runs the chain it always ran.  After step(n) a member's records are bit for bit those of its own run(n) under
+// set_attention_form(0).  Single-threaded use.
 #pragma once
 
 #include <string>
@@ -78,6 +83,10 @@ class BatchDecoder {
     void *bound_[BITNET_HIP_BATCH_MAX] = {};         // the sampler each of its entries holds
     bool sample_in_chain_ = false;  // some member has sampled: the sampling launch is part of every step from then on
     bool graph_sig_ = false;        // ... and whether the captured chain has it
+    bitnet_hip_logprob_args *lp_table_ = nullptr;             // device: [n_] entries, one launch (bitnet_hip_logprob_batch_dev)
+    bitnet_hip_logprob_args lp_host_[BITNET_HIP_BATCH_MAX] = {};  // what it holds
+    bool lp_in_chain_ = false;      // some member has had logprobs on: the logprob launch is part of every step from then on
+    bool graph_lp_sig_ = false;     // ... and whether the captured chain has it
     int captures_ = 0;
 };
 

@@ -212,6 +212,8 @@ void Decoder::batch_objects(void *ptrs[3]) const { ptrs[0] = n_forced_, ptrs[1] 
 Decoder::~Decoder() {
     drop_graphs();
     if (sampler_) bitnet_hip_sampler_destroy(sampler_);
+    for (void *p : {(void *)lp_records_, lp_scratch_})
+        if (p) hipFree(p);
     if (owner_) {  // borrowed objects stay the owner's
         for (auto &L : layers_) L.qkv = L.o = L.gateup = L.down = 0, L.attn_norm = L.ffn_norm = nullptr;
         embed_ = nullptr, final_norm_ = nullptr;
@@ -260,18 +262,61 @@ void Decoder::drop_graphs() {
     }
 }
 
-int Decoder::pick_token(void *stream) {
+int Decoder::pick_token(void *stream, bool record) {
     hipStream_t s = (hipStream_t)stream;
     const size_t H = c_.hidden;
     if (!sampling_) {
         // greedy token (T:1589, T:1599-1630, sampling.rs:189-202)
         BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, token_, pos_,
                                        history_, n_forced_, s));
-        return 0;
+    } else {
+        BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, nullptr, nullptr,
+                                       nullptr, nullptr, s));
+        BCHK(bitnet_hip_sample_dev(sampler_, logits_, (size_t)c_.vocab, token_, pos_, history_, n_forced_, s));
     }
-    BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, nullptr, nullptr,
-                                   nullptr, nullptr, s));
-    BCHK(bitnet_hip_sample_dev(sampler_, logits_, (size_t)c_.vocab, token_, pos_, history_, n_forced_, s));
+    if (record && lp_top_n_ >= 0) {
+        // the logits tap, after the pick (engine.rs:1182-1210): the position is p + 1 by now and history[p + 1] holds the token
+        bitnet_hip_logprob_args a;
+        logprob_entry(&a);
+        BCHK(bitnet_hip_logprob_dev(&a, (size_t)c_.vocab, s));
+    }
+    return 0;
+}
+
+void Decoder::logprob_entry(bitnet_hip_logprob_args *out) const {
+    *out = bitnet_hip_logprob_args{};
+    if (lp_top_n_ < 0) return;
+    out->logits_dev = logits_, out->pos_dev = pos_, out->history_dev = history_;
+    out->records_dev = lp_records_, out->scratch_dev = lp_scratch_;
+    out->capacity = (uint32_t)c_.max_pos, out->top_n = (uint32_t)lp_top_n_;
+}
+
+int Decoder::set_logprobs(int top_n) {
+    if (top_n < -1 || top_n > BITNET_HIP_LOGPROB_TOP_MAX) return fail_arg("set_logprobs: top_n must be -1 (off) or 0..20");
+    if (top_n == lp_top_n_) return 0;
+    if (top_n >= 0 && !lp_records_) {
+        const size_t rb = (size_t)c_.max_pos * sizeof(bitnet_hip_logprob_record), sb = bitnet_hip_logprob_scratch_bytes((size_t)c_.vocab);
+        if (!sb) return fail_arg("set_logprobs: vocabulary out of range");
+        HCHK(hipMalloc((void **)&lp_records_, rb));
+        HCHK(hipMemset(lp_records_, 0xff, rb));
+        HCHK(hipMalloc(&lp_scratch_, sb));
+        HCHK(hipMemset(lp_scratch_, 0, sb));
+        // one launch of an empty entry: the kernel is loaded before a capture can meet it
+        bitnet_hip_logprob_args none{};
+        BCHK(bitnet_hip_logprob_dev(&none, (size_t)c_.vocab, stream_));
+        HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    }
+    drop_graphs();  // the launch and its top_n are part of the captured step
+    lp_top_n_ = top_n;
+    return 0;
+}
+
+int Decoder::logprobs(int first, int n, bitnet_hip_logprob_record *out) {
+    if (lp_top_n_ < 0) return fail_arg("logprobs: switched off (set_logprobs first)");
+    if (first < 0 || n < 0 || first > c_.max_pos || n > c_.max_pos - first) return fail_arg("logprobs: range outside [0, max_pos)");
+    if (n > 0 && !out) return fail_arg("logprobs: null output");
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    if (n > 0) HCHK(hipMemcpy(out, lp_records_ + first, (size_t)n * sizeof(bitnet_hip_logprob_record), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -441,6 +486,10 @@ int Decoder::reset() {
     HCHK(hipMemset(pos_, 0, 4));
     HCHK(hipMemset(n_forced_, 0, 4));
     HCHK(hipMemset(history_, 0, ((size_t)c_.max_pos + 2) * 4));
+    if (lp_records_) {
+        HCHK(hipMemset(lp_records_, 0xff, (size_t)c_.max_pos * sizeof(bitnet_hip_logprob_record)));
+        HCHK(hipMemset(lp_scratch_, 0, 16));  // a clean hand-over, as bitnet_hip_sampler_reset re-arms the sampler's
+    }
     return 0;
 }
 
@@ -583,7 +632,7 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
         }
         if (tr) TRACE("t" + std::to_string(tr->seq) + "_all_layers_out", "all_layers_out", -1, x_, H);
         if (with_logits) {
-            if (int rc = pick_token(s)) return rc;
+            if (int rc = pick_token(s, !tr)) return rc;
             TRACE(tp + "logits", "logits", -1, logits_, (size_t)c_.vocab);
         } else {
             BCHK(bitnet_hip_advance_pos_dev(pos_, s));
@@ -625,7 +674,7 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
     if (tr) TRACE("t" + std::to_string(tr->seq) + "_all_layers_out", "all_layers_out", -1, x_, H);
     if (with_logits) {
         // final norm + tied logits + greedy token (T:1589, T:1599-1630, sampling.rs:189-202)
-        if (int rc = pick_token(s)) return rc;
+        if (int rc = pick_token(s, !tr)) return rc;
         TRACE(tp + "logits", "logits", -1, logits_, (size_t)c_.vocab);
     } else {
         BCHK(bitnet_hip_advance_pos_dev(pos_, s));
@@ -684,7 +733,7 @@ int Decoder::step_launches_reference(bool with_logits) {
         BCHK(bitnet_hip_add_dev(x2_, ref_t_, x_, H, s));
     }
     if (with_logits) {
-        if (int rc = pick_token(s)) return rc;
+        if (int rc = pick_token(s, false)) return rc;
     } else {
         BCHK(bitnet_hip_advance_pos_dev(pos_, s));
     }
@@ -1121,6 +1170,8 @@ int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
         d->host_forced_ = forced;
         HCHK(hipMemcpy(d->n_forced_, &forced, 4, hipMemcpyHostToDevice));
         if (d->sampler_) BCHK(bitnet_hip_sampler_reset(d->sampler_));
+        // a destination's log-probabilities start at the fork point
+        if (d->lp_top_n_ >= 0) HCHK(hipMemset(d->lp_records_, 0xff, (size_t)c_.max_pos * sizeof(bitnet_hip_logprob_record)));
     }
     return 0;
 }
@@ -1788,6 +1839,11 @@ int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *fin
 int bitnet_host_reset(void *d) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->reset(); }
 int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_sampling(cfg); }
 int bitnet_host_sampling_draws(void *d, uint64_t *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->sampling_draws(out); }
+int bitnet_host_set_logprobs(void *d, int top_n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_logprobs(top_n); }
+int bitnet_host_logprobs(void *d, int first, int n, void *records_out) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->logprobs(first, n, static_cast<bitnet_hip_logprob_record *>(records_out));
+}
 int bitnet_host_feed(void *d, const int32_t *tokens, int n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->feed(tokens, n); }
 int bitnet_host_set_kv_f16(void *d, int on) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_kv_f16(on != 0); }
 int bitnet_host_set_act_mode(void *d, int mode) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_act_mode(mode); }

@@ -108,6 +108,21 @@ class Decoder {
     // a new config on an existing sampler does not (the graphs read it from device memory).
     int set_sampling(const bitnet_hip_sampling_config *cfg);
     int sampling_draws(uint64_t *out);
+    // The reference's logits tap on the generation path (GenerationConfig::{logits_tap_steps, logits_topk, logits_cb}, crates/bitnet-inference/src/
+    // config.rs:87-93, engine.rs:1182-1210; the CLI's LogitStep records, crates/bitnet-cli/src/main.rs:1337-1373) on the device: top_n = -1 (default)
+    // off, 0..BITNET_HIP_LOGPROB_TOP_MAX on.  On, every with-logits step appends ONE bitnet_hip_logprob_dev launch after the pick -- run, prefill /
+    // extend / score / finish_prefill with logits -- which leaves record [position of the token just placed]: that token (chosen, or forced: echo
+    // log-probabilities), its raw logit, the row's log-sum-exp and the top_n (id, logit) pairs; a prompt of n tokens with logits leaves record n.
+    // Steps without logits, run_reference and trace_step record nothing.  Switching on allocates max_pos records (cleared to 0xFF bytes: token
+    // -1 = never written) and the kernel's scratch, once.  Switching on or off, or another top_n, drops the captured graphs as set_sampling does;
+    // off, the step is launch for launch what it was.  reset() clears the records, rewind() leaves them, fork() clears those of every destination
+    // that has them (a destination's log-probabilities start at the fork point; the source is untouched).
+    int set_logprobs(int top_n);
+    int logprob_top_n() const { return lp_top_n_; }
+    // Synchronises and copies records [first, first + n) to the host.  Refuses a range outside [0, max_pos) and a decoder with logprobs off.
+    int logprobs(int first, int n, bitnet_hip_logprob_record *out);
+    // what a batch binds for this member: its bitnet_hip_logprob_args, an empty entry (null records) with logprobs off
+    void logprob_entry(bitnet_hip_logprob_args *out) const;
     // Put `n` forced tokens at positions [pos, pos+n) of the history (the prompt).
     int feed(const int32_t *tokens, int n);
     // Run `n` single-token steps (T:1482-1504 body each).  with_logits=false skips the
@@ -265,7 +280,7 @@ class Decoder {
     size_t pf_past_ = 0;  // cached positions under the prompt forward in flight (0: fresh sequence)
     void release_layer(Layer &L);  // frees the layer's handles, subtracts their bytes, drops the captured graphs
     void drop_graphs();
-    int pick_token(void *stream);  // final norm + tied logits + the next token (greedy argmax or the sampler)
+    int pick_token(void *stream, bool record = true);  // final norm + tied logits + the next token (greedy argmax or the sampler) [+ its logprob record]
     int adopt_projections(Layer &L, bitnet_hip_weights_t h[7]);
     std::vector<Layer> layers_;
     void *embed_ = nullptr;
@@ -283,6 +298,9 @@ class Decoder {
     int32_t *pos_ = nullptr, *n_forced_ = nullptr, *history_ = nullptr, *token_ = nullptr;
     bitnet_hip_sampler *sampler_ = nullptr;
     bool sampling_ = false;
+    int lp_top_n_ = -1;  // set_logprobs
+    bitnet_hip_logprob_record *lp_records_ = nullptr;  // [max_pos]
+    void *lp_scratch_ = nullptr;
     int host_forced_ = 0;
     // fork: device pointer tables, allocated at the first fork FROM this decoder: [0] its own K caches [n_layers], [1] its V caches (built once),
     // then the destinations' K [8][n_layers] and V [8][n_layers] (uploaded per call)
@@ -353,6 +371,8 @@ int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *fin
 int bitnet_host_reset(void *d);
 int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg);  // NULL = greedy
 int bitnet_host_sampling_draws(void *d, uint64_t *out);
+int bitnet_host_set_logprobs(void *d, int top_n);                             // Decoder::set_logprobs: -1 off, 0..20 on
+int bitnet_host_logprobs(void *d, int first, int n, void *records_out);       // Decoder::logprobs: n bitnet_hip_logprob_record
 int bitnet_host_feed(void *d, const int32_t *tokens, int n);
 int bitnet_host_run(void *d, int n, int with_logits, int use_graph, float *elapsed_ms);
 int bitnet_host_run_reference(void *d, int n, int with_logits);

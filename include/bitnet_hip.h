@@ -717,6 +717,50 @@ int bitnet_hip_sample_batch_set(bitnet_hip_sample_batch *table, size_t slot, bit
                                 int32_t *token_dev, int32_t *pos_dev, int32_t *history_dev, const int32_t *n_forced_dev);
 int bitnet_hip_sample_batch_dev(bitnet_hip_sample_batch *table, void *stream);
 
+/* ---- per-token log-probabilities and top-N logits: the generation path's logits tap -------------------------------
+ * The reference's GenerationConfig::{logits_tap_steps, logits_topk, logits_cb} (crates/bitnet-inference/src/config.rs:87-93), called after
+ * sampling with (step, topk [(id, raw logit)], chosen) (crates/bitnet-inference/src/engine.rs:1182-1210), and the CLI's
+ * --dump-logit-steps N --logits-topk K `LogitStep` records (crates/bitnet-cli/src/main.rs:1337-1373) -- on the device, after the pick, with
+ * no host round trip per token.  One launch AFTER bitnet_hip_logits_f16_dev's greedy pick or bitnet_hip_sample_dev: by then *pos_dev is
+ * p + 1 and history_dev[p + 1] holds the chosen (or forced) token.  With q = *pos_dev and t = history_dev[q] the launch writes
+ * records_dev[q] when 0 <= q < capacity, and nothing otherwise (its hand-over is re-armed either way).  l = logits_dev, the raw f32 row
+ * the sampler reads: no penalty, no temperature (the reference passes &logits to its tap).
+ *   top list: the CLI's rule (main.rs:1344-1350): finite entries first, by descending logit (-0.0 == +0.0), then ascending id; every
+ *     non-finite entry (NaN, +inf, -inf) after every finite one, by ascending id.  Comparisons only: the list is exact.  Entries
+ *     j >= n_top of the record keep their bytes.
+ *   lse: M = max_i l_i with NaN read as -inf; lse = M + log(sum_i exp(l_i - M)); +inf if M is +inf, -inf if M is -inf.  Deterministic:
+ *     per-workgroup (max, sum) partials are merged in workgroup-index order, and the partition depends on vocab alone, so repeated
+ *     launches and the two entry points give the same bits.
+ *   log-probability of the token: logit - lse, formed by the host in f32.
+ * scratch_dev: bitnet_hip_logprob_scratch_bytes(vocab) bytes (0 for a vocabulary this library refuses: 0 or > 2^20), this entry's own,
+ * 16-byte aligned, zeroed once by the caller; history_dev holds at least `capacity` entries.
+ * bitnet_hip_logprob_dev: one sequence, args on the host.  bitnet_hip_logprob_batch_dev: n_slots = 1..BITNET_HIP_BATCH_MAX entries read from
+ * a DEVICE table by the kernel (a captured graph follows later writes to it); an entry with records_dev == NULL is empty: nothing is read
+ * or written for it; top_n beyond the maximum is clamped.  Per bound slot the record and the re-armed scratch are bit for bit what
+ * bitnet_hip_logprob_dev on that entry alone leaves (one kernel body serves both).  Both are exactly one kernel launch, asynchronous and
+ * capture-safe (no allocation, copy or synchronisation); the batched entry launches even when every entry is empty.  INVALID_ARGUMENT
+ * before anything launches and before the GPU is touched: NULL args_host / table_dev; vocab 0 or > 2^20; n_slots outside
+ * 1..BITNET_HIP_BATCH_MAX; for bitnet_hip_logprob_dev top_n > BITNET_HIP_LOGPROB_TOP_MAX, or a NULL logits_dev, pos_dev, history_dev or
+ * scratch_dev together with a non-NULL records_dev. */
+#define BITNET_HIP_LOGPROB_TOP_MAX 20
+typedef struct bitnet_hip_logprob_record {
+    int32_t token;      /* history[q]; -1 = never written (records are cleared to 0xFF bytes) */
+    int32_t n_top;      /* min(top_n, vocab) */
+    float   logit;      /* raw l[token], NaN read as -inf; NaN if token is outside [0, vocab) */
+    float   lse;        /* log sum_i exp(l_i), NaN read as -inf */
+    int32_t top_id[BITNET_HIP_LOGPROB_TOP_MAX];
+    float   top_logit[BITNET_HIP_LOGPROB_TOP_MAX];   /* raw bits of l[top_id[j]] */
+} bitnet_hip_logprob_record;
+typedef struct bitnet_hip_logprob_args {
+    const float *logits_dev; const int32_t *pos_dev; const int32_t *history_dev;
+    bitnet_hip_logprob_record *records_dev;   /* NULL: empty entry */
+    void *scratch_dev;                        /* bitnet_hip_logprob_scratch_bytes(vocab), this entry's own, zeroed once by the caller */
+    uint32_t capacity, top_n;                 /* records in records_dev; 0..BITNET_HIP_LOGPROB_TOP_MAX */
+} bitnet_hip_logprob_args;
+size_t bitnet_hip_logprob_scratch_bytes(size_t vocab);
+int bitnet_hip_logprob_dev(const bitnet_hip_logprob_args *args_host, size_t vocab, void *stream);
+int bitnet_hip_logprob_batch_dev(const bitnet_hip_logprob_args *table_dev, size_t n_slots, size_t vocab, void *stream);
+
 /* ---- measurement aid -------------------------------------------------------
  * Measured HBM read ceiling of the device (quote the roofline fraction against the vendor
  * figure AND a measured stream ceiling): a read-only streaming kernel (non-temporal 16-byte loads, one

@@ -176,6 +176,12 @@ class HipLib:
         L.bitnet_hip_attention_extend_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz]
         L.bitnet_hip_attention_extend_workspace_bytes.restype = _sz
         L.bitnet_hip_attention_extend_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, C.c_int, _vp]
+        L.bitnet_hip_attention_packed_row_align.argtypes = [_sz, _sz]
+        L.bitnet_hip_attention_packed_row_align.restype = _sz
+        L.bitnet_hip_attention_packed_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.bitnet_hip_attention_packed_workspace_bytes.restype = _sz
+        L.bitnet_hip_attention_packed_dev.argtypes = [_vp, _sz, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _sz, _sz, _sz, _sz,
+                                                      _vp, _sz, _vp, C.c_int, _vp]
         L.bitnet_hip_attention_prefill_sharded_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz]
         L.bitnet_hip_attention_prefill_sharded_workspace_bytes.restype = _sz
         L.bitnet_hip_attention_prefill_sharded_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp]
@@ -451,6 +457,47 @@ class HipLib:
         self._check(self.c.bitnet_hip_attention_extend_dev(_optr(qkv), _optr(rope_sin), _optr(rope_cos), _optr(kcache), _optr(vcache), n_heads, n_kv,
                                                            head_dim, max_pos, past_len, seq_len, _optr(workspace), workspace_bytes, _optr(out), flags,
                                                            _vp(stream)))
+
+    def attention_packed_row_align(self, n_heads: int, n_kv: int) -> int:
+        """Row alignment of a segment's first row in attention_packed_dev: the attention workgroup's query tile, 64 rows for an even
+        n_heads / n_kv, 128 for an odd one; 0 for head counts it refuses."""
+        return int(self.c.bitnet_hip_attention_packed_row_align(n_heads, n_kv))
+
+    @staticmethod
+    def _i32_table(a):
+        """host int32 array (or None) -> (keep-alive array, ctypes pointer)"""
+        if a is None:
+            return None, None
+        t = _np(a, np.int32)
+        return t, t.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def attention_packed_workspace_bytes(self, n_heads: int, n_kv: int, n_rows: int, past, len_) -> int:
+        """Workspace of attention_packed_dev for segments (past[s], len_[s]) inside n_rows packed rows; 0 for sizes it refuses,
+        non-decreasing in every past[s] and len_[s]."""
+        pa, pp = self._i32_table(past)
+        la, lp = self._i32_table(len_)
+        n_seq = 0 if pa is None else pa.size
+        return int(self.c.bitnet_hip_attention_packed_workspace_bytes(n_heads, n_kv, n_rows, n_seq, pp, lp))
+
+    def attention_packed_dev(self, qkv, n_rows, rope_sin, rope_cos, row0, len_, past, kcaches, vcaches, n_heads, n_kv, head_dim, max_pos, workspace,
+                             workspace_bytes, out, flags: int = 0, stream: int = 0, n_seq: int | None = None) -> None:
+        """attention_extend_dev for SEVERAL sequences in one prep + one attention launch: segment s owns packed rows row0[s] .. row0[s] +
+        len_[s] - 1 (row0 a multiple of attention_packed_row_align), its tokens sit at positions past[s] .. over kcaches[s] / vcaches[s]
+        (tensors or raw device pointers), and its queries see its own keys only.  row0 / len_ / past are host arrays; rows outside every
+        segment are padding (finite outputs, no cache traffic).  flags: ATTN_CACHE_F16 (1) | ATTN_OUT_F16 (2)."""
+        ra, rp = self._i32_table(row0)
+        la, lp = self._i32_table(len_)
+        pa, pp = self._i32_table(past)
+
+        def table(caches):
+            if caches is None:
+                return None
+            vals = [None if c is None else (c if isinstance(c, int) else c.data_ptr()) for c in caches]
+            return (_vp * max(len(vals), 1))(*vals)
+
+        n = (ra.size if ra is not None else 0) if n_seq is None else n_seq
+        self._check(self.c.bitnet_hip_attention_packed_dev(_optr(qkv), n_rows, _optr(rope_sin), _optr(rope_cos), n, rp, lp, pp, table(kcaches), table(vcaches),
+                                                           n_heads, n_kv, head_dim, max_pos, _optr(workspace), workspace_bytes, _optr(out), flags, _vp(stream)))
 
     def attention_prefill_sharded_workspace_bytes(self, n_heads: int, n_kv: int, n_q: int, n_ctx: int) -> int:
         return int(self.c.bitnet_hip_attention_prefill_sharded_workspace_bytes(n_heads, n_kv, n_q, n_ctx))
@@ -990,6 +1037,8 @@ class HostDecoder:
         L.bitnet_host_rewind.restype = C.c_int
         L.bitnet_host_fork.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]
         L.bitnet_host_fork.restype = C.c_int
+        L.bitnet_host_prefill_packed.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.bitnet_host_prefill_packed.restype = C.c_int
         L.bitnet_host_cached_prefix.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
         L.bitnet_host_cached_prefix.restype = C.c_int
         self.cfg = cfg
@@ -1181,6 +1230,26 @@ class HostDecoder:
         front of the new tokens to keep it in the context."""
         ms = C.c_float(0)
         self._check(self.c.bitnet_host_extend(self.h, n, int(with_logits), digits, C.byref(ms)))
+        return ms.value
+
+    def prefill_packed(self, members, ns, with_logits: bool = True, digits: int = 2) -> float:
+        """ONE prompt forward for up to 64 sequences (this decoder's owner or borrowers of the same weights, the same cache type), member i at
+        its own position p_i -- fresh or live -- with ns[i] fed tokens to take in: history tokens [p_i, p_i + ns[i]) of all members go
+        through every layer as the rows of one matrix, the attention keeps every member to its own keys and caches, and every member ends as
+        its own extend(ns[i], with_logits, digits) would leave it (position p_i + ns[i]; with_logits picks its next token with its own
+        argmax or sampler, and its logprob record when on).  This decoder is the driver (its stream, its prompt buffers, its error text, its
+        saturation_fallbacks()): `members` starts with it, or it is put in front.  Members may sit in HostBatch slots; run(), extend(),
+        fork_into() and the batch step go on afterwards.  Carry-on rule as for extend: after a with-logits pack every member's picked token
+        sits unconsumed at history[position()] and feed() writes onto that slot -- feed it again in front of the new tokens to keep it."""
+        members = list(members)
+        if not members or members[0] is not self:
+            members = [self] + members
+        ns = _np(ns, np.int32)
+        if ns.size != len(members):
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, f"prefill_packed: {len(members)} members (the driver included), {ns.size} lengths")
+        arr = (C.c_void_p * len(members))(*[m.h if m is not None else None for m in members])
+        ms = C.c_float(0)
+        self._check(self.c.bitnet_host_prefill_packed(arr, ns.ctypes.data_as(C.POINTER(C.c_int32)), len(members), int(with_logits), digits, C.byref(ms)))
         return ms.value
 
     def rewind(self, n: int) -> None:

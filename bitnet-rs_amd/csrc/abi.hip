@@ -1398,6 +1398,62 @@ int bitnet_hip_attention_extend_dev(const float *qkv, const float *rope_sin, con
     BH_GUARD_END
 }
 
+size_t bitnet_hip_attention_packed_row_align(size_t n_heads, size_t n_kv_heads) {
+    if (n_heads == 0 || n_kv_heads == 0 || n_heads >= ((size_t)1 << 30) || n_heads % n_kv_heads != 0) return 0;
+    return (size_t)attn_packed_row_align((int)n_heads, (int)n_kv_heads);
+}
+
+size_t bitnet_hip_attention_packed_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t n_rows, size_t n_seq, const int32_t *past, const int32_t *len) {
+    const size_t lim = (size_t)1 << 24;
+    if (n_heads == 0 || n_kv_heads == 0 || n_heads >= lim || n_heads % n_kv_heads != 0 || n_rows == 0 || n_rows >= lim || n_seq == 0 || n_seq > BITNET_HIP_PACK_MAX ||
+        !past || !len)
+        return 0;
+    return attn_packed_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_rows, (int)n_seq, past, len);
+}
+
+int bitnet_hip_attention_packed_dev(const float *qkv, size_t n_rows, const float *rope_sin, const float *rope_cos, size_t n_seq, const int32_t *row0,
+                                    const int32_t *len, const int32_t *past, void *const *kcache, void *const *vcache, size_t n_heads, size_t n_kv_heads,
+                                    size_t head_dim, size_t max_pos, void *workspace, size_t workspace_bytes, void *out, int flags, void *stream) {
+    BH_GUARD_BEGIN
+    // every refusal comes before anything launches: the two kernels write wherever the table sends them
+    if (n_seq == 0 || n_seq > BITNET_HIP_PACK_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: n_seq %zu outside 1..%d", n_seq, BITNET_HIP_PACK_MAX);
+    if (!qkv || !rope_sin || !rope_cos || !row0 || !len || !past || !kcache || !vcache || !workspace || !out)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_packed_dev");
+    if (n_kv_heads == 0 || n_heads == 0 || n_heads % n_kv_heads != 0)  // T:215-220
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
+    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: head_dim %zu unsupported (128)", head_dim);
+    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: unknown flag bits 0x%x", flags);
+    const size_t align = bitnet_hip_attention_packed_row_align(n_heads, n_kv_heads);
+    if (align == 0 || n_rows == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: sizes out of range");
+    for (size_t s = 0; s < n_seq; ++s) {
+        if (!kcache[s] || !vcache[s]) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segment %zu has a null cache", s);
+        if (len[s] < 1) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segment %zu: len must be at least 1", s);
+        if (past[s] < 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segment %zu: negative past", s);
+        if ((size_t)past[s] + (size_t)len[s] > max_pos)
+            return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: segment %zu, past %d, len %d, max_pos %zu", s, past[s], len[s], max_pos);  // T:1190-1194
+        if (row0[s] < 0 || (size_t)row0[s] % align != 0)
+            return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segment %zu: row0 %d is not a multiple of the row alignment %zu", s, row0[s], align);
+        if ((size_t)row0[s] + (size_t)len[s] > n_rows)
+            return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segment %zu ends beyond n_rows %zu", s, n_rows);
+        for (size_t t = 0; t < s; ++t) {
+            if (row0[s] < row0[t] + len[t] && row0[t] < row0[s] + len[s])
+                return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segments %zu and %zu overlap", t, s);
+            if (kcache[s] == kcache[t] || vcache[s] == vcache[t] || kcache[s] == vcache[t] || vcache[s] == kcache[t])
+                return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segments %zu and %zu share a cache", t, s);
+        }
+        if (kcache[s] == vcache[s]) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segment %zu: one cache for k and v", s);
+    }
+    const size_t need = bitnet_hip_attention_packed_workspace_bytes(n_heads, n_kv_heads, n_rows, n_seq, past, len);
+    if (need == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: sizes out of range");
+    if (workspace_bytes < need) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
+    BH_HIP_TRY(launch_attn_packed(qkv, (int)n_rows, rope_sin, rope_cos, (int)n_seq, row0, len, past, kcache, vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim,
+                                  (int)max_pos, workspace, workspace_bytes, out, flags, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 int bitnet_hip_attention_prefill_gathered_dev(const float *q, size_t ld_q, const int32_t *q_block_pos, size_t n_q, const void *kv_gathered,
                                               size_t n_ctx, size_t world, int kv_is_f16, const float *rope_sin, const float *rope_cos,
                                               void *kcache, void *vcache, int cache_f16, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,

@@ -285,6 +285,11 @@ hipError_t launch_attn_prefill(const float *q, int ld_q, const int *q_block_pos,
 size_t attn_extend_workspace_bytes(int n_heads, int n_kv, int past, int seq);
 hipError_t launch_attn_extend(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, int n_heads, int n_kv,
                               int D, int max_pos, int past, int seq, void *workspace, size_t workspace_bytes, void *out, int flags, hipStream_t stream);
+int attn_packed_row_align(int n_heads, int n_kv);
+size_t attn_packed_workspace_bytes(int n_heads, int n_kv, int n_rows, int n_seq, const int *past, const int *len);
+hipError_t launch_attn_packed(const float *qkv, int n_rows, const float *rope_sin, const float *rope_cos, int n_seq, const int *row0, const int *len,
+                              const int *past, void *const *kcache, void *const *vcache, int n_heads, int n_kv, int D, int max_pos, void *workspace,
+                              size_t workspace_bytes, void *out, int flags, hipStream_t stream);
 hipError_t launch_pack_cols(const float *src, size_t ld, size_t col0, size_t ncols, size_t rows, void *dst, int f16, hipStream_t stream);
 hipError_t launch_stream_read(const void *buf, size_t bytes, unsigned *sink, hipStream_t stream);
 hipError_t launch_logits_f16(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab,

@@ -231,8 +231,12 @@ __device__ __forceinline__ float max_over_g(float v) {
     return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
 
-template <int HW, int NW, int NQ>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(PrefillArgs p) {
+// One body, two kernels: PK = false is k_prefill_attn (one sequence: block positions from q_block_pos, keys 0 .. p.T - 1 of the one image);
+// PK = true is k_prefill_attn_packed, whose 64-row query blocks belong to DIFFERENT sequences: block b reads its record q_rec[b] =
+// {absolute position of its first row, first key tile of its sequence inside the packed images, key count of its sequence, live rows}
+// once, here in the prologue, and everything below the prologue is the same code (see launch_attn_packed).
+template <int HW, int NW, int NQ, bool PK>
+__device__ __forceinline__ void prefill_attn_body(const PrefillArgs &p, const int4 *q_rec) {
     constexpr int QW = NW / HW, QG = 16 * QW * NQ;  // wave columns per workgroup, queries per workgroup
     static_assert(NW == 4, "tile staging deals 32 pieces to 4 waves");
     extern __shared__ __attribute__((aligned(16))) uint8_t kv_lds[];  // [2][K tile | V^T tile]
@@ -243,12 +247,16 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
     const int h = hg * HW + wave % HW, kvh = h / (p.n_heads / p.n_kv);  // HW divides the group: one KV head per workgroup
     const int qbase = qg * QG + (wave / HW) * 16 * NQ;            // first query row of this wave (16 NQ rows inside one 64-row block)
     const int blk64 = qbase >> 6;                                 // the 64-row block the wave's rows lie in
-    const int bpos = (p.q_block_pos ? p.q_block_pos[blk64 < (p.nq + kQB - 1) / kQB ? blk64 : 0] : blk64 * kQB) + (qbase & 63);
+    int4 rec = {0, 0, 0, 0};
+    if (PK) rec = q_rec[blk64];  // (every block up to nq_pad / 64 has a record)
+    const int bpos = (PK ? rec.x : p.q_block_pos ? p.q_block_pos[blk64 < (p.nq + kQB - 1) / kQB ? blk64 : 0] : blk64 * kQB) + (qbase & 63);
+    const int T = PK ? __builtin_amdgcn_readfirstlane(rec.z) : p.T;  // keys of this block's sequence
+    const int q_live = PK ? __builtin_amdgcn_readfirstlane(rec.w) - (qbase & 63) : 0;  // packed: rows of the wave that belong to a sequence (the rest is padding)
     if (tid == 0) s_last = 0;
     __syncthreads();
     {   // last key tile any query of the workgroup sees
         const int top = bpos + 16 * NQ - 1;
-        const int need = p.causal ? (top < p.T ? top : p.T - 1) / kQB : (p.T - 1) / kQB;
+        const int need = p.causal ? (top < T ? top : T - 1) / kQB : (T - 1) / kQB;
         if (lane == 0) atomicMax(&s_last, need);
     }
     __syncthreads();
@@ -276,7 +284,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
     }
     int qlim[NQ];  // highest visible key position of this lane's query in group q
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) qlim[q] = p.causal ? bpos + 16 * q + c : p.T - 1;
+    for (int q = 0; q < NQ; ++q) qlim[q] = p.causal ? bpos + 16 * q + c : T - 1;
     // Q^T operands: 8 consecutive dims per k-slot group, kept in registers for the whole block (filled below, behind the first tile requests)
     h8 qreg[NQ][4];
     v4f o[NQ][8];
@@ -289,9 +297,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
         l_run[q] = 0.0f;
     }
     // softmax in base 2; the scale is already in q (k_prefill_prep)
-    const int qmin = __builtin_amdgcn_readfirstlane(p.causal ? bpos : p.T - 1);  // lowest key limit of any query of this wave
-    const uint8_t *kbase = reinterpret_cast<const uint8_t *>(p.kh + (size_t)kvh * p.Tpad * kPD);
-    const uint8_t *vbase = reinterpret_cast<const uint8_t *>(p.vt + (size_t)kvh * kPD * p.Tpad);
+    const int qmin = __builtin_amdgcn_readfirstlane(p.causal ? bpos : T - 1);  // lowest key limit of any query of this wave
+    const size_t koff = PK ? (size_t)__builtin_amdgcn_readfirstlane(rec.y) : 0;  // packed: first key tile of the block's sequence in the images
+    const uint8_t *kbase = reinterpret_cast<const uint8_t *>(p.kh + (size_t)kvh * p.Tpad * kPD) + koff * kKTile;
+    const uint8_t *vbase = reinterpret_cast<const uint8_t *>(p.vt + (size_t)kvh * kPD * p.Tpad) + koff * (kQB * 2);
     // Tile staging by LDS-DMA: a K tile is 16 pieces of 1 KiB (4 keys), a V^T tile 16 pieces (8 dim rows x 128 B); wave w moves
     // pieces 4 w .. 4 w + 3 of each.  A lane fetches the 16-byte unit that belongs at ITS slot of the piece (the XOR swizzles
     // above), so the unpadded tiles read conflict-free.  Byte offsets from the tile's first byte (scalar base):
@@ -352,7 +361,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int row = qbase + 16 * q + c;
-            const bool live = row < p.nq;
+            const bool live = PK ? 16 * q + c < q_live : row < p.nq;
             const float *qp = p.q + (size_t)h * p.hs_q + (size_t)(live ? row : 0) * p.ld_q + 8 * g;
             float x[4][8];
 #pragma unroll
@@ -564,6 +573,15 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(Prefi
     }
 }
 
+template <int HW, int NW, int NQ>
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn(PrefillArgs p) {
+    prefill_attn_body<HW, NW, NQ, false>(p, nullptr);
+}
+template <int HW, int NW, int NQ>
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_prefill_attn_packed(PrefillArgs p, const int4 *q_rec) {
+    prefill_attn_body<HW, NW, NQ, true>(p, q_rec);
+}
+
 // out[row][head][:] = sum_s 2^(m_s - M) o_s / sum_s 2^(m_s - M) l_s over the key splits; 32 threads (4 dims each) per (row, head)
 __global__ __launch_bounds__(256) void k_prefill_merge(PrefillArgs p) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -607,19 +625,24 @@ static int attn_ksplit(int n_heads, int n_kv, int nq_pad, int T) {
     return s < 1 ? 1 : s > 8 ? 8 : s;
 }
 
-static hipError_t launch_attn_kernel(const PrefillArgs &p, hipStream_t stream) {
+// q_rec: the per-block records of a packed call (launch_attn_packed): the same grid on k_prefill_attn_packed, never key-split
+static hipError_t launch_attn_kernel(const PrefillArgs &p, hipStream_t stream, const int4 *q_rec = nullptr) {
     const int group = p.n_heads / p.n_kv;
     const unsigned z = (unsigned)p.ksplit;
     void (*ak)(PrefillArgs);
+    void (*akp)(PrefillArgs, const int4 *);
     dim3 grid;
     if (group % 4 == 0) {  // 4 waves = the 4 heads of a KV head x 32 queries each; two such workgroups per CU
         ak = k_prefill_attn<4, 4, 2>;
+        akp = k_prefill_attn_packed<4, 4, 2>;
         grid = dim3((unsigned)(p.nq_pad / 32), (unsigned)(p.n_heads / 4), z);
     } else if (group % 2 == 0) {  // 2 heads x 2 wave columns x 32 queries
         ak = k_prefill_attn<2, 4, 2>;
+        akp = k_prefill_attn_packed<2, 4, 2>;
         grid = dim3((unsigned)(p.nq_pad / 64), (unsigned)(p.n_heads / 2), z);
     } else {
         ak = k_prefill_attn<1, 4, 2>;
+        akp = k_prefill_attn_packed<1, 4, 2>;
         grid = dim3((unsigned)(p.nq_pad / 128), (unsigned)p.n_heads, z);
     }
     // Workgroups are dispatched in linear id order (x fastest).  With the query groups in x, head group 0's blocks all start before head
@@ -630,6 +653,13 @@ static hipError_t launch_attn_kernel(const PrefillArgs &p, hipStream_t stream) {
     PrefillArgs pa = p;
     pa.head_fast = head_fast ? 1 : 0;
     if (head_fast) grid = dim3(grid.y, grid.x, grid.z);
+    if (q_rec) {
+        if (p.ksplit != 1) return hipErrorInvalidValue;
+        const hipError_t er = raise_dynamic_lds(akp, 2 * kKVBuf);
+        if (er != hipSuccess) return er;
+        hipLaunchKernelGGL(akp, grid, dim3(256), 2 * kKVBuf, stream, pa, q_rec);
+        return hipGetLastError();
+    }
     const hipError_t er = raise_dynamic_lds(ak, 2 * kKVBuf);  // two tile buffers = 64 KiB of dynamic LDS (+ a static word)
     if (er != hipSuccess) return er;
     hipLaunchKernelGGL(ak, grid, dim3(256), 2 * kKVBuf, stream, pa);
@@ -740,15 +770,14 @@ struct ExtendPrepArgs {
     int n_qblocks;
 };
 
-__global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
+// One 64-position tile of one sequence: t0 = its first position (cache side), img_t0 = its first position inside the f16 images (the same
+// for k_extend_prep; a packed image holds several sequences' tiles one after the other, p.Tpad = all of them).
+__device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float (*tile)[kPD + 4], int t0, int img_t0) {
     // every global access is 16 bytes wide (8 for f16) and contiguous along the fastest index of its tensor, as in k_prefill_prep;
     // only the 4-position (f16: 2-position) groups that straddle `past` or T fall back to single elements
-    __shared__ __attribute__((aligned(16))) float tile[kQB][kPD + 4];
-    const int tid = threadIdx.x, t0 = blockIdx.x * kQB;
+    const int tid = threadIdx.x;
     const bool is_k = (int)blockIdx.y < p.n_kv;
     const int kvh = is_k ? (int)blockIdx.y : (int)blockIdx.y - p.n_kv;
-    if (blockIdx.x == 0 && blockIdx.y == 0)
-        for (int b = tid; b < p.n_qblocks; b += 256) p.q_block_pos[b] = p.past + kQB * b;
     const int dp = p.past - t0, dl = p.T - t0;
     const int n_past = dp < 0 ? 0 : dp > kQB ? kQB : dp;  // tile rows [0, n_past) come from the cache,
     const int n_live = dl > kQB ? kQB : dl;               // [n_past, n_live) from the new rows, [n_live, 64) are zeros
@@ -864,7 +893,7 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
     }
     // ---- the f16 images of the whole tile, in k_prefill_prep's order ----
     if (is_k) {
-        _Float16 *dst = p.kh + ((size_t)kvh * p.Tpad + t0) * kPD;
+        _Float16 *dst = p.kh + ((size_t)kvh * p.Tpad + img_t0) * kPD;
         for (int i = 0; i < 8; ++i) {
             const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
             const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
@@ -877,9 +906,16 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
             const int idx = tid + 256 * i, d = idx >> 4, t4 = idx & 15, tok = t4 * 4;
             const int slot = 32 * (t4 >> 3) + 8 * (t4 & 3) + 4 * ((t4 >> 2) & 1);
             const h4 h = {(_Float16)tile[tok][d], (_Float16)tile[tok + 1][d], (_Float16)tile[tok + 2][d], (_Float16)tile[tok + 3][d]};
-            *reinterpret_cast<h4 *>(vt + (size_t)d * p.Tpad + t0 + slot) = h;
+            *reinterpret_cast<h4 *>(vt + (size_t)d * p.Tpad + img_t0 + slot) = h;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
+    __shared__ __attribute__((aligned(16))) float tile[kQB][kPD + 4];
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int b = threadIdx.x; b < p.n_qblocks; b += 256) p.q_block_pos[b] = p.past + kQB * b;
+    extend_prep_tile(p, tile, blockIdx.x * kQB, blockIdx.x * kQB);
 }
 
 // A bound on attn_prefill_workspace_bytes(n_heads, n_kv, nq', T') over all nq' <= nq, T' <= T (the key split's partials vanish once the
@@ -966,6 +1002,203 @@ hipError_t launch_attn_extend(const float *qkv, const float *rope_sin, const flo
     // misaligned query rows: the f16 query image of k_prefill_prep (its query slabs alone), positions from the array filled above
     if (!p.q_in_kernel) hipLaunchKernelGGL(k_prefill_prep, dim3((unsigned)(p.nq_pad / kQB), (unsigned)n_heads), dim3(256), 0, stream, p);
     return launch_attn_kernel(p, stream);
+}
+
+// ---- SEVERAL sequences' new tokens in one pair of launches (the prompt side of the batched decode step) ----
+// The packed rows [n_rows, (heads + 2 kv) * 128] hold up to kPackMax segments; segment s = one sequence: rows row0[s] .. row0[s] + len[s] - 1
+// are its len[s] new tokens at positions past[s] .., over ITS caches.  row0 is a multiple of the attention workgroup's query tile
+// (attn_packed_row_align: a workgroup stages ONE set of key tiles for all its waves, so it must lie inside one segment); rows between
+// segments are padding.  Per segment the arithmetic is launch_attn_extend's:
+//
+//   k_packed_prep  grid (all segments' 64-position tiles, 2 kv): workgroup x finds its segment in the table (kernel arguments: the call
+//                  stays asynchronous, there is no upload) and runs k_extend_prep's tile body on that segment's caches and rows; the f16
+//                  images are ONE pair [kv][sum Tpad_s][128] / [kv][128][sum Tpad_s], segment s's tiles at tile offset sum_{s' < s} Tpad_s' / 64
+//                  (table order).  Its first workgroup also writes the per-block records.
+//   q_rec[b]       {position of the block's first row, tile offset of its segment, key count past + len of its segment, live rows}, one
+//                  int4 per 64-row block up to nq_pad / 64.  A padding block behind a segment's end inside the same workgroup tile (odd
+//                  groups: 128-row tiles) carries that segment's offset and 0 live rows; a tile no segment starts in reads tile 0 with one key.
+//                  Rows that are not live multiply zeros (finite outputs, no cache traffic).
+//   k_prefill_attn_packed  the attention body with position, key count and image offset from q_rec[block] instead of q_block_pos / p.T.
+//                  No key split: a packed call exists because it has many query blocks.
+constexpr int kPackMax = 64;  // BITNET_HIP_PACK_MAX
+struct PackedPrepArgs {
+    ExtendPrepArgs e;  // what all segments share (k_new / v_new: packed row 0; Tpad: all segments' tiles); past, T and the caches are per segment
+    int4 *q_rec;
+    int n_qblocks, n_seq, align_blocks;  // 64-row blocks up to nq_pad, segments, blocks per attention workgroup tile (1 or 2)
+    int row0[kPackMax], len[kPackMax], past[kPackMax];
+    void *kcache[kPackMax], *vcache[kPackMax];
+};
+
+__global__ __launch_bounds__(256) void k_packed_prep(PackedPrepArgs a) {
+    __shared__ __attribute__((aligned(16))) float tile[kQB][kPD + 4];
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
+        for (int b = threadIdx.x; b < a.n_qblocks; b += 256) {
+            const int g0 = b / a.align_blocks * a.align_blocks;  // first block of the workgroup tile: a segment starts there or the tile is padding
+            int4 r = {0, 0, 1, 0};
+            int off = 0;
+            for (int s = 0; s < a.n_seq; ++s) {
+                const int T = a.past[s] + a.len[s], end = a.row0[s] + a.len[s];
+                if (g0 * kQB >= a.row0[s] && g0 * kQB < end) {
+                    const int live = end - b * kQB;
+                    r = int4{a.past[s] + b * kQB - a.row0[s], off, T, live < 0 ? 0 : live > kQB ? kQB : live};
+                }
+                off += (T + kQB - 1) / kQB;
+            }
+            a.q_rec[b] = r;
+        }
+    }
+    int s = 0, off = 0;
+    for (; s < a.n_seq; ++s) {
+        const int nt = (a.past[s] + a.len[s] + kQB - 1) / kQB;
+        if ((int)blockIdx.x < off + nt) break;
+        off += nt;
+    }
+    if (s >= a.n_seq) return;  // (the grid is exactly the tiles of the table)
+    ExtendPrepArgs e = a.e;
+    e.k_new += (size_t)a.row0[s] * e.ld;
+    e.v_new += (size_t)a.row0[s] * e.ld;
+    e.kcache = a.kcache[s];
+    e.vcache = a.vcache[s];
+    e.past = a.past[s];
+    e.T = a.past[s] + a.len[s];
+    extend_prep_tile(e, tile, ((int)blockIdx.x - off) * kQB, (int)blockIdx.x * kQB);
+}
+
+// the f16 query image of a packed call whose rows are not 16-byte aligned (k_prefill_prep's query slabs with the block's position and live
+// row count from its record): grid (nq_pad / 64, heads)
+__global__ __launch_bounds__(256) void k_packed_qprep(PrefillArgs p, const int4 *q_rec) {
+    __shared__ __attribute__((aligned(16))) float tile[kQB][kPD + 4];
+    const int h = blockIdx.y, t0 = blockIdx.x * kQB, tid = threadIdx.x;
+    const int4 r = q_rec[blockIdx.x];
+    const float *src = p.q + (size_t)h * p.hs_q;
+    for (int i = 0; i < 8; ++i) {
+        const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
+        float4 v = {0.f, 0.f, 0.f, 0.f};
+        if (tok < r.w) {
+            const float *e = src + (size_t)(t0 + tok) * p.ld_q + d;
+            v = float4{e[0], e[1], e[2], e[3]};
+        }
+        *reinterpret_cast<float4 *>(&tile[tok][d]) = v;
+    }
+    __syncthreads();
+    for (int i = 0; i < 4; ++i) {  // split-half RoPE, the arithmetic of k_prefill_prep
+        const int idx = tid + 256 * i, tok = idx >> 4, j = (idx & 15) * 4;
+        const int pos = tok < r.w ? r.x + tok : 0;
+        const float4 s = *reinterpret_cast<const float4 *>(p.rope_sin + (size_t)pos * 64 + j), c = *reinterpret_cast<const float4 *>(p.rope_cos + (size_t)pos * 64 + j);
+        const float4 x0 = *reinterpret_cast<const float4 *>(&tile[tok][j]), x1 = *reinterpret_cast<const float4 *>(&tile[tok][64 + j]);
+        *reinterpret_cast<float4 *>(&tile[tok][j]) = float4{x0.x * c.x - x1.x * s.x, x0.y * c.y - x1.y * s.y, x0.z * c.z - x1.z * s.z, x0.w * c.w - x1.w * s.w};
+        *reinterpret_cast<float4 *>(&tile[tok][64 + j]) = float4{x0.x * s.x + x1.x * c.x, x0.y * s.y + x1.y * c.y, x0.z * s.z + x1.z * c.z, x0.w * s.w + x1.w * c.w};
+    }
+    __syncthreads();
+    const float qmul = 1.4426950408889634f * p.scale;
+    _Float16 *dst = p.qh + ((size_t)h * p.nq_pad + t0) * kPD;
+    for (int i = 0; i < 8; ++i) {
+        const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
+        const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
+        *reinterpret_cast<h4 *>(dst + (size_t)tok * kPD + d) = (h4){(_Float16)(v.x * qmul), (_Float16)(v.y * qmul), (_Float16)(v.z * qmul), (_Float16)(v.w * qmul)};
+    }
+}
+
+int attn_packed_row_align(int n_heads, int n_kv) {
+    if (n_heads <= 0 || n_kv <= 0 || n_heads % n_kv != 0) return 0;
+    return (n_heads / n_kv) % 2 == 0 ? 64 : 128;  // the query tile of k_prefill_attn<4,4,2> / <2,4,2>, of <1,4,2> (launch_attn_kernel)
+}
+
+// all segments' key tiles, or 0 when a size is out of range (the images' 32-bit byte offsets hold 2^24 positions)
+static size_t packed_tiles(int n_seq, const int *past, const int *len) {
+    if (n_seq < 1 || n_seq > kPackMax || !past || !len) return 0;
+    size_t tiles = 0;
+    for (int s = 0; s < n_seq; ++s) {
+        if (past[s] < 0 || len[s] < 1 || (size_t)past[s] + (size_t)len[s] >= ((size_t)1 << 24)) return 0;
+        tiles += ((size_t)past[s] + (size_t)len[s] + kQB - 1) / kQB;
+    }
+    return tiles * kQB < ((size_t)1 << 24) ? tiles : 0;
+}
+// q image + k / v^T images of all tiles + the records: a sum of terms that each grow with past[s] and len[s]
+size_t attn_packed_workspace_bytes(int n_heads, int n_kv, int n_rows, int n_seq, const int *past, const int *len) {
+    const size_t tiles = packed_tiles(n_seq, past, len);
+    if (n_heads <= 0 || n_kv <= 0 || n_heads % n_kv != 0 || n_rows < 1 || n_rows >= (1 << 24) || tiles == 0) return 0;
+    const size_t qpad = div_ceil((size_t)n_rows, kQPad) * kQPad;
+    return attn_f16_bytes(n_heads, n_kv, qpad, tiles * kQB) + div_ceil(qpad / kQB * sizeof(int4), 256) * 256 + 256;
+}
+
+hipError_t launch_attn_packed(const float *qkv, int n_rows, const float *rope_sin, const float *rope_cos, int n_seq, const int *row0, const int *len,
+                              const int *past, void *const *kcache, void *const *vcache, int n_heads, int n_kv, int D, int max_pos, void *workspace,
+                              size_t workspace_bytes, void *out, int flags, hipStream_t stream) {
+    const int align = attn_packed_row_align(n_heads, n_kv);
+    const size_t need = attn_packed_workspace_bytes(n_heads, n_kv, n_rows, n_seq, past, len);
+    if (D != kPD || align == 0 || need == 0 || !row0 || !kcache || !vcache || !workspace || workspace_bytes < need) return hipErrorInvalidValue;
+    for (int s = 0; s < n_seq; ++s)  // every write of the two kernels stays inside its segment's rows and cache slots (the ABI also refuses overlaps)
+        if (row0[s] < 0 || row0[s] % align != 0 || (size_t)row0[s] + (size_t)len[s] > (size_t)n_rows || (size_t)past[s] + (size_t)len[s] > (size_t)max_pos || !kcache[s] || !vcache[s])
+            return hipErrorInvalidValue;
+    const int ld = (n_heads + 2 * n_kv) * kPD;
+    const size_t tiles = packed_tiles(n_seq, past, len);
+    PrefillArgs p;
+    p.q = qkv;
+    p.k = qkv + (size_t)n_heads * kPD;
+    p.v = p.k + (size_t)n_kv * kPD;
+    p.zz_world = p.zz_chunk = p.kv_f16 = 0;
+    p.cache_f16 = flags & 1;
+    p.out_f16 = (flags >> 1) & 1;
+    p.ld_q = p.ld_kv = ld;
+    p.hs_q = p.hs_kv = kPD;
+    p.out_hs = kPD;
+    p.out_ld = n_heads * kPD;
+    p.rope = 1;
+    p.causal = 1;
+    p.scale = 1.0f / sqrtf((float)kPD);
+    p.q_block_pos = nullptr;
+    p.nq = n_rows;
+    p.nq_pad = (int)(div_ceil((size_t)n_rows, kQPad) * kQPad);
+    p.rope_sin = rope_sin;
+    p.rope_cos = rope_cos;
+    p.kcache = p.vcache = nullptr;  // per segment: PackedPrepArgs
+    p.n_heads = n_heads;
+    p.n_kv = n_kv;
+    p.max_pos = max_pos;
+    p.T = 0;                        // per block: q_rec
+    p.Tpad = (int)(tiles * kQB);
+    uint8_t *ws = reinterpret_cast<uint8_t *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    p.qh = reinterpret_cast<_Float16 *>(ws);
+    p.kh = p.qh + (size_t)n_heads * p.nq_pad * kPD;
+    p.vt = p.kh + (size_t)n_kv * p.Tpad * kPD;
+    p.out = static_cast<float *>(out);
+    p.ksplit = 1;
+    p.split_tiles = attn_split_tiles();
+    p.part_o = p.part_ml = nullptr;
+    int4 *q_rec = reinterpret_cast<int4 *>(ws + attn_f16_bytes(n_heads, n_kv, (size_t)p.nq_pad, (size_t)p.Tpad));
+    p.phase = 1;
+    p.slot0 = 0;
+    static const bool q_in_kernel = !(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL") && atoi(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL")) == 0);
+    p.q_in_kernel = q_in_kernel && ((uintptr_t)qkv & 15) == 0 ? 1 : 0;
+    PackedPrepArgs a;
+    a.e.k_new = p.k;
+    a.e.v_new = p.v;
+    a.e.ld = ld;
+    a.e.rope_sin = rope_sin;
+    a.e.rope_cos = rope_cos;
+    a.e.kcache = a.e.vcache = nullptr;
+    a.e.n_kv = n_kv;
+    a.e.max_pos = max_pos;
+    a.e.past = a.e.T = 0;
+    a.e.Tpad = p.Tpad;
+    a.e.cache_f16 = p.cache_f16;
+    a.e.kh = p.kh;
+    a.e.vt = p.vt;
+    a.e.q_block_pos = nullptr;
+    a.e.n_qblocks = 0;
+    a.q_rec = q_rec;
+    a.n_qblocks = p.nq_pad / kQB;
+    a.n_seq = n_seq;
+    a.align_blocks = align / kQB;
+    for (int s = 0; s < kPackMax; ++s) {
+        const bool on = s < n_seq;
+        a.row0[s] = on ? row0[s] : 0, a.len[s] = on ? len[s] : 0, a.past[s] = on ? past[s] : 0;
+        a.kcache[s] = on ? kcache[s] : nullptr, a.vcache[s] = on ? vcache[s] : nullptr;
+    }
+    hipLaunchKernelGGL(k_packed_prep, dim3((unsigned)tiles, (unsigned)(2 * n_kv)), dim3(256), 0, stream, a);
+    if (!p.q_in_kernel) hipLaunchKernelGGL(k_packed_qprep, dim3((unsigned)(p.nq_pad / kQB), (unsigned)n_heads), dim3(256), 0, stream, p, (const int4 *)q_rec);
+    return launch_attn_kernel(p, stream, q_rec);
 }
 
 // rows x [col0, col0 + ncols) of a row-major f32 matrix -> a compact [rows, ncols] buffer, f32 or f16: the k|v columns of the

@@ -13,7 +13,8 @@
 // maintained: last_hidden() (the residual stream lives in the batch's own buffers).
 //
 // Scheduling is set_slot(): members join and leave between steps (continuous batching); prompts go through the member's own prefill / extend
-// before it joins, or the member takes over a live sequence's prefix (Decoder::fork: one copy launch for up to 8 members).  The step is ONE linear chain on one stream (no forked capture branches), captured once per batch: slot changes rewrite the
+// before it joins -- or through ONE Decoder::prefill_packed for up to 64 members at once, each at its own position with its own number of new tokens
+// (members already sitting in slots included) -- or the member takes over a live sequence's prefix (Decoder::fork: one copy launch for up to 8 members).  The step is ONE linear chain on one stream (no forked capture branches), captured once per batch: slot changes rewrite the
 // device pointer tables the kernels read and need no re-capture.  Sampling goes the same way: a sampling member gets logits only from the head, and
 // ONE bitnet_hip_sample_batch_dev launch after it serves every sampling member through a device table of per-slot sampler state (an empty
 // entry: nothing to do), so a member switching its sampling on or off, a sampling member leaving or a greedy one taking its place re-captures

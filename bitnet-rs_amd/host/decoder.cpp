@@ -967,11 +967,18 @@ int Decoder::ensure_chain_buffers(size_t N) {
 
 // The attention of one layer of a prompt forward over the N rows in pf_qkv_ (all three forms of the layer loop come here): on a fresh
 // sequence the whole-prompt operator, on a live one (pf_past_ cached positions: Decoder::extend) the continuation operator, which reads the
-// past keys from the cache and takes every slot at or beyond pf_past_ from the new rows.
+// past keys from the cache and takes every slot at or beyond pf_past_ from the new rows; with a pack in flight (pack_members_) the packed operator.
 int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16) {
     const size_t NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, D = (size_t)c_.head_dim, MP = (size_t)c_.max_pos;
     const int flags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
-    if (pf_past_ > 0)
+    if (!pack_members_.empty()) {
+        // a pack in flight (prefill_packed): the N rows are several members' segments, each over its OWN caches of this layer
+        const size_t li = (size_t)(&L - layers_.data()), n = pack_members_.size();
+        void *kc[BITNET_HIP_PACK_MAX], *vc[BITNET_HIP_PACK_MAX];
+        for (size_t i = 0; i < n; ++i) kc[i] = pack_members_[i]->layers_[li].kcache, vc[i] = pack_members_[i]->layers_[li].vcache;
+        BCHK(bitnet_hip_attention_packed_dev(pf_qkv_, N, rope_sin_, rope_cos_, n, pack_row0_.data(), pack_len_.data(), pack_past_.data(), kc, vc, NH, NK, D, MP,
+                                             pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
+    } else if (pf_past_ > 0)
         BCHK(bitnet_hip_attention_extend_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, pf_past_, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
     else if (out_f16)
         BCHK(bitnet_hip_attention_prefill_flags_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
@@ -1197,10 +1204,151 @@ int Decoder::cached_prefix(const int32_t *tokens, int n) {
 // History tokens [p, p + n) through every layer as [n, *] matrices; p = the position (0: a fresh sequence and the whole-prompt attention;
 // otherwise the continuation operator over the p cached positions).  The callers hold the guards.
 int Decoder::prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms) {
-    const size_t H = c_.hidden, QD = (size_t)c_.n_heads * c_.head_dim, KD = (size_t)c_.n_kv_heads * c_.head_dim, F = c_.ffn;
+    const size_t H = c_.hidden;
     pf_past_ = (size_t)p;
     const size_t attn_need = p == 0 ? bitnet_hip_attention_prefill_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)n)
                                     : bitnet_hip_attention_extend_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)p, (size_t)n);
+    if (int rc = ensure_prompt_buffers(n, attn_need)) return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    Event ev0, ev1;
+    HCHK(hipEventCreate(&ev0.e));
+    HCHK(hipEventCreate(&ev1.e));
+    hipEvent_t e0 = ev0.e, e1 = ev1.e;
+    if (!force_scaled_) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this prompt
+    HCHK(hipEventRecord(e0, s));
+    const size_t N = (size_t)n;
+    BCHK(bitnet_hip_embed_f16_dev(embed_, history_, pos_, N, H, (size_t)c_.vocab, pf_x_, s));  // rows history[*pos_ + i], *pos_ == p
+    bool f16_rows = false;
+    if (int rc = prompt_layers(N, digits, &f16_rows)) return rc;
+    if (f16_rows) {
+        // f16 hand-over rows carry no row scale: a value beyond +-65504 (outlier channels x gamma: none in the synthetic models, possible in a real
+        // checkpoint) is clamped AND counted (bitnet_hip_f16_saturations).  A prompt that clamped anything is repeated on the digit planes --
+        // 30-bit fixed point behind a per-row power-of-two scale (digits = 4: a row whose outlier is 10^5 times its typical element still keeps 13 bits of
+        // those; the 2-digit and row-scaled f16 forms would flush them) -- before its logits are taken (ADVICE r04: no silent saturation).
+        HCHK(hipStreamSynchronize(s));
+        if (bitnet_hip_f16_saturations(1) > 0) {
+            force_scaled_ = true;
+            ++saturation_fallbacks_;
+            const int rc = prompt_forward(p, n, with_logits, 4, elapsed_ms);  // (a continuation rewrites only the new positions)
+            force_scaled_ = false;
+            return rc;
+        }
+    }
+    {
+        const int rc = finish_prefill(p + n, pf_x_ + (N - 1) * H, with_logits);
+        if (rc) return rc;
+    }
+    HCHK(hipEventRecord(e1, s));
+    HCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HCHK(hipEventElapsedTime(&ms, e0, e1));
+    if (elapsed_ms) *elapsed_ms = ms;
+    return 0;
+}
+
+int Decoder::prefill_packed(Decoder *const *members, const int *n, int n_members, bool with_logits, int digits, float *elapsed_ms) {
+    if (!members || !members[0] || members[0]->dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;  // no driver to carry the text
+    Decoder &drv = *members[0];
+    // every refusal comes before the first write
+    if (n_members < 1 || n_members > BITNET_HIP_PACK_MAX) return drv.fail_arg("prefill_packed: n_members must be 1..64");
+    if (!n) return drv.fail_arg("prefill_packed: null lengths");
+    std::vector<int32_t> past((size_t)n_members), len((size_t)n_members);
+    for (int i = 0; i < n_members; ++i) {
+        Decoder *d = members[i];
+        if (!d) return drv.fail_arg("prefill_packed: null member");
+        if (d->dead_) return drv.fail_arg("prefill_packed: dead member");
+        for (int j = 0; j < i; ++j)
+            if (members[j] == d) return drv.fail_arg("prefill_packed: a member is repeated");
+        if (d->root() != drv.root()) return drv.fail_arg("prefill_packed: all members must run on the same weights (an owner and its borrowers)");
+        if (d->kv_f16_ != drv.kv_f16_) return drv.fail_arg("prefill_packed: mixed KV cache types");
+        if (!d->embed_) return drv.fail_arg("model globals not set");
+    }
+    for (int i = 0; i < n_members; ++i) {
+        Decoder *d = members[i];
+        const int p = d->position();
+        if (p < 0) {
+            drv.err_ = d->err_;
+            return BITNET_HIP_ERR_GPU;
+        }
+        if (n[i] < 1) return drv.fail_arg("prefill_packed: every member takes at least 1 token");
+        if (n[i] > d->host_forced_ - p) return drv.fail_arg("prefill: feed() the prompt tokens first");  // (no p + n: a huge n must not wrap)
+        if (n[i] > drv.c_.max_pos - 1 - p) return drv.fail_arg("KV cache overflow");  // T:1190-1194
+        past[(size_t)i] = p, len[(size_t)i] = n[i];
+    }
+    return drv.packed_forward(members, past, len, with_logits, digits, elapsed_ms);
+}
+
+// The pack's rows: member i's n_i tokens from row row0_i on, row0 a multiple of the packed attention's row alignment; the rows between a member's
+// last token and the next member's first are padding (the embeddings of the history entries that follow -- fed, picked or zero: valid tokens --
+// so every matmul row is finite and of a token's scale; the attention neither reads nor caches them).  This decoder is the driver.
+int Decoder::packed_forward(Decoder *const *members, const std::vector<int32_t> &past, const std::vector<int32_t> &len, bool with_logits, int digits,
+                            float *elapsed_ms) {
+    const size_t H = c_.hidden, NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, M = past.size();
+    const size_t align = bitnet_hip_attention_packed_row_align(NH, NK);
+    if (align == 0) return fail_arg("prefill_packed: head counts out of range");
+    std::vector<int32_t> row0(M);
+    size_t N = 0;
+    for (size_t i = 0; i < M; ++i) {
+        row0[i] = (int32_t)((N + align - 1) / align * align);
+        N = (size_t)row0[i] + (size_t)len[i];
+    }
+    const size_t attn_need = bitnet_hip_attention_packed_workspace_bytes(NH, NK, N, M, past.data(), len.data());
+    if (attn_need == 0) return fail_arg("prefill_packed: sizes out of range");
+    if (int rc = ensure_prompt_buffers((int)N, attn_need)) return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    Event ev0, ev1;
+    HCHK(hipEventCreate(&ev0.e));
+    HCHK(hipEventCreate(&ev1.e));
+    if (!force_scaled_) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this pack
+    HCHK(hipEventRecord(ev0.e, s));
+    for (size_t i = 0; i < M; ++i) {
+        Decoder *d = members[i];
+        // rows history[p + r]: the member's tokens, then (up to the next member's first row) what follows them in its history, as far as the history goes
+        const size_t want = i + 1 < M ? (size_t)row0[i + 1] - (size_t)row0[i] : (size_t)len[i], have = (size_t)c_.max_pos + 2 - (size_t)past[i];
+        const size_t rows = want < have ? want : have;
+        float *dst = pf_x_ + (size_t)row0[i] * H;
+        BCHK(bitnet_hip_embed_f16_dev(d->embed_, d->history_, d->pos_, rows, H, (size_t)c_.vocab, dst, s));
+        for (size_t r = rows; r < want; ++r)  // (a member within a tile of the cache's end: its last token again)
+            HCHK(hipMemcpyAsync(dst + r * H, dst + ((size_t)len[i] - 1) * H, H * 4, hipMemcpyDeviceToDevice, s));
+    }
+    pack_members_.assign(members, members + M);
+    pack_row0_ = row0, pack_len_ = len, pack_past_ = past;
+    bool f16_rows = false;
+    const int rc_layers = prompt_layers(N, digits, &f16_rows);
+    pack_members_.clear();
+    if (rc_layers) return rc_layers;
+    if (f16_rows) {
+        // the saturation rule of prompt_forward: if any f16 hand-over value clamped, the WHOLE pack is repeated on the digit planes
+        HCHK(hipStreamSynchronize(s));
+        if (bitnet_hip_f16_saturations(1) > 0) {
+            force_scaled_ = true;
+            ++saturation_fallbacks_;
+            const int rc = packed_forward(members, past, len, with_logits, 4, elapsed_ms);
+            force_scaled_ = false;
+            return rc;
+        }
+    }
+    // the hand-over: every member's own head, pick and log-probability record on its own stream, from its last token's row
+    HCHK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < M; ++i) {
+        Decoder *d = members[i];
+        const int rc = d->finish_prefill(past[i] + len[i], pf_x_ + ((size_t)row0[i] + (size_t)len[i] - 1) * H, with_logits);
+        if (rc) {
+            if (d != this) err_ = d->err_;
+            return rc;
+        }
+    }
+    HCHK(hipEventRecord(ev1.e, s));
+    HCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
+    if (elapsed_ms) *elapsed_ms = ms;
+    return 0;
+}
+
+// The per-row buffers of a prompt forward of n rows and its attention workspace, grown on demand.
+int Decoder::ensure_prompt_buffers(int n, size_t attn_need) {
+    const size_t H = c_.hidden, QD = (size_t)c_.n_heads * c_.head_dim, KD = (size_t)c_.n_kv_heads * c_.head_dim, F = c_.ffn;
     if (n > pf_cap_ || attn_need > pf_attn_ws_bytes_) {
         const size_t N = (size_t)(n > pf_cap_ ? n : pf_cap_);  // the row buffers never shrink: a short turn at a long context keeps the prompt's
         const size_t attn_bytes = attn_need > pf_attn_ws_bytes_ ? attn_need : pf_attn_ws_bytes_;
@@ -1220,15 +1368,13 @@ int Decoder::prompt_forward(int p, int n, bool with_logits, int digits, float *e
         HCHK(hipMalloc(&pf_attn_ws_, pf_attn_ws_bytes_));
         pf_cap_ = (int)N;
     }
+    return 0;
+}
+
+// Every layer over the N rows in pf_x_ (embeddings in, residual stream of the last block out), on the matmul chain N rows and `digits` select;
+// *f16_rows: the chain handed f16 rows from kernel to kernel, so the caller owes the saturation check.  prompt_forward and prefill_packed.
+int Decoder::prompt_layers(size_t N, int digits, bool *f16_rows) {
     hipStream_t s = (hipStream_t)stream_;
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
-    hipEvent_t e0 = ev0.e, e1 = ev1.e;
-    if (!force_scaled_) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this prompt
-    HCHK(hipEventRecord(e0, s));
-    const size_t N = (size_t)n;
-    BCHK(bitnet_hip_embed_f16_dev(embed_, history_, pos_, N, H, (size_t)c_.vocab, pf_x_, s));  // rows history[*pos_ + i], *pos_ == p
     const bool chain = chain_applies(digits);
     if (chain) {
         const int rc = prefill_chain_layers(N);
@@ -1275,29 +1421,7 @@ int Decoder::prompt_forward(int p, int n, bool with_logits, int digits, float *e
                                          pf_gemm_ws_bytes_, s));
         BCHK(bitnet_hip_matmul_fused_dev(L.down, pf_h_, pf_x_, N, nullptr, 0.f, pf_x_, 0, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
     }
-    if (chain || qb || h16) {
-        // f16 hand-over rows carry no row scale: a value beyond +-65504 (outlier channels x gamma: none in the synthetic models, possible in a real
-        // checkpoint) is clamped AND counted (bitnet_hip_f16_saturations).  A prompt that clamped anything is repeated on the digit planes --
-        // 30-bit fixed point behind a per-row power-of-two scale (digits = 4: a row whose outlier is 10^5 times its typical element still keeps 13 bits of
-        // those; the 2-digit and row-scaled f16 forms would flush them) -- before its logits are taken (ADVICE r04: no silent saturation).
-        HCHK(hipStreamSynchronize(s));
-        if (bitnet_hip_f16_saturations(1) > 0) {
-            force_scaled_ = true;
-            ++saturation_fallbacks_;
-            const int rc = prompt_forward(p, n, with_logits, 4, elapsed_ms);  // (a continuation rewrites only the new positions)
-            force_scaled_ = false;
-            return rc;
-        }
-    }
-    {
-        const int rc = finish_prefill(p + n, pf_x_ + (N - 1) * H, with_logits);
-        if (rc) return rc;
-    }
-    HCHK(hipEventRecord(e1, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, e0, e1));
-    if (elapsed_ms) *elapsed_ms = ms;
+    *f16_rows = chain || qb || h16;
     return 0;
 }
 
@@ -1861,6 +1985,13 @@ int bitnet_host_prefill(void *d, int n, int with_logits, int digits, float *elap
 int bitnet_host_extend(void *d, int n, int with_logits, int digits, float *elapsed_ms) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
     return D->extend(n, with_logits != 0, digits, elapsed_ms);
+}
+int bitnet_host_prefill_packed(void *const *members, const int32_t *n, int n_members, int with_logits, int digits, float *elapsed_ms) {
+    if (!members || !live(members[0])) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    Decoder *ms[BITNET_HIP_PACK_MAX] = {};
+    ms[0] = live(members[0]);  // the driver carries the error text, whatever n_members is
+    for (int i = 1; i < n_members && i < BITNET_HIP_PACK_MAX; ++i) ms[i] = live(members[i]);  // a null or dead handle: refused as a null member
+    return Decoder::prefill_packed(ms, n, n_members, with_logits != 0, digits, elapsed_ms);
 }
 int bitnet_host_rewind(void *d, int n) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);

@@ -157,6 +157,22 @@ class Decoder {
     // the new tokens (feed([picked] + new), extend(1 + len(new))); one that does not (an end-of-turn marker it replaces) just feeds
     // the new tokens.
     int extend(int n, bool with_logits, int digits, float *elapsed_ms);
+    // PACKED prompt forward: ONE launch chain for n_members = 1..64 sequences, member i at its own position p_i (fresh or live) with its own n[i]
+    // new tokens -- the reference's forward over [B, T, H] (crates/bitnet-transformer/src/lib.rs:1437-1478) for sequences that are NOT in lock
+    // step, as BatchDecoder is for the decode step.  History tokens [p_i, p_i + n[i]) of every member go through every layer together as the
+    // rows of one matrix (member i's rows start at a multiple of bitnet_hip_attention_packed_row_align; the rows between are padding: valid
+    // tokens' embeddings that no cache sees); the matmuls are row-independent, and the attention (bitnet_hip_attention_packed_dev) lets each
+    // member's queries see its own keys only and fills each member's own caches.  Every member ends as its own extend(n[i], with_logits, digits)
+    // leaves it: position p_i + n[i], slots [p_i, p_i + n[i]) of every layer filled, with_logits picks the next token into history[p_i + n[i]]
+    // by the member's OWN argmax or sampler (with its log-probability record when its tap is on); run(), extend(), fork() and
+    // BatchDecoder::step() go on, and extend's carry-on rule holds.  "As extend": the same arithmetic class, not the same bits -- the row
+    // count of the whole pack selects the matmul tiles and the chain (last_prefill_path() of the driver).
+    // members[0] is the DRIVER: the forward runs on its stream and in its prompt buffers (grown for the padded row total), the error text
+    // goes on it, and saturation_fallbacks() of the driver counts a pack that clamped an f16 hand-over value and was repeated -- whole --
+    // at 4 digits.  The tail is finish_prefill on each member (its own head on its own stream).  Synchronises before returning.
+    // Refused, with nothing modified: n_members outside 1..64; a null, dead or repeated member; members with different root() or kv_f16();
+    // n[i] < 1; p_i + n[i] beyond the fed tokens; p_i + n[i] > max_pos - 1; model globals not set.  Members may sit in BatchDecoder slots.
+    static int prefill_packed(Decoder *const *members, const int *n, int n_members, bool with_logits, int digits, float *elapsed_ms);
     // Keep the first n positions of the sequence, 0 <= n <= position(): the position becomes n and the forced count min(forced, n), on
     // host and device.  The cache bytes stay as they are (the decode attention gives slots beyond the position zero weight, the
     // continuation attention never reads a slot at or beyond its past length), and so do the sampler's counts and word counter:
@@ -278,6 +294,13 @@ class Decoder {
     int prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms);  // the body of prefill (p == 0) and extend
     int prompt_attention(Layer &L, size_t N, void *out, bool out_f16);                   // one layer's attention of a prompt forward
     size_t pf_past_ = 0;  // cached positions under the prompt forward in flight (0: fresh sequence)
+    int ensure_prompt_buffers(int n, size_t attn_need);             // the per-row buffers and the attention workspace of a prompt forward of n rows
+    int prompt_layers(size_t N, int digits, bool *f16_rows);        // every layer over the N rows in pf_x_ (prompt_forward, packed_forward)
+    int packed_forward(Decoder *const *members, const std::vector<int32_t> &past, const std::vector<int32_t> &len, bool with_logits, int digits,
+                       float *elapsed_ms);                          // the body of prefill_packed, on the driver
+    // the pack in flight (empty: none): prompt_attention then calls the packed operator with every member's caches of the layer
+    std::vector<Decoder *> pack_members_;
+    std::vector<int32_t> pack_row0_, pack_len_, pack_past_;
     void release_layer(Layer &L);  // frees the layer's handles, subtracts their bytes, drops the captured graphs
     void drop_graphs();
     int pick_token(void *stream, bool record = true);  // final norm + tied logits + the next token (greedy argmax or the sampler) [+ its logprob record]
@@ -383,6 +406,8 @@ int bitnet_host_act_mode(void *d);
 int bitnet_host_prefill(void *d, int n, int with_logits, int digits, float *elapsed_ms);
 int bitnet_host_finish_prefill(void *d, int n, const float *last_row, int with_logits);
 int bitnet_host_extend(void *d, int n, int with_logits, int digits, float *elapsed_ms);  // Decoder::extend
+// Decoder::prefill_packed: members[0] drives and carries the error text
+int bitnet_host_prefill_packed(void *const *members, const int32_t *n, int n_members, int with_logits, int digits, float *elapsed_ms);
 int bitnet_host_rewind(void *d, int n);                                                    // Decoder::rewind
 int bitnet_host_fork(void *src, void *const *dsts, int n_dst, int n);                      // Decoder::fork; the error text goes on src
 int bitnet_host_cached_prefix(void *d, const int32_t *tokens, int n);                      // Decoder::cached_prefix; -1 on error

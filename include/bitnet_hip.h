@@ -549,6 +549,33 @@ int bitnet_hip_attention_extend_dev(const float *qkv_dev, const float *rope_sin_
                                     void *kcache_dev, void *vcache_dev, size_t n_heads, size_t n_kv_heads, size_t head_dim,
                                     size_t max_pos, size_t past_len, size_t seq_len, void *workspace_dev, size_t workspace_bytes,
                                     void *out_dev, int flags, void *stream);
+/* SEVERAL sequences' new tokens in ONE prep launch and ONE attention launch: the prompt-side twin of the batched decode step (the
+ * reference's forward takes [B, T, H] in lock step, crates/bitnet-transformer/src/lib.rs:1437-1478; here every sequence has its own
+ * position and its own number of new tokens).  qkv_dev: [n_rows, n_heads*D + 2*n_kv*D], the raw projections.  Segment s = one sequence
+ * owns rows row0[s] .. row0[s] + len[s] - 1; for it the call is bitnet_hip_attention_extend_dev(those rows, past[s], len[s]) on
+ * kcache[s] / vcache[s]: RoPE of q and k at positions past[s] .., k / v appended at those slots (exact f32, or rounded once to f16),
+ * causal GQA attention of each new query over keys 0 .. its own position OF ITS OWN SEQUENCE.  Slots < past[s] are read and never
+ * written, slots >= past[s] + len[s] are neither read nor written; past[s] == 0 reads nothing from the cache.
+ *   - row0[s] is a multiple of bitnet_hip_attention_packed_row_align(n_heads, n_kv_heads) -- the attention workgroup's query tile, which
+ *     must lie inside one segment: 64 rows when n_heads / n_kv_heads is even, 128 when it is odd (0 for invalid head counts) -- and segments
+ *     do not overlap; their order in the table is free.  Rows that belong to no segment are padding: they are not read, nothing is
+ *     written to any cache for them, their output rows are unspecified but finite.
+ *   - row0, len, past, kcache, vcache are HOST arrays of n_seq = 1..BITNET_HIP_PACK_MAX entries (the cache entries are device pointers); they
+ *     travel as kernel arguments, so the call is asynchronous on `stream` without an upload: no allocation, no synchronisation, and the arrays
+ *     may be reused as soon as it returns.  All caches have max_pos slots, head_dim 128 and the type flags says.
+ *   - out_dev: [n_rows, n_heads*D]; flags: BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16 as above.
+ *   - BITNET_HIP_ERR_INVALID_ARGUMENT before anything launches: n_seq outside 1..BITNET_HIP_PACK_MAX; NULL tables, buffers or caches; len < 1;
+ *     past < 0; past + len > max_pos ("KV cache overflow"); a misaligned or overlapping row0; a segment beyond n_rows; head_dim != 128;
+ *     n_heads % n_kv_heads != 0; one cache pointer in two places; a workspace that is too small; unknown flag bits.
+ * The workspace size is 0 for invalid sizes and non-decreasing in every past[s] and len[s]. */
+#define BITNET_HIP_PACK_MAX 64
+size_t bitnet_hip_attention_packed_row_align(size_t n_heads, size_t n_kv_heads);
+size_t bitnet_hip_attention_packed_workspace_bytes(size_t n_heads, size_t n_kv_heads, size_t n_rows, size_t n_seq, const int32_t *past,
+                                                   const int32_t *len);
+int bitnet_hip_attention_packed_dev(const float *qkv_dev, size_t n_rows, const float *rope_sin_dev, const float *rope_cos_dev, size_t n_seq,
+                                    const int32_t *row0, const int32_t *len, const int32_t *past, void *const *kcache_dev,
+                                    void *const *vcache_dev, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,
+                                    void *workspace_dev, size_t workspace_bytes, void *out_dev, int flags, void *stream);
 /* bitnet_hip_gemv_attn_merge_dev (short contexts) with the QAct outputs of gemv_q_dev */
 int bitnet_hip_gemv_attn_merge_q_dev(bitnet_hip_weights_t w, const float *attn_scratch_dev, size_t n_heads,
                                      size_t n_kv_heads, size_t max_pos, const int32_t *pos_dev, float *y_dev,

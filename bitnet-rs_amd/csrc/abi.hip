@@ -1296,6 +1296,15 @@ size_t bitnet_hip_attention_prefill_sharded_workspace_bytes(size_t n_heads, size
     return attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_q, (int)n_ctx);
 }
 
+// the refusals every prompt attention entry states, each at its own place in the entry's order of checks (`entry`: a size function's 0 is refused first)
+static int check_attn_flags(int flags, const char *entry, const char *hint = "") {
+    return flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16) ? set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x%s", entry, flags, hint) : BITNET_HIP_OK;
+}
+static int check_attn_workspace(size_t need, size_t workspace_bytes, const char *entry = nullptr) {
+    if (entry && need == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: sizes out of range", entry);
+    return workspace_bytes < need ? set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes) : BITNET_HIP_OK;
+}
+
 static int check_prefill_args(const void *a, const void *b, const void *rs, const void *rc, const void *kc, const void *vc,
                               const void *ws, const void *out, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,
                               size_t n_ctx) {
@@ -1323,11 +1332,8 @@ static int attention_prefill_body(const float *q, size_t ld_q, const int32_t *q_
         if (ld_q < n_heads * head_dim || ld_kv < 2 * n_kv_heads * head_dim)
             return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_sharded: row strides too small (ld_q %zu, ld_kv %zu)", ld_q, ld_kv);
     }
-    if (check_flags && (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_flags_dev: unknown flag bits 0x%x", flags);
-    const size_t need = attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_q, (int)n_ctx);
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
+    if (check_flags && (rc = check_attn_flags(flags, "attention_prefill_flags_dev"))) return rc;
+    if ((rc = check_attn_workspace(attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_q, (int)n_ctx), workspace_bytes))) return rc;
     BH_HIP_TRY(launch_attn_prefill(q, (int)ld_q, q_block_pos, (int)n_q, kv, (int)ld_kv, (int)n_ctx, rope_sin, rope_cos, static_cast<float *>(kcache),
                                    static_cast<float *>(vcache), (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, workspace, workspace_bytes,
                                    static_cast<float *>(out), (hipStream_t)stream, 0, 0, flags));
@@ -1387,11 +1393,8 @@ int bitnet_hip_attention_extend_dev(const float *qkv, const float *rope_sin, con
     int rc = check_prefill_args(qkv, qkv, rope_sin, rope_cos, kcache, vcache, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, past_len + seq_len);
     if (rc) return rc;
     if (seq_len == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_extend_dev: seq_len must be at least 1");
-    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_extend_dev: unknown flag bits 0x%x", flags);
-    const size_t need = bitnet_hip_attention_extend_workspace_bytes(n_heads, n_kv_heads, past_len, seq_len);
-    if (need == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_extend_dev: sizes out of range");
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
+    if ((rc = check_attn_flags(flags, "attention_extend_dev"))) return rc;
+    if ((rc = check_attn_workspace(bitnet_hip_attention_extend_workspace_bytes(n_heads, n_kv_heads, past_len, seq_len), workspace_bytes, "attention_extend_dev"))) return rc;
     BH_HIP_TRY(launch_attn_extend(qkv, rope_sin, rope_cos, kcache, vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos, (int)past_len,
                                   (int)seq_len, workspace, workspace_bytes, out, flags, (hipStream_t)stream));
     return BITNET_HIP_OK;
@@ -1423,8 +1426,7 @@ int bitnet_hip_attention_packed_dev(const float *qkv, size_t n_rows, const float
     if (n_kv_heads == 0 || n_heads == 0 || n_heads % n_kv_heads != 0)  // T:215-220
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
     if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: head_dim %zu unsupported (128)", head_dim);
-    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: unknown flag bits 0x%x", flags);
+    if (int rc = check_attn_flags(flags, "attention_packed_dev")) return rc;
     const size_t align = bitnet_hip_attention_packed_row_align(n_heads, n_kv_heads);
     if (align == 0 || n_rows == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: sizes out of range");
     for (size_t s = 0; s < n_seq; ++s) {
@@ -1445,9 +1447,7 @@ int bitnet_hip_attention_packed_dev(const float *qkv, size_t n_rows, const float
         }
         if (kcache[s] == vcache[s]) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: segment %zu: one cache for k and v", s);
     }
-    const size_t need = bitnet_hip_attention_packed_workspace_bytes(n_heads, n_kv_heads, n_rows, n_seq, past, len);
-    if (need == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_packed_dev: sizes out of range");
-    if (workspace_bytes < need) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
+    if (int rc = check_attn_workspace(bitnet_hip_attention_packed_workspace_bytes(n_heads, n_kv_heads, n_rows, n_seq, past, len), workspace_bytes, "attention_packed_dev")) return rc;
     BH_HIP_TRY(launch_attn_packed(qkv, (int)n_rows, rope_sin, rope_cos, (int)n_seq, row0, len, past, kcache, vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim,
                                   (int)max_pos, workspace, workspace_bytes, out, flags, (hipStream_t)stream));
     return BITNET_HIP_OK;
@@ -1469,17 +1469,15 @@ int bitnet_hip_attention_prefill_gathered_phase_dev(const float *q, size_t ld_q,
                                                     size_t max_pos, void *workspace, size_t workspace_bytes, float *out, int phase, void *stream) {
     BH_GUARD_BEGIN
     if (phase < 0 || phase > 2) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_gathered: phase must be 0, 1 or 2, got %d", phase);
-    if (cache_f16 & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16))  // a flag word here: unknown bits are refused, as attention_prefill_flags_dev does
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_gathered_phase: unknown flag bits 0x%x (BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)", cache_f16);
+    // a flag word here: unknown bits are refused, as attention_prefill_flags_dev does
+    if (int rc = check_attn_flags(cache_f16, "attention_prefill_gathered_phase", " (BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)")) return rc;
     int rc = check_prefill_args(q, kv_gathered, rope_sin, rope_cos, kcache, vcache, workspace, out, n_heads, n_kv_heads, head_dim, max_pos, n_ctx);
     if (rc) return rc;
     if (n_q == 0 || !q_block_pos) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_gathered: n_q and q_block_pos must be given");
     if (world == 0 || n_ctx % (2 * world * 64) != 0)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_gathered: context %zu must be a multiple of 2 * world * 64 (world %zu)", n_ctx, world);
     if (ld_q < n_heads * head_dim) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_prefill_gathered: row stride too small (ld_q %zu)", ld_q);
-    const size_t need = attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_q, (int)n_ctx);
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "workspace too small: expected %zu, got %zu", need, workspace_bytes);
+    if ((rc = check_attn_workspace(attn_prefill_workspace_bytes((int)n_heads, (int)n_kv_heads, (int)n_q, (int)n_ctx), workspace_bytes))) return rc;
     BH_HIP_TRY(launch_attn_prefill(q, (int)ld_q, q_block_pos, (int)n_q, static_cast<const float *>(kv_gathered), (int)(2 * n_kv_heads * head_dim), (int)n_ctx,
                                    rope_sin, rope_cos, static_cast<float *>(kcache), static_cast<float *>(vcache), (int)n_heads, (int)n_kv_heads, (int)head_dim,
                                    (int)max_pos, workspace, workspace_bytes, out, (hipStream_t)stream, (int)world, kv_is_f16 ? 1 : 0, cache_f16 & 3, phase));

@@ -84,6 +84,14 @@ __device__ __forceinline__ int zz_row(const PrefillArgs &p, int t) {
     return r * 2 * p.zz_chunk + (first ? 0 : p.zz_chunk) + off;
 }
 
+// split-half RoPE (crates/bitnet-rope/src/lib.rs:59-93, T:134-163) of 4 adjacent pairs (j .. j + 3, 64 + j ..) of one row of a staged slab, at position pos
+__device__ __forceinline__ void rope_rotate4(float (*tile)[kPD + 4], int tok, int j, const float *rope_sin, const float *rope_cos, int pos) {
+    const float4 s = *reinterpret_cast<const float4 *>(rope_sin + (size_t)pos * 64 + j), c = *reinterpret_cast<const float4 *>(rope_cos + (size_t)pos * 64 + j);
+    const float4 x0 = *reinterpret_cast<const float4 *>(&tile[tok][j]), x1 = *reinterpret_cast<const float4 *>(&tile[tok][64 + j]);
+    *reinterpret_cast<float4 *>(&tile[tok][j]) = float4{x0.x * c.x - x1.x * s.x, x0.y * c.y - x1.y * s.y, x0.z * c.z - x1.z * s.z, x0.w * c.w - x1.w * s.w};
+    *reinterpret_cast<float4 *>(&tile[tok][64 + j]) = float4{x0.x * s.x + x1.x * c.x, x0.y * s.y + x1.y * c.y, x0.z * s.z + x1.z * c.z, x0.w * s.w + x1.w * c.w};
+}
+
 // grid (max(nq_pad, Tpad) / 64, heads + 2 kv): slot < heads: query head (rows of p.q, positions from
 // q_block_pos); then k heads, then v heads (rows of p.kv, position = row).
 __global__ __launch_bounds__(256) void k_prefill_prep(PrefillArgs p) {
@@ -130,10 +138,7 @@ __global__ __launch_bounds__(256) void k_prefill_prep(PrefillArgs p) {
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + 256 * i, tok = idx >> 4, j = (idx & 15) * 4;
             const int pos = t0 + tok < n_rows ? pos0 + tok : 0;
-            const float4 s = *reinterpret_cast<const float4 *>(p.rope_sin + (size_t)pos * 64 + j), c = *reinterpret_cast<const float4 *>(p.rope_cos + (size_t)pos * 64 + j);
-            const float4 x0 = *reinterpret_cast<const float4 *>(&tile[tok][j]), x1 = *reinterpret_cast<const float4 *>(&tile[tok][64 + j]);
-            *reinterpret_cast<float4 *>(&tile[tok][j]) = float4{x0.x * c.x - x1.x * s.x, x0.y * c.y - x1.y * s.y, x0.z * c.z - x1.z * s.z, x0.w * c.w - x1.w * s.w};
-            *reinterpret_cast<float4 *>(&tile[tok][64 + j]) = float4{x0.x * s.x + x1.x * c.x, x0.y * s.y + x1.y * c.y, x0.z * s.z + x1.z * c.z, x0.w * s.w + x1.w * c.w};
+            rope_rotate4(tile, tok, j, p.rope_sin, p.rope_cos, pos);
         }
         __syncthreads();
     }
@@ -610,41 +615,49 @@ __global__ __launch_bounds__(256) void k_prefill_merge(PrefillArgs p) {
     *reinterpret_cast<float4 *>(p.out + row * p.out_ld + h * p.out_hs + 4 * d4) = float4{a.x * inv, a.y * inv, a.z * inv, a.w * inv};
 }
 
+// Workgroup tile of k_prefill_attn for a head shape: 4 waves = hw query heads of ONE KV head x (4 / hw) wave columns of 32 queries, qg query rows
+struct AttnTile {
+    int hw, qg;
+};
+static AttnTile attn_tile(int n_heads, int n_kv) {
+    const int group = n_heads / n_kv, hw = group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 1;
+    return {hw, 16 * (4 / hw) * 2};
+}
+
 // key splits of a launch (grid.z): only when the query blocks alone leave CUs idle (fewer than two workgroups per CU), as many
 // as the longest block has 16-tile parts, at most 8
 static int attn_split_tiles() {
     static const int v = [] { const char *e = getenv("BITNET_HIP_ATTN_SPLIT_TILES"); const int x = e ? atoi(e) : kTilesPerSplit; return x < 1 ? 1 : x; }();
     return v;
 }
-static int attn_ksplit(int n_heads, int n_kv, int nq_pad, int T) {
-    const int group = n_heads / n_kv, hw = group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 1, qg = 16 * (4 / hw) * 2;
-    const long n_wg = (long)(nq_pad / qg) * (n_heads / hw);
-    const int tiles = (T + kQB - 1) / kQB;
-    if (n_wg >= 512) return 1;
-    const int s = (tiles + attn_split_tiles() - 1) / attn_split_tiles();
+static int attn_key_parts(int T) {
+    const int tiles = (T + kQB - 1) / kQB, s = (tiles + attn_split_tiles() - 1) / attn_split_tiles();
     return s < 1 ? 1 : s > 8 ? 8 : s;
+}
+static int attn_ksplit(int n_heads, int n_kv, int nq_pad, int T) {
+    const AttnTile t = attn_tile(n_heads, n_kv);
+    const long n_wg = (long)(nq_pad / t.qg) * (n_heads / t.hw);
+    return n_wg >= 512 ? 1 : attn_key_parts(T);
+}
+// k_prefill_attn reads the f32 query rows itself; a launcher adds its own alignment condition (PrefillArgs::q_in_kernel)
+static bool attn_q_in_kernel() {
+    static const bool v = !(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL") && atoi(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL")) == 0);
+    return v;
 }
 
 // q_rec: the per-block records of a packed call (launch_attn_packed): the same grid on k_prefill_attn_packed, never key-split
 static hipError_t launch_attn_kernel(const PrefillArgs &p, hipStream_t stream, const int4 *q_rec = nullptr) {
-    const int group = p.n_heads / p.n_kv;
-    const unsigned z = (unsigned)p.ksplit;
+    // hw 4: 4 waves = the 4 heads of a KV head x 32 queries each, two such workgroups per CU; 2: 2 heads x 2 wave columns x 32 queries
+    const AttnTile t = attn_tile(p.n_heads, p.n_kv);
     void (*ak)(PrefillArgs);
     void (*akp)(PrefillArgs, const int4 *);
-    dim3 grid;
-    if (group % 4 == 0) {  // 4 waves = the 4 heads of a KV head x 32 queries each; two such workgroups per CU
-        ak = k_prefill_attn<4, 4, 2>;
-        akp = k_prefill_attn_packed<4, 4, 2>;
-        grid = dim3((unsigned)(p.nq_pad / 32), (unsigned)(p.n_heads / 4), z);
-    } else if (group % 2 == 0) {  // 2 heads x 2 wave columns x 32 queries
-        ak = k_prefill_attn<2, 4, 2>;
-        akp = k_prefill_attn_packed<2, 4, 2>;
-        grid = dim3((unsigned)(p.nq_pad / 64), (unsigned)(p.n_heads / 2), z);
-    } else {
-        ak = k_prefill_attn<1, 4, 2>;
-        akp = k_prefill_attn_packed<1, 4, 2>;
-        grid = dim3((unsigned)(p.nq_pad / 128), (unsigned)p.n_heads, z);
-    }
+    if (t.hw == 4)
+        ak = k_prefill_attn<4, 4, 2>, akp = k_prefill_attn_packed<4, 4, 2>;
+    else if (t.hw == 2)
+        ak = k_prefill_attn<2, 4, 2>, akp = k_prefill_attn_packed<2, 4, 2>;
+    else
+        ak = k_prefill_attn<1, 4, 2>, akp = k_prefill_attn_packed<1, 4, 2>;
+    dim3 grid((unsigned)(p.nq_pad / t.qg), (unsigned)(p.n_heads / t.hw), (unsigned)p.ksplit);
     // Workgroups are dispatched in linear id order (x fastest).  With the query groups in x, head group 0's blocks all start before head
     // group 1's first: on a causal prompt (640 workgroups for 512 slots at 4096 tokens x 20 heads) the LAST head group's longest blocks only
     // start once earlier groups' short ones have finished, and stand alone at the end.  With the head groups in x the order is longest
@@ -668,14 +681,90 @@ static hipError_t launch_attn_kernel(const PrefillArgs &p, hipStream_t stream, c
     return hipGetLastError();
 }
 
-static size_t attn_f16_bytes(int n_heads, int n_kv, size_t qpad, size_t tpad) {
-    return div_ceil(((size_t)n_heads * qpad + 2 * (size_t)n_kv * tpad) * kPD * sizeof(_Float16), 256) * 256;
+// The workspace of one call, as byte offsets from its 256-byte aligned base: the f16 images (q [head][qpad][128], k [kv][tpad][128],
+// v^T [kv][128][tpad]), the key split's partials, then the launcher's own array (q_block_pos of an extend, q_rec of a packed call), every
+// part rounded to 256 bytes.  The size functions return `total`, the launchers carve from the same object.
+struct AttnLayout {
+    size_t qpad, tpad;        // query rows padded to kQPad, key positions padded to kQB
+    int ksplit;               // key splits of the launch (attn_ksplit; 1: the partials are not used)
+    size_t qh, kh, vt;        // the f16 images
+    size_t part_o, part_ml;   // [ksplit][qpad][heads][128], [ksplit][qpad][heads][2]
+    size_t tail;              // int q_block_pos[qpad / 64] (extend) / int4 q_rec[qpad / 64] (packed)
+    size_t total;             // + 256: the caller's pointer need not be aligned
+};
+enum class AttnPartials { kExact, kBound, kNone };  // what is reserved for the key split's partials
+// kExact: what this launch's ksplit needs.  kBound (extend): a bound on kExact over all nq' <= nq, T' <= T -- the partials vanish once the query
+// blocks alone fill the chip, so the exact size is not monotone; the bound is non-decreasing in both lengths: the most parts T keys have, for
+// the most query rows a split launch has (attn_ksplit: n_wg < 512).  kNone (packed): never key-split.
+static AttnLayout attn_layout(int n_heads, int n_kv, size_t nq, size_t T, AttnPartials partials, size_t tail_elem_bytes) {
+    AttnLayout L;
+    L.qpad = div_ceil(nq, kQPad) * kQPad;
+    L.tpad = div_ceil(T, kQB) * kQB;
+    L.ksplit = partials == AttnPartials::kNone ? 1 : attn_ksplit(n_heads, n_kv, (int)L.qpad, (int)T);
+    int parts = L.ksplit;
+    size_t part_rows = L.qpad;
+    if (partials == AttnPartials::kBound) {
+        const AttnTile t = attn_tile(n_heads, n_kv);
+        const size_t q_split_max = (size_t)(511 / (n_heads / t.hw)) * t.qg;
+        parts = attn_key_parts((int)T);
+        part_rows = L.qpad < q_split_max ? L.qpad : q_split_max;
+    }
+    L.qh = 0;
+    L.kh = L.qh + (size_t)n_heads * L.qpad * kPD * sizeof(_Float16);
+    L.vt = L.kh + (size_t)n_kv * L.tpad * kPD * sizeof(_Float16);
+    L.part_o = div_ceil(L.vt + (size_t)n_kv * kPD * L.tpad * sizeof(_Float16), 256) * 256;
+    L.part_ml = L.part_o + (size_t)L.ksplit * L.qpad * n_heads * kPD * sizeof(float);
+    L.tail = L.part_o + (parts > 1 ? (size_t)parts * part_rows * n_heads * (kPD + 2) * sizeof(float) : 0);
+    L.total = L.tail + div_ceil(L.qpad / kQB * tail_elem_bytes, 256) * 256 + 256;
+    return L;
 }
 
 size_t attn_prefill_workspace_bytes(int n_heads, int n_kv, int nq, int T) {
-    const size_t qpad = div_ceil((size_t)nq, kQPad) * kQPad, tpad = div_ceil((size_t)T, kQB) * kQB;
-    const int ks = attn_ksplit(n_heads, n_kv, (int)qpad, T);
-    return attn_f16_bytes(n_heads, n_kv, qpad, tpad) + (ks > 1 ? (size_t)ks * qpad * n_heads * (kPD + 2) * sizeof(float) : 0) + 256;
+    return attn_layout(n_heads, n_kv, (size_t)nq, (size_t)T, AttnPartials::kExact, 0).total;
+}
+
+static uint8_t *attn_ws_base(void *workspace) { return reinterpret_cast<uint8_t *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }
+
+// What the whole-prompt, extend, packed and generic launchers share: element (head h, row t, dim d) of q / k / v at base + h * 128 + t * ld + d
+// ([row][head][dim] rows), the transformer's RoPE, causal mask and 1/sqrt(d), the images and partials of the layout.  flags: bit 0 f16 caches,
+// bit 1 f16 output rows.  Everything else is zero: absolute key order, f32 k|v rows, phase 0, q from the f16 image, no q_block_pos.
+static PrefillArgs attn_args(const AttnLayout &L, uint8_t *ws, const float *q, int ld_q, const float *k, const float *v, int ld_kv, int nq, int T,
+                             const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, int n_heads, int n_kv, int max_pos, void *out,
+                             int flags) {
+    PrefillArgs p{};
+    p.q = q;
+    p.k = k;
+    p.v = v;
+    p.ld_q = ld_q;
+    p.ld_kv = ld_kv;
+    p.hs_q = p.hs_kv = kPD;
+    p.out_hs = kPD;
+    p.out_ld = n_heads * kPD;
+    p.rope = 1;
+    p.causal = 1;
+    p.scale = 1.0f / sqrtf((float)kPD);
+    p.nq = nq;
+    p.nq_pad = (int)L.qpad;
+    p.rope_sin = rope_sin;
+    p.rope_cos = rope_cos;
+    p.kcache = static_cast<float *>(kcache);
+    p.vcache = static_cast<float *>(vcache);
+    p.n_heads = n_heads;
+    p.n_kv = n_kv;
+    p.max_pos = max_pos;
+    p.T = T;
+    p.Tpad = (int)L.tpad;
+    p.qh = reinterpret_cast<_Float16 *>(ws + L.qh);
+    p.kh = reinterpret_cast<_Float16 *>(ws + L.kh);
+    p.vt = reinterpret_cast<_Float16 *>(ws + L.vt);
+    p.out = static_cast<float *>(out);
+    p.cache_f16 = flags & 1;
+    p.out_f16 = (flags >> 1) & 1;  // bit 1 of the flag word: f16 output rows
+    p.ksplit = L.ksplit;
+    p.split_tiles = attn_split_tiles();
+    p.part_o = reinterpret_cast<float *>(ws + L.part_o);
+    p.part_ml = reinterpret_cast<float *>(ws + L.part_ml);
+    return p;
 }
 
 // q: nq query rows (stride ld_q floats) whose 64-row blocks sit at absolute positions q_block_pos
@@ -687,51 +776,18 @@ hipError_t launch_attn_prefill(const float *q, int ld_q, const int *q_block_pos,
     if (phase < 0 || phase > 2) return hipErrorInvalidValue;
     if (D != kPD || T <= 0 || nq <= 0 || T > max_pos || n_heads % n_kv != 0) return hipErrorInvalidValue;
     if (zz_world < 0 || (zz_world > 0 && (T % (2 * zz_world * kQB) != 0))) return hipErrorInvalidValue;
-    if (!workspace || workspace_bytes < attn_prefill_workspace_bytes(n_heads, n_kv, nq, T)) return hipErrorInvalidValue;
-    PrefillArgs p;
-    p.q = q;
-    p.k = kv;
-    p.v = kv + (size_t)n_kv * kPD;  // (f16 rows: the prep kernel indexes k heads then v heads from p.k itself)
+    const AttnLayout L = attn_layout(n_heads, n_kv, (size_t)nq, (size_t)T, AttnPartials::kExact, 0);
+    if (!workspace || workspace_bytes < L.total) return hipErrorInvalidValue;
+    // (f16 rows: the prep kernel indexes k heads then v heads from p.k itself)
+    PrefillArgs p = attn_args(L, attn_ws_base(workspace), q, ld_q, kv, kv + (size_t)n_kv * kPD, ld_kv, nq, T, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv, max_pos, out, cache_f16);
+    p.q_block_pos = q_block_pos;
     p.zz_world = zz_world;
     p.zz_chunk = zz_world > 0 ? T / (2 * zz_world) : 0;
     p.kv_f16 = kv_f16;
-    p.cache_f16 = cache_f16 & 1;
-    p.out_f16 = (cache_f16 >> 1) & 1;  // bit 1 of the flag word: f16 output rows
-    p.ld_q = ld_q;
-    p.ld_kv = ld_kv;
-    p.hs_q = p.hs_kv = kPD;
-    p.out_hs = kPD;
-    p.out_ld = n_heads * kPD;
-    p.rope = 1;
-    p.causal = 1;
-    p.scale = 1.0f / sqrtf((float)kPD);
-    p.q_block_pos = q_block_pos;
-    p.nq = nq;
-    p.nq_pad = (int)(div_ceil((size_t)nq, kQPad) * kQPad);
-    p.rope_sin = rope_sin;
-    p.rope_cos = rope_cos;
-    p.kcache = kcache;
-    p.vcache = vcache;
-    p.n_heads = n_heads;
-    p.n_kv = n_kv;
-    p.max_pos = max_pos;
-    p.T = T;
-    p.Tpad = (int)(div_ceil((size_t)T, kQB) * kQB);
-    uint8_t *ws = reinterpret_cast<uint8_t *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    p.qh = reinterpret_cast<_Float16 *>(ws);
-    p.kh = p.qh + (size_t)n_heads * p.nq_pad * kPD;
-    p.vt = p.kh + (size_t)n_kv * p.Tpad * kPD;
-    p.out = out;
-    p.ksplit = attn_ksplit(n_heads, n_kv, p.nq_pad, T);
-    p.split_tiles = attn_split_tiles();
-    p.part_o = reinterpret_cast<float *>(ws + attn_f16_bytes(n_heads, n_kv, (size_t)p.nq_pad, (size_t)p.Tpad));
-    p.part_ml = p.part_o + (size_t)p.ksplit * p.nq_pad * n_heads * kPD;
     p.phase = phase;
     const unsigned nbq = (unsigned)(p.nq_pad / kQB), nbk = (unsigned)(p.Tpad / kQB);
-    static const bool q_in_kernel = !(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL") && atoi(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL")) == 0);
     // the attention kernel needs 16-byte aligned f32 query rows for its own q path; anything else keeps the f16 image of the prep kernel
-    p.q_in_kernel = q_in_kernel && (ld_q & 3) == 0 && ((uintptr_t)q & 15) == 0 ? 1 : 0;
-    p.slot0 = 0;
+    p.q_in_kernel = attn_q_in_kernel() && (ld_q & 3) == 0 && ((uintptr_t)q & 15) == 0 ? 1 : 0;
     if (phase == 1) {  // the query slabs alone (nothing to do when the attention kernel prepares them itself)
         if (!p.q_in_kernel) hipLaunchKernelGGL(k_prefill_prep, dim3(nbq, (unsigned)n_heads), dim3(256), 0, stream, p);
         return hipGetLastError();
@@ -769,6 +825,16 @@ struct ExtendPrepArgs {
     int *q_block_pos;    // [n_qblocks]: past + 64 b, filled here so that the call stays asynchronous on its stream
     int n_qblocks;
 };
+
+// a staged slab -> [64 tokens][128] halves, contiguous, times mul: 8 bytes per thread and iteration (k_extend_prep, k_packed_qprep;
+// k_prefill_prep keeps its own lambda: through this function hipcc hoists its address arithmetic differently)
+__device__ __forceinline__ void store_rows_f16(const float (*tile)[kPD + 4], _Float16 *dst, float mul) {
+    for (int i = 0; i < 8; ++i) {
+        const int tid = threadIdx.x, idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
+        const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
+        *reinterpret_cast<h4 *>(dst + (size_t)tok * kPD + d) = (h4){(_Float16)(v.x * mul), (_Float16)(v.y * mul), (_Float16)(v.z * mul), (_Float16)(v.w * mul)};
+    }
+}
 
 // One 64-position tile of one sequence: t0 = its first position (cache side), img_t0 = its first position inside the f16 images (the same
 // for k_extend_prep; a packed image holds several sequences' tiles one after the other, p.Tpad = all of them).
@@ -845,10 +911,7 @@ __device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float 
             const int idx = tid + 256 * i, tok = idx >> 4, j = (idx & 15) * 4;
             if (tok < n_past || tok >= n_live) continue;
             const int pos = t0 + tok;
-            const float4 s = *reinterpret_cast<const float4 *>(p.rope_sin + (size_t)pos * 64 + j), c = *reinterpret_cast<const float4 *>(p.rope_cos + (size_t)pos * 64 + j);
-            const float4 x0 = *reinterpret_cast<const float4 *>(&tile[tok][j]), x1 = *reinterpret_cast<const float4 *>(&tile[tok][64 + j]);
-            *reinterpret_cast<float4 *>(&tile[tok][j]) = float4{x0.x * c.x - x1.x * s.x, x0.y * c.y - x1.y * s.y, x0.z * c.z - x1.z * s.z, x0.w * c.w - x1.w * s.w};
-            *reinterpret_cast<float4 *>(&tile[tok][64 + j]) = float4{x0.x * s.x + x1.x * c.x, x0.y * s.y + x1.y * c.y, x0.z * s.z + x1.z * c.z, x0.w * s.w + x1.w * c.w};
+            rope_rotate4(tile, tok, j, p.rope_sin, p.rope_cos, pos);
         }
         __syncthreads();
     }
@@ -893,12 +956,7 @@ __device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float 
     }
     // ---- the f16 images of the whole tile, in k_prefill_prep's order ----
     if (is_k) {
-        _Float16 *dst = p.kh + ((size_t)kvh * p.Tpad + img_t0) * kPD;
-        for (int i = 0; i < 8; ++i) {
-            const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
-            const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
-            *reinterpret_cast<h4 *>(dst + (size_t)tok * kPD + d) = (h4){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-        }
+        store_rows_f16(tile, p.kh + ((size_t)kvh * p.Tpad + img_t0) * kPD, 1.0f);
     } else {
         // the V^T key permutation inside each group of 32 (k_prefill_prep): key 4 a + 16 b + j at slot 8 a + 4 b + j
         _Float16 *vt = p.vt + (size_t)kvh * kPD * p.Tpad;
@@ -918,87 +976,52 @@ __global__ __launch_bounds__(256) void k_extend_prep(ExtendPrepArgs p) {
     extend_prep_tile(p, tile, blockIdx.x * kQB, blockIdx.x * kQB);
 }
 
-// A bound on attn_prefill_workspace_bytes(n_heads, n_kv, nq', T') over all nq' <= nq, T' <= T (the key split's partials vanish once the
-// query blocks alone fill the chip, so the exact size is not monotone), plus the q_block_pos array: non-decreasing in both lengths.
-static size_t extend_partial_bytes(int n_heads, int n_kv, size_t qpad, int T) {
-    const int group = n_heads / n_kv, hw = group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 1, qg = 16 * (4 / hw) * 2;
-    const size_t q_split_max = (size_t)(511 / (n_heads / hw)) * qg;  // the most query rows a split launch has (attn_ksplit: n_wg < 512)
-    const int tiles = (T + kQB - 1) / kQB;
-    int ks = (tiles + attn_split_tiles() - 1) / attn_split_tiles();
-    ks = ks < 1 ? 1 : ks > 8 ? 8 : ks;
-    return ks > 1 ? (size_t)ks * (qpad < q_split_max ? qpad : q_split_max) * n_heads * (kPD + 2) * sizeof(float) : 0;
+// what k_extend_prep / k_packed_prep take from the attention's arguments; q_block_pos: the array k_extend_prep fills (null: packed, records instead)
+static ExtendPrepArgs extend_prep_args(const PrefillArgs &p, int past, int *q_block_pos) {
+    ExtendPrepArgs e{};
+    e.k_new = p.k;
+    e.v_new = p.v;
+    e.ld = p.ld_kv;
+    e.rope_sin = p.rope_sin;
+    e.rope_cos = p.rope_cos;
+    e.kcache = p.kcache;
+    e.vcache = p.vcache;
+    e.n_kv = p.n_kv;
+    e.max_pos = p.max_pos;
+    e.past = past;
+    e.T = p.T;
+    e.Tpad = p.Tpad;
+    e.cache_f16 = p.cache_f16;
+    e.kh = p.kh;
+    e.vt = p.vt;
+    e.q_block_pos = q_block_pos;
+    e.n_qblocks = q_block_pos ? p.nq_pad / kQB : 0;
+    return e;
+}
+
+// the images and (a bound on) the partials of attn_prefill_workspace_bytes, plus the q_block_pos array: non-decreasing in both lengths
+static AttnLayout extend_layout(int n_heads, int n_kv, int past, int seq) {
+    return attn_layout(n_heads, n_kv, (size_t)seq, (size_t)past + seq, AttnPartials::kBound, sizeof(int));
 }
 size_t attn_extend_workspace_bytes(int n_heads, int n_kv, int past, int seq) {
     if (n_heads <= 0 || n_kv <= 0 || n_heads % n_kv != 0 || past < 0 || seq <= 0) return 0;
-    const size_t qpad = div_ceil((size_t)seq, kQPad) * kQPad, tpad = div_ceil((size_t)past + seq, kQB) * kQB;
-    return attn_f16_bytes(n_heads, n_kv, qpad, tpad) + extend_partial_bytes(n_heads, n_kv, qpad, past + seq) + div_ceil(qpad / kQB * sizeof(int), 256) * 256 + 256;
+    return extend_layout(n_heads, n_kv, past, seq).total;
 }
 
 hipError_t launch_attn_extend(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache, int n_heads, int n_kv,
                               int D, int max_pos, int past, int seq, void *workspace, size_t workspace_bytes, void *out, int flags, hipStream_t stream) {
     if (D != kPD || past < 0 || seq <= 0 || n_kv <= 0 || n_heads % n_kv != 0 || (size_t)past + seq > (size_t)max_pos) return hipErrorInvalidValue;
     if (!workspace || workspace_bytes < attn_extend_workspace_bytes(n_heads, n_kv, past, seq)) return hipErrorInvalidValue;
-    const int ld = (n_heads + 2 * n_kv) * kPD, T = past + seq;
-    PrefillArgs p;
-    p.q = qkv;
-    p.k = qkv + (size_t)n_heads * kPD;
-    p.v = p.k + (size_t)n_kv * kPD;
-    p.zz_world = p.zz_chunk = p.kv_f16 = 0;
-    p.cache_f16 = flags & 1;
-    p.out_f16 = (flags >> 1) & 1;
-    p.ld_q = p.ld_kv = ld;
-    p.hs_q = p.hs_kv = kPD;
-    p.out_hs = kPD;
-    p.out_ld = n_heads * kPD;
-    p.rope = 1;
-    p.causal = 1;
-    p.scale = 1.0f / sqrtf((float)kPD);
-    p.nq = seq;
-    p.nq_pad = (int)(div_ceil((size_t)seq, kQPad) * kQPad);
-    p.rope_sin = rope_sin;
-    p.rope_cos = rope_cos;
-    p.kcache = static_cast<float *>(kcache);
-    p.vcache = static_cast<float *>(vcache);
-    p.n_heads = n_heads;
-    p.n_kv = n_kv;
-    p.max_pos = max_pos;
-    p.T = T;
-    p.Tpad = (int)(div_ceil((size_t)T, kQB) * kQB);
-    uint8_t *ws = reinterpret_cast<uint8_t *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    p.qh = reinterpret_cast<_Float16 *>(ws);
-    p.kh = p.qh + (size_t)n_heads * p.nq_pad * kPD;
-    p.vt = p.kh + (size_t)n_kv * p.Tpad * kPD;
-    p.out = static_cast<float *>(out);
-    p.ksplit = attn_ksplit(n_heads, n_kv, p.nq_pad, T);
-    p.split_tiles = attn_split_tiles();
-    const size_t f16b = attn_f16_bytes(n_heads, n_kv, (size_t)p.nq_pad, (size_t)p.Tpad);
-    p.part_o = reinterpret_cast<float *>(ws + f16b);
-    p.part_ml = p.part_o + (size_t)p.ksplit * p.nq_pad * n_heads * kPD;
-    int *qbp = reinterpret_cast<int *>(ws + f16b + extend_partial_bytes(n_heads, n_kv, (size_t)p.nq_pad, T));
+    const AttnLayout L = extend_layout(n_heads, n_kv, past, seq);
+    const int ld = (n_heads + 2 * n_kv) * kPD;
+    const float *k = qkv + (size_t)n_heads * kPD;
+    uint8_t *ws = attn_ws_base(workspace);
+    PrefillArgs p = attn_args(L, ws, qkv, ld, k, k + (size_t)n_kv * kPD, ld, seq, past + seq, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv, max_pos, out, flags);
+    int *qbp = reinterpret_cast<int *>(ws + L.tail);
     p.q_block_pos = qbp;
     p.phase = 1;
-    p.slot0 = 0;
-    static const bool q_in_kernel = !(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL") && atoi(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL")) == 0);
-    p.q_in_kernel = q_in_kernel && ((uintptr_t)qkv & 15) == 0 ? 1 : 0;
-    ExtendPrepArgs e;
-    e.k_new = p.k;
-    e.v_new = p.v;
-    e.ld = ld;
-    e.rope_sin = rope_sin;
-    e.rope_cos = rope_cos;
-    e.kcache = kcache;
-    e.vcache = vcache;
-    e.n_kv = n_kv;
-    e.max_pos = max_pos;
-    e.past = past;
-    e.T = T;
-    e.Tpad = p.Tpad;
-    e.cache_f16 = p.cache_f16;
-    e.kh = p.kh;
-    e.vt = p.vt;
-    e.q_block_pos = qbp;
-    e.n_qblocks = p.nq_pad / kQB;
-    hipLaunchKernelGGL(k_extend_prep, dim3((unsigned)(p.Tpad / kQB), (unsigned)(2 * n_kv)), dim3(256), 0, stream, e);
+    p.q_in_kernel = attn_q_in_kernel() && ((uintptr_t)qkv & 15) == 0 ? 1 : 0;
+    hipLaunchKernelGGL(k_extend_prep, dim3((unsigned)(p.Tpad / kQB), (unsigned)(2 * n_kv)), dim3(256), 0, stream, extend_prep_args(p, past, qbp));
     // misaligned query rows: the f16 query image of k_prefill_prep (its query slabs alone), positions from the array filled above
     if (!p.q_in_kernel) hipLaunchKernelGGL(k_prefill_prep, dim3((unsigned)(p.nq_pad / kQB), (unsigned)n_heads), dim3(256), 0, stream, p);
     return launch_attn_kernel(p, stream);
@@ -1084,24 +1107,17 @@ __global__ __launch_bounds__(256) void k_packed_qprep(PrefillArgs p, const int4 
     for (int i = 0; i < 4; ++i) {  // split-half RoPE, the arithmetic of k_prefill_prep
         const int idx = tid + 256 * i, tok = idx >> 4, j = (idx & 15) * 4;
         const int pos = tok < r.w ? r.x + tok : 0;
-        const float4 s = *reinterpret_cast<const float4 *>(p.rope_sin + (size_t)pos * 64 + j), c = *reinterpret_cast<const float4 *>(p.rope_cos + (size_t)pos * 64 + j);
-        const float4 x0 = *reinterpret_cast<const float4 *>(&tile[tok][j]), x1 = *reinterpret_cast<const float4 *>(&tile[tok][64 + j]);
-        *reinterpret_cast<float4 *>(&tile[tok][j]) = float4{x0.x * c.x - x1.x * s.x, x0.y * c.y - x1.y * s.y, x0.z * c.z - x1.z * s.z, x0.w * c.w - x1.w * s.w};
-        *reinterpret_cast<float4 *>(&tile[tok][64 + j]) = float4{x0.x * s.x + x1.x * c.x, x0.y * s.y + x1.y * c.y, x0.z * s.z + x1.z * c.z, x0.w * s.w + x1.w * c.w};
+        rope_rotate4(tile, tok, j, p.rope_sin, p.rope_cos, pos);
     }
     __syncthreads();
     const float qmul = 1.4426950408889634f * p.scale;
-    _Float16 *dst = p.qh + ((size_t)h * p.nq_pad + t0) * kPD;
-    for (int i = 0; i < 8; ++i) {
-        const int idx = tid + 256 * i, tok = idx >> 5, d = (idx & 31) * 4;
-        const float4 v = *reinterpret_cast<const float4 *>(&tile[tok][d]);
-        *reinterpret_cast<h4 *>(dst + (size_t)tok * kPD + d) = (h4){(_Float16)(v.x * qmul), (_Float16)(v.y * qmul), (_Float16)(v.z * qmul), (_Float16)(v.w * qmul)};
-    }
+    store_rows_f16(tile, p.qh + ((size_t)h * p.nq_pad + t0) * kPD, qmul);
 }
 
 int attn_packed_row_align(int n_heads, int n_kv) {
     if (n_heads <= 0 || n_kv <= 0 || n_heads % n_kv != 0) return 0;
-    return (n_heads / n_kv) % 2 == 0 ? 64 : 128;  // the query tile of k_prefill_attn<4,4,2> / <2,4,2>, of <1,4,2> (launch_attn_kernel)
+    const int qg = attn_tile(n_heads, n_kv).qg;  // the query tile of k_prefill_attn<4,4,2> / <2,4,2> / <1,4,2> (launch_attn_kernel) ...
+    return qg < kQB ? kQB : qg;                  // ... in whole 64-row blocks: a block has ONE record
 }
 
 // all segments' key tiles, or 0 when a size is out of range (the images' 32-bit byte offsets hold 2^24 positions)
@@ -1115,11 +1131,13 @@ static size_t packed_tiles(int n_seq, const int *past, const int *len) {
     return tiles * kQB < ((size_t)1 << 24) ? tiles : 0;
 }
 // q image + k / v^T images of all tiles + the records: a sum of terms that each grow with past[s] and len[s]
+static AttnLayout packed_layout(int n_heads, int n_kv, int n_rows, size_t tiles) {
+    return attn_layout(n_heads, n_kv, (size_t)n_rows, tiles * kQB, AttnPartials::kNone, sizeof(int4));
+}
 size_t attn_packed_workspace_bytes(int n_heads, int n_kv, int n_rows, int n_seq, const int *past, const int *len) {
     const size_t tiles = packed_tiles(n_seq, past, len);
     if (n_heads <= 0 || n_kv <= 0 || n_heads % n_kv != 0 || n_rows < 1 || n_rows >= (1 << 24) || tiles == 0) return 0;
-    const size_t qpad = div_ceil((size_t)n_rows, kQPad) * kQPad;
-    return attn_f16_bytes(n_heads, n_kv, qpad, tiles * kQB) + div_ceil(qpad / kQB * sizeof(int4), 256) * 256 + 256;
+    return packed_layout(n_heads, n_kv, n_rows, tiles).total;
 }
 
 hipError_t launch_attn_packed(const float *qkv, int n_rows, const float *rope_sin, const float *rope_cos, int n_seq, const int *row0, const int *len,
@@ -1133,60 +1151,16 @@ hipError_t launch_attn_packed(const float *qkv, int n_rows, const float *rope_si
             return hipErrorInvalidValue;
     const int ld = (n_heads + 2 * n_kv) * kPD;
     const size_t tiles = packed_tiles(n_seq, past, len);
-    PrefillArgs p;
-    p.q = qkv;
-    p.k = qkv + (size_t)n_heads * kPD;
-    p.v = p.k + (size_t)n_kv * kPD;
-    p.zz_world = p.zz_chunk = p.kv_f16 = 0;
-    p.cache_f16 = flags & 1;
-    p.out_f16 = (flags >> 1) & 1;
-    p.ld_q = p.ld_kv = ld;
-    p.hs_q = p.hs_kv = kPD;
-    p.out_hs = kPD;
-    p.out_ld = n_heads * kPD;
-    p.rope = 1;
-    p.causal = 1;
-    p.scale = 1.0f / sqrtf((float)kPD);
-    p.q_block_pos = nullptr;
-    p.nq = n_rows;
-    p.nq_pad = (int)(div_ceil((size_t)n_rows, kQPad) * kQPad);
-    p.rope_sin = rope_sin;
-    p.rope_cos = rope_cos;
-    p.kcache = p.vcache = nullptr;  // per segment: PackedPrepArgs
-    p.n_heads = n_heads;
-    p.n_kv = n_kv;
-    p.max_pos = max_pos;
-    p.T = 0;                        // per block: q_rec
-    p.Tpad = (int)(tiles * kQB);
-    uint8_t *ws = reinterpret_cast<uint8_t *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    p.qh = reinterpret_cast<_Float16 *>(ws);
-    p.kh = p.qh + (size_t)n_heads * p.nq_pad * kPD;
-    p.vt = p.kh + (size_t)n_kv * p.Tpad * kPD;
-    p.out = static_cast<float *>(out);
-    p.ksplit = 1;
-    p.split_tiles = attn_split_tiles();
-    p.part_o = p.part_ml = nullptr;
-    int4 *q_rec = reinterpret_cast<int4 *>(ws + attn_f16_bytes(n_heads, n_kv, (size_t)p.nq_pad, (size_t)p.Tpad));
+    const AttnLayout L = packed_layout(n_heads, n_kv, n_rows, tiles);
+    const float *k = qkv + (size_t)n_heads * kPD;
+    // T = 0: the key count is per block (q_rec); no caches: they are per segment (PackedPrepArgs)
+    uint8_t *ws = attn_ws_base(workspace);
+    PrefillArgs p = attn_args(L, ws, qkv, ld, k, k + (size_t)n_kv * kPD, ld, n_rows, 0, rope_sin, rope_cos, nullptr, nullptr, n_heads, n_kv, max_pos, out, flags);
+    int4 *q_rec = reinterpret_cast<int4 *>(ws + L.tail);
     p.phase = 1;
-    p.slot0 = 0;
-    static const bool q_in_kernel = !(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL") && atoi(getenv("BITNET_HIP_ATTN_Q_IN_KERNEL")) == 0);
-    p.q_in_kernel = q_in_kernel && ((uintptr_t)qkv & 15) == 0 ? 1 : 0;
+    p.q_in_kernel = attn_q_in_kernel() && ((uintptr_t)qkv & 15) == 0 ? 1 : 0;
     PackedPrepArgs a;
-    a.e.k_new = p.k;
-    a.e.v_new = p.v;
-    a.e.ld = ld;
-    a.e.rope_sin = rope_sin;
-    a.e.rope_cos = rope_cos;
-    a.e.kcache = a.e.vcache = nullptr;
-    a.e.n_kv = n_kv;
-    a.e.max_pos = max_pos;
-    a.e.past = a.e.T = 0;
-    a.e.Tpad = p.Tpad;
-    a.e.cache_f16 = p.cache_f16;
-    a.e.kh = p.kh;
-    a.e.vt = p.vt;
-    a.e.q_block_pos = nullptr;
-    a.e.n_qblocks = 0;
+    a.e = extend_prep_args(p, 0, nullptr);  // k_new / v_new: packed row 0; past, T and the caches are per segment
     a.q_rec = q_rec;
     a.n_qblocks = p.nq_pad / kQB;
     a.n_seq = n_seq;
@@ -1224,40 +1198,16 @@ hipError_t launch_pack_cols(const float *src, size_t ld, size_t col0, size_t nco
 // the reference's fused_attention_hip stub (K/rocm/attention.rs:54-65), one batch element.
 hipError_t launch_attn_generic(const float *q, const float *k, const float *v, float *out, int n_heads, int seq, int causal,
                                float scale, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (seq <= 0 || n_heads <= 0 || !workspace || workspace_bytes < attn_prefill_workspace_bytes(n_heads, n_heads, seq, seq))
-        return hipErrorInvalidValue;
-    PrefillArgs p;
-    p.q = q;
-    p.k = k;
-    p.v = v;
-    p.ld_q = p.ld_kv = kPD;
-    p.hs_q = p.hs_kv = seq * kPD;
+    if (seq <= 0 || n_heads <= 0 || !workspace) return hipErrorInvalidValue;
+    const AttnLayout L = attn_layout(n_heads, n_heads, (size_t)seq, (size_t)seq, AttnPartials::kExact, 0);
+    if (workspace_bytes < L.total) return hipErrorInvalidValue;
+    PrefillArgs p = attn_args(L, attn_ws_base(workspace), q, kPD, k, v, kPD, seq, seq, nullptr, nullptr, nullptr, nullptr, n_heads, n_heads, seq, out, 0);
+    p.hs_q = p.hs_kv = seq * kPD;  // [head][row][dim] tensors, in and out
     p.out_hs = seq * kPD;
     p.out_ld = kPD;
     p.rope = 0;
     p.causal = causal;
     p.scale = scale;
-    p.q_block_pos = nullptr;
-    p.zz_world = p.zz_chunk = p.kv_f16 = p.cache_f16 = p.out_f16 = p.head_fast = p.phase = 0;
-    p.nq = seq;
-    p.nq_pad = (int)(div_ceil((size_t)seq, kQPad) * kQPad);
-    p.rope_sin = p.rope_cos = nullptr;
-    p.kcache = p.vcache = nullptr;
-    p.n_heads = p.n_kv = n_heads;
-    p.max_pos = seq;
-    p.T = seq;
-    p.Tpad = (int)(div_ceil((size_t)seq, kQB) * kQB);
-    uint8_t *ws = reinterpret_cast<uint8_t *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    p.qh = reinterpret_cast<_Float16 *>(ws);
-    p.kh = p.qh + (size_t)n_heads * p.nq_pad * kPD;
-    p.vt = p.kh + (size_t)n_heads * p.Tpad * kPD;
-    p.out = out;
-    p.ksplit = attn_ksplit(n_heads, n_heads, p.nq_pad, seq);
-    p.split_tiles = attn_split_tiles();
-    p.slot0 = 0;
-    p.q_in_kernel = 0;
-    p.part_o = reinterpret_cast<float *>(ws + attn_f16_bytes(n_heads, n_heads, (size_t)p.nq_pad, (size_t)p.Tpad));
-    p.part_ml = p.part_o + (size_t)p.ksplit * p.nq_pad * n_heads * kPD;
     const unsigned nb = (unsigned)(p.nq_pad / kQB);
     hipLaunchKernelGGL(k_prefill_prep, dim3(nb, (unsigned)(3 * n_heads)), dim3(256), 0, stream, p);
     return launch_attn_kernel(p, stream);

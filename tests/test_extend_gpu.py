@@ -56,6 +56,16 @@ class Op:
     def dev(self, a):
         return self.t.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
+    def rows(self, a, misalign=False):
+        """-> (the tensor that owns the rows, their device pointer); misalign: 4 bytes off a 16-byte boundary, where the query image comes
+        from the prep launch instead of the attention kernel's own f32 reads (tests/test_attention_packed_gpu.py Pack.call)"""
+        if not misalign:
+            buf = self.dev(a)
+            return buf, buf.data_ptr()
+        buf = self.t.zeros(a.size + 1, dtype=self.t.float32, device="cuda")
+        buf[1:] = self.dev(a).ravel()
+        return buf, buf.data_ptr() + 4
+
     def prefill(self, qkv, kc=None, vc=None):
         """the one-shot prompt operator over all rows of qkv (fresh sequence)"""
         T = qkv.shape[0]
@@ -70,13 +80,14 @@ class Op:
         self.t.cuda.synchronize()
         return out.cpu().numpy()
 
-    def extend(self, qkv_new, past, out_f16=False):
+    def extend(self, qkv_new, past, out_f16=False, misalign=False):
         n = qkv_new.shape[0]
+        buf, q_ptr = self.rows(qkv_new, misalign)
         wsb = self.hip.attention_extend_workspace_bytes(self.n_heads, self.n_kv, past, n)
         assert wsb > 0
         ws = self.t.full((wsb,), 0xFF, dtype=self.t.uint8, device="cuda")  # NaN patterns: nothing the call did not write may be read
         out = self.t.full((n, self.n_heads * D), float("nan"), dtype=self.t.float16 if out_f16 else self.t.float32, device="cuda")
-        self.hip.attention_extend_dev(self.dev(qkv_new), self.sin_d, self.cos_d, self.kc, self.vc, self.n_heads, self.n_kv, D, self.max_pos, past, n, ws, wsb,
+        self.hip.attention_extend_dev(q_ptr, self.sin_d, self.cos_d, self.kc, self.vc, self.n_heads, self.n_kv, D, self.max_pos, past, n, ws, wsb,
                                       out, (CACHE_F16 if self.f16 else 0) | (OUT_F16 if out_f16 else 0))
         self.t.cuda.synchronize()
         return out.float().cpu().numpy()
@@ -199,6 +210,36 @@ def test_f16_output_rows_and_a_reused_workspace(hip, oracle, torch_):
         assert np.all(np.abs(b.astype(np.float64) - a) <= half_ulp + 2.0 ** -23 * np.abs(a))
     with pytest.raises(Exception, match="KV cache overflow"):
         op.extend(qkv[:60], 200)
+
+
+@pytest.mark.parametrize("f16", [False, True])
+@pytest.mark.parametrize("past,n,n_heads,n_kv", [(37, 70, 4, 2), (64, 65, 3, 3)])
+def test_misaligned_rows_take_the_query_prep_launch(hip, oracle, torch_, past, n, n_heads, n_kv, f16):
+    """q|k|v rows 4 bytes off a 16-byte boundary: k_extend_prep reads them element by element and the query image comes from k_prefill_prep's
+    query slabs at the positions k_extend_prep wrote.  The operator's gates against float64 (6e-3, cosine 0.9999), 2e-4 of max|aligned|
+    against the aligned call on the same values, and the same caches bit for bit."""
+    max_pos, T = 512, past + n
+    rng = np.random.default_rng(100 * past + n + (7 if f16 else 0))
+    qkv = rng.normal(0, 1.3, (T, (n_heads + 2 * n_kv) * D)).astype(np.float32)
+    outs, ops = [], []
+    for misalign in (False, True):
+        op = Op(hip, oracle, torch_, n_heads, n_kv, max_pos, f16)
+        op.prefill(qkv[:past])
+        outs.append(op.extend(qkv[past:], past, misalign=misalign).reshape(n, n_heads, D))
+        ops.append(op)
+    aligned, got = outs
+    pos = np.arange(T)
+    _, k_all, v_all = er.split_qkv(qkv, n_heads, n_kv)
+    k_all = er.rope_np(k_all, ops[0].sin[pos, None, :], ops[0].cos[pos, None, :])
+    want, _, _ = er.extend_f64(qkv[past:], k_all[:past], v_all[:past], n_heads, n_kv, ops[0].sin, ops[0].cos)
+    assert np.isfinite(got).all()
+    err, c, d = float(np.max(np.abs(got - want))), cosine(got, want), float(np.max(np.abs(got - aligned)))
+    print(f"misaligned extend past={past} n={n} heads={n_heads}/{n_kv} f16={f16}: max|diff| vs f64 {err:.3e} cosine {c:.8f}; "
+          f"vs aligned {d:.3e} of max|aligned| {np.max(np.abs(aligned)):.3f}")
+    assert err <= 6e-3 and c >= 0.9999
+    assert d <= 2e-4 * np.max(np.abs(aligned))
+    iv = torch_.int16 if f16 else torch_.int32
+    assert torch_.equal(ops[1].kc.view(iv), ops[0].kc.view(iv)) and torch_.equal(ops[1].vc.view(iv), ops[0].vc.view(iv))
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------

@@ -76,6 +76,61 @@ def test_prefill_attention_matches_f64_reference(hip, oracle, torch_, T, n_heads
         hip.attention_prefill_dev(dev(qkv), dev(sin), dev(cos), kc, vc, n_heads, n_kv, D, 16 if T > 16 else 0, T, ws, wsb, out)
 
 
+def prefill_f64(qkv, sin, cos, n_heads, n_kv):
+    """causal GQA attention over a whole prompt in float64 -> [T, heads, D]; sin / cos [max_pos, D / 2]"""
+    T, D = qkv.shape[0], 128
+    q = qkv[:, : n_heads * D].reshape(T, n_heads, D).astype(np.float64)
+    k = qkv[:, n_heads * D:(n_heads + n_kv) * D].reshape(T, n_kv, D).astype(np.float64)
+    v = qkv[:, (n_heads + n_kv) * D:].reshape(T, n_kv, D).astype(np.float64)
+    q, k = rope_np(q, sin[:T, None, :], cos[:T, None, :]), rope_np(k, sin[:T, None, :], cos[:T, None, :])
+    want = np.zeros((T, n_heads, D))
+    mask = np.triu(np.ones((T, T), bool), 1)
+    for h in range(n_heads):
+        s = q[:, h] @ k[:, h // (n_heads // n_kv)].T / np.sqrt(D)
+        s[mask] = -np.inf
+        pm = np.exp(s - s.max(axis=1, keepdims=True))
+        want[:, h] = (pm / pm.sum(axis=1, keepdims=True)) @ v[:, h // (n_heads // n_kv)]
+    return want
+
+
+@pytest.mark.parametrize("f16", [False, True])
+@pytest.mark.parametrize("T,n_heads,n_kv", [(70, 4, 2), (130, 3, 3)])
+def test_prefill_attention_misaligned_rows(hip, oracle, torch_, T, n_heads, n_kv, f16):
+    """q|k|v rows 4 bytes off a 16-byte boundary through bitnet_hip_attention_prefill_flags_dev: k_prefill_prep then prepares the query image
+    too (one launch over heads + 2 kv slots, scalar loads) instead of the attention kernel reading the f32 rows.  The operator's gates against
+    float64, 2e-4 of max|aligned| against the aligned call on the same values, and the same caches bit for bit."""
+    D, max_pos = 128, 512
+    rng = np.random.default_rng(10 * T + (7 if f16 else 0))
+    qkv = rng.normal(0, 1.5, (T, (n_heads + 2 * n_kv) * D)).astype(np.float32)
+    sin, cos = oracle.rope_tables(D, max_pos, 10000.0)
+    sin, cos = sin.reshape(max_pos, D // 2), cos.reshape(max_pos, D // 2)
+    want = prefill_f64(qkv, sin, cos, n_heads, n_kv)
+    dev = lambda a: torch_.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+    sin_d, cos_d = dev(sin), dev(cos)
+    wsb = hip.attention_prefill_workspace_bytes(n_heads, n_kv, T)
+    dt, iv = (torch_.float16, torch_.int16) if f16 else (torch_.float32, torch_.int32)
+
+    def run(misalign):
+        buf = torch_.zeros(qkv.size + 1, device="cuda")
+        buf[1 if misalign else 0:][:qkv.size] = dev(qkv).ravel()
+        kc, vc = torch_.zeros(n_kv * max_pos * D, dtype=dt, device="cuda"), torch_.zeros(n_kv * max_pos * D, dtype=dt, device="cuda")
+        ws = torch_.full((wsb,), 0xFF, dtype=torch_.uint8, device="cuda")  # NaN patterns: nothing the call did not write may be read
+        out = torch_.full((T, n_heads * D), float("nan"), device="cuda")
+        hip.attention_prefill_flags_dev(buf.data_ptr() + (4 if misalign else 0), sin_d, cos_d, kc, vc, n_heads, n_kv, D, max_pos, T, ws, wsb, out, 1 if f16 else 0)
+        torch_.cuda.synchronize()
+        return out.cpu().numpy().reshape(T, n_heads, D), kc.view(iv), vc.view(iv)
+
+    aligned, kc0, vc0 = run(False)
+    got, kc1, vc1 = run(True)
+    assert np.isfinite(got).all()
+    err, c, d = float(np.max(np.abs(got - want))), cosine(got, want), float(np.max(np.abs(got - aligned)))
+    print(f"misaligned prefill T={T} heads={n_heads}/{n_kv} f16={f16}: max|diff| vs f64 {err:.3e} cosine {c:.8f}; "
+          f"vs aligned {d:.3e} of max|aligned| {np.max(np.abs(aligned)):.3f}")
+    assert err <= 6e-3 and c >= 0.9999
+    assert d <= 2e-4 * np.max(np.abs(aligned))
+    assert torch_.equal(kc1, kc0) and torch_.equal(vc1, vc0)
+
+
 SMALL = dict(hidden=512, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=128, ffn=1024, vocab=2048, max_pos=160, eps=1e-5, rope_theta=10000.0)
 WIDE = dict(hidden=2560, n_layers=2, n_heads=20, n_kv_heads=5, head_dim=128, ffn=6912, vocab=4096, max_pos=96, eps=1e-5, rope_theta=500000.0)
 

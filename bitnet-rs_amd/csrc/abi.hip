@@ -1551,7 +1551,8 @@ int bitnet_hip_logits_f16_dev(const void *table, const float *x, const float *ga
                               int32_t *history_dev, const int32_t *n_forced_dev, void *stream) {
     BH_GUARD_BEGIN
     if (!table || !x || !logits || !scratch) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to logits_f16_dev");
-    if (hidden % 512 != 0 || hidden > 8192) return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits: hidden %zu must be a multiple of 512, <= 8192", hidden);
+    if (hidden == 0 || hidden % 512 != 0 || hidden > 8192)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits: hidden %zu must be a multiple of 512, <= 8192", hidden);
     if (n_wg == 0 || n_wg > 65535) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logits: bad workgroup count %zu", n_wg);
     float *bv = static_cast<float *>(scratch);
     int *bi = reinterpret_cast<int *>(bv + n_wg);

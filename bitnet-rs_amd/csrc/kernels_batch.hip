@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void k_embed_q_batch(const _Float16 *__restric
 // lane l takes elements 512 c + 8 l + i in the order c, i as a fused multiply-add chain from 0 (what `acc += x * (float)w` compiles to in
 // k_logits_f16: v_fma_mix_f32), then the xor butterfly 32 .. 1 -- the batch-1 bits whatever R and the grid are.  The final norm is batch-1's
 // (block256_sum_f; its variance sum compiles to a fused multiply-add, written out here).  GUARD instances (hidden / 512 not an instance of its
-// own) also restate batch-1's padding: chunks past hidden / 512 add 0 * (chunk 0 of the row), which turns an accumulated -0 into +0.
+// own) also restate batch-1's padding: chunks past hidden / 512 add 0 * 0, which turns an accumulated -0 into +0.
 template <int NCH, int R, bool GUARD>
 __global__ __launch_bounds__(256) void k_logits_f16_batch(const _Float16 *__restrict__ table, const float *__restrict__ x, const float *__restrict__ gamma,
                                                           float eps, int hidden, int vocab, int n_seq, float *const *__restrict__ logits_ptrs,
@@ -354,8 +354,12 @@ __global__ __launch_bounds__(256) void k_logits_f16_batch(const _Float16 *__rest
         for (int r = 0; r < R; ++r) {
             const _Float16 *e = table + (size_t)(row + r < vocab ? row + r : vocab - 1) * hidden + 8 * lane;
 #pragma unroll
-            for (int c = 0; c < NCH; ++c)
-                w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const h8 *>(e + 512 * ((!GUARD || c < nchunks) ? c : 0)));
+            for (int c = 0; c < NCH; ++c) {
+                if (!GUARD || c < nchunks)
+                    w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const h8 *>(e + 512 * c));
+                else
+                    w[r][c] = (h8)(_Float16)0.0f;
+            }
         }
 #pragma unroll
         for (int b = 0; b < kBatchMax; ++b) {

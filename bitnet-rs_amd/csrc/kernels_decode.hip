@@ -78,7 +78,7 @@ constexpr int kLogitChunks = 16;  // 512 columns each
 
 // NCH = hidden / 512 (compile time: the activation slice lives in NCH*8 registers), R = vocabulary rows
 // per wave iteration (R * hidden * 2 bytes in flight per wave).
-// GUARD: hidden / 512 may be smaller than NCH (generic instance), chunks past it are skipped.
+// GUARD: hidden / 512 may be smaller than NCH (generic instance), chunks past it are padding: they add 0 * 0 to the row's sum.
 template <int NCH, int R, bool GUARD = false>
 __global__ __launch_bounds__(256) void k_logits_f16(const _Float16 *__restrict__ table, const float *__restrict__ x,
                                                     const float *__restrict__ gamma, float eps, int hidden, int vocab,
@@ -118,8 +118,13 @@ __global__ __launch_bounds__(256) void k_logits_f16(const _Float16 *__restrict__
             // rows past the end re-read the last row (never stored)
             const _Float16 *e = table + (size_t)(row + r < vocab ? row + r : vocab - 1) * hidden + 8 * lane;
 #pragma unroll
-            for (int c = 0; c < NCH; ++c)
-                w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const h8 *>(e + 512 * ((!GUARD || c < nchunks) ? c : 0)));
+            for (int c = 0; c < NCH; ++c) {
+                // a chunk past hidden / 512 is padding: zeros, not a second read of chunk 0 (0 * Inf of a table entry there would be NaN)
+                if (!GUARD || c < nchunks)
+                    w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const h8 *>(e + 512 * c));
+                else
+                    w[r][c] = (h8)(_Float16)0.0f;
+            }
         }
         float acc[R];
 #pragma unroll

@@ -137,6 +137,21 @@ def test_new_entry_points_validate_arguments_without_a_gpu(lib):
     assert b"Null pointer" in c.bitnet_hip_get_last_error()
 
 
+def test_logits_head_refuses_shapes_it_has_no_instance_for_without_a_gpu(lib, pkg):
+    """bitnet_hip_logits_f16_dev: hidden must be one of the kernel's instances (a multiple of 512 up to 8192; 0 is none), the workgroup count a
+    grid size.  Refused before the launch."""
+    import ctypes as C
+
+    buf = (C.c_uint8 * 4096)()
+    p = C.cast(buf, C.c_void_p)
+    head = lambda hidden, n_wg=8: lib.c.bitnet_hip_logits_f16_dev(p, p, None, 1e-5, hidden, 100, p, p, n_wg, None, None, None, None, None)
+    for hidden in (768, 8704):
+        assert head(hidden) == pkg.ERR_UNSUPPORTED and f"hidden {hidden} must be a multiple of 512, <= 8192" in lib.last_error(), hidden
+    assert head(0) == pkg.ERR_UNSUPPORTED
+    for n_wg in (0, 65536):
+        assert head(512, n_wg) == pkg.ERR_INVALID_ARGUMENT, n_wg
+
+
 def test_rejected_config_gives_a_dead_decoder_that_refuses_every_call(pkg):
     """a configuration the kernels cannot take (here hidden % 512 != 0, as untrusted GGUF metadata could say)
     used to leave an object whose layer table was empty while its layer count was not -- set_layer_* indexed past it.

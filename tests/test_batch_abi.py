@@ -69,6 +69,23 @@ def test_batch_entry_points_refuse_bad_arguments_without_a_device(lib):
     assert c.bitnet_hip_logits_f16_batch_dev(p, p, None, 1e-5, 512, 100, 2, p, None, 8, None, None, None, None, None) == INVALID and "Null pointer" in err()
 
 
+def test_batched_head_refuses_shapes_it_cannot_launch_without_a_device(lib):
+    """hidden outside the instances, more vectors than the LDS holds (152 KiB beside the kernel's static arrays) and a workgroup count outside the
+    grid's range: all refused before the launch, with the code and the wording a caller can act on."""
+    c = lib.c
+    buf = (C.c_uint8 * 4096)()
+    p = C.cast(buf, C.c_void_p)
+    UNSUPPORTED = -3  # BITNET_HIP_ERR_UNSUPPORTED
+    head = lambda hidden, n_seq, n_wg=8: c.bitnet_hip_logits_f16_batch_dev(p, p, None, 1e-5, hidden, 100, n_seq, p, p, n_wg, None, None, None, None, None)
+    for n_seq, hidden in ((8, 5120), (5, 8192)):   # 160 KiB each; 8 x 4608 (144 KiB) and 4 x 8192 (128 KiB) are the largest that run
+        assert head(hidden, n_seq) == UNSUPPORTED and "do not fit the LDS" in lib.last_error(), (n_seq, hidden)
+    for hidden in (768, 8704):
+        assert head(hidden, 2) == UNSUPPORTED and f"hidden {hidden} must be a multiple of 512, <= 8192" in lib.last_error(), hidden
+    assert head(0, 2) == UNSUPPORTED
+    for n_wg in (0, 65536):
+        assert head(512, 2, n_wg) == INVALID, n_wg
+
+
 def test_host_batch_shim_refuses_without_a_device(pkg):
     c = C.CDLL(pkg.HOST_LIB_PATH)
     c.bitnet_host_batch_create.restype = C.c_void_p

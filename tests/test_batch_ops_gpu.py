@@ -129,7 +129,7 @@ POSITIONS = [0, 63, 64, 127, 128, 191, 200, 319]
 
 
 @pytest.mark.parametrize("kv_f16", [False, True])
-@pytest.mark.parametrize("n_heads,n_kv", [(20, 5), (2, 2)])
+@pytest.mark.parametrize("n_heads,n_kv", [(20, 5), (2, 2), (6, 2)])
 def test_attention_batch_bits_equal_batch1(hip, oracle, torch_, n_heads, n_kv, kv_f16):
     D, max_pos, n_seq = 128, 320, 8
     rng = np.random.default_rng(n_heads * 3 + n_kv + kv_f16)

@@ -120,9 +120,12 @@ def test_fused_gemv_ln_residual_silu(hip, pkg, oracle, torch_):
 
 SMALL = dict(hidden=512, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=128, ffn=1024, vocab=2048, max_pos=64, eps=1e-5, rope_theta=10000.0)
 WIDE = dict(hidden=2560, n_layers=2, n_heads=20, n_kv_heads=5, head_dim=128, ffn=6912, vocab=4096, max_pos=48, eps=1e-5, rope_theta=500000.0)
+# a query group of 3 (the attention records are combined by their own launch: the merging o-projection takes groups 1, 2, 4) on hidden 1536 (the
+# guarded <8, 2> instance of the logits head)
+GROUP3 = dict(hidden=1536, n_layers=2, n_heads=12, n_kv_heads=4, head_dim=128, ffn=2048, vocab=2048, max_pos=64, eps=1e-5, rope_theta=10000.0)
 
 
-@pytest.mark.parametrize("cfgd,n_prompt,n_new", [(SMALL, 5, 12), (WIDE, 4, 6)])
+@pytest.mark.parametrize("cfgd,n_prompt,n_new", [(SMALL, 5, 12), (WIDE, 4, 6), (GROUP3, 4, 6)])
 def test_decode_tokens_match_oracle(hip, pkg, oracle, synth, cfgd, n_prompt, n_new):
     cfg = synth.ModelConfig(**cfgd)
     layers = [synth.make_layer(cfg, l) for l in range(cfg.n_layers)]
@@ -216,7 +219,8 @@ def test_decode_across_chunk_boundaries_teacher_forced(hip, pkg, oracle, synth):
     (512, [0, 1, 62, 63, 64, 65, 127, 128, 129, 300, 511], 8, 2),
     (512, [0, 63, 64, 200], 4, 2),      # query group of 2
     (512, [5, 64, 191], 3, 3),          # no grouping
-    (8192, [0, 100, 3071, 3072, 5000, 8100], 8, 2)])
+    (8192, [0, 100, 3071, 3072, 5000, 8100], 8, 2),
+    (512, [0, 63, 64, 127, 128, 200], 6, 2)])   # query group of 3: the fourth RoPE wave has no head of its own
 @pytest.mark.parametrize("wide", [False, True])
 def test_attention_decode_op_vs_f64(hip, oracle, torch_, max_pos, positions, n_heads, n_kv, wide):
     """One-token attention (RoPE + append + GQA softmax) at many context lengths against a f64 numpy
@@ -376,7 +380,8 @@ def test_decode_is_bit_reproducible_run_to_run(hip, pkg, synth):
 
 
 @pytest.mark.parametrize("max_pos,positions,n_heads,n_kv,wide", [(512, [0, 1, 63, 64, 65, 127, 128, 300, 511], 8, 2, False), (512, [0, 64, 191], 3, 3, False),
-                                                                (8192, [0, 100, 3071, 3072, 5000, 8100], 8, 2, True), (4608, [4100, 4223, 4224], 20, 5, True)])
+                                                                (8192, [0, 100, 3071, 3072, 5000, 8100], 8, 2, True), (4608, [4100, 4223, 4224], 20, 5, True),
+                                                                (512, [0, 63, 64, 127, 128, 200], 6, 2, False), (512, [0, 63, 64, 127, 128, 200], 6, 2, True)])  # query group of 3
 def test_attention_decode_f16_kv_vs_f64(hip, oracle, torch_, max_pos, positions, n_heads, n_kv, wide):
     """BITNET_HIP_ATTN_KV_F16: the cache holds f16 (K [kv][chunk][64 dim pairs][64 positions][2], V [kv][pos][128]), k / v are
     rounded once when appended.  Against a f64 reference that uses the SAME f16 values: the arithmetic (f32 accumulate) is as

@@ -918,55 +918,57 @@ int bitnet_hip_embed_f16_dev(const void *table, const int32_t *tokens_dev, const
     BH_GUARD_END
 }
 
+// The decode attention entries' shape rules, one place each: check_attn_heads (T:215-220), then check_attn_head_dim.  The batched entry has a
+// line of its own between the two, which is why they are two functions.
+static int check_attn_heads(size_t n_heads, size_t n_kv_heads) {
+    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
+    return BITNET_HIP_OK;
+}
+static int check_attn_head_dim(size_t n_heads, size_t n_kv_heads, size_t head_dim) {
+    if (head_dim != 128 || n_heads / n_kv_heads > 4)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "attention_decode: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)", head_dim,
+                         n_heads / n_kv_heads);
+    return BITNET_HIP_OK;
+}
+
+// The body of the four batch-1 decode attention entries.  `missing` = the entry's own null-pointer set (`entry` names it in the message);
+// combine = false leaves the chunk records in `scratch`, halves = 2 is the 128-position form.
+static int attention_decode(const char *entry, bool missing, const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache,
+                            size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos, const int32_t *pos_dev, float *scratch, float *out,
+                            void *qact_out, bool combine, int halves, int kv_f16, void *stream) {
+    BH_GUARD_BEGIN
+    if (missing) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to %s", entry);
+    if (int rc = check_attn_heads(n_heads, n_kv_heads)) return rc;
+    if (int rc = check_attn_head_dim(n_heads, n_kv_heads, head_dim)) return rc;
+    BH_HIP_TRY(launch_attn_decode(qkv, rope_sin, rope_cos, static_cast<float *>(kcache), static_cast<float *>(vcache), (int)n_heads, (int)n_kv_heads,
+                                  (int)head_dim, (int)max_pos, pos_dev, scratch, out, (hipStream_t)stream, combine, halves, qact_out, kv_f16));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 int bitnet_hip_attention_decode_dev(const float *qkv, const float *rope_sin, const float *rope_cos, float *kcache,
                                     float *vcache, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,
                                     const int32_t *pos_dev, float *scratch, float *out, void *stream) {
-    BH_GUARD_BEGIN
-    if (!qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch || !out)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_decode_dev");
-    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)  // T:215-220
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
-    if (head_dim != 128 || n_heads / n_kv_heads > 4)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "attention_decode: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)",
-                         head_dim, n_heads / n_kv_heads);
-    BH_HIP_TRY(launch_attn_decode(qkv, rope_sin, rope_cos, kcache, vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim,
-                                  (int)max_pos, pos_dev, scratch, out, (hipStream_t)stream));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    const bool missing = !qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch || !out;
+    return attention_decode("attention_decode_dev", missing, qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv_heads, head_dim, max_pos, pos_dev, scratch,
+                            out, /*qact_out*/ nullptr, /*combine*/ true, /*halves*/ 1, /*kv_f16*/ 0, stream);
 }
 
 int bitnet_hip_attention_decode_wide_dev(const float *qkv, const float *rope_sin, const float *rope_cos, float *kcache,
                                          float *vcache, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,
                                          const int32_t *pos_dev, float *scratch, float *out, void *stream) {
-    BH_GUARD_BEGIN
-    if (!qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch || !out)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_decode_wide_dev");
-    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
-    if (head_dim != 128 || n_heads / n_kv_heads > 4)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "attention_decode: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)",
-                         head_dim, n_heads / n_kv_heads);
-    BH_HIP_TRY(launch_attn_decode(qkv, rope_sin, rope_cos, kcache, vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim,
-                                  (int)max_pos, pos_dev, scratch, out, (hipStream_t)stream, true, 2));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    const bool missing = !qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch || !out;
+    return attention_decode("attention_decode_wide_dev", missing, qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv_heads, head_dim, max_pos, pos_dev,
+                            scratch, out, /*qact_out*/ nullptr, /*combine*/ true, /*halves*/ 2, /*kv_f16*/ 0, stream);
 }
 
 int bitnet_hip_attention_decode_partial_dev(const float *qkv, const float *rope_sin, const float *rope_cos, float *kcache,
                                             float *vcache, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos,
                                             const int32_t *pos_dev, float *scratch, void *stream) {
-    BH_GUARD_BEGIN
-    if (!qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_decode_partial_dev");
-    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
-    if (head_dim != 128 || n_heads / n_kv_heads > 4)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "attention_decode: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)",
-                         head_dim, n_heads / n_kv_heads);
-    BH_HIP_TRY(launch_attn_decode(qkv, rope_sin, rope_cos, kcache, vcache, (int)n_heads, (int)n_kv_heads, (int)head_dim,
-                                  (int)max_pos, pos_dev, scratch, nullptr, (hipStream_t)stream, false));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    const bool missing = !qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch;
+    return attention_decode("attention_decode_partial_dev", missing, qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv_heads, head_dim, max_pos, pos_dev,
+                            scratch, /*out*/ nullptr, /*qact_out*/ nullptr, /*combine*/ false, /*halves*/ 1, /*kv_f16*/ 0, stream);
 }
 
 size_t bitnet_hip_attention_merge_max_keys(void) { return (size_t)4 * 64; }
@@ -990,34 +992,30 @@ static int gemv_attn_merge(bitnet_hip_weights_t h, const float *attn_scratch_dev
     if (records != 4 && !(qact_out && gemvq_supported(*w) && w->cols <= 2560))
         return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_attn_merge_rec_q_dev: %d records need a QAct matrix of at most 2560 columns (got %zux%zu)", records,
                          w->rows, w->cols);
+    // the merge fields and outputs, which GemvQIo and GemvFusion name alike
+    auto fill = [&](auto &f) {
+        f.residual = residual_dev;
+        f.qout = qact_out;
+        f.gamma_out = gamma_out_dev;
+        f.stats_out = stats_out;
+        f.attn_rec = attn_scratch_dev;
+        f.attn_pos = pos_dev;
+        f.attn_chunk_log2 = chunk_log2;
+        f.attn_chunks_max = (int)div_ceil(max_pos, (size_t)1 << chunk_log2);
+        f.attn_group_log2 = group == 4 ? 2 : group == 2 ? 1 : 0;
+    };
     if (qact_out && gemvq_supported(*w) && w->cols <= 4096) {
         // QAct consumer form: the workgroup merges the records and quantises them once, into its LDS image (kernels_gemvq.hip MRG)
         GemvQIo io;
-        io.residual = residual_dev;
+        fill(io);
         io.y = y_dev;
-        io.qout = qact_out;
-        io.gamma_out = gamma_out_dev;
-        io.stats_out = stats_out;
-        io.attn_rec = attn_scratch_dev;
-        io.attn_pos = pos_dev;
-        io.attn_chunk_log2 = chunk_log2;
-        io.attn_chunks_max = (int)div_ceil(max_pos, (size_t)1 << chunk_log2);
-        io.attn_group_log2 = group == 4 ? 2 : group == 2 ? 1 : 0;
         io.attn_records = records;
         hipError_t e = launch_gemv_q(*w, io, (hipStream_t)stream);
         if (e != hipSuccess) return set_error(BITNET_HIP_ERR_GPU, "kernel launch failed: %s", hipGetErrorString(e));
         return BITNET_HIP_OK;
     }
     GemvFusion fu;
-    fu.residual = residual_dev;
-    fu.attn_rec = attn_scratch_dev;
-    fu.attn_pos = pos_dev;
-    fu.attn_chunk_log2 = chunk_log2;
-    fu.attn_chunks_max = (int)div_ceil(max_pos, (size_t)1 << fu.attn_chunk_log2);
-    fu.attn_group_log2 = group == 4 ? 2 : group == 2 ? 1 : 0;
-    fu.qout = qact_out;
-    fu.gamma_out = gamma_out_dev;
-    fu.stats_out = stats_out;
+    fill(fu);
     return run_gemv(*w, attn_scratch_dev, y_dev, 1, fu, (hipStream_t)stream, BITNET_HIP_KERNEL_MFMA);
     BH_GUARD_END
 }
@@ -1073,17 +1071,14 @@ int bitnet_hip_gemv_q_supported(bitnet_hip_weights_t h) {
     return w && gemvq_supported(*w) ? 1 : 0;
 }
 
-int bitnet_hip_gemv_q_dev(bitnet_hip_weights_t h, const void *qact_in, const double *stats_in, const float *ln_gamma_dev, float ln_eps,
-                          const float *residual_dev, int flags, float *y_dev, void *qact_out, const float *gamma_out_dev, double *stats_out,
-                          void *stream) {
-    BH_GUARD_BEGIN
-    const WeightsRef w = lookup(h);
-    if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
-    if (!qact_in || (!y_dev && !qact_out)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_q_dev");
-    if (!gemvq_supported(*w))
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_dev: matrix %zux%zu (block %zu) is not on the QAct path (cols %% 256 == 0, rows %% 16 == 0, no scales or 32-element blocks)",
-                         w->rows, w->cols, w->block_size);
-    GemvQIo io;
+// What bitnet_hip_gemv_q_dev and bitnet_hip_gemv_q_batch_dev share behind their own first lines (handle and null pointers, in each entry's
+// order): is the matrix on the QAct path, `io` from the arguments, silu * up pairing, the LayerNorm binding and its column limit.  `entry`
+// names the caller in the messages.
+static int gemv_q_front(const char *entry, const Weights &w, const void *qact_in, const double *stats_in, const float *ln_gamma_dev, float ln_eps,
+                        const float *residual_dev, int flags, float *y_dev, void *qact_out, const float *gamma_out_dev, double *stats_out, GemvQIo &io) {
+    if (!gemvq_supported(w))
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "%s: matrix %zux%zu (block %zu) is not on the QAct path (cols %% 256 == 0, rows %% 16 == 0, no scales or 32-element blocks)",
+                         entry, w.rows, w.cols, w.block_size);
     io.qin = qact_in;
     io.stats_in = stats_in;
     io.ln_gamma = ln_gamma_dev;
@@ -1094,12 +1089,24 @@ int bitnet_hip_gemv_q_dev(bitnet_hip_weights_t h, const void *qact_in, const dou
     io.qout = qact_out;
     io.gamma_out = gamma_out_dev;
     io.stats_out = stats_out;
-    if (io.silu_mul && (!w->paired || residual_dev || w->rows % 32 != 0))
+    if (io.silu_mul && (!w.paired || residual_dev || w.rows % 32 != 0))
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
-    if (ln_gamma_dev && (!stats_in || !w->ln_g || w->ln_gamma_bound != ln_gamma_dev))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "gemv_q_dev: LayerNorm needs stats_in and the gamma bound with bitnet_hip_weights_bind_ln");
-    if (ln_gamma_dev && w->cols > 4096)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_dev: LayerNorm input of %zu columns (<= 4096)", w->cols);
+    if (ln_gamma_dev && (!stats_in || !w.ln_g || w.ln_gamma_bound != ln_gamma_dev))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: LayerNorm needs stats_in and the gamma bound with bitnet_hip_weights_bind_ln", entry);
+    if (ln_gamma_dev && w.cols > 4096) return set_error(BITNET_HIP_ERR_UNSUPPORTED, "%s: LayerNorm input of %zu columns (<= 4096)", entry, w.cols);
+    return BITNET_HIP_OK;
+}
+
+int bitnet_hip_gemv_q_dev(bitnet_hip_weights_t h, const void *qact_in, const double *stats_in, const float *ln_gamma_dev, float ln_eps,
+                          const float *residual_dev, int flags, float *y_dev, void *qact_out, const float *gamma_out_dev, double *stats_out,
+                          void *stream) {
+    BH_GUARD_BEGIN
+    const WeightsRef w = lookup(h);
+    if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
+    if (!qact_in || (!y_dev && !qact_out)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_q_dev");
+    GemvQIo io;
+    if (int rc = gemv_q_front("gemv_q_dev", *w, qact_in, stats_in, ln_gamma_dev, ln_eps, residual_dev, flags, y_dev, qact_out, gamma_out_dev, stats_out, io))
+        return rc;
     hipError_t e = launch_gemv_q(*w, io, (hipStream_t)stream);
     if (e != hipSuccess) return set_error(BITNET_HIP_ERR_GPU, "kernel launch failed: %s", hipGetErrorString(e));
     return BITNET_HIP_OK;
@@ -1109,20 +1116,30 @@ int bitnet_hip_gemv_q_dev(bitnet_hip_weights_t h, const void *qact_in, const dou
 int bitnet_hip_attention_decode_q_dev(const float *qkv, const float *rope_sin, const float *rope_cos, void *kcache, void *vcache,
                                       size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_pos, const int32_t *pos_dev,
                                       float *scratch, int flags, float *out, void *qact_out, void *stream) {
-    const int wide = (flags & BITNET_HIP_ATTN_WIDE) != 0, kv16 = (flags & BITNET_HIP_ATTN_KV_F16) != 0, partial = (flags & BITNET_HIP_ATTN_PARTIAL) != 0;
-    BH_GUARD_BEGIN
-    if (!qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch || (!out && !qact_out && !partial))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_decode_q_dev");
-    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
-    if (head_dim != 128 || n_heads / n_kv_heads > 4)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "attention_decode: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)",
-                         head_dim, n_heads / n_kv_heads);
-    BH_HIP_TRY(launch_attn_decode(qkv, rope_sin, rope_cos, static_cast<float *>(kcache), static_cast<float *>(vcache), (int)n_heads, (int)n_kv_heads,
-                                  (int)head_dim, (int)max_pos, pos_dev, scratch, out, (hipStream_t)stream, !partial, wide ? 2 : 1, qact_out, kv16));
-    return BITNET_HIP_OK;
-    BH_GUARD_END
+    const bool partial = (flags & BITNET_HIP_ATTN_PARTIAL) != 0;
+    const bool missing = !qkv || !rope_sin || !rope_cos || !kcache || !vcache || !pos_dev || !scratch || (!out && !qact_out && !partial);
+    return attention_decode("attention_decode_q_dev", missing, qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv_heads, head_dim, max_pos, pos_dev, scratch,
+                            out, qact_out, /*combine*/ !partial, /*halves*/ (flags & BITNET_HIP_ATTN_WIDE) ? 2 : 1, /*kv_f16*/ (flags & BITNET_HIP_ATTN_KV_F16) != 0,
+                            stream);
 }
+
+/* ---- the logits head's entries, batch-1 (further down) and batched: their shared limits and scratch split ---- */
+
+static int check_logits_hidden(size_t hidden) {
+    if (hidden == 0 || hidden % 512 != 0 || hidden > 8192)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits: hidden %zu must be a multiple of 512, <= 8192", hidden);
+    return BITNET_HIP_OK;
+}
+static int check_logits_n_wg(size_t n_wg) {
+    if (n_wg == 0 || n_wg > 65535) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logits: bad workgroup count %zu", n_wg);
+    return BITNET_HIP_OK;
+}
+// the per-workgroup maxima in `scratch`: n values, then their n indices
+struct BestScratch {
+    float *val;
+    int *idx;
+    BestScratch(void *scratch, size_t n) : val(static_cast<float *>(scratch)), idx(reinterpret_cast<int *>(val + n)) {}
+};
 
 /* ---- several sequences per launch (kernels_batch.hip; k_attn_partial_batch / k_attn_combine_batch in kernels_attn.hip) ---- */
 
@@ -1153,27 +1170,10 @@ int bitnet_hip_gemv_q_batch_dev(bitnet_hip_weights_t h, size_t n_seq, const void
     if (!qact_in || (!y_dev && !qact_out)) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_q_batch_dev");
     const WeightsRef w = lookup(h);
     if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
-    if (!gemvq_supported(*w))
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_batch_dev: matrix %zux%zu (block %zu) is not on the QAct path (cols %% 256 == 0, rows %% 16 == 0, no scales or 32-element blocks)",
-                         w->rows, w->cols, w->block_size);
     GemvQIo io;
-    io.qin = qact_in;
-    io.stats_in = stats_in;
-    io.ln_gamma = ln_gamma_dev;
-    io.ln_eps = ln_eps;
-    io.residual = residual_dev;
-    io.silu_mul = (flags & BITNET_HIP_FUSE_SILU_MUL) != 0;
-    io.y = y_dev;
-    io.qout = qact_out;
-    io.gamma_out = gamma_out_dev;
-    io.stats_out = stats_out;
-    if (io.silu_mul && (!w->paired || residual_dev || w->rows % 32 != 0))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no residual");
-    if (ln_gamma_dev && (!stats_in || !w->ln_g || w->ln_gamma_bound != ln_gamma_dev))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "gemv_q_batch_dev: LayerNorm needs stats_in and the gamma bound with bitnet_hip_weights_bind_ln");
-    if (ln_gamma_dev && w->cols > 4096)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_batch_dev: LayerNorm input of %zu columns (<= 4096)", w->cols);
-    const size_t lds = gemv_q_batch_lds_bytes(*w, ln_gamma_dev != nullptr, io.silu_mul, (int)n_seq);
+    if (int rc = gemv_q_front("gemv_q_batch_dev", *w, qact_in, stats_in, ln_gamma_dev, ln_eps, residual_dev, flags, y_dev, qact_out, gamma_out_dev, stats_out, io))
+        return rc;
+    const size_t lds = gemv_q_batch_lds_bytes(*w, gemv_geometry(*w, io.silu_mul), ln_gamma_dev != nullptr, (int)n_seq);
     if (lds > 160 * 1024)
         return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_batch_dev: %zu vectors of %zu columns need %zu bytes of LDS (160 KiB): take them in smaller groups",
                          n_seq, w->cols, lds);
@@ -1192,12 +1192,9 @@ int bitnet_hip_attention_decode_batch_dev(const float *qkv, const float *rope_si
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_decode_batch_dev");
     if (flags & ~BITNET_HIP_ATTN_KV_F16)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_decode_batch_dev: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16: 64-position records + combine only)", flags);
-    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
+    if (int rc = check_attn_heads(n_heads, n_kv_heads)) return rc;
     if (max_pos == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_decode_batch_dev: max_pos 0");
-    if (head_dim != 128 || n_heads / n_kv_heads > 4)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "attention_decode: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)", head_dim,
-                         n_heads / n_kv_heads);
+    if (int rc = check_attn_head_dim(n_heads, n_kv_heads, head_dim)) return rc;
     BH_HIP_TRY(launch_attn_decode_batch(qkv, rope_sin, rope_cos, reinterpret_cast<float *const *>(kcache_ptrs_dev), reinterpret_cast<float *const *>(vcache_ptrs_dev),
                                         reinterpret_cast<const int *const *>(pos_ptrs_dev), (int)n_seq, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos,
                                         scratch, out, qact_out, (flags & BITNET_HIP_ATTN_KV_F16) != 0, (hipStream_t)stream));
@@ -1211,15 +1208,13 @@ int bitnet_hip_logits_f16_batch_dev(const void *table, const float *x, const flo
     BH_GUARD_BEGIN
     if (int rc = check_n_seq(n_seq, "logits_f16_batch_dev")) return rc;
     if (!table || !x || !logits_ptrs_dev || !scratch) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to logits_f16_batch_dev");
-    if (hidden == 0 || hidden % 512 != 0 || hidden > 8192)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits: hidden %zu must be a multiple of 512, <= 8192", hidden);
-    if (n_seq * hidden * sizeof(float) > 152 * 1024)
+    if (int rc = check_logits_hidden(hidden)) return rc;
+    if (n_seq * hidden * sizeof(float) > 152 * 1024)  // (between the two shared checks, where it always stood)
         return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits_f16_batch_dev: %zu vectors of %zu columns do not fit the LDS (152 KiB): take them in smaller groups", n_seq,
                          hidden);
-    if (n_wg == 0 || n_wg > 65535) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logits: bad workgroup count %zu", n_wg);
-    float *bv = static_cast<float *>(scratch);
-    int *bi = reinterpret_cast<int *>(bv + n_seq * n_wg);
-    BH_HIP_TRY(launch_logits_f16_batch(table, x, gamma, eps, (int)hidden, (int)vocab, (int)n_seq, logits_ptrs_dev, bv, bi, (int)n_wg,
+    if (int rc = check_logits_n_wg(n_wg)) return rc;
+    const BestScratch best(scratch, n_seq * n_wg);
+    BH_HIP_TRY(launch_logits_f16_batch(table, x, gamma, eps, (int)hidden, (int)vocab, (int)n_seq, logits_ptrs_dev, best.val, best.idx, (int)n_wg,
                                        reinterpret_cast<int *const *>(token_ptrs_dev), reinterpret_cast<int *const *>(pos_ptrs_dev),
                                        reinterpret_cast<int *const *>(history_ptrs_dev), reinterpret_cast<const int *const *>(n_forced_ptrs_dev),
                                        (hipStream_t)stream));
@@ -1551,14 +1546,12 @@ int bitnet_hip_logits_f16_dev(const void *table, const float *x, const float *ga
                               int32_t *history_dev, const int32_t *n_forced_dev, void *stream) {
     BH_GUARD_BEGIN
     if (!table || !x || !logits || !scratch) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to logits_f16_dev");
-    if (hidden == 0 || hidden % 512 != 0 || hidden > 8192)
-        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "logits: hidden %zu must be a multiple of 512, <= 8192", hidden);
-    if (n_wg == 0 || n_wg > 65535) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logits: bad workgroup count %zu", n_wg);
-    float *bv = static_cast<float *>(scratch);
-    int *bi = reinterpret_cast<int *>(bv + n_wg);
-    BH_HIP_TRY(launch_logits_f16(table, x, gamma, eps, (int)hidden, (int)vocab, logits, bv, bi, (int)n_wg, (hipStream_t)stream));
+    if (int rc = check_logits_hidden(hidden)) return rc;
+    if (int rc = check_logits_n_wg(n_wg)) return rc;
+    const BestScratch best(scratch, n_wg);
+    BH_HIP_TRY(launch_logits_f16(table, x, gamma, eps, (int)hidden, (int)vocab, logits, best.val, best.idx, (int)n_wg, (hipStream_t)stream));
     if (token_dev || pos_dev)
-        BH_HIP_TRY(launch_argmax_final(bv, bi, (int)n_wg, token_dev, pos_dev, history_dev, n_forced_dev, (hipStream_t)stream));
+        BH_HIP_TRY(launch_argmax_final(best.val, best.idx, (int)n_wg, token_dev, pos_dev, history_dev, n_forced_dev, (hipStream_t)stream));
     return BITNET_HIP_OK;
     BH_GUARD_END
 }
@@ -1567,9 +1560,8 @@ int bitnet_hip_argmax_dev(const float *v, size_t n, void *scratch, size_t n_wg, 
     BH_GUARD_BEGIN
     if (!v || !scratch || !token_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to argmax_dev");
     if (n == 0 || n_wg == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "argmax: empty input");
-    float *bv = static_cast<float *>(scratch);
-    int *bi = reinterpret_cast<int *>(bv + n_wg);
-    BH_HIP_TRY(launch_argmax(v, (int)n, bv, bi, (int)n_wg, token_dev, (hipStream_t)stream));
+    const BestScratch best(scratch, n_wg);
+    BH_HIP_TRY(launch_argmax(v, (int)n, best.val, best.idx, (int)n_wg, token_dev, (hipStream_t)stream));
     return BITNET_HIP_OK;
     BH_GUARD_END
 }

@@ -8,6 +8,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <memory>
@@ -148,7 +149,43 @@ hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m
                             hipStream_t stream);
 bool mfma_supported(const Weights &w);
 int mfma_pick_ksplit(size_t rows, size_t cols, bool paired, int nw);
+// The K partition of one decode GEMV launch (kernels_mfma.hip, beside mfma_pick_ksplit): launch_gemv_mfma, launch_gemv_q and launch_gemv_q_batch
+// take every one of these numbers from here, so the batched launch cannot choose another partition than batch-1 (its per-vector bit identity).
+struct GemvGeom {
+    int ksplit, ks_log2;  // K ranges per row tile = waves sharing a tile (1, 2, 4 or 8)
+    int nblk;             // 256-column blocks per row
+    int ring, ring_t;     // blocks per wave, and the instantiated RING that holds them (LDS plane stride)
+    int tiles_per_wg;
+    unsigned grid;
+    int sc;               // 32-block weight scales: 0 none, 1 f32 tiles, 2 f16 tiles
+};
+GemvGeom gemv_geometry(const Weights &w, bool silu_mul, int n_waves = 8);
 bool gemvq_supported(const Weights &w);
+// What k_gemv_q's and k_gemv_q_batch's argument structs begin with (they derive from it: the kernels see the members where they always were),
+// and its one fill (kernels_gemvq.hip), which also refuses what these members cannot express: scale tiles missing, a LayerNorm that is not the
+// bound one or comes without statistics, silu * up on an unpaired matrix or with a residual.
+struct GemvQPrefix {
+    const uint8_t *tiles;    // [n_tiles][nblk][64 lanes][16 B] code tiles (k_retile)
+    const void *stiles;      // [n_tiles][nblk][64 lanes] x {f16 x 2 | f32 x 2}: 32-block scales (k_retile_scales[_h]) or null
+    int rows, cols, nblk;
+    uint32_t lut;
+    int ks_log2;             // K ranges per row tile = waves sharing a tile
+    const uint8_t *qin;      // QAct records [nblk][576]; batched: [n_seq][qbytes]
+    const double *stats_in;  // LN: (sum, sum of squares) per 16 columns; batched: [n_seq][n_stats][2]
+    int n_stats;
+    const float *ln_g;       // LN: g_r = W[r,:] . gamma (bitnet_hip_weights_bind_ln)
+    float ln_eps;
+    double inv_cols;
+    const float *residual;   // optional: v = residual + W x; batched: [n_seq][out_rows]
+    float *y;                // optional f32 output; batched: [n_seq][out_rows]
+    int silu_mul;            // rows are (gate tile, up tile) pairs: v = silu(gate) * up
+    uint8_t *qout;           // optional QAct output (for the next GEMV); batched: [n_seq][qout_bytes]
+    const float *gamma_out;  // optional: the next GEMV's LayerNorm weight (u = v * gamma); shared by a batch
+    double *stats_out;       // optional: (sum, sum of squares) per 16 output rows; batched: [n_seq][out_rows / 16][2]
+};
+static_assert(offsetof(GemvQPrefix, qin) == 40 && offsetof(GemvQPrefix, inv_cols) == 80 && offsetof(GemvQPrefix, stats_out) == 128 && sizeof(GemvQPrefix) == 136,
+              "the kernels' argument layout: the derived structs' own members begin at 136");
+hipError_t fill_gemv_q_prefix(GemvQPrefix &a, const Weights &w, const GemvQIo &io, const GemvGeom &g);
 hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream);
 hipError_t launch_quant_act(const float *x, const float *gamma, size_t n, void *qout, double *stats, hipStream_t stream);
 hipError_t launch_embed_q(const void *table, const int *tokens, const int *offset_ptr, int hidden, int vocab, float *x_out,
@@ -157,7 +194,7 @@ hipError_t launch_embed_q(const void *table, const int *tokens, const int *offse
 //      per-sequence state (caches, positions, histories, logits rows) is reached through DEVICE pointer tables, a NULL entry = idle slot ----
 constexpr int kBatchMax = 8;  // BITNET_HIP_BATCH_MAX
 hipError_t launch_gemv_q_batch(const Weights &w, const GemvQIo &io, int n_seq, hipStream_t stream);
-size_t gemv_q_batch_lds_bytes(const Weights &w, bool ln, bool silu_mul, int n_seq);
+size_t gemv_q_batch_lds_bytes(const Weights &w, const GemvGeom &g, bool ln, int n_seq);
 hipError_t launch_embed_q_batch(const void *table, const int *const *history_ptrs, const int *const *pos_ptrs, int n_seq, int hidden, int vocab,
                                 float *x_out, const float *gamma, void *qout, double *stats, hipStream_t stream);
 hipError_t launch_attn_decode_batch(const float *qkv, const float *rope_sin, const float *rope_cos, float *const *kc_ptrs, float *const *vc_ptrs,
@@ -292,6 +329,14 @@ hipError_t launch_attn_packed(const float *qkv, int n_rows, const float *rope_si
                               size_t workspace_bytes, void *out, int flags, hipStream_t stream);
 hipError_t launch_pack_cols(const float *src, size_t ld, size_t col0, size_t ncols, size_t rows, void *dst, int f16, hipStream_t stream);
 hipError_t launch_stream_read(const void *buf, size_t bytes, unsigned *sink, hipStream_t stream);
+// The logits head's kernel instance for a hidden size (kernels_decode.hip): k_logits_f16<nch, r, guard> and k_logits_f16_batch<nch, r, guard>.
+// nch x 512 columns are what a row is padded to, so both launchers pick from here; rows5 = rows per wave of the 2560-column instance
+// (2, 3 or 4: R does not enter a row's arithmetic).  nch == 0: hidden is no multiple of 512 or beyond 8192.
+struct LogitsInstance {
+    int nch, r;
+    bool guard;
+};
+LogitsInstance logits_instance(int hidden, int rows5);
 hipError_t launch_logits_f16(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab,
                              float *logits, float *best_val, int *best_idx, int n_wg, hipStream_t stream);
 hipError_t launch_argmax_final(const float *best_val, const int *best_idx, int n, int *token_out, int *pos_ptr,

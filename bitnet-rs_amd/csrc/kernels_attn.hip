@@ -509,6 +509,9 @@ size_t attn_scratch_floats(int n_kv, int max_pos) {
     return (size_t)n_kv * ((max_pos + kAttnChunk - 1) / kAttnChunk) * kRec;
 }
 
+// k_attn_combine's / k_attn_combine_batch's instance for a record count: NR trips of 8 records cover it (1, 2, 5 or 8)
+static int attn_combine_nr(int n_rec) { return n_rec <= 8 ? 1 : n_rec <= 16 ? 2 : n_rec <= 40 ? 5 : 8; }
+
 hipError_t launch_attn_decode(const float *qkv, const float *rope_sin, const float *rope_cos, float *kcache,
                               float *vcache, int n_heads, int n_kv, int D, int max_pos, const int *pos_ptr,
                               float *scratch, float *out, hipStream_t stream, bool combine, int halves, void *qout, int kv_f16) {
@@ -521,7 +524,8 @@ hipError_t launch_attn_decode(const float *qkv, const float *rope_sin, const flo
     // combine == false: the chunk records stay in `scratch` for a consumer that merges them itself
     // (launch_gemv_mfma with GemvFusion::attn_rec)
     if (combine) {
-        auto cfn = n_rec <= 8 ? k_attn_combine<1> : n_rec <= 16 ? k_attn_combine<2> : n_rec <= 40 ? k_attn_combine<5> : k_attn_combine<8>;
+        const int nr = attn_combine_nr(n_rec);
+        auto cfn = nr == 1 ? k_attn_combine<1> : nr == 2 ? k_attn_combine<2> : nr == 5 ? k_attn_combine<5> : k_attn_combine<8>;
         hipLaunchKernelGGL(cfn, dim3(n_kv, n_heads / n_kv), dim3(256), 0, stream, scratch, n_kv, n_heads / n_kv, n_rec, halves == 2 ? 7 : 6, pos_ptr, out,
                            static_cast<uint8_t *>(qout));
     }
@@ -537,8 +541,8 @@ hipError_t launch_attn_decode_batch(const float *qkv, const float *rope_sin, con
     auto kfn = kv_f16 ? k_attn_partial_batch<true> : k_attn_partial_batch<false>;
     hipLaunchKernelGGL(kfn, dim3(n_kv, n_rec, n_seq), dim3(256), 0, stream, qkv, rope_sin, rope_cos, kc_ptrs, vc_ptrs, n_heads, n_kv, n_heads / n_kv, max_pos,
                        pos_ptrs, scratch, qkv_stride, scratch_stride);
-    // the combine instance launch_attn_decode takes for this record count
-    auto cfn = n_rec <= 8 ? k_attn_combine_batch<1> : n_rec <= 16 ? k_attn_combine_batch<2> : n_rec <= 40 ? k_attn_combine_batch<5> : k_attn_combine_batch<8>;
+    const int nr = attn_combine_nr(n_rec);
+    auto cfn = nr == 1 ? k_attn_combine_batch<1> : nr == 2 ? k_attn_combine_batch<2> : nr == 5 ? k_attn_combine_batch<5> : k_attn_combine_batch<8>;
     hipLaunchKernelGGL(cfn, dim3(n_kv, n_heads / n_kv, n_seq), dim3(256), 0, stream, scratch, n_kv, n_heads / n_kv, n_rec, pos_ptrs, kc_ptrs, vc_ptrs, out,
                        static_cast<uint8_t *>(qout), scratch_stride, (size_t)n_heads * kD, qact_bytes((size_t)n_heads * kD));
     return hipGetLastError();

@@ -20,27 +20,11 @@ namespace {
 
 constexpr int kGemvBatchLdsMax = 160 * 1024;  // gfx950: 160 KiB of LDS per workgroup
 
-struct GemvQBatchArgs {
-    const uint8_t *tiles;    // as GemvQArgs (kernels_gemvq.hip)
-    const void *stiles;
-    int rows, cols, nblk;
-    uint32_t lut;
-    int ks_log2;
-    const uint8_t *qin;      // [n_seq][qbytes] QAct records
-    const double *stats_in;  // [n_seq][n_stats][2]
-    int n_stats;
-    const float *ln_g;
-    float ln_eps;
-    double inv_cols;
-    const float *residual;   // [n_seq][out_rows]
-    float *y;                // [n_seq][out_rows]
-    int silu_mul;
-    uint8_t *qout;           // [n_seq][qout_bytes]
-    const float *gamma_out;  // [out_rows], shared
-    double *stats_out;       // [n_seq][out_rows / 16][2]
+struct GemvQBatchArgs : GemvQPrefix {  // tiles .. stats_out as k_gemv_q's (common.hpp), every per-vector buffer [n_seq] of them
     int n_seq, out_rows;
     uint32_t qbytes, qout_bytes;
 };
+static_assert(sizeof(GemvQBatchArgs) == 152, "the layout k_gemv_q_batch was compiled for: the prefix, then these members");
 
 // LayerNorm row statistics of one vector from its (sum, sum of squares) pairs in LDS: k_gemv_q's epilogue prologue, expression for expression
 __device__ __forceinline__ void ln_row_stats(const uint8_t *cs, int n_stats, int lane, double inv_cols, float ln_eps, double &ln_mean, double &ln_rdenom) {
@@ -485,56 +469,29 @@ hipError_t launch_embed_q_batch(const void *table, const int *const *history_ptr
     return hipGetLastError();
 }
 
-size_t gemv_q_batch_lds_bytes(const Weights &w, bool ln, bool silu_mul, int n_seq) {
-    const int nblk = (int)(w.cols / 256);
-    const int ksplit = mfma_pick_ksplit(w.rows, w.cols, silu_mul, 8);
-    const int ring = (int)div_ceil((size_t)nblk, (size_t)ksplit);
-    const int ring_t = ring <= 2 ? 2 : ring;
-    const int nb = n_seq <= 2 ? 2 : n_seq <= 4 ? 4 : 8;
-    return (size_t)ring_t * kQRec + (size_t)n_seq * kQRec * nblk + (ln ? (size_t)n_seq * (w.cols / 16) * 16 : 0) + (size_t)nb * 8 * 16 * sizeof(float);
+static int gemv_batch_nb(int n_seq) { return n_seq <= 2 ? 2 : n_seq <= 4 ? 4 : 8; }  // the instantiated vector count NB
+
+size_t gemv_q_batch_lds_bytes(const Weights &w, const GemvGeom &g, bool ln, int n_seq) {
+    return (size_t)g.ring_t * kQRec + (size_t)n_seq * kQRec * g.nblk + (ln ? (size_t)n_seq * (w.cols / 16) * 16 : 0) +
+           (size_t)gemv_batch_nb(n_seq) * 8 * 16 * sizeof(float);
 }
 
 hipError_t launch_gemv_q_batch(const Weights &w, const GemvQIo &io, int n_seq, hipStream_t stream) {
     if (!w.tiles || !gemvq_supported(w) || !io.qin || io.attn_rec || n_seq < 1 || n_seq > kBatchMax) return hipErrorInvalidValue;
-    const int sc = !w.scaled ? 0 : w.scales_f16 ? 2 : 1;
-    if (sc == 2 && !w.scale_tiles_h) return hipErrorInvalidValue;
-    if (sc == 1 && !w.scale_tiles) return hipErrorInvalidValue;
-    const bool ln = io.ln_gamma != nullptr;
-    if (ln && !(w.ln_g && w.ln_gamma_bound == io.ln_gamma && io.stats_in)) return hipErrorInvalidValue;
-    if (io.silu_mul && (!w.paired || io.residual)) return hipErrorInvalidValue;
-    GemvQBatchArgs a;
-    a.tiles = w.tiles;
-    a.stiles = sc == 2 ? (const void *)w.scale_tiles_h : sc == 1 ? (const void *)w.scale_tiles : nullptr;
-    a.rows = (int)w.rows;
-    a.cols = (int)w.cols;
-    a.nblk = (int)(w.cols / 256);
-    a.lut = w.lut;
     const int nw = 8;
-    const int ksplit = mfma_pick_ksplit(w.rows, w.cols, io.silu_mul, nw);  // batch-1's K partition
-    a.ks_log2 = ksplit == 8 ? 3 : ksplit == 4 ? 2 : ksplit == 2 ? 1 : 0;
-    a.qin = static_cast<const uint8_t *>(io.qin);
-    a.stats_in = io.stats_in;
-    a.n_stats = (int)(w.cols / 16);
-    a.ln_g = w.ln_g;
-    a.ln_eps = io.ln_eps;
-    a.inv_cols = 1.0 / (double)w.cols;
-    a.residual = io.residual;
-    a.y = io.y;
-    a.silu_mul = io.silu_mul ? 1 : 0;
-    a.qout = static_cast<uint8_t *>(io.qout);
-    a.gamma_out = io.gamma_out;
-    a.stats_out = io.stats_out;
+    const GemvGeom g = gemv_geometry(w, io.silu_mul, nw);  // batch-1's K partition
+    GemvQBatchArgs a;
+    const hipError_t ef = fill_gemv_q_prefix(a, w, io, g);
+    if (ef != hipSuccess) return ef;
     a.n_seq = n_seq;
     a.out_rows = (int)(io.silu_mul ? w.rows / 2 : w.rows);
     a.qbytes = (uint32_t)kQRec * (uint32_t)a.nblk;
     a.qout_bytes = (uint32_t)qact_bytes((size_t)a.out_rows);
-    const int tiles_per_wg = nw / ksplit;
-    const unsigned grid = (unsigned)div_ceil(w.rows / 16, (size_t)tiles_per_wg);
-    const int ring = (int)div_ceil((size_t)a.nblk, (size_t)ksplit);
+    const bool ln = io.ln_gamma != nullptr;
+    const int ring = g.ring, sc = g.sc, nb = gemv_batch_nb(n_seq);
     if (ring > 5 || (ln && a.n_stats > 256)) return hipErrorInvalidValue;
-    const size_t lds = gemv_q_batch_lds_bytes(w, ln, io.silu_mul, n_seq);
+    const size_t lds = gemv_q_batch_lds_bytes(w, g, ln, n_seq);
     if (lds > (size_t)kGemvBatchLdsMax) return hipErrorInvalidValue;
-    const int nb = n_seq <= 2 ? 2 : n_seq <= 4 ? 4 : 8;
     void (*kfn)(GemvQBatchArgs) = nullptr;
 #define BH_BPICK3(RINGv, NBv)                                                                                                                        \
     if (!kfn && ring <= RINGv && nb == NBv)                                                                                                          \
@@ -549,23 +506,21 @@ hipError_t launch_gemv_q_batch(const Weights &w, const GemvQIo &io, int n_seq, h
         const hipError_t e = raise_dynamic_lds(kfn, kGemvBatchLdsMax);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(nw * 64), lds, stream, a);
+    hipLaunchKernelGGL(kfn, dim3(g.grid), dim3(nw * 64), lds, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_logits_f16_batch(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab, int n_seq,
                                    float *const *logits_ptrs, float *best_val, int *best_idx, int n_wg, int *const *token_ptrs, int *const *pos_ptrs,
                                    int *const *history_ptrs, const int *const *n_forced_ptrs, hipStream_t stream) {
-    if (hidden % 512 != 0 || hidden > 8192 || n_seq < 1 || n_seq > kBatchMax) return hipErrorInvalidValue;
+    if (n_seq < 1 || n_seq > kBatchMax) return hipErrorInvalidValue;
+    const LogitsInstance li = logits_instance(hidden, 4);  // launch_logits_f16's instance, hence its padding; R is free: it does not enter a row's arithmetic
     void (*kfn)(const _Float16 *, const float *, const float *, float, int, int, int, float *const *, float *, int *) = nullptr;
-    switch (hidden / 512) {  // the instances (hence the padding) of launch_logits_f16; R is free: it does not enter a row's arithmetic
-        case 1: kfn = k_logits_f16_batch<1, 4, false>; break;
-        case 2: kfn = k_logits_f16_batch<2, 4, false>; break;
-        case 4: kfn = k_logits_f16_batch<4, 4, false>; break;
-        case 5: kfn = k_logits_f16_batch<5, 4, false>; break;
-        case 8: kfn = k_logits_f16_batch<8, 2, false>; break;
-        default: kfn = hidden / 512 <= 8 ? k_logits_f16_batch<8, 2, true> : k_logits_f16_batch<16, 1, true>; break;
-    }
+#define BH_LBPICK(NCHv, Rv, Gv) \
+    if (li.nch == NCHv && li.r == Rv && li.guard == Gv) kfn = k_logits_f16_batch<NCHv, Rv, Gv>;
+    BH_LBPICK(1, 4, false) BH_LBPICK(2, 4, false) BH_LBPICK(4, 4, false) BH_LBPICK(5, 4, false) BH_LBPICK(8, 2, false) BH_LBPICK(8, 2, true) BH_LBPICK(16, 1, true)
+#undef BH_LBPICK
+    if (!kfn) return hipErrorInvalidValue;
     const size_t lds = (size_t)n_seq * hidden * sizeof(float);
     constexpr int kLdsMax = 152 * 1024;  // beside the kernel's static arrays
     if (lds > (size_t)kLdsMax) return hipErrorInvalidValue;  // 8 vectors of more than 4864 columns: take them in two calls

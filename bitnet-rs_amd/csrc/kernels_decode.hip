@@ -210,19 +210,27 @@ __global__ __launch_bounds__(256) void k_argmax_final(const float *__restrict__ 
     }
 }
 
+LogitsInstance logits_instance(int hidden, int rows5) {
+    const int n = hidden / 512;
+    if (hidden <= 0 || hidden % 512 != 0 || n > kLogitChunks) return {0, 0, false};
+    if (n == 1 || n == 2 || n == 4) return {n, 4, false};
+    if (n == 5) return {5, rows5 == 2 || rows5 == 3 ? rows5 : 4, false};  // 2560: bitnet-b1.58-2B-4T
+    if (n == 8) return {8, 2, false};
+    return n < 8 ? LogitsInstance{8, 2, true} : LogitsInstance{16, 1, true};  // padded to the next instance, guarded loads
+}
+
 hipError_t launch_logits_f16(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab,
                              float *logits, float *best_val, int *best_idx, int n_wg, hipStream_t stream) {
-    if (hidden % 512 != 0 || hidden > 512 * kLogitChunks) return hipErrorInvalidValue;
-    void (*kfn)(const _Float16 *, const float *, const float *, float, int, int, float *, float *, int *) = nullptr;
     static const int rows = getenv("BITNET_HIP_LOGIT_ROWS") ? atoi(getenv("BITNET_HIP_LOGIT_ROWS")) : 3;  // tuning knob, read once
-    switch (hidden / 512) {
-        case 1: kfn = k_logits_f16<1, 4>; break;
-        case 2: kfn = k_logits_f16<2, 4>; break;
-        case 4: kfn = k_logits_f16<4, 4>; break;
-        case 5: kfn = rows == 2 ? k_logits_f16<5, 2> : rows == 3 ? k_logits_f16<5, 3> : k_logits_f16<5, 4>; break;  // 2560: bitnet-b1.58-2B-4T
-        case 8: kfn = k_logits_f16<8, 2>; break;
-        default: kfn = hidden / 512 <= 8 ? k_logits_f16<8, 2, true> : k_logits_f16<16, 1, true>; break;
-    }
+    const LogitsInstance li = logits_instance(hidden, rows);
+    void (*kfn)(const _Float16 *, const float *, const float *, float, int, int, float *, float *, int *) = nullptr;
+#define BH_LPICK(NCHv, Rv, Gv) \
+    if (li.nch == NCHv && li.r == Rv && li.guard == Gv) kfn = k_logits_f16<NCHv, Rv, Gv>;
+    // (the order the instances were always first named in -- <5, 3>, <5, 4>, <5, 2> -- is the order they are emitted in: EXPERIMENTS 21.1)
+    BH_LPICK(1, 4, false) BH_LPICK(2, 4, false) BH_LPICK(4, 4, false) BH_LPICK(5, 3, false) BH_LPICK(5, 4, false) BH_LPICK(5, 2, false)
+    BH_LPICK(8, 2, false) BH_LPICK(8, 2, true) BH_LPICK(16, 1, true)
+#undef BH_LPICK
+    if (!kfn) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kfn, dim3(n_wg), dim3(256), (size_t)hidden * sizeof(float), stream, static_cast<const _Float16 *>(table), x, gamma,
                        eps, hidden, vocab, logits, best_val, best_idx);
     return hipGetLastError();

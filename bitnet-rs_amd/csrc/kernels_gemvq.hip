@@ -56,24 +56,7 @@ __device__ __forceinline__ int load_uniform_i(const int *p) {
     return *reinterpret_cast<const __attribute__((address_space(4))) int *>(reinterpret_cast<uintptr_t>(p));
 }
 
-struct GemvQArgs {
-    const uint8_t *tiles;    // [n_tiles][nblk][64 lanes][16 B] code tiles (k_retile)
-    const void *stiles;      // [n_tiles][nblk][64 lanes] x {f16 x 2 | f32 x 2}: 32-block scales (k_retile_scales[_h]) or null
-    int rows, cols, nblk;
-    uint32_t lut;
-    int ks_log2;             // K ranges per row tile = waves sharing a tile
-    const uint8_t *qin;      // QAct records [nblk][576]
-    const double *stats_in;  // LN: (sum, sum of squares) per 16 columns
-    int n_stats;
-    const float *ln_g;       // LN: g_r = W[r,:] . gamma (bitnet_hip_weights_bind_ln)
-    float ln_eps;
-    double inv_cols;
-    const float *residual;   // optional: v = residual + W x
-    float *y;                // optional f32 output
-    int silu_mul;            // rows are (gate tile, up tile) pairs: v = silu(gate) * up
-    uint8_t *qout;           // optional QAct output (for the next GEMV)
-    const float *gamma_out;  // optional: the next GEMV's LayerNorm weight (u = v * gamma)
-    double *stats_out;       // optional: (sum, sum of squares) per 16 output rows
+struct GemvQArgs : GemvQPrefix {  // tiles .. stats_out: common.hpp
     // MRG: the activation vector is the decode attention's output, assembled HERE from its per-chunk records
     // (launch_attn_decode(..., combine = false): (m, l)[4] + un-normalised P.V [4][128] per KV head and 64-position chunk)
     const float *attn_rec;
@@ -81,6 +64,7 @@ struct GemvQArgs {
     int attn_chunks_max, attn_group_log2, attn_chunk_log2;  // records per KV head, log2 heads per KV head, log2 positions per record (6 / 7)
     unsigned long long *stamps;  // diagnostic builds only
 };
+static_assert(sizeof(GemvQArgs) == 176, "the layout k_gemv_q was compiled for: the prefix, then these members");
 
 // NW waves per workgroup; RING = 256-column blocks per wave, all in flight at once; SC = weight scales per 32-block:
 // 0 none (QK256), 1 f32, 2 f16; LN = LayerNorm after the product; NCP = 8-KiB passes of the cooperative QAct copy.
@@ -525,26 +509,17 @@ hipError_t launch_embed_q(const void *table, const int *tokens, const int *offse
     return hipGetLastError();
 }
 
-hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream) {
-    if (!w.tiles || !gemvq_supported(w) || (!io.qin && !io.attn_rec)) return hipErrorInvalidValue;
-    const bool sc_any = w.scaled;
-    const int sc = !sc_any ? 0 : w.scales_f16 ? 2 : 1;
-    if (sc == 2 && !w.scale_tiles_h) return hipErrorInvalidValue;
-    if (sc == 1 && !w.scale_tiles) return hipErrorInvalidValue;
-    GemvQArgs a;
+hipError_t fill_gemv_q_prefix(GemvQPrefix &a, const Weights &w, const GemvQIo &io, const GemvGeom &g) {
     a.tiles = w.tiles;
-    a.stiles = sc == 2 ? (const void *)w.scale_tiles_h : sc == 1 ? (const void *)w.scale_tiles : nullptr;
+    a.stiles = g.sc == 2 ? (const void *)w.scale_tiles_h : g.sc == 1 ? (const void *)w.scale_tiles : nullptr;
+    if (g.sc && !a.stiles) return hipErrorInvalidValue;
     a.rows = (int)w.rows;
     a.cols = (int)w.cols;
-    a.nblk = (int)(w.cols / 256);
+    a.nblk = g.nblk;
     a.lut = w.lut;
-    // (16-wave workgroups -- 4 waves per SIMD, half the K range each -- measured slower in round 2, gate|up 5.46 vs 5.23 us, and were removed)
-    const int nw = 8;
-    const int ksplit = mfma_pick_ksplit(w.rows, w.cols, io.silu_mul, 8);
-    a.ks_log2 = ksplit == 8 ? 3 : ksplit == 4 ? 2 : ksplit == 2 ? 1 : 0;
+    a.ks_log2 = g.ks_log2;
     a.qin = static_cast<const uint8_t *>(io.qin);
-    const bool ln = io.ln_gamma != nullptr;
-    if (ln && !(w.ln_g && w.ln_gamma_bound == io.ln_gamma && io.stats_in)) return hipErrorInvalidValue;  // LayerNorm only in the after-product form
+    if (io.ln_gamma && !(w.ln_g && w.ln_gamma_bound == io.ln_gamma && io.stats_in)) return hipErrorInvalidValue;  // LayerNorm only in the after-product form
     a.stats_in = io.stats_in;
     a.n_stats = (int)(w.cols / 16);
     a.ln_g = w.ln_g;
@@ -553,21 +528,30 @@ hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream
     a.residual = io.residual;
     a.y = io.y;
     a.silu_mul = io.silu_mul ? 1 : 0;
+    if (io.silu_mul && (!w.paired || io.residual)) return hipErrorInvalidValue;
     a.qout = static_cast<uint8_t *>(io.qout);
     a.gamma_out = io.gamma_out;
     a.stats_out = io.stats_out;
+    return hipSuccess;
+}
+
+hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream) {
+    if (!w.tiles || !gemvq_supported(w) || (!io.qin && !io.attn_rec)) return hipErrorInvalidValue;
+    // (16-wave workgroups -- 4 waves per SIMD, half the K range each -- measured slower in round 2, gate|up 5.46 vs 5.23 us, and were removed)
+    const int nw = 8;
+    const GemvGeom g = gemv_geometry(w, io.silu_mul, nw);
+    GemvQArgs a;
+    const hipError_t ef = fill_gemv_q_prefix(a, w, io, g);
+    if (ef != hipSuccess) return ef;
     a.attn_rec = io.attn_rec;
     a.attn_pos = io.attn_pos;
     a.attn_chunks_max = io.attn_chunks_max;
     a.attn_group_log2 = io.attn_group_log2;
     a.attn_chunk_log2 = io.attn_chunk_log2;
     a.stamps = g_mfma_stamps;
-    if (io.silu_mul && (!w.paired || io.residual)) return hipErrorInvalidValue;
-    const int tiles_per_wg = nw / ksplit;
-    const unsigned grid = (unsigned)div_ceil(w.rows / 16, (size_t)tiles_per_wg);
-    const int ring = (int)div_ceil((size_t)a.nblk, (size_t)ksplit);
-    const size_t qbytes = (size_t)kQRec * a.nblk;
-    const int ncp = (int)div_ceil(qbytes, (size_t)16 * nw * 64);
+    const bool ln = io.ln_gamma != nullptr;
+    const int ring = g.ring, sc = g.sc;
+    const int ncp = (int)div_ceil((size_t)kQRec * a.nblk, (size_t)16 * nw * 64);
     if (ring > 5 || ncp > 3 || (ln && a.n_stats > nw * 64)) return hipErrorInvalidValue;
     void (*kfn)(GemvQArgs) = nullptr;
 #define BH_QPICK2(RINGv, NCPv)                                                                                                        \
@@ -595,9 +579,8 @@ hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream
 #undef BH_QMRG
     }
     if (!kfn) return hipErrorInvalidValue;
-    const int ring_t = ring <= 2 ? 2 : ring;
-    const size_t lds = (size_t)ring_t * kQRec + (size_t)ncp * 16 * nw * 64 + (ln ? (size_t)nw * 64 * 16 : 0) + (size_t)nw * 16 * sizeof(float);
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(nw * 64), lds, stream, a);
+    const size_t lds = (size_t)g.ring_t * kQRec + (size_t)ncp * 16 * nw * 64 + (ln ? (size_t)nw * 64 * 16 : 0) + (size_t)nw * 16 * sizeof(float);
+    hipLaunchKernelGGL(kfn, dim3(g.grid), dim3(nw * 64), lds, stream, a);
     return hipGetLastError();
 }
 

@@ -583,27 +583,43 @@ int mfma_pick_ksplit(size_t rows, size_t cols, bool paired, int nw) {
     return ks;
 }
 
+// Everything the three decode GEMV launchers derive from the K split.  nblk and the grid round up: k_gemv_mfma alone takes ragged shapes
+// (the QAct kernels' cols % 256 == 0, rows % 16 == 0 make the rounding a no-op for them).
+GemvGeom gemv_geometry(const Weights &w, bool silu_mul, int n_waves) {
+    GemvGeom g;
+    g.ksplit = mfma_pick_ksplit(w.rows, w.cols, silu_mul, n_waves);
+    g.ks_log2 = g.ksplit == 8 ? 3 : g.ksplit == 4 ? 2 : g.ksplit == 2 ? 1 : 0;
+    g.nblk = (int)div_ceil(w.cols, 256);
+    g.ring = (int)div_ceil((size_t)g.nblk, (size_t)g.ksplit);
+    g.ring_t = g.ring <= 2 ? 2 : g.ring;
+    g.tiles_per_wg = n_waves / g.ksplit;
+    g.grid = (unsigned)div_ceil(div_ceil(w.rows, 16), (size_t)g.tiles_per_wg);
+    g.sc = !(w.scaled && w.block_size == 32) ? 0 : w.scales_f16 ? 2 : 1;
+    return g;
+}
+
 hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m, const GemvFusion &fu,
                             hipStream_t stream) {
     if (!w.tiles) return hipErrorInvalidValue;
+    const int nw = 8;  // (16-wave workgroups were a round-1 tuning knob that never paid: removed)
+    const GemvGeom g = gemv_geometry(w, fu.silu_mul, nw);
     MfmaArgs a;
     a.tiles = w.tiles;
     a.rows = (int)w.rows;
     a.cols = (int)w.cols;
-    a.nblk = (int)div_ceil(w.cols, 256);
+    a.nblk = g.nblk;
     a.lut = w.lut;
-    const int nw = 8;  // (16-wave workgroups were a round-1 tuning knob that never paid: removed)
-    a.ksplit = mfma_pick_ksplit(w.rows, w.cols, fu.silu_mul, nw);
-    a.ks_log2 = a.ksplit == 8 ? 3 : a.ksplit == 4 ? 2 : a.ksplit == 2 ? 1 : 0;
+    a.ksplit = g.ksplit;
+    a.ks_log2 = g.ks_log2;
     a.inv_cols = 1.0 / (double)w.cols;
     a.ln_gamma = fu.ln_gamma;
     a.ln_eps = fu.ln_eps;
     a.ln_g = (fu.ln_gamma && w.ln_g && w.ln_gamma_bound == fu.ln_gamma) ? w.ln_g : nullptr;
     a.wscale = (w.scaled && w.block_size == 256) ? w.scales : nullptr;
     if (w.scaled && w.block_size == 256 && !w.scales) return hipErrorInvalidValue;
-    const bool bs32_any = w.scaled && w.block_size == 32;
-    a.stiles = (bs32_any && !w.scales_f16) ? w.scale_tiles : nullptr;
-    a.stiles_h = (bs32_any && w.scales_f16) ? w.scale_tiles_h : nullptr;
+    a.stiles = g.sc == 1 ? w.scale_tiles : nullptr;
+    a.stiles_h = g.sc == 2 ? w.scale_tiles_h : nullptr;
+    if (g.sc && !a.stiles && !a.stiles_h) return hipErrorInvalidValue;
     a.silu_mul = fu.silu_mul ? 1 : 0;
     a.attn_rec = fu.attn_rec;
     a.attn_pos = fu.attn_pos;
@@ -615,31 +631,25 @@ hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m
     a.stats_out = fu.stats_out;
     if (fu.qout && (w.rows % 16 != 0 || m != 1 || (fu.silu_mul && w.rows % 32 != 0))) return hipErrorInvalidValue;
     a.stamps = g_mfma_stamps;
-    const int tiles_per_wg = nw / a.ksplit;
-    const unsigned grid = (unsigned)div_ceil(div_ceil(w.rows, 16), tiles_per_wg);
     const size_t out_rows = fu.silu_mul ? w.rows / 2 : w.rows;
     // template selection: RING = blocks per wave, NV = statistics float4 per thread
-    const int ring = (int)div_ceil((size_t)a.nblk, (size_t)a.ksplit);
     const bool ln = fu.ln_gamma != nullptr, ln2 = a.ln_g != nullptr;
-    const int bs32 = a.stiles ? 1 : a.stiles_h ? 2 : 0;
-    if (bs32_any && !bs32) return hipErrorInvalidValue;
     const int nv = ln ? (int)div_ceil(w.cols / 4, (size_t)nw * 64) : 1;
-    if (ring > kRing || nv > kNVMAX) return hipErrorInvalidValue;
+    if (g.ring > kRing || nv > kNVMAX) return hipErrorInvalidValue;
     void (*kfn)(MfmaArgs) = nullptr;
 #define BH_PICK(NWv, RINGv, NVv)                                                                          \
-    if (nw == NWv && ring <= RINGv && nv <= NVv && !kfn)                                                  \
-        kfn = ln2 ? (bs32 == 2 ? k_gemv_mfma<NWv, RINGv, NVv, 2, 2> : bs32 == 1 ? k_gemv_mfma<NWv, RINGv, NVv, 2, 1> : k_gemv_mfma<NWv, RINGv, NVv, 2, 0>) \
-              : ln ? (bs32 == 2 ? k_gemv_mfma<NWv, RINGv, NVv, 1, 2> : bs32 == 1 ? k_gemv_mfma<NWv, RINGv, NVv, 1, 1> : k_gemv_mfma<NWv, RINGv, NVv, 1, 0>) \
-                   : (bs32 == 2 ? k_gemv_mfma<NWv, RINGv, 1, 0, 2> : bs32 == 1 ? k_gemv_mfma<NWv, RINGv, 1, 0, 1> : k_gemv_mfma<NWv, RINGv, 1, 0, 0>);
+    if (nw == NWv && g.ring <= RINGv && nv <= NVv && !kfn)                                                \
+        kfn = ln2 ? (g.sc == 2 ? k_gemv_mfma<NWv, RINGv, NVv, 2, 2> : g.sc == 1 ? k_gemv_mfma<NWv, RINGv, NVv, 2, 1> : k_gemv_mfma<NWv, RINGv, NVv, 2, 0>) \
+              : ln ? (g.sc == 2 ? k_gemv_mfma<NWv, RINGv, NVv, 1, 2> : g.sc == 1 ? k_gemv_mfma<NWv, RINGv, NVv, 1, 1> : k_gemv_mfma<NWv, RINGv, NVv, 1, 0>) \
+                   : (g.sc == 2 ? k_gemv_mfma<NWv, RINGv, 1, 0, 2> : g.sc == 1 ? k_gemv_mfma<NWv, RINGv, 1, 0, 1> : k_gemv_mfma<NWv, RINGv, 1, 0, 0>);
     if (fu.attn_rec) {  // x merged from the decode attention's chunk records: the o-projection shape only
-        if (ln || m != 1 || nw != 8 || ring > 2 || w.cols % 128 != 0 || !fu.attn_pos || fu.attn_chunks_max < 1) return hipErrorInvalidValue;
-        kfn = bs32 == 2 ? k_gemv_mfma<8, 2, 1, 0, 2, 1> : bs32 == 1 ? k_gemv_mfma<8, 2, 1, 0, 1, 1> : k_gemv_mfma<8, 2, 1, 0, 0, 1>;
+        if (ln || m != 1 || nw != 8 || g.ring > 2 || w.cols % 128 != 0 || !fu.attn_pos || fu.attn_chunks_max < 1) return hipErrorInvalidValue;
+        kfn = g.sc == 2 ? k_gemv_mfma<8, 2, 1, 0, 2, 1> : g.sc == 1 ? k_gemv_mfma<8, 2, 1, 0, 1, 1> : k_gemv_mfma<8, 2, 1, 0, 0, 1>;
     }
     BH_PICK(8, 2, 2) BH_PICK(8, 2, 4) BH_PICK(8, 3, 2) BH_PICK(8, 3, 4) BH_PICK(8, 4, 2) BH_PICK(8, 4, 4) BH_PICK(8, 5, 2) BH_PICK(8, 5, 4)
 #undef BH_PICK
     if (!kfn) return hipErrorInvalidValue;
-    const int ring_t = ring <= 2 ? 2 : ring;  // the instantiated RING (LDS plane stride)
-    const size_t lds = (size_t)nw * (bs32 ? 5 : 4) * (ring_t * 256 + 16) + 2 * nw * sizeof(double) + nw * 16 * sizeof(float) +
+    const size_t lds = (size_t)nw * (g.sc ? 5 : 4) * (g.ring_t * 256 + 16) + 2 * nw * sizeof(double) + nw * 16 * sizeof(float) +
                        ((ln && !ln2) ? w.cols * sizeof(float) : 0);
     if (lds > 64 * 1024) {
         const hipError_t e = raise_dynamic_lds(kfn, 160 * 1024);
@@ -652,7 +662,7 @@ hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m
         a.x = x + m0 * w.cols;
         a.y = y + m0 * out_rows;
         a.residual = fu.residual ? fu.residual + m0 * w.rows : nullptr;
-        hipLaunchKernelGGL(kfn, dim3(grid, (unsigned)mc), dim3(nw * 64), lds, stream, a);
+        hipLaunchKernelGGL(kfn, dim3(g.grid, (unsigned)mc), dim3(nw * 64), lds, stream, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

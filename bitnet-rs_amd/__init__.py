@@ -195,6 +195,10 @@ class HipLib:
         L.bitnet_hip_sampler_destroy.argtypes = [_vp]
         L.bitnet_hip_sampler_destroy.restype = None
         L.bitnet_hip_sampler_configure.argtypes = [_vp, C.POINTER(SamplingConfig)]
+        L.bitnet_hip_sampler_create_ex.argtypes = [_sz, C.POINTER(SamplingConfigEx), C.POINTER(_vp)]
+        L.bitnet_hip_sampler_create_ex.restype = C.c_int
+        L.bitnet_hip_sampler_configure_ex.argtypes = [_vp, C.POINTER(SamplingConfigEx)]
+        L.bitnet_hip_sampler_configure_ex.restype = C.c_int
         L.bitnet_hip_sampler_reset.argtypes = [_vp]
         L.bitnet_hip_sampler_draws.argtypes = [_vp, C.POINTER(C.c_uint64)]
         L.bitnet_hip_sample_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -682,9 +686,12 @@ class HipLib:
         self._check(self.c.bitnet_hip_argmax_dev(_ptr(v), n, _ptr(scratch), n_wg, _ptr(token), _vp(stream)))
 
     def sampler(self, vocab: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
-                seed: int | None = None) -> "Sampler":
-        """A device sampler (bitnet_hip_sampler_*): the reference's Sampler::new(temperature, top_k, top_p, repetition_penalty, seed)."""
-        return Sampler(self, vocab, SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed))
+                seed: int | None = None, *, min_p: float = 0.0, typical_p: float = 1.0, frequency_penalty: float = 0.0,
+                presence_penalty: float = 0.0) -> "Sampler":
+        """A device sampler (bitnet_hip_sampler_*): the reference's Sampler::new(temperature, top_k, top_p, repetition_penalty, seed), with
+        the chain stages of bitnet_hip_sampling_config_ex (min-p, typical-p, frequency / presence penalty; the defaults switch them off)."""
+        return Sampler(self, vocab, SamplingConfigEx.make(temperature, top_k, top_p, repetition_penalty, seed, min_p, typical_p,
+                                                          frequency_penalty, presence_penalty))
 
     def sample_batch(self, vocab: int, n_slots: int) -> "SampleBatch":
         """A table of n_slots sampler bindings served by one launch (bitnet_hip_sample_batch_*)."""
@@ -748,13 +755,28 @@ class SamplingConfig(C.Structure):
         return cls(float(temperature), int(top_k), float(top_p), float(repetition_penalty), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
+class SamplingConfigEx(C.Structure):
+    """bitnet_hip_sampling_config_ex"""
+    _fields_ = [("base", SamplingConfig), ("min_p", C.c_float), ("typical_p", C.c_float), ("frequency_penalty", C.c_float),
+                ("presence_penalty", C.c_float)]
+
+    @classmethod
+    def make(cls, temperature: float, top_k: int, top_p: float, repetition_penalty: float, seed: int | None = None, min_p: float = 0.0,
+             typical_p: float = 1.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0) -> "SamplingConfigEx":
+        return cls(SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed), float(min_p), float(typical_p),
+                   float(frequency_penalty), float(presence_penalty))
+
+
 class Sampler:
     """One bitnet_hip_sampler: state (config, ChaCha20 key, word counter, token counts) in device memory."""
 
-    def __init__(self, lib: HipLib, vocab: int, cfg: SamplingConfig):
+    def __init__(self, lib: HipLib, vocab: int, cfg: "SamplingConfig | SamplingConfigEx"):
         self.lib, self.vocab = lib, int(vocab)
         h = _vp()
-        lib._check(lib.c.bitnet_hip_sampler_create(vocab, C.byref(cfg), C.byref(h)))
+        if isinstance(cfg, SamplingConfigEx):
+            lib._check(lib.c.bitnet_hip_sampler_create_ex(vocab, C.byref(cfg), C.byref(h)))
+        else:
+            lib._check(lib.c.bitnet_hip_sampler_create(vocab, C.byref(cfg), C.byref(h)))
         self.h = h
 
     def close(self) -> None:
@@ -768,9 +790,10 @@ class Sampler:
         except Exception:  # noqa: BLE001 -- interpreter shutdown
             pass
 
-    def configure(self, temperature: float, top_k: int, top_p: float, repetition_penalty: float, seed: int | None = None) -> None:
-        cfg = SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed)
-        self.lib._check(self.lib.c.bitnet_hip_sampler_configure(self.h, C.byref(cfg)))
+    def configure(self, temperature: float, top_k: int, top_p: float, repetition_penalty: float, seed: int | None = None, *,
+                  min_p: float = 0.0, typical_p: float = 1.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0) -> None:
+        cfg = SamplingConfigEx.make(temperature, top_k, top_p, repetition_penalty, seed, min_p, typical_p, frequency_penalty, presence_penalty)
+        self.lib._check(self.lib.c.bitnet_hip_sampler_configure_ex(self.h, C.byref(cfg)))
 
     def reset(self) -> None:
         self.lib._check(self.lib.c.bitnet_hip_sampler_reset(self.h))
@@ -1025,6 +1048,8 @@ class HostDecoder:
         L.bitnet_host_weight_bytes.argtypes = [C.c_void_p]
         L.bitnet_host_weight_bytes.restype = C.c_uint64
         L.bitnet_host_set_sampling.argtypes = [C.c_void_p, C.POINTER(SamplingConfig)]
+        L.bitnet_host_set_sampling_ex.argtypes = [C.c_void_p, C.POINTER(SamplingConfigEx)]
+        L.bitnet_host_set_sampling_ex.restype = C.c_int
         L.bitnet_host_sampling_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.bitnet_host_set_logprobs.argtypes = [C.c_void_p, C.c_int]
         L.bitnet_host_set_logprobs.restype = C.c_int
@@ -1103,15 +1128,17 @@ class HostDecoder:
         self._fed = 0
 
     def set_sampling(self, temperature: float | None, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
-                     seed: int | None = None) -> None:
+                     seed: int | None = None, *, min_p: float = 0.0, typical_p: float = 1.0, frequency_penalty: float = 0.0,
+                     presence_penalty: float = 0.0) -> None:
         """The reference's Sampler::new(temperature, top_k, top_p, repetition_penalty, seed) behind every with-logits step, on the
-        device and inside the captured graphs.  set_sampling(None): greedy argmax, as a decoder that never called this.
+        device and inside the captured graphs, with the chain stages of bitnet_hip_sampling_config_ex (off by default).
+        set_sampling(None): greedy argmax, as a decoder that never called this.
         seed None: from os.urandom, as the reference seeds from entropy."""
         if temperature is None:
             self._check(self.c.bitnet_host_set_sampling(self.h, None))
             return
-        cfg = SamplingConfig.make(temperature, top_k, top_p, repetition_penalty, seed)
-        self._check(self.c.bitnet_host_set_sampling(self.h, C.byref(cfg)))
+        cfg = SamplingConfigEx.make(temperature, top_k, top_p, repetition_penalty, seed, min_p, typical_p, frequency_penalty, presence_penalty)
+        self._check(self.c.bitnet_host_set_sampling_ex(self.h, C.byref(cfg)))
 
     def sampling_draws(self) -> int:
         """ChaCha20 words the decoder's sampler has consumed since its last reset / set_sampling (one per non-greedy token)."""

@@ -321,15 +321,21 @@ int Decoder::logprobs(int first, int n, bitnet_hip_logprob_record *out) {
 }
 
 int Decoder::set_sampling(const bitnet_hip_sampling_config *cfg) {
+    if (!cfg) return set_sampling_ex(nullptr);
+    const bitnet_hip_sampling_config_ex x{*cfg, 0.0f, 1.0f, 0.0f, 0.0f};
+    return set_sampling_ex(&x);
+}
+
+int Decoder::set_sampling_ex(const bitnet_hip_sampling_config_ex *cfg) {
     if (!cfg) {
         if (sampling_) drop_graphs();
         sampling_ = false;
         return 0;
     }
     if (!sampler_) {
-        BCHK(bitnet_hip_sampler_create((size_t)c_.vocab, cfg, &sampler_));
+        BCHK(bitnet_hip_sampler_create_ex((size_t)c_.vocab, cfg, &sampler_));
     } else {
-        BCHK(bitnet_hip_sampler_configure(sampler_, cfg));
+        BCHK(bitnet_hip_sampler_configure_ex(sampler_, cfg));
     }
     if (!sampling_) drop_graphs();
     sampling_ = true;
@@ -1962,6 +1968,7 @@ int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *fin
 }
 int bitnet_host_reset(void *d) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->reset(); }
 int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_sampling(cfg); }
+int bitnet_host_set_sampling_ex(void *d, const bitnet_hip_sampling_config_ex *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_sampling_ex(cfg); }
 int bitnet_host_sampling_draws(void *d, uint64_t *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->sampling_draws(out); }
 int bitnet_host_set_logprobs(void *d, int top_n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_logprobs(top_n); }
 int bitnet_host_logprobs(void *d, int first, int n, void *records_out) {

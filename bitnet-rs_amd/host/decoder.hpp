@@ -107,6 +107,8 @@ class Decoder {
     // cfg == NULL = greedy argmax as before (same kernels, same tokens).  Switching on / off drops the captured graphs,
     // a new config on an existing sampler does not (the graphs read it from device memory).
     int set_sampling(const bitnet_hip_sampling_config *cfg);
+    // the same with min-p, typical-p and the additive penalties (bitnet_hip_sampling_config_ex); set_sampling is this with neutral values
+    int set_sampling_ex(const bitnet_hip_sampling_config_ex *cfg);
     int sampling_draws(uint64_t *out);
     // The reference's logits tap on the generation path (GenerationConfig::{logits_tap_steps, logits_topk, logits_cb}, crates/bitnet-inference/src/
     // config.rs:87-93, engine.rs:1182-1210; the CLI's LogitStep records, crates/bitnet-cli/src/main.rs:1337-1373) on the device: top_n = -1 (default)
@@ -393,6 +395,7 @@ int bitnet_host_set_layer_i2s(void *d, int layer, const float *attn_norm, const 
 int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *final_norm);
 int bitnet_host_reset(void *d);
 int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg);  // NULL = greedy
+int bitnet_host_set_sampling_ex(void *d, const bitnet_hip_sampling_config_ex *cfg);  // NULL = greedy
 int bitnet_host_sampling_draws(void *d, uint64_t *out);
 int bitnet_host_set_logprobs(void *d, int top_n);                             // Decoder::set_logprobs: -1 off, 0..20 on
 int bitnet_host_logprobs(void *d, int first, int n, void *records_out);       // Decoder::logprobs: n bitnet_hip_logprob_record

@@ -702,6 +702,39 @@ void bitnet_hip_sampler_destroy(bitnet_hip_sampler *sampler);
 /* New config and seed: the key is re-derived and the word counter restarts at 0; the counts stay.  Synchronous copy:
  * not capture-safe, but graphs captured before it stay valid and follow it. */
 int bitnet_hip_sampler_configure(bitnet_hip_sampler *sampler, const bitnet_hip_sampling_config *cfg);
+/* The sampler chain: min-p, typical-p and the additive penalties of the reference's serving front ends around the stages above.
+ * A stage removes entries (-inf); the next one sees the softmax of the survivors.  The order is fixed:
+ *   counts; ADDITIVE PENALTIES; repetition penalty; NaN -> -inf; greedy shortcut; temperature; top-k; top-p; MIN-P; TYPICAL-P;
+ *   softmax; draw.
+ * Additive penalties (crates/bitnet-sampling/src/strategies.rs RepetitionPenaltyConfig::apply :247-259): for a token with
+ *   occurrence count c > 0, x -= frequency_penalty * (float)c, then x -= presence_penalty, two separate f32 operations in front
+ *   of the multiplicative penalty.  For bitnet_hip_sample_dev c is how often this sampler chose the token since the last reset (not
+ *   the compounding exponent of the repetition penalty); for bitnet_hip_sample_host it is the token's occurrences in that call's
+ *   list (ids >= vocab skipped).  Both 0: the stage is skipped.  Negative values are a bonus.
+ * Min-p (crates/bitnet-logits/src/lib.rs apply_min_p :299-310, strategies.rs MinPSampler :37-50): with p the softmax of the
+ *   survivors, an entry is removed iff p_i < min_p * max_j p_j.  Clamped to [0, 1]; <= 0 off; 1 keeps the entries tied at the maximum.
+ * Typical-p (lib.rs apply_typical :337-381, strategies.rs TypicalSampler :73-86): over the survivors with p > 0, H = -sum p ln p,
+ *   d_i = |(-ln p_i) - H|; entries are taken by ascending d until the running sum of p first reaches >= typical_p (the entry that
+ *   crosses is kept), the rest are removed, and so is a survivor whose probability is 0.  The reference sorts unstably, so it
+ *   leaves the order of equal deviations open: here it is ascending token id.  Clamped to [0, 1]; >= 1 off; 0 keeps the single most
+ *   typical entry.  With 1 <= top_k <= BITNET_HIP_SAMPLE_SMALL_K the stage runs over the k survivors in one lane in the reference's
+ *   order; on the full-vocabulary path it is a radix select over the deviations with fixed-point mass sums (the roundings are listed in
+ *   csrc/kernels_sample.hip), equal except where a deciding comparison lies within those roundings of its threshold.
+ * The greedy shortcut needs min_p <= 0 and typical_p >= 1 beside temperature 1, top_k 0, top_p 1 (or temperature 0); the additive
+ *   penalties apply in front of its argmax, which stays bit-exact and draws no word.
+ * On a row with no finite maximum both new stages are no-ops.
+ * Invalid beside the base config's: min_p NaN; typical_p NaN; frequency_penalty or presence_penalty NaN or infinite.
+ * bitnet_hip_sampler_create / _configure are these two with min_p 0, typical_p 1 and both penalties 0.  configure_ex is
+ * synchronous and not capture-safe; graphs captured before it follow it; the counts stay. */
+typedef struct bitnet_hip_sampling_config_ex {
+    bitnet_hip_sampling_config base;
+    float min_p;              /* <= 0: off */
+    float typical_p;          /* >= 1: off */
+    float frequency_penalty;  /* 0: off */
+    float presence_penalty;   /* 0: off */
+} bitnet_hip_sampling_config_ex;
+int bitnet_hip_sampler_create_ex(size_t vocab, const bitnet_hip_sampling_config_ex *cfg, bitnet_hip_sampler **out);
+int bitnet_hip_sampler_configure_ex(bitnet_hip_sampler *sampler, const bitnet_hip_sampling_config_ex *cfg);
 /* Clears the counts (a new generation) and the word counter, and re-arms the launch hand-over (a launch cut short leaves it
  * unbalanced).  Synchronous; call it with no sample_dev / sample_host in flight.  Not capture-safe. */
 int bitnet_hip_sampler_reset(bitnet_hip_sampler *sampler);

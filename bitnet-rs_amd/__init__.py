@@ -148,6 +148,13 @@ class HipLib:
         L.bitnet_hip_attention_decode_batch_dev.restype = C.c_int
         L.bitnet_hip_logits_f16_batch_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_logits_f16_batch_dev.restype = C.c_int
+        # the wide decode step (up to 64 sequences as dense matrix rows; per-sequence state through device pointer tables)
+        L.bitnet_hip_embed_rows_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]
+        L.bitnet_hip_embed_rows_dev.restype = C.c_int
+        L.bitnet_hip_attention_decode_rows_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp]
+        L.bitnet_hip_attention_decode_rows_dev.restype = C.c_int
+        L.bitnet_hip_pick_rows_dev.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_pick_rows_dev.restype = C.c_int
         # fork of a live sequence's KV state: source tables [n_layers], destination tables [n_dst][n_layers] of device pointers
         L.bitnet_hip_kv_fork_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]
         L.bitnet_hip_kv_fork_dev.restype = C.c_int
@@ -609,6 +616,21 @@ class HipLib:
         self._check(self.c.bitnet_hip_logits_f16_batch_dev(_ptr(table), _ptr(x), _optr(gamma), eps, hidden, vocab, n_seq, _ptr(logits_ptrs), _ptr(scratch),
                                                            n_wg, _optr(token_ptrs), _optr(pos_ptrs), _optr(history_ptrs), _optr(n_forced_ptrs), _vp(stream)))
 
+    # ---- the wide decode step: n_seq <= 64 sequences as dense rows; *_ptrs = int64 device tensors of n_seq device pointers (0 = idle row) ----
+    def embed_rows_dev(self, table, history_ptrs, pos_ptrs, n_seq: int, hidden: int, vocab: int, x_out, stream: int = 0) -> None:
+        self._check(self.c.bitnet_hip_embed_rows_dev(_ptr(table), _ptr(history_ptrs), _ptr(pos_ptrs), n_seq, hidden, vocab, _ptr(x_out), _vp(stream)))
+
+    def attention_decode_rows_dev(self, qkv, rope_sin, rope_cos, kcache_ptrs, vcache_ptrs, pos_ptrs, n_seq: int, n_heads, n_kv, head_dim, max_pos, key_bound,
+                                  scratch, out, kv_f16: bool = False, out_f16: bool = False, stream: int = 0) -> None:
+        flags = (1 if kv_f16 else 0) | (2 if out_f16 else 0)  # BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16
+        self._check(self.c.bitnet_hip_attention_decode_rows_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kcache_ptrs), _ptr(vcache_ptrs), _ptr(pos_ptrs),
+                                                                n_seq, n_heads, n_kv, head_dim, max_pos, key_bound, _ptr(scratch), flags, _ptr(out), _vp(stream)))
+
+    def pick_rows_dev(self, logits, argmax, n_seq: int, vocab: int, logits_ptrs, token_ptrs=None, pos_ptrs=None, history_ptrs=None, n_forced_ptrs=None,
+                      stream: int = 0) -> None:
+        self._check(self.c.bitnet_hip_pick_rows_dev(_ptr(logits), _ptr(argmax), n_seq, vocab, _ptr(logits_ptrs), _optr(token_ptrs), _optr(pos_ptrs),
+                                                    _optr(history_ptrs), _optr(n_forced_ptrs), _vp(stream)))
+
     def kv_fork_dev(self, src_k_ptrs, src_v_ptrs, dst_k_ptrs, dst_v_ptrs, n_layers: int, n_dst: int, n_kv: int, head_dim: int, max_pos: int,
                     n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
         """Cache slots [0, n_positions) of every layer's K and V of one source into n_dst destinations, bit for bit, in one launch.  *_ptrs: int64
@@ -1064,6 +1086,8 @@ class HostDecoder:
         L.bitnet_host_fork.restype = C.c_int
         L.bitnet_host_prefill_packed.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.bitnet_host_prefill_packed.restype = C.c_int
+        L.bitnet_host_step_wide.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.bitnet_host_step_wide.restype = C.c_int
         L.bitnet_host_cached_prefix.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
         L.bitnet_host_cached_prefix.restype = C.c_int
         self.cfg = cfg
@@ -1277,6 +1301,21 @@ class HostDecoder:
         arr = (C.c_void_p * len(members))(*[m.h if m is not None else None for m in members])
         ms = C.c_float(0)
         self._check(self.c.bitnet_host_prefill_packed(arr, ns.ctypes.data_as(C.POINTER(C.c_int32)), len(members), int(with_logits), digits, C.byref(ms)))
+        return ms.value
+
+    def step_wide(self, members, n: int = 1, digits: int = 2) -> float:
+        """n decode steps for up to 64 live sequences (this decoder's owner or borrowers of the same weights, the same cache type) through ONE
+        matrix forward per step: the members' current tokens are the dense rows of one matrix, every weight matrix is read once on the
+        many-row matmuls, each row attends over its own cache, one pass over the embedding table gives every member's logits.  Every member
+        ends as its own n x extend(1, True, digits) would leave it (same arithmetic class, not the same bits): position + n, last_logits(),
+        its own greedy pick or sampler draw, its logprob records.  This decoder is the driver (its stream, its prompt buffers, its error
+        text, its saturation_fallbacks()): `members` starts with it, or it is put in front.  Members may sit in HostBatch slots."""
+        members = list(members)
+        if not members or members[0] is not self:
+            members = [self] + members
+        arr = (C.c_void_p * len(members))(*[m.h if m is not None else None for m in members])
+        ms = C.c_float(0)
+        self._check(self.c.bitnet_host_step_wide(arr, len(members), n, digits, C.byref(ms)))
         return ms.value
 
     def rewind(self, n: int) -> None:

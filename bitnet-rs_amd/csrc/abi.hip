@@ -1222,6 +1222,74 @@ int bitnet_hip_logits_f16_batch_dev(const void *table, const float *x, const flo
     BH_GUARD_END
 }
 
+/* ---- the wide decode step: up to BITNET_HIP_WIDE_MAX sequences as dense matrix rows (kernels_wide.hip; k_attn_*_rows in kernels_attn.hip) ---- */
+
+static int check_n_rows(size_t n_seq, const char *who) {
+    if (n_seq == 0 || n_seq > BITNET_HIP_WIDE_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_seq %zu must be 1..%d", who, n_seq, BITNET_HIP_WIDE_MAX);
+    return BITNET_HIP_OK;
+}
+
+int bitnet_hip_embed_rows_dev(const void *table, const int32_t *const *history_ptrs_dev, const int32_t *const *pos_ptrs_dev, size_t n_seq, size_t hidden,
+                              size_t vocab, float *x_out_dev, void *stream) {
+    BH_GUARD_BEGIN
+    if (int rc = check_n_rows(n_seq, "embed_rows_dev")) return rc;
+    if (!table || !history_ptrs_dev || !pos_ptrs_dev || !x_out_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to embed_rows_dev");
+    if (hidden == 0 || hidden % 8 != 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "embed_rows: hidden %zu must be a positive multiple of 8", hidden);
+    size_t elems = 0;
+    if (vocab == 0 || vocab > (size_t)INT32_MAX || hidden > (size_t)INT32_MAX || __builtin_mul_overflow(vocab, hidden, &elems) ||
+        __builtin_mul_overflow(elems, sizeof(uint16_t), &elems))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (embed_rows_dev: hidden %zu, vocab %zu)", hidden, vocab);
+    BH_HIP_TRY(launch_embed_rows(table, reinterpret_cast<const int *const *>(history_ptrs_dev), reinterpret_cast<const int *const *>(pos_ptrs_dev), (int)n_seq,
+                                 (int)hidden, (int)vocab, x_out_dev, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_attention_decode_rows_dev(const float *qkv, const float *rope_sin, const float *rope_cos, void *const *kcache_ptrs_dev,
+                                         void *const *vcache_ptrs_dev, const int32_t *const *pos_ptrs_dev, size_t n_seq, size_t n_heads, size_t n_kv_heads,
+                                         size_t head_dim, size_t max_pos, size_t key_bound, float *scratch, int flags, void *out, void *stream) {
+    BH_GUARD_BEGIN
+    if (int rc = check_n_rows(n_seq, "attention_decode_rows_dev")) return rc;
+    if (!qkv || !rope_sin || !rope_cos || !kcache_ptrs_dev || !vcache_ptrs_dev || !pos_ptrs_dev || !scratch || !out)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to attention_decode_rows_dev");
+    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_decode_rows_dev: unknown flag bits 0x%x (BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)", flags);
+    if (int rc = check_attn_heads(n_heads, n_kv_heads)) return rc;
+    if (head_dim != 128 || n_heads / n_kv_heads > 4)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_decode_rows_dev: head_dim %zu / group %zu unsupported (head_dim 128, group <= 4)", head_dim,
+                         n_heads / n_kv_heads);
+    // the grid's y and the record offsets are 32-bit: max_pos as the decoder bounds it, the scratch of one sequence below 2^31 floats
+    size_t rec_floats = 0;
+    if (max_pos == 0 || max_pos > ((size_t)1 << 24) || n_heads > 65535 || __builtin_mul_overflow(n_kv_heads, (max_pos + 63) / 64, &rec_floats) ||
+        __builtin_mul_overflow(rec_floats, (size_t)kAttnRecFloats, &rec_floats) || rec_floats >= ((size_t)1 << 31))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (attention_decode_rows_dev: n_kv_heads %zu, max_pos %zu)", n_kv_heads,
+                         max_pos);
+    if (key_bound == 0 || key_bound > max_pos)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "attention_decode_rows_dev: key_bound %zu must be 1..max_pos %zu", key_bound, max_pos);
+    BH_HIP_TRY(launch_attn_decode_rows(qkv, rope_sin, rope_cos, reinterpret_cast<float *const *>(kcache_ptrs_dev), reinterpret_cast<float *const *>(vcache_ptrs_dev),
+                                       reinterpret_cast<const int *const *>(pos_ptrs_dev), (int)n_seq, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_pos,
+                                       (int)key_bound, scratch, out, (flags & BITNET_HIP_ATTN_CACHE_F16) != 0, (flags & BITNET_HIP_ATTN_OUT_F16) != 0,
+                                       (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_pick_rows_dev(const float *logits_dev, const int32_t *argmax_dev, size_t n_seq, size_t vocab, float *const *logits_ptrs_dev,
+                             int32_t *const *token_ptrs_dev, int32_t *const *pos_ptrs_dev, int32_t *const *history_ptrs_dev,
+                             const int32_t *const *n_forced_ptrs_dev, void *stream) {
+    BH_GUARD_BEGIN
+    if (int rc = check_n_rows(n_seq, "pick_rows_dev")) return rc;
+    if (!logits_dev || !argmax_dev || !logits_ptrs_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to pick_rows_dev");
+    if (vocab == 0 || vocab > (size_t)INT32_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (pick_rows_dev: vocab %zu)", vocab);
+    BH_HIP_TRY(launch_pick_rows(logits_dev, reinterpret_cast<const int *>(argmax_dev), (int)n_seq, (int)vocab, logits_ptrs_dev,
+                                reinterpret_cast<int *const *>(token_ptrs_dev), reinterpret_cast<int *const *>(pos_ptrs_dev),
+                                reinterpret_cast<int *const *>(history_ptrs_dev), reinterpret_cast<const int *const *>(n_forced_ptrs_dev), (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 /* ---- fork of a live sequence's KV state (kernels_kvfork.hip) ---- */
 
 int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const *src_v_ptrs_dev, void *const *dst_k_ptrs_dev, void *const *dst_v_ptrs_dev,

@@ -203,6 +203,15 @@ hipError_t launch_attn_decode_batch(const float *qkv, const float *rope_sin, con
 hipError_t launch_logits_f16_batch(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab, int n_seq,
                                    float *const *logits_ptrs, float *best_val, int *best_idx, int n_wg, int *const *token_ptrs, int *const *pos_ptrs,
                                    int *const *history_ptrs, const int *const *n_forced_ptrs, hipStream_t stream);
+// ---- the wide decode step (kernels_wide.hip, kernels_attn.hip): up to kWideMax sequences as the dense rows of the many-row matmul chain ----
+constexpr int kWideMax = 64;  // BITNET_HIP_WIDE_MAX
+hipError_t launch_embed_rows(const void *table, const int *const *history_ptrs, const int *const *pos_ptrs, int n_seq, int hidden, int vocab, float *x_out,
+                             hipStream_t stream);
+hipError_t launch_attn_decode_rows(const float *qkv, const float *rope_sin, const float *rope_cos, float *const *kc_ptrs, float *const *vc_ptrs,
+                                   const int *const *pos_ptrs, int n_seq, int n_heads, int n_kv, int D, int max_pos, int key_bound, float *scratch, void *out,
+                                   int kv_f16, int out_f16, hipStream_t stream);
+hipError_t launch_pick_rows(const float *logits, const int *argmax, int n_seq, int vocab, float *const *logits_ptrs, int *const *token_ptrs, int *const *pos_ptrs,
+                            int *const *history_ptrs, const int *const *n_forced_ptrs, hipStream_t stream);
 // kernels_kvfork.hip: cache slots [0, n) of every layer's K and V of one source into n_dst destinations, one launch; rows = 32-bit words per
 // position and KV head (128 for f32 caches, 64 for f16), head_words = ceil(max_pos / 64) * 64 * rows
 hipError_t launch_kv_fork(const void *const *src_k, const void *const *src_v, void *const *dst_k, void *const *dst_v, size_t n_layers, size_t n_dst,

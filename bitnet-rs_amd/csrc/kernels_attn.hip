@@ -397,11 +397,11 @@ __global__ __launch_bounds__(256) void k_attn_partial_batch(const float *__restr
 // records were written by other CUs' workgroups, so every dependent trip is a cross-XCD miss (~0.7-1 us); with
 // 8 * NR >= n_chunks_max the whole merge is ONE round trip.  Records past the context are valid memory (the scratch buffer
 // is sized for max_pos and zero-filled once) and are dropped by their index.
-// (body shared with k_attn_combine_batch, as attn_partial_body)
-template <int NR>
+// (body shared with k_attn_combine_batch, as attn_partial_body; ROWS: the rows form's key bound and f16 output, compiled out of the other two)
+template <int NR, bool ROWS = false>
 __device__ __forceinline__ void attn_combine_body(const float *__restrict__ scratch, int n_kv, int group, int n_chunks_max, int chunk_log2,
                                                   const int *__restrict__ pos_ptr, float *__restrict__ out, uint8_t *__restrict__ qout, const int kvh,
-                                                  const int g) {
+                                                  const int g, const int key_bound = 0x7fffffff, _Float16 *__restrict__ out_h = nullptr) {
     const int tid = threadIdx.x, d4 = tid & 31, part = tid >> 5;
     __shared__ float sm[8], sl[8];
     __shared__ __attribute__((aligned(16))) float sa[8][kD];
@@ -417,6 +417,7 @@ __device__ __forceinline__ void attn_combine_body(const float *__restrict__ scra
         o[u] = *reinterpret_cast<const float4 *>(rec + 2 * kMaxGroup + g * kD + 4 * d4);
     }
     const int t_k = *pos_ptr + 1;
+    if (ROWS && t_k > key_bound) return;  // the rows form only: a sequence past the caller's bound is idle (block-uniform; behind the record requests, before any store)
     const int n_chunks = (t_k + (1 << chunk_log2) - 1) >> chunk_log2;  // records of 64 or 128 positions
     float m = -INFINITY, l = 0.0f;
     float4 a = {0.f, 0.f, 0.f, 0.f};
@@ -479,6 +480,7 @@ __device__ __forceinline__ void attn_combine_body(const float *__restrict__ scra
         const float v = acc / L;
         const int col = (kvh * group + g) * kD + tid;
         if (out) out[col] = v;
+        if (ROWS && out_h) out_h[col] = (_Float16)v;  // the rows form: one rounding to nearest-even, the matmuls' f16 row format
         // the o-projection's input as a QAct (qact.hpp): 16 consecutive dims = one group, no LayerNorm in between (T:542)
         if (qout) qact_emit(qout, nullptr, col >> 4, col & 15, v, v);
     }
@@ -503,6 +505,42 @@ __global__ __launch_bounds__(256) void k_attn_combine_batch(const float *__restr
     if (!pp || !kc_ptrs[b] || !vc_ptrs[b]) return;  // block-uniform
     attn_combine_body<NR>(scratch + (size_t)b * scratch_stride, n_kv, group, n_chunks_max, 6, pp, out ? out + (size_t)b * out_stride : nullptr,
                           qout ? qout + (size_t)b * qout_stride : nullptr, blockIdx.x, blockIdx.y);
+}
+
+// ---- the ROWS form: up to kWideMax sequences, one query row each, for the many-row matmul chain (Decoder::step_wide) ----------------------
+// k_attn_partial_batch / k_attn_combine_batch with two differences.  (1) The record grid covers ceil(key_bound / 64) records, not max_pos / 64:
+// at 64 sequences, 5 KV heads and max_pos 4096 the batch grid is 20480 workgroups per layer of which a 200-key context uses 1280.  The caller
+// promises *pos < key_bound; a sequence that breaks the promise is IDLE for the launch in both kernels (block-uniform tests): no cache byte, no
+// record and no output row of it is written.  The scratch layout stays the batch's (n_rec = ceil(max_pos / 64) records per KV head), so a
+// sequence's record area is where every other form of the attention expects it.  (2) The combine writes f32 rows or f16 rows.
+// Same bodies, hence the same bits as the batch and the batch-1 64-position-record form for every sequence.
+template <bool KV16>
+__global__ __launch_bounds__(256) void k_attn_partial_rows(const float *__restrict__ qkv, const float *__restrict__ rope_sin,
+                                                           const float *__restrict__ rope_cos, float *const *__restrict__ kc_ptrs,
+                                                           float *const *__restrict__ vc_ptrs, int n_heads, int n_kv, int group, int max_pos,
+                                                           const int *const *__restrict__ pos_ptrs, float *__restrict__ scratch, size_t qkv_stride,
+                                                           size_t scratch_stride, int key_bound, unsigned n_rec) {
+    const int b = blockIdx.z;
+    float *kc = kc_ptrs[b], *vc = vc_ptrs[b];
+    const int *pp = pos_ptrs[b];
+    if (!kc || !vc || !pp) return;  // block-uniform
+    const int pos = *pp;
+    if (pos < 0 || pos >= key_bound) return;  // block-uniform: beyond the caller's bound = idle
+    attn_partial_body<1, KV16>(qkv + (size_t)b * qkv_stride, rope_sin, rope_cos, kc, vc, n_heads, n_kv, group, max_pos, pp, scratch + (size_t)b * scratch_stride,
+                               nullptr, blockIdx.x, blockIdx.y, n_rec);
+}
+
+// grid (n_kv, group, n_seq); n_chunks_max = the layout's record count (max_pos), NR covers the records of key_bound
+template <int NR>
+__global__ __launch_bounds__(256) void k_attn_combine_rows(const float *__restrict__ scratch, int n_kv, int group, int n_chunks_max,
+                                                           const int *const *__restrict__ pos_ptrs, float *const *__restrict__ kc_ptrs,
+                                                           float *const *__restrict__ vc_ptrs, float *__restrict__ out, _Float16 *__restrict__ out_h,
+                                                           size_t scratch_stride, size_t out_stride, int key_bound) {
+    const int b = blockIdx.z;
+    const int *pp = pos_ptrs[b];
+    if (!pp || !kc_ptrs[b] || !vc_ptrs[b]) return;  // block-uniform
+    attn_combine_body<NR, true>(scratch + (size_t)b * scratch_stride, n_kv, group, n_chunks_max, 6, pp, out ? out + (size_t)b * out_stride : nullptr, nullptr,
+                                blockIdx.x, blockIdx.y, key_bound, out_h ? out_h + (size_t)b * out_stride : nullptr);
 }
 
 size_t attn_scratch_floats(int n_kv, int max_pos) {
@@ -545,6 +583,24 @@ hipError_t launch_attn_decode_batch(const float *qkv, const float *rope_sin, con
     auto cfn = nr == 1 ? k_attn_combine_batch<1> : nr == 2 ? k_attn_combine_batch<2> : nr == 5 ? k_attn_combine_batch<5> : k_attn_combine_batch<8>;
     hipLaunchKernelGGL(cfn, dim3(n_kv, n_heads / n_kv, n_seq), dim3(256), 0, stream, scratch, n_kv, n_heads / n_kv, n_rec, pos_ptrs, kc_ptrs, vc_ptrs, out,
                        static_cast<uint8_t *>(qout), scratch_stride, (size_t)n_heads * kD, qact_bytes((size_t)n_heads * kD));
+    return hipGetLastError();
+}
+
+hipError_t launch_attn_decode_rows(const float *qkv, const float *rope_sin, const float *rope_cos, float *const *kc_ptrs, float *const *vc_ptrs,
+                                   const int *const *pos_ptrs, int n_seq, int n_heads, int n_kv, int D, int max_pos, int key_bound, float *scratch, void *out,
+                                   int kv_f16, int out_f16, hipStream_t stream) {
+    if (D != kD || n_kv <= 0 || n_heads / n_kv > kMaxGroup || n_seq < 1 || n_seq > kWideMax || max_pos <= 0 || key_bound < 1 || key_bound > max_pos)
+        return hipErrorInvalidValue;
+    const int n_rec = (max_pos + kAttnChunk - 1) / kAttnChunk, n_rec_bound = (key_bound + kAttnChunk - 1) / kAttnChunk;
+    const size_t qkv_stride = (size_t)(n_heads + 2 * n_kv) * kD, scratch_stride = attn_scratch_floats(n_kv, max_pos);
+    auto kfn = kv_f16 ? k_attn_partial_rows<true> : k_attn_partial_rows<false>;
+    hipLaunchKernelGGL(kfn, dim3(n_kv, n_rec_bound, n_seq), dim3(256), 0, stream, qkv, rope_sin, rope_cos, kc_ptrs, vc_ptrs, n_heads, n_kv, n_heads / n_kv, max_pos,
+                       pos_ptrs, scratch, qkv_stride, scratch_stride, key_bound, (unsigned)n_rec);
+    const int nr = attn_combine_nr(n_rec_bound);  // the records up front cover the bound; records merge in index order whatever NR is
+    auto cfn = nr == 1 ? k_attn_combine_rows<1> : nr == 2 ? k_attn_combine_rows<2> : nr == 5 ? k_attn_combine_rows<5> : k_attn_combine_rows<8>;
+    hipLaunchKernelGGL(cfn, dim3(n_kv, n_heads / n_kv, n_seq), dim3(256), 0, stream, scratch, n_kv, n_heads / n_kv, n_rec, pos_ptrs, kc_ptrs, vc_ptrs,
+                       out_f16 ? nullptr : static_cast<float *>(out), out_f16 ? static_cast<_Float16 *>(out) : nullptr, scratch_stride, (size_t)n_heads * kD,
+                       key_bound);
     return hipGetLastError();
 }
 

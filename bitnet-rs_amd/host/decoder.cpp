@@ -231,7 +231,8 @@ Decoder::~Decoder() {
         if (p) hipFree(p);
     for (void *p : {(void *)pf_x_, (void *)pf_qkv_, (void *)pf_att_, (void *)pf_h_, pf_gemm_ws_, pf_attn_ws_, sp_kv_send_, sp_kv_all_,
                     (void *)sp_block_pos_, (void *)sp_tokens_, pf_xh_, pf_atth_, pf_hh_, (void *)pf_stats_, pf_qb_, (void *)sc_tgt_, (void *)sc_am_,
-                    (void *)sc_nll_, (void *)sc_logits_, sc_ws_, (void *)fork_tables_})
+                    (void *)sc_nll_, (void *)sc_logits_, sc_ws_, (void *)fork_tables_, (void *)wide_tables_, (void *)wide_scratch_, (void *)wide_logits_,
+                    (void *)wide_nll_, (void *)wide_am_, (void *)wide_tgt_, wide_ws_})
         if (p) hipFree(p);
     for (void *e : sp_tev_)
         if (e) hipEventDestroy((hipEvent_t)e);
@@ -973,11 +974,19 @@ int Decoder::ensure_chain_buffers(size_t N) {
 
 // The attention of one layer of a prompt forward over the N rows in pf_qkv_ (all three forms of the layer loop come here): on a fresh
 // sequence the whole-prompt operator, on a live one (pf_past_ cached positions: Decoder::extend) the continuation operator, which reads the
-// past keys from the cache and takes every slot at or beyond pf_past_ from the new rows; with a pack in flight (pack_members_) the packed operator.
+// past keys from the cache and takes every slot at or beyond pf_past_ from the new rows; with a pack in flight (pack_members_) the packed operator;
+// with a wide step in flight (wide_n_) the decode attention over the rows' own caches.
 int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16) {
     const size_t NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, D = (size_t)c_.head_dim, MP = (size_t)c_.max_pos;
     const int flags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
-    if (!pack_members_.empty()) {
+    if (wide_n_ > 0) {
+        // a wide step in flight (step_wide): the N rows are N members' current tokens, each over its OWN caches of this layer at its own position
+        const size_t li = (size_t)(&L - layers_.data());
+        BCHK(bitnet_hip_attention_decode_rows_dev(pf_qkv_, rope_sin_, rope_cos_, wide_tables_ + (2 * li) * BITNET_HIP_WIDE_MAX,
+                                                  wide_tables_ + (2 * li + 1) * BITNET_HIP_WIDE_MAX,
+                                                  reinterpret_cast<const int32_t *const *>(wide_tables_ + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
+                                                  (size_t)wide_key_bound_, wide_scratch_, flags, out, stream_));
+    } else if (!pack_members_.empty()) {
         // a pack in flight (prefill_packed): the N rows are several members' segments, each over its OWN caches of this layer
         const size_t li = (size_t)(&L - layers_.data()), n = pack_members_.size();
         void *kc[BITNET_HIP_PACK_MAX], *vc[BITNET_HIP_PACK_MAX];
@@ -1342,6 +1351,134 @@ int Decoder::packed_forward(Decoder *const *members, const std::vector<int32_t> 
         if (rc) {
             if (d != this) err_ = d->err_;
             return rc;
+        }
+    }
+    HCHK(hipEventRecord(ev1.e, s));
+    HCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
+    if (elapsed_ms) *elapsed_ms = ms;
+    return 0;
+}
+
+int Decoder::step_wide(Decoder *const *members, int n_members, int n_steps, int digits, float *elapsed_ms) {
+    if (!members || !members[0] || members[0]->dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;  // no driver to carry the text
+    Decoder &drv = *members[0];
+    // every refusal comes before the first write
+    if (n_members < 1 || n_members > BITNET_HIP_WIDE_MAX) return drv.fail_arg("step_wide: n_members must be 1..64");
+    if (n_steps < 1) return drv.fail_arg("step_wide: n_steps must be at least 1");
+    for (int i = 0; i < n_members; ++i) {
+        Decoder *d = members[i];
+        if (!d) return drv.fail_arg("step_wide: null member");
+        if (d->dead_) return drv.fail_arg("step_wide: dead member");
+        for (int j = 0; j < i; ++j)
+            if (members[j] == d) return drv.fail_arg("step_wide: a member is repeated");
+        if (d->root() != drv.root()) return drv.fail_arg("step_wide: all members must run on the same weights (an owner and its borrowers)");
+        if (d->kv_f16_ != drv.kv_f16_) return drv.fail_arg("step_wide: mixed KV cache types");
+        if (!d->embed_) return drv.fail_arg("model globals not set");
+    }
+    int max_p = 0;
+    for (int i = 0; i < n_members; ++i) {
+        Decoder *d = members[i];
+        const int p = d->position();
+        if (p < 0) {
+            drv.err_ = d->err_;
+            return BITNET_HIP_ERR_GPU;
+        }
+        if (n_steps > drv.c_.max_pos - 1 - p) return drv.fail_arg("KV cache overflow");  // T:1190-1194 (no p + n_steps: a huge count must not wrap)
+        max_p = p > max_p ? p : max_p;
+    }
+    return drv.wide_forward(members, n_members, n_steps, max_p, digits, elapsed_ms);
+}
+
+// The wide step's chain, n_steps times: gather, layers (prompt_attention takes the rows attention while wide_n_ is set), saturation check, head,
+// hand-over, then the samplers and logits taps member by member.  This decoder is the driver; max_p = the largest position before the call.
+int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms) {
+    const size_t H = c_.hidden, V = (size_t)c_.vocab, NL = layers_.size(), W = BITNET_HIP_WIDE_MAX;
+    hipStream_t s = (hipStream_t)stream_;
+    const size_t ws_need = bitnet_hip_score_workspace_bytes((size_t)M, H, V);
+    if (ws_need == 0) return fail_arg("step_wide: dimensions too large");
+    if (!wide_tables_) HCHK(hipMalloc((void **)&wide_tables_, (2 * NL + 6) * W * sizeof(void *)));
+    if (M > wide_cap_ || ws_need > wide_ws_bytes_) {
+        const size_t cap = (size_t)(M > wide_cap_ ? M : wide_cap_), sb = bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos);
+        for (void *q : {(void *)wide_scratch_, (void *)wide_logits_, (void *)wide_nll_, (void *)wide_am_, (void *)wide_tgt_, wide_ws_})
+            if (q) hipFree(q);
+        wide_scratch_ = wide_logits_ = wide_nll_ = nullptr;
+        wide_am_ = wide_tgt_ = nullptr;
+        wide_ws_ = nullptr;
+        wide_cap_ = 0, wide_ws_bytes_ = 0;
+        const size_t wb = bitnet_hip_score_workspace_bytes(cap, H, V);
+        HCHK(hipMalloc((void **)&wide_scratch_, cap * sb));
+        HCHK(hipMemsetAsync(wide_scratch_, 0, cap * sb, s));  // the combine requests records past the context (and drops them by index): valid, finite memory
+        HCHK(dalloc(&wide_logits_, cap * V));
+        HCHK(dalloc(&wide_nll_, cap));
+        HCHK(dalloc(&wide_am_, cap));
+        HCHK(dalloc(&wide_tgt_, cap));
+        HCHK(hipMemsetAsync(wide_tgt_, 0xff, cap * 4, s));  // target -1: no NLL, the head leaves logits and argmax
+        HCHK(hipMalloc(&wide_ws_, wb));
+        wide_cap_ = (int)cap, wide_ws_bytes_ = wb;
+    }
+    if (int rc = ensure_prompt_buffers(M, 16)) return rc;
+    // the pointer tables, uploaded once per call: [2 l] / [2 l + 1] layer l's K / V caches, then position, history, forced count, logits row and
+    // the pick's token / position entries (NULL for a member that samples: its sampler does the hand-over)
+    {
+        std::vector<void *> t((2 * NL + 6) * W, nullptr);
+        for (int i = 0; i < M; ++i) {
+            Decoder *d = members[i];
+            for (size_t l = 0; l < NL; ++l) t[(2 * l) * W + i] = d->layers_[l].kcache, t[(2 * l + 1) * W + i] = d->layers_[l].vcache;
+            void **g = t.data() + 2 * NL * W;
+            g[0 * W + i] = d->pos_, g[1 * W + i] = d->history_, g[2 * W + i] = d->n_forced_, g[3 * W + i] = d->logits_;
+            g[4 * W + i] = d->sampling_ ? nullptr : d->token_, g[5 * W + i] = d->sampling_ ? nullptr : d->pos_;
+        }
+        HCHK(hipMemcpy(wide_tables_, t.data(), t.size() * sizeof(void *), hipMemcpyHostToDevice));
+    }
+    void **g = wide_tables_ + 2 * NL * W;
+    const int32_t *const *pos_t = reinterpret_cast<const int32_t *const *>(g), *const *hist_t = reinterpret_cast<const int32_t *const *>(g + W);
+    Event ev0, ev1;
+    HCHK(hipEventCreate(&ev0.e));
+    HCHK(hipEventCreate(&ev1.e));
+    HCHK(hipEventRecord(ev0.e, s));
+    struct InFlight {  // an error return must not leave the rows attention or the repeat's matmul forms switched on
+        int &n;
+        bool &scaled;
+        ~InFlight() { n = 0, scaled = false; }
+    } in_flight{wide_n_, force_scaled_};
+    for (int step = 0; step < n_steps; ++step) {
+        wide_key_bound_ = max_p + step + 1;
+        int dg = digits;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            if (attempt == 0) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this step
+            BCHK(bitnet_hip_embed_rows_dev(embed_, hist_t, pos_t, (size_t)M, H, V, pf_x_, s));
+            wide_n_ = M;
+            bool f16_rows = false;
+            const int rc = prompt_layers((size_t)M, dg, &f16_rows);
+            wide_n_ = 0;
+            if (rc) return rc;
+            if (!f16_rows || attempt == 1) break;
+            // the saturation rule of prompt_forward: if any f16 hand-over value clamped, the WHOLE step is repeated on the digit planes.  The
+            // positions move only in the pick below, so the repeat rewrites the same cache slots.
+            HCHK(hipStreamSynchronize(s));
+            if (bitnet_hip_f16_saturations(1) == 0) break;
+            force_scaled_ = true;
+            ++saturation_fallbacks_;
+            dg = 4;
+        }
+        force_scaled_ = false;
+        BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, (size_t)M, wide_tgt_, wide_nll_, wide_am_, wide_logits_, (size_t)M, wide_ws_,
+                                      wide_ws_bytes_, s));
+        BCHK(bitnet_hip_pick_rows_dev(wide_logits_, wide_am_, (size_t)M, V, reinterpret_cast<float *const *>(g + 3 * W), reinterpret_cast<int32_t *const *>(g + 4 * W),
+                                      reinterpret_cast<int32_t *const *>(g + 5 * W), reinterpret_cast<int32_t *const *>(g + W),
+                                      reinterpret_cast<const int32_t *const *>(g + 2 * W), s));
+        for (int i = 0; i < M; ++i) {  // pick_token's arrangement, on the driver's stream: the member's own sampler, then its own record
+            Decoder *d = members[i];
+            if (d->sampling_) {
+                if (bitnet_hip_sample_dev(d->sampler_, d->logits_, V, d->token_, d->pos_, d->history_, d->n_forced_, s) != 0) return fail("step_wide: bitnet_hip_sample_dev");
+            }
+            if (d->lp_top_n_ >= 0) {
+                bitnet_hip_logprob_args a;
+                d->logprob_entry(&a);
+                if (bitnet_hip_logprob_dev(&a, V, s) != 0) return fail("step_wide: bitnet_hip_logprob_dev");
+            }
         }
     }
     HCHK(hipEventRecord(ev1.e, s));
@@ -1999,6 +2136,13 @@ int bitnet_host_prefill_packed(void *const *members, const int32_t *n, int n_mem
     ms[0] = live(members[0]);  // the driver carries the error text, whatever n_members is
     for (int i = 1; i < n_members && i < BITNET_HIP_PACK_MAX; ++i) ms[i] = live(members[i]);  // a null or dead handle: refused as a null member
     return Decoder::prefill_packed(ms, n, n_members, with_logits != 0, digits, elapsed_ms);
+}
+int bitnet_host_step_wide(void *const *members, int n_members, int n_steps, int digits, float *elapsed_ms) {
+    if (!members || !live(members[0])) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    Decoder *ms[BITNET_HIP_WIDE_MAX] = {};
+    ms[0] = live(members[0]);  // the driver carries the error text, whatever n_members is
+    for (int i = 1; i < n_members && i < BITNET_HIP_WIDE_MAX; ++i) ms[i] = static_cast<Decoder *>(members[i]);  // (a dead member is told from a null one)
+    return Decoder::step_wide(ms, n_members, n_steps, digits, elapsed_ms);
 }
 int bitnet_host_rewind(void *d, int n) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);

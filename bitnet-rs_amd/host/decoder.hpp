@@ -175,6 +175,28 @@ class Decoder {
     // Refused, with nothing modified: n_members outside 1..64; a null, dead or repeated member; members with different root() or kv_f16();
     // n[i] < 1; p_i + n[i] beyond the fed tokens; p_i + n[i] > max_pos - 1; model globals not set.  Members may sit in BatchDecoder slots.
     static int prefill_packed(Decoder *const *members, const int *n, int n_members, bool with_logits, int digits, float *elapsed_ms);
+    // WIDE decode step: n_steps single-token steps for n_members = 1..64 live sequences through ONE matrix forward per step -- the route between
+    // BatchDecoder (8 slots, the batch-1 GEMV restated per vector) and prefill_packed with n[i] = 1 (every member's row on a 64-row boundary, one
+    // head launch per member).  Per step the members' current tokens history[p_i] become the M dense rows of one matrix
+    // (bitnet_hip_embed_rows_dev), every layer runs on the many-row matmul chain that M rows and `digits` select (prompt_layers: every weight
+    // matrix is read once), each row attends over its own member's cache at its own position (bitnet_hip_attention_decode_rows_dev, the decode
+    // attention's 64-position records), all M logits rows come from one pass over the embedding table (bitnet_hip_score_f16_dev) and
+    // bitnet_hip_pick_rows_dev hands each row to its member: the logits into the member's own logits buffer, and for a greedy member the token,
+    // its history entry and its position.  A member that samples then draws with its own sampler, and a member whose logits tap is on records,
+    // in member order on the driver's stream (one launch each, as pick_token arranges them).
+    // Every member ends as its own n_steps x extend(1, true, digits) would leave it -- "as extend": the same arithmetic class, not the same bits
+    // (the matmul tiles follow M, and the head rounds its operand to f16 as score() does): position p_i + n_steps; slots [p_i, p_i + n_steps) of
+    // every layer filled and every other slot untouched bit for bit; history and forced tokens honoured as run() honours them (a fed token at
+    // p + 1 stays); last_logits(); the sampler state; log-probability records p_i + 1 .. p_i + n_steps.  run(), extend(), fork(),
+    // prefill_packed() and BatchDecoder::step() go on from there.  last_hidden() is NOT maintained.
+    // members[0] is the DRIVER: the forward runs on its stream and in its prompt buffers, the error text goes on it, and its
+    // saturation_fallbacks() counts a step that clamped an f16 hand-over value and was repeated -- whole -- at 4 digits (the positions move
+    // only in the pick, so the repeat rewrites the same slots).  The positions are read once, before the first launch; step s bounds the
+    // attention's record grid by the largest position + s + 1.  Eager launches; synchronises before returning.  The logits matrix, the head's
+    // workspace, the device pointer tables and the attention scratch of 64 sequences are allocated at the first call and grow on demand.
+    // Refused, with nothing modified: n_members outside 1..64; n_steps < 1; a null, dead or repeated member; members with different root() or
+    // kv_f16(); model globals not set; p_i + n_steps > max_pos - 1 ("KV cache overflow").  Members may sit in BatchDecoder slots.
+    static int step_wide(Decoder *const *members, int n_members, int n_steps, int digits, float *elapsed_ms);
     // Keep the first n positions of the sequence, 0 <= n <= position(): the position becomes n and the forced count min(forced, n), on
     // host and device.  The cache bytes stay as they are (the decode attention gives slots beyond the position zero weight, the
     // continuation attention never reads a slot at or beyond its past length), and so do the sampler's counts and word counter:
@@ -303,6 +325,18 @@ class Decoder {
     // the pack in flight (empty: none): prompt_attention then calls the packed operator with every member's caches of the layer
     std::vector<Decoder *> pack_members_;
     std::vector<int32_t> pack_row0_, pack_len_, pack_past_;
+    // the wide step in flight (wide_n_ == 0: none): prompt_attention then calls the rows attention with the layer's cache pointer tables
+    int wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms);  // the body of step_wide, on the driver
+    int wide_n_ = 0, wide_key_bound_ = 0;
+    // wide buffers (none before the first call): device pointer tables [2 * n_layers + 6][64] -- per layer K then V caches, then position, history,
+    // forced count, logits row, and the pick's token / position tables (NULL for a member that samples) --, the attention scratch of wide_cap_
+    // sequences (zero-filled), the head's [wide_cap_, vocab] logits, argmax, nll, targets (-1) and workspace
+    void **wide_tables_ = nullptr;
+    int wide_cap_ = 0;
+    float *wide_scratch_ = nullptr, *wide_logits_ = nullptr, *wide_nll_ = nullptr;
+    int32_t *wide_am_ = nullptr, *wide_tgt_ = nullptr;
+    void *wide_ws_ = nullptr;
+    size_t wide_ws_bytes_ = 0;
     void release_layer(Layer &L);  // frees the layer's handles, subtracts their bytes, drops the captured graphs
     void drop_graphs();
     int pick_token(void *stream, bool record = true);  // final norm + tied logits + the next token (greedy argmax or the sampler) [+ its logprob record]
@@ -411,6 +445,8 @@ int bitnet_host_finish_prefill(void *d, int n, const float *last_row, int with_l
 int bitnet_host_extend(void *d, int n, int with_logits, int digits, float *elapsed_ms);  // Decoder::extend
 // Decoder::prefill_packed: members[0] drives and carries the error text
 int bitnet_host_prefill_packed(void *const *members, const int32_t *n, int n_members, int with_logits, int digits, float *elapsed_ms);
+// Decoder::step_wide: members[0] drives and carries the error text
+int bitnet_host_step_wide(void *const *members, int n_members, int n_steps, int digits, float *elapsed_ms);
 int bitnet_host_rewind(void *d, int n);                                                    // Decoder::rewind
 int bitnet_host_fork(void *src, void *const *dsts, int n_dst, int n);                      // Decoder::fork; the error text goes on src
 int bitnet_host_cached_prefix(void *d, const int32_t *tokens, int n);                      // Decoder::cached_prefix; -1 on error

@@ -504,6 +504,46 @@ int bitnet_hip_logits_f16_batch_dev(const void *table_f16_dev, const float *x_de
                                     size_t vocab, size_t n_seq, float *const *logits_ptrs_dev, void *scratch_dev, size_t n_wg,
                                     int32_t *const *token_ptrs_dev, int32_t *const *pos_ptrs_dev, int32_t *const *history_ptrs_dev,
                                     const int32_t *const *n_forced_ptrs_dev, void *stream);
+/* ---- the WIDE decode step: up to BITNET_HIP_WIDE_MAX live sequences as the dense rows of one matrix ---------------------------------
+ * Between the batched step above (8 vectors, the batch-1 GEMV restated per vector) and the packed prompt forward (every member's rows on a
+ * 64-row boundary) sits the step that puts M <= 64 sequences' current tokens into M dense rows: bitnet_hip_embed_rows_dev gathers them, the
+ * many-row matmuls (bitnet_hip_matmul_fused_dev / _f16_dev) read every weight matrix once, bitnet_hip_attention_decode_rows_dev lets each row
+ * attend over its own sequence's cache, bitnet_hip_score_f16_dev (targets -1, argmax, logits_rows = M) takes all logits rows from one pass
+ * over the table and bitnet_hip_pick_rows_dev hands every row over to its sequence.  Conventions of the batched entries: per-sequence state
+ * through DEVICE arrays of n_seq device pointers, a NULL entry = an idle row (nothing is read or written for it); asynchronous and
+ * capture-safe (no allocation, no synchronisation).  BITNET_HIP_ERR_INVALID_ARGUMENT before anything launches: n_seq outside
+ * 1..BITNET_HIP_WIDE_MAX, a NULL required pointer, head_dim != 128, n_heads % n_kv_heads != 0 or a group larger than 4, unknown flag bits,
+ * sizes that overflow. */
+#define BITNET_HIP_WIDE_MAX 64
+/* Row b of x_out_dev [n_seq, hidden] f32 = the embedding of history_ptrs[b][*pos_ptrs[b]], the token clamped to the vocabulary: bit for bit
+ * what bitnet_hip_embed_f16_dev writes for that token.  An idle row (NULL history or position) is ZERO-FILLED: the matmuls read every row.
+ * hidden % 8 == 0. */
+int bitnet_hip_embed_rows_dev(const void *table_f16_dev, const int32_t *const *history_ptrs_dev, const int32_t *const *pos_ptrs_dev, size_t n_seq,
+                              size_t hidden, size_t vocab, float *x_out_dev, void *stream);
+/* bitnet_hip_attention_decode_batch_dev for up to 64 sequences with a ROW output.  qkv_dev: [n_seq, n_heads*D + 2*n_kv*D] dense.  Sequence b,
+ * at p = *pos_ptrs[b]: RoPE on q and k at p, k and v appended at slot p of its own caches (exact f32, or rounded once to f16 under
+ * BITNET_HIP_ATTN_CACHE_F16), attention over keys 0..p.  out_dev: [n_seq, n_heads*D] f32, or f16 rows under BITNET_HIP_ATTN_OUT_F16 (the
+ * input format of bitnet_hip_matmul_f16_dev and of BITNET_HIP_FUSE_X_F16).  The kernels share their bodies with the batched and the batch-1
+ * 64-position-record form: a row's f32 output and its cache bytes are BIT FOR BIT theirs; the f16 output is that f32 value rounded once to
+ * nearest-even.
+ * key_bound, 1..max_pos: the caller promises *pos_ptrs[b] < key_bound for every bound sequence, and the record grid covers
+ * ceil(key_bound / 64) records instead of max_pos / 64 (64 sequences x 5 KV heads x 64 records are 20480 workgroups per layer, most of
+ * which would leave at once).  A sequence that breaks the promise is treated as IDLE for the launch: its caches, its records and its output
+ * row keep their bytes.  Any key_bound that covers every position gives the same bits.
+ * scratch_dev: n_seq areas of bitnet_hip_attention_scratch_bytes(n_kv_heads, max_pos), zero-filled once before first use. */
+int bitnet_hip_attention_decode_rows_dev(const float *qkv_dev, const float *rope_sin_dev, const float *rope_cos_dev, void *const *kcache_ptrs_dev,
+                                         void *const *vcache_ptrs_dev, const int32_t *const *pos_ptrs_dev, size_t n_seq, size_t n_heads,
+                                         size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t key_bound, float *scratch_dev, int flags,
+                                         void *out_dev, void *stream);
+/* The hand-over behind the head, one launch.  logits_dev: the head's [n_seq, vocab] f32 matrix; argmax_dev: its per-row argmax (lowest index
+ * on ties, NaN = -inf: what bitnet_hip_score_f16_dev leaves; clamped to the vocabulary).  Row b: the logits row is copied to logits_ptrs[b]
+ * (NULL: idle row); where token_ptrs[b] / pos_ptrs[b] are given, the greedy hand-over of bitnet_hip_logits_f16_dev with p = *pos_ptrs[b]:
+ * *token_ptrs[b] = argmax, history_ptrs[b][p + 1] = token unless p + 1 < *n_forced_ptrs[b], *pos_ptrs[b] = p + 1.  A row with a logits
+ * pointer but neither a token nor a position pointer gets logits only (a sequence that samples).  token / pos / history / n_forced tables may
+ * be NULL as a whole or per entry. */
+int bitnet_hip_pick_rows_dev(const float *logits_dev, const int32_t *argmax_dev, size_t n_seq, size_t vocab, float *const *logits_ptrs_dev,
+                             int32_t *const *token_ptrs_dev, int32_t *const *pos_ptrs_dev, int32_t *const *history_ptrs_dev,
+                             const int32_t *const *n_forced_ptrs_dev, void *stream);
 /* ---- fork of a live sequence: the KV state of a prompt prefix, copied on the device ------------------------------------
  * The reference caches prompt prefixes on the host (crates/bitnet-inference/src/prefix_cache.rs: lookup, :173, returns the longest cached
  * prefix and its opaque `cached_state` bytes; insert, :212, stores one).  This entry replaces those host-side bytes with a device-to-device

@@ -481,6 +481,7 @@ __device__ __forceinline__ void store_wave_tiles(const GemmArgs &p, float (&val)
             if (token < p.m) {
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
+                    if (ra + 16 * pr >= half_rows) continue;  // a (gate, up) pair past the last row (half rows % 32 != 0: the clamped tiles recompute the last one)
                     h4 o;
                     bool sat = false;
 #pragma unroll

@@ -196,6 +196,14 @@ class HipLib:
         L.bitnet_hip_attention_scratch_bytes.restype = _sz
         L.bitnet_hip_logits_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_argmax_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _vp]
+        L.bitnet_hip_head_screen_bytes.argtypes = [_sz, _sz]
+        L.bitnet_hip_head_screen_bytes.restype = _sz
+        L.bitnet_hip_head_screen_ws_bytes.argtypes = [_sz, _sz, _sz]
+        L.bitnet_hip_head_screen_ws_bytes.restype = _sz
+        L.bitnet_hip_head_screen_build_dev.argtypes = [_vp, _sz, _sz, _vp, _vp]
+        L.bitnet_hip_head_screen_build_dev.restype = C.c_int
+        L.bitnet_hip_logits_screen_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
+        L.bitnet_hip_logits_screen_dev.restype = C.c_int
         L.bitnet_hip_hbm_read_ceiling.argtypes = [_sz, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]
         # the sampler entries are bound here, with the rest, never lazily (a handle bound on first use crashed a process once)
         L.bitnet_hip_sampler_create.argtypes = [_sz, C.POINTER(SamplingConfig), C.POINTER(_vp)]
@@ -704,6 +712,21 @@ class HipLib:
         self._check(self.c.bitnet_hip_score_f16_dev(_optr(table), _optr(x), _optr(gamma), eps, hidden, vocab, n_rows, _optr(targets), _optr(nll),
                                                     _optr(argmax), _optr(logits), logits_rows, _optr(workspace), workspace_bytes, _vp(stream)))
 
+    def head_screen_bytes(self, hidden: int, vocab: int) -> int:
+        """bytes of the screening image of a [vocab, hidden] f16 table; 0: no screened head for this hidden size"""
+        return int(self.c.bitnet_hip_head_screen_bytes(hidden, vocab))
+
+    def head_screen_ws_bytes(self, hidden: int, vocab: int, n_wg: int) -> int:
+        return int(self.c.bitnet_hip_head_screen_ws_bytes(hidden, vocab, n_wg))
+
+    def head_screen_build_dev(self, table, hidden: int, vocab: int, image, stream: int = 0) -> None:
+        self._check(self.c.bitnet_hip_head_screen_build_dev(_ptr(table), hidden, vocab, _ptr(image), _vp(stream)))
+
+    def logits_screen_dev(self, table, x, gamma, eps, hidden, vocab, image, ws, scratch, n_wg, token=None, pos=None, history=None, n_forced=None, stream: int = 0) -> None:
+        """bitnet_hip_logits_f16_dev's greedy pick without the logits: the int8 screen, then the surviving rows from the f16 table"""
+        opt = lambda t: _ptr(t) if t is not None else None
+        self._check(self.c.bitnet_hip_logits_screen_dev(_ptr(table), _ptr(x), opt(gamma), eps, hidden, vocab, _ptr(image), _ptr(ws), _ptr(scratch), n_wg, opt(token), opt(pos), opt(history), opt(n_forced), _vp(stream)))
+
     def argmax_dev(self, v, n: int, scratch, n_wg: int, token, stream: int = 0) -> None:
         self._check(self.c.bitnet_hip_argmax_dev(_ptr(v), n, _ptr(scratch), n_wg, _ptr(token), _vp(stream)))
 
@@ -1041,6 +1064,12 @@ class HostDecoder:
         L.bitnet_host_create_shared.argtypes = [C.c_void_p]
         L.bitnet_host_set_attention_form.argtypes = [C.c_void_p, C.c_int]
         L.bitnet_host_set_attention_form.restype = C.c_int
+        L.bitnet_host_set_head_screen.argtypes = [C.c_void_p, C.c_int]
+        L.bitnet_host_set_head_screen.restype = C.c_int
+        L.bitnet_host_head_screen.argtypes = [C.c_void_p]
+        L.bitnet_host_head_screen.restype = C.c_int
+        L.bitnet_host_head_screen_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.bitnet_host_head_screen_stats.restype = C.c_int
         L.bitnet_host_release.argtypes = [C.c_void_p]
         L.bitnet_host_release.restype = None
         L.bitnet_host_create.restype = C.c_void_p
@@ -1125,6 +1154,22 @@ class HostDecoder:
         """-1: the attention form follows the position (default); 0: 64-position records + combine at every position, the form a
         HostBatch step runs -- run() under form 0 gives the bits a batch reproduces."""
         self._check(self.c.bitnet_host_set_attention_form(self.h, form))
+
+    def set_head_screen(self, on: bool) -> None:
+        """the screened greedy head (default on, env BITNET_HOST_HEAD_SCREEN): plain greedy steps pick their token through the int8 screen
+        of the embedding table; off, every step runs the full f16 head.  Same tokens, same last_logits().  Drops the captured graphs."""
+        self._check(self.c.bitnet_host_set_head_screen(self.h, 1 if on else 0))
+
+    def head_screen(self) -> int:
+        """1: plain greedy steps take the screened head (switched on AND an image exists); 0: they take the full head"""
+        return int(self.c.bitnet_host_head_screen(self.h))
+
+    def head_screen_stats(self) -> tuple[int, int, int]:
+        """device counters of this decoder's screened head: (rows the last launch rescored from the f16 table, launches so far, rows
+        rescored over all launches); (0, 0, 0) while no image exists.  Synchronises."""
+        out = (C.c_uint32 * 3)()
+        self._check(self.c.bitnet_host_head_screen_stats(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def load_gguf(self, gguf: "GgufFile") -> None:
         self.c.bitnet_host_load_gguf.argtypes = [C.c_void_p, C.c_void_p]

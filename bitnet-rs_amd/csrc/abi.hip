@@ -1624,6 +1624,41 @@ int bitnet_hip_logits_f16_dev(const void *table, const float *x, const float *ga
     BH_GUARD_END
 }
 
+/* ---- the screened greedy head (kernels_head.hip) ---- */
+
+size_t bitnet_hip_head_screen_bytes(size_t hidden, size_t vocab) { return head_screen_bytes(hidden, vocab); }
+
+size_t bitnet_hip_head_screen_ws_bytes(size_t hidden, size_t vocab, size_t n_wg) {
+    if (!head_screen_bytes(hidden, vocab) || n_wg == 0 || n_wg > 65535) return 0;
+    return head_screen_ws(nullptr, hidden, vocab, n_wg).floats * sizeof(float);
+}
+
+int bitnet_hip_head_screen_build_dev(const void *table, size_t hidden, size_t vocab, void *image, void *stream) {
+    BH_GUARD_BEGIN
+    if (!table || !image) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to head_screen_build_dev");
+    if (!head_screen_bytes(hidden, vocab))
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "head_screen: no instance for hidden %zu (512, 1024, 2048, 2560, 4096) or vocab %zu out of range", hidden, vocab);
+    BH_HIP_TRY(launch_head_screen_build(table, (int)hidden, (int)vocab, image, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_logits_screen_dev(const void *table, const float *x, const float *gamma, float eps, size_t hidden, size_t vocab, const void *image,
+                                 float *ws, void *scratch, size_t n_wg, int32_t *token_dev, int32_t *pos_dev, int32_t *history_dev,
+                                 const int32_t *n_forced_dev, void *stream) {
+    BH_GUARD_BEGIN
+    if (!table || !x || !image || !ws || !scratch) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to logits_screen_dev");
+    if (!head_screen_bytes(hidden, vocab))
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "head_screen: no instance for hidden %zu (512, 1024, 2048, 2560, 4096) or vocab %zu out of range", hidden, vocab);
+    if (int rc = check_logits_n_wg(n_wg)) return rc;
+    const BestScratch best(scratch, n_wg);
+    BH_HIP_TRY(launch_head_screen(table, x, gamma, eps, (int)hidden, (int)vocab, image, ws, best.val, best.idx, (int)n_wg, (hipStream_t)stream));
+    if (token_dev || pos_dev)
+        BH_HIP_TRY(launch_argmax_final(best.val, best.idx, head_rescore_wgs((int)n_wg), token_dev, pos_dev, history_dev, n_forced_dev, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 int bitnet_hip_argmax_dev(const float *v, size_t n, void *scratch, size_t n_wg, int32_t *token_dev, void *stream) {
     BH_GUARD_BEGIN
     if (!v || !scratch || !token_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to argmax_dev");

@@ -352,5 +352,18 @@ hipError_t launch_argmax_final(const float *best_val, const int *best_idx, int n
                                int *history, const int *n_forced, hipStream_t stream);
 hipError_t launch_argmax(const float *v, int n, float *best_val, int *best_idx, int n_wg, int *token_out,
                          hipStream_t stream);
+// The screened greedy head (kernels_head.hip): the int8 screening image of the f16 table (0 bytes: no instance for this hidden size), the
+// float workspace both launches share, and the two launches that leave head_rescore_wgs(n_wg) partials for launch_argmax_final.
+struct HeadScreenWs {
+    float *ub, *lb_max, *x, *rescored;
+    unsigned *count;
+    size_t floats;
+};
+size_t head_screen_bytes(size_t hidden, size_t vocab);
+HeadScreenWs head_screen_ws(float *ws, size_t hidden, size_t vocab, size_t n_wg);
+int head_rescore_wgs(int n_wg);
+hipError_t launch_head_screen_build(const void *table, int hidden, int vocab, void *image, hipStream_t stream);
+hipError_t launch_head_screen(const void *table, const float *x, const float *gamma, float eps, int hidden, int vocab, const void *image, float *ws,
+                              float *best_val, int *best_idx, int n_wg, hipStream_t stream);
 
 }  // namespace bitnet_hip

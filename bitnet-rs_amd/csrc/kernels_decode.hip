@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "head.hpp"
 #include "wave.hpp"
 
 namespace bitnet_hip {
@@ -90,51 +91,21 @@ __global__ __launch_bounds__(256) void k_logits_f16(const _Float16 *__restrict__
     __shared__ int wbi[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // final norm (T:1589), recomputed per workgroup: 10 KB from L2
-    float s = 0.0f;
-    for (int i = tid; i < hidden; i += 256) s += x[i];
-    const float mean = gamma ? block256_sum_f(s, slot) / (float)hidden : 0.0f;
-    float ss = 0.0f;
-    for (int i = tid; i < hidden; i += 256) {
-        const float d = x[i] - mean;
-        ss += d * d;
-    }
-    const float denom = gamma ? sqrtf(block256_sum_f(ss, slot) / (float)hidden + eps) : 1.0f;
-    for (int i = tid; i < hidden; i += 256) xs[i] = gamma ? (x[i] - mean) / denom * gamma[i] : x[i];
-    __syncthreads();
+    head_final_norm(x, gamma, eps, hidden, xs, slot);
     const int nchunks = hidden >> 9;
     float xr[NCH][8];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xr[c][i] = (!GUARD || c < nchunks) ? xs[512 * c + 8 * lane + i] : 0.0f;
+    head_lane_x<NCH, GUARD>(xs, nchunks, lane, xr);
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     const int total_waves = gridDim.x * 4;
     for (int row = (blockIdx.x * 4 + wave) * R; row < vocab; row += total_waves * R) {
         h8 w[R][NCH];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            // the table is read once per token by one wave: non-temporal (MI355X_MICROARCH.md, nt-weights);
-            // rows past the end re-read the last row (never stored)
-            const _Float16 *e = table + (size_t)(row + r < vocab ? row + r : vocab - 1) * hidden + 8 * lane;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                // a chunk past hidden / 512 is padding: zeros, not a second read of chunk 0 (0 * Inf of a table entry there would be NaN)
-                if (!GUARD || c < nchunks)
-                    w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const h8 *>(e + 512 * c));
-                else
-                    w[r][c] = (h8)(_Float16)0.0f;
-            }
-        }
+        for (int r = 0; r < R; ++r)  // rows past the end re-read the last row (never stored)
+            head_lane_row<NCH, GUARD>(table + (size_t)(row + r < vocab ? row + r : vocab - 1) * hidden + 8 * lane, nchunks, w[r]);
         float acc[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            acc[r] = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[r] += xr[c][i] * (float)w[r][c][i];
-        }
+        for (int r = 0; r < R; ++r) acc[r] = head_lane_dot<NCH>(xr, w[r]);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1)
 #pragma unroll

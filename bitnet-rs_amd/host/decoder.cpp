@@ -87,6 +87,8 @@ Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n
     if (const char *e = getenv("BITNET_HOST_KV16")) kv_f16_ = atoi(e) != 0;  // opt-in f16 KV cache (long contexts)
     if (const char *e = getenv("BITNET_HOST_ACT")) act_mode_ = atoi(e) != 0 ? 1 : 0;  // 0: exact f32 activations between the kernels
     if (const char *e = getenv("BITNET_HOST_PREFILL_CHAIN")) prefill_chain_ = atoi(e) != 0 ? 1 : 0;  // the prompt forward's f16 activation chain
+    if (const char *e = getenv("BITNET_HOST_HEAD_SCREEN")) head_screen_on_ = atoi(e) != 0;  // 0: every step on the full f16 head
+    if (const char *e = getenv("BITNET_HOST_SCREEN_WGS")) screen_wgs_ = atoi(e) > 0 && atoi(e) <= 65535 ? atoi(e) : screen_wgs_;  // tuning knob
     if (bitnet_hip_init(-1) != 0) {
         const char *e = bitnet_hip_get_last_error();
         err_ = e ? e : "bitnet_hip_init failed";
@@ -124,7 +126,9 @@ Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n
     ok &= dalloc(&ref_n_, H > (size_t)c_.ffn ? H : (size_t)c_.ffn) == hipSuccess && dalloc(&ref_gu_, 2 * (size_t)c_.ffn) == hipSuccess &&
           dalloc(&ref_t_, H) == hipSuccess;
     ok &= dalloc(&logits_, (size_t)c_.vocab) == hipSuccess;
-    ok &= hipMalloc(&scratch_, 8 * (size_t)logits_wgs_) == hipSuccess;
+    ok &= hipMalloc(&scratch_, 8 * (size_t)(logits_wgs_ > screen_wgs_ ? logits_wgs_ : screen_wgs_)) == hipSuccess;
+    if (const size_t wb = bitnet_hip_head_screen_ws_bytes(H, (size_t)c_.vocab, (size_t)screen_wgs_))  // 0: no screened head at this hidden size
+        ok = ok && hipMalloc((void **)&screen_ws_, wb) == hipSuccess && hipMemset(screen_ws_, 0, wb) == hipSuccess;
     {
         const size_t sb = bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos);
         // zero-filled: the merging o-projection reads records of chunks past the context (and gives them zero weight)
@@ -189,6 +193,7 @@ Decoder::Decoder(Decoder &owner, int) : Decoder(owner.c_) {
     hipFree(final_norm_);
     final_norm_ = owner.final_norm_;
     embed_ = owner.embed_;
+    screen_ = owner.screen_;
     weight_bytes_ = owner.weight_bytes_;
     act_mode_ = owner.act_mode_;
     owner_ = &owner;
@@ -207,7 +212,10 @@ int Decoder::set_attention_form(int form) {
     return 0;
 }
 
-void Decoder::batch_objects(void *ptrs[3]) const { ptrs[0] = n_forced_, ptrs[1] = logits_, ptrs[2] = sampler_; }
+void Decoder::batch_objects(void *ptrs[3]) {
+    refresh_logits();  // the batch writes this row from now on
+    ptrs[0] = n_forced_, ptrs[1] = logits_, ptrs[2] = sampler_;
+}
 
 Decoder::~Decoder() {
     drop_graphs();
@@ -216,7 +224,7 @@ Decoder::~Decoder() {
         if (p) hipFree(p);
     if (owner_) {  // borrowed objects stay the owner's
         for (auto &L : layers_) L.qkv = L.o = L.gateup = L.down = 0, L.attn_norm = L.ffn_norm = nullptr;
-        embed_ = nullptr, final_norm_ = nullptr;
+        embed_ = nullptr, final_norm_ = nullptr, screen_ = nullptr;
         owner_->borrowers_--;
     }
     for (auto &L : layers_) {
@@ -225,7 +233,7 @@ Decoder::~Decoder() {
         for (float *p : {L.attn_norm, L.ffn_norm, L.kcache, L.vcache})
             if (p) hipFree(p);
     }
-    for (void *p : {(void *)embed_, (void *)final_norm_, (void *)rope_sin_, (void *)rope_cos_, (void *)x_, (void *)x2_,
+    for (void *p : {(void *)embed_, screen_, (void *)screen_ws_, (void *)final_norm_, (void *)rope_sin_, (void *)rope_cos_, (void *)x_, (void *)x2_,
                     (void *)qkv_, (void *)att_, (void *)h_, (void *)ref_n_, (void *)ref_gu_, (void *)ref_t_, qa_x_, qa_x2_, qa_att_, qa_h_, (void *)st_x_, (void *)st_x2_, (void *)logits_, scratch_, (void *)attn_scratch_, (void *)pos_, (void *)n_forced_,
                     (void *)history_, (void *)token_})
         if (p) hipFree(p);
@@ -261,11 +269,66 @@ void Decoder::drop_graphs() {
         if (graph_[i]) hipGraphDestroy((hipGraph_t)graph_[i]);
         graph_exec_[i] = graph_[i] = nullptr;
     }
+    graphs_screened_ = -1;
 }
 
-int Decoder::pick_token(void *stream, bool record) {
+// Plain greedy decode reads no logits: the tap, the sampler and the tracer are the step's only readers of logits_, and a batch slot writes it.
+bool Decoder::screen_step(bool need_logits) const {
+    return head_screen_on_ && screen_ && screen_ws_ && !sampling_ && lp_top_n_ < 0 && !batch_ && !need_logits;
+}
+
+int Decoder::ensure_screen_image() {
+    if (owner_) {
+        if (int rc = owner_->ensure_screen_image()) {
+            err_ = owner_->err_;
+            return rc;
+        }
+        screen_ = owner_->screen_;
+        return 0;
+    }
+    const size_t H = c_.hidden, V = c_.vocab, bytes = bitnet_hip_head_screen_bytes(H, V);
+    if (!bytes || !embed_) return 0;  // no instance for this hidden size, or no table yet (set_globals builds it)
+    if (!screen_) HCHK(hipMalloc(&screen_, bytes));
+    BCHK(bitnet_hip_head_screen_build_dev(embed_, H, V, screen_, stream_));
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    return 0;
+}
+
+int Decoder::set_head_screen(bool on) {
+    if (on && !screen_)
+        if (int rc = ensure_screen_image()) return rc;
+    if (on != head_screen_on_) drop_graphs();
+    head_screen_on_ = on;
+    return 0;
+}
+
+int Decoder::head_screen_stats(uint32_t out[3]) {
+    out[0] = out[1] = out[2] = 0;
+    if (!screen_ws_) return 0;
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    HCHK(hipMemcpy(out, screen_x() + (size_t)c_.hidden, 12, hipMemcpyDeviceToHost));  // the counter words follow the saved input
+    return 0;
+}
+
+int Decoder::refresh_logits() {
+    if (!logits_stale_) return 0;
+    BCHK(bitnet_hip_logits_f16_dev(embed_, screen_x(), final_norm_, c_.eps, (size_t)c_.hidden, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_,
+                                   nullptr, nullptr, nullptr, nullptr, stream_));
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    logits_stale_ = false;
+    return 0;
+}
+
+int Decoder::pick_token(void *stream, bool record, bool need_logits) {
     hipStream_t s = (hipStream_t)stream;
     const size_t H = c_.hidden;
+    pick_screened_ = screen_step(need_logits);
+    if (pick_screened_) {
+        // the full head's token from the int8 screen + the surviving rows of the f16 table; logits_ stays as it is (refresh_logits)
+        BCHK(bitnet_hip_logits_screen_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, screen_, screen_ws_, scratch_, (size_t)screen_wgs_, token_, pos_,
+                                          history_, n_forced_, s));
+        return 0;
+    }
     if (!sampling_) {
         // greedy token (T:1589, T:1599-1630, sampling.rs:189-202)
         BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, token_, pos_,
@@ -480,10 +543,12 @@ int Decoder::set_layer_specs(int layer, const float *attn_norm, const float *ffn
 
 int Decoder::set_globals(const uint16_t *embed_f16, const float *final_norm) {
     if (int rc = weights_locked()) return rc;
+    if (int rc = refresh_logits()) return rc;  // logits still owed from a screened step belong to the table that is about to go
     const size_t n = (size_t)c_.vocab * c_.hidden * 2;
     if (!embed_) HCHK(hipMalloc(&embed_, n));
     HCHK(hipMemcpy(embed_, embed_f16, n, hipMemcpyHostToDevice));
     HCHK(hipMemcpy(final_norm_, final_norm, (size_t)c_.hidden * 4, hipMemcpyHostToDevice));
+    if (head_screen_on_ || screen_) return ensure_screen_image();  // the image follows the table
     return 0;
 }
 
@@ -639,7 +704,7 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
         }
         if (tr) TRACE("t" + std::to_string(tr->seq) + "_all_layers_out", "all_layers_out", -1, x_, H);
         if (with_logits) {
-            if (int rc = pick_token(s, !tr)) return rc;
+            if (int rc = pick_token(s, !tr, tr != nullptr)) return rc;
             TRACE(tp + "logits", "logits", -1, logits_, (size_t)c_.vocab);
         } else {
             BCHK(bitnet_hip_advance_pos_dev(pos_, s));
@@ -681,7 +746,7 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
     if (tr) TRACE("t" + std::to_string(tr->seq) + "_all_layers_out", "all_layers_out", -1, x_, H);
     if (with_logits) {
         // final norm + tied logits + greedy token (T:1589, T:1599-1630, sampling.rs:189-202)
-        if (int rc = pick_token(s, !tr)) return rc;
+        if (int rc = pick_token(s, !tr, tr != nullptr)) return rc;
         TRACE(tp + "logits", "logits", -1, logits_, (size_t)c_.vocab);
     } else {
         BCHK(bitnet_hip_advance_pos_dev(pos_, s));
@@ -714,6 +779,7 @@ int Decoder::trace_step(const char *dir, bool with_logits) {
     tr.stream = stream_;
     const int rc = step_launches(with_logits, form_at(p), &tr);
     if (rc) return rc;
+    if (with_logits) picked(pick_screened_);
     HCHK(hipStreamSynchronize((hipStream_t)stream_));
     return 0;
 }
@@ -765,6 +831,7 @@ int Decoder::run_reference(int n, bool with_logits) {
     for (int i = 0; i < n; ++i) {
         const int rc = step_launches_reference(with_logits);
         if (rc) return rc;
+        if (with_logits) picked(pick_screened_);
     }
     HCHK(hipStreamSynchronize((hipStream_t)stream_));
     // the reference-order kernels rebuilt a row-major copy of every matrix: give them back (one copy of the weights on the device)
@@ -806,7 +873,9 @@ int Decoder::prepare_graphs(bool with_logits) {
 
 int Decoder::ensure_graph(bool with_logits, int form) {
     const int gi = 2 * form + (with_logits ? 1 : 0);
+    if (graphs_screened_ != (int)screen_step(false)) drop_graphs();  // captured under another head (a batch slot taken or left since)
     if (graph_exec_[gi]) return 0;
+    graphs_screened_ = (int)screen_step(false);
     hipStream_t s = (hipStream_t)stream_;
     hipGraph_t g = nullptr;
     HCHK(hipStreamBeginCapture(s, hipStreamCaptureModeGlobal));
@@ -867,6 +936,7 @@ int Decoder::run(int n, bool with_logits, bool use_graph, float *elapsed_ms) {
             int rc = step_launches(with_logits, form_at(p + i));
             if (rc) return rc;
         }
+        if (with_logits) picked(screen_step(false));
     }
     HCHK(hipEventRecord(e1, s));
     HCHK(hipStreamSynchronize(s));
@@ -1427,6 +1497,7 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
             Decoder *d = members[i];
             for (size_t l = 0; l < NL; ++l) t[(2 * l) * W + i] = d->layers_[l].kcache, t[(2 * l + 1) * W + i] = d->layers_[l].vcache;
             void **g = t.data() + 2 * NL * W;
+            if (d->refresh_logits()) return fail("step_wide: refresh_logits");  // the pick writes this row from now on
             g[0 * W + i] = d->pos_, g[1 * W + i] = d->history_, g[2 * W + i] = d->n_forced_, g[3 * W + i] = d->logits_;
             g[4 * W + i] = d->sampling_ ? nullptr : d->token_, g[5 * W + i] = d->sampling_ ? nullptr : d->pos_;
         }
@@ -1882,6 +1953,7 @@ int Decoder::finish_prefill(int n, const float *last_row, bool with_logits) {
     HCHK(hipStreamSynchronize(s));  // `last` is a stack variable
     if (with_logits && last_row) {
         if (int rc = pick_token(s)) return rc;
+        picked(pick_screened_);
     } else {
         BCHK(bitnet_hip_advance_pos_dev(pos_, s));
     }
@@ -1912,6 +1984,7 @@ int Decoder::history(int32_t *out, int n) {
     return 0;
 }
 int Decoder::last_logits(float *out) {
+    if (int rc = refresh_logits()) return rc;  // after a screened step: the full head once, on the head input that step saved
     HCHK(hipMemcpy(out, logits_, (size_t)c_.vocab * 4, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1955,9 +2028,13 @@ int Decoder::probe_kernel(int kind, int reps, float *us_per_launch, double *byte
             case 2: rc = bitnet_hip_gemv_fused_dev(L.o, att_, x2_, 1, nullptr, 0.f, x_, 0, stream_); break;
             case 3: rc = bitnet_hip_gemv_fused_dev(L.gateup, x2_, h_, 1, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL, stream_); break;
             case 4: rc = bitnet_hip_gemv_fused_dev(L.down, h_, x_, 1, nullptr, 0.f, x2_, 0, stream_); break;
-            default:
-                rc = bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_,
-                                               (size_t)logits_wgs_, token_, nullptr, nullptr, nullptr, stream_);
+            default:  // the head form a plain step runs now
+                if (screen_step(false))
+                    rc = bitnet_hip_logits_screen_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, screen_, screen_ws_, scratch_, (size_t)screen_wgs_,
+                                                      token_, nullptr, nullptr, nullptr, stream_);
+                else
+                    rc = bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_,
+                                                   (size_t)logits_wgs_, token_, nullptr, nullptr, nullptr, stream_);
                 break;
         }
         ++launches;
@@ -1987,6 +2064,7 @@ int Decoder::probe_kernel(int kind, int reps, float *us_per_launch, double *byte
     hipGraphExecDestroy(ex);
     hipGraphDestroy(g);
     (void)p0;
+    if (kind > 4) picked(screen_step(false));  // the head ran on x_ as it stands: logits_ is that head's, at once or on demand
     if (us_per_launch) *us_per_launch = ms * 1e3f / (float)(reps * launches);
     if (bytes_per_launch) {
         size_t ab = 0;
@@ -2010,7 +2088,16 @@ int Decoder::probe_kernel(int kind, int reps, float *us_per_launch, double *byte
             case 2: bitnet_hip_weights_info(L.o, nullptr, nullptr, &ab); *bytes_per_launch = (double)ab + 4.0 * c_.n_heads * c_.head_dim + 8.0 * H; break;
             case 3: bitnet_hip_weights_info(L.gateup, nullptr, nullptr, &ab); *bytes_per_launch = (double)ab + 8.0 * H + 4.0 * c_.ffn; break;
             case 4: bitnet_hip_weights_info(L.down, nullptr, nullptr, &ab); *bytes_per_launch = (double)ab + 4.0 * c_.ffn + 8.0 * H; break;
-            default: *bytes_per_launch = 2.0 * (double)c_.vocab * H + 8.0 * H + 4.0 * c_.vocab; break;
+            default:
+                if (screen_step(false)) {
+                    // the int8 image + ub written and read + the rows the last launch rescored + x and gamma
+                    uint32_t st[3] = {0, 0, 0};
+                    if (int rc2 = head_screen_stats(st)) return rc2;
+                    *bytes_per_launch = (double)bitnet_hip_head_screen_bytes(H, (size_t)c_.vocab) + 8.0 * c_.vocab + 2.0 * (double)st[0] * H + 8.0 * H;
+                } else {
+                    *bytes_per_launch = 2.0 * (double)c_.vocab * H + 8.0 * H + 4.0 * c_.vocab;
+                }
+                break;
         }
     }
     return 0;
@@ -2208,6 +2295,13 @@ int bitnet_host_form_at(void *d, int pos) { LIVE(-1); return pos < 0 ? -1 : D->f
 int bitnet_host_last_prefill_path(void *d) { LIVE(-1); return D->last_prefill_path(); }
 int bitnet_host_saturation_fallbacks(void *d) { LIVE(-1); return D->saturation_fallbacks(); }
 int bitnet_host_history(void *d, int32_t *out, int n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->history(out, n); }
+int bitnet_host_set_head_screen(void *d, int on) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_head_screen(on != 0); }
+int bitnet_host_head_screen(void *d) { LIVE(-1); return D->head_screen() ? 1 : 0; }
+int bitnet_host_head_screen_stats(void *d, uint32_t *out3) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    if (!out3) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    return D->head_screen_stats(out3);
+}
 int bitnet_host_last_logits(void *d, float *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->last_logits(out); }
 int bitnet_host_last_hidden(void *d, float *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->last_hidden(out); }
 int bitnet_host_blake3_hex(const void *data, size_t len, char *out65) {

@@ -85,7 +85,18 @@ class Decoder {
     // differently).  Drops nothing: graphs are kept per form.
     int set_attention_form(int form);
     // what a batch needs beside layer_objects / global_objects: {forced count, logits row, sampler (null until set_sampling)}
-    void batch_objects(void *ptrs[3]) const;
+    // (a logits row that waits for its lazy recomputation -- see set_head_screen -- is brought up to date first: others will write it)
+    void batch_objects(void *ptrs[3]);
+    // The SCREENED greedy head (bitnet_hip_logits_screen_dev): on (default; env BITNET_HOST_HEAD_SCREEN=0 switches it off), a with-logits step
+    // with sampling off, the logits tap off, no tracer and no batch slot picks its token through the int8 screening image of the embedding
+    // table -- built on the device when set_globals fills the table, vocab * hidden + 8 * vocab bytes, the owner's for a borrower -- and
+    // rescoring of the few rows the screen cannot exclude: the full head's token bit for bit, from half its bytes, and no logits vector.
+    // last_logits() after such a step runs the full head once on the head input the screen saved: the bits the full head would have left.
+    // Hidden sizes without a screening instance keep the full head.  Drops the captured graphs.
+    int set_head_screen(bool on);
+    bool head_screen() const { return screen_step(false); }  // would a plain greedy step take the screened head now?
+    // device counters of this decoder's screened head: rows the last launch rescored, launches, rows rescored by all launches.  Synchronises.
+    int head_screen_stats(uint32_t out[3]);
     bool sampling() const { return sampling_; }
     float eps() const { return c_.eps; }
 
@@ -339,7 +350,21 @@ class Decoder {
     size_t wide_ws_bytes_ = 0;
     void release_layer(Layer &L);  // frees the layer's handles, subtracts their bytes, drops the captured graphs
     void drop_graphs();
-    int pick_token(void *stream, bool record = true);  // final norm + tied logits + the next token (greedy argmax or the sampler) [+ its logprob record]
+    // final norm + tied logits + the next token (greedy argmax or the sampler) [+ its logprob record]; need_logits: a reader of logits_
+    // follows in this step (the tracer), so the full head.  Leaves pick_screened_; whoever EXECUTES the launches (not a capture) calls picked().
+    int pick_token(void *stream, bool record = true, bool need_logits = false);
+    bool screen_step(bool need_logits) const;
+    void picked(bool screened) { logits_stale_ = screened; }
+    int ensure_screen_image();  // the owner's image, built if missing (set_globals, set_head_screen)
+    int refresh_logits();       // logits_ stale after a screened step: the full head once on the saved head input
+    // the head input the last screened launch saved: behind ub and the lb maxima in the workspace (layout: include/bitnet_hip.h)
+    float *screen_x() const { return screen_ws_ + ((size_t)c_.vocab + 3) / 4 * 4 + ((size_t)screen_wgs_ + 3) / 4 * 4; }
+    void *screen_ = nullptr;        // int8 screening image of embed_ (borrowed with it)
+    float *screen_ws_ = nullptr;    // ub, lb maxima, saved head input, counters, rescored rows (bitnet_hip_head_screen_ws_bytes); own
+    bool head_screen_on_ = true;    // BITNET_HOST_HEAD_SCREEN / set_head_screen
+    bool pick_screened_ = false;    // what the last pick_token issued (or captured)
+    bool logits_stale_ = false;     // the last executed head was the screened one: logits_ does not hold its logits yet
+    int graphs_screened_ = -1;      // screen_step(false) when the live graphs were captured (-1: none captured)
     int adopt_projections(Layer &L, bitnet_hip_weights_t h[7]);
     std::vector<Layer> layers_;
     void *embed_ = nullptr;
@@ -404,6 +429,7 @@ class Decoder {
     void *graph_exec_[kGraphs] = {};  // [2 * form + with_logits], forms 0..3 (form_at)
     void *graph_[kGraphs] = {};
     int logits_wgs_ = 512;  // two workgroups per CU: whole rounds on the 256 CUs (768 / 1280 workgroups are 15-20 % slower)
+    int screen_wgs_ = 512;  // the screening launch's grid (BITNET_HOST_SCREEN_WGS)
 };
 
 }  // namespace bitnet_host
@@ -420,6 +446,9 @@ void bitnet_host_destroy(void *d);  // drops the caller's reference: the object 
 void *bitnet_host_create_shared(void *owner);
 void bitnet_host_release(void *d);  // one reference less (what bitnet_host_destroy does); a batch slot lets its member go with it
 int bitnet_host_set_attention_form(void *d, int form);  // -1 automatic (form_at), 0 = 64-position records + combine everywhere
+int bitnet_host_set_head_screen(void *d, int on);       // Decoder::set_head_screen
+int bitnet_host_head_screen(void *d);                   // Decoder::head_screen: 1 the screened head, 0 the full head; -1 for a dead handle
+int bitnet_host_head_screen_stats(void *d, uint32_t *out3);  // Decoder::head_screen_stats
 const char *bitnet_host_error(void *d);
 int bitnet_host_set_layer_qk256(void *d, int layer, const float *attn_norm, const float *ffn_norm,
                                 const uint8_t *q, const uint8_t *k, const uint8_t *v, const uint8_t *o,

@@ -696,6 +696,25 @@ int bitnet_hip_logits_f16_dev(const void *table_f16_dev, const float *x_dev, con
                               void *scratch_dev, size_t n_workgroups, int32_t *token_dev,
                               int32_t *pos_dev, int32_t *history_dev, const int32_t *n_forced_dev,
                               void *stream);
+/* The SCREENED greedy head: the token, history entry and position bitnet_hip_logits_f16_dev would leave, bit for bit (ties, NaN -> -inf and
+ * forced tokens included), from about half the bytes -- and NO logits vector.  An int8 screening image of the table (built once per table on
+ * the device: per row int8 codes, an f32 scale and an f32 error coefficient; bitnet_hip_head_screen_bytes bytes, 0 = no instance for this
+ * hidden size: 512, 1024, 2048, 2560 and 4096 have one) gives every row a proven interval [lb, ub] around the f32 logit the full head would
+ * compute; the rows whose ub is not below the largest lb are then computed from the f16 table with the full head's own arithmetic, and the
+ * pick is taken among them.  The result never depends on how many rows that is (non-finite input: all of them).
+ * ws_dev: bitnet_hip_head_screen_ws_bytes bytes of floats, with V4 = vocab rounded up to 4 and N4 = n_workgroups rounded up to 4:
+ *   [0, vocab) ub | [V4, V4 + n_workgroups) per-workgroup maxima of lb | [V4 + N4, + hidden) a copy of x_dev | three uint32 words at
+ *   V4 + N4 + hidden: rows this launch rescored, launches so far (+1 per launch), rows rescored by all launches (zero the words once) |
+ *   [V4 + N4 + hidden + 4, + vocab) the rescored logits (rows not rescored: untouched).
+ * Every other argument is bitnet_hip_logits_f16_dev's. */
+size_t bitnet_hip_head_screen_bytes(size_t hidden, size_t vocab);
+size_t bitnet_hip_head_screen_ws_bytes(size_t hidden, size_t vocab, size_t n_workgroups);
+int bitnet_hip_head_screen_build_dev(const void *table_f16_dev, size_t hidden, size_t vocab, void *image_dev, void *stream);
+int bitnet_hip_logits_screen_dev(const void *table_f16_dev, const float *x_dev, const float *gamma_dev,
+                                 float eps, size_t hidden, size_t vocab, const void *image_dev, float *ws_dev,
+                                 void *scratch_dev, size_t n_workgroups, int32_t *token_dev,
+                                 int32_t *pos_dev, int32_t *history_dev, const int32_t *n_forced_dev,
+                                 void *stream);
 /* argmax over a device vector with the same tie/NaN rules; scratch as above. */
 int bitnet_hip_argmax_dev(const float *v_dev, size_t n, void *scratch_dev, size_t n_workgroups,
                           int32_t *token_dev, void *stream);

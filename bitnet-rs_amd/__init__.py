@@ -158,6 +158,9 @@ class HipLib:
         # fork of a live sequence's KV state: source tables [n_layers], destination tables [n_dst][n_layers] of device pointers
         L.bitnet_hip_kv_fork_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]
         L.bitnet_hip_kv_fork_dev.restype = C.c_int
+        # context shift of a live sequence's KV state, in place: K / V tables [n_layers] of device pointers, the RoPE tables [max_pos, 64]
+        L.bitnet_hip_kv_shift_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]
+        L.bitnet_hip_kv_shift_dev.restype = C.c_int
         L.bitnet_hip_gemv_attn_merge_rec_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
         L.bitnet_hip_attention_merge_q_max_keys.restype = _sz
         L.bitnet_hip_attention_merge_q_max_keys.argtypes = []
@@ -646,6 +649,14 @@ class HipLib:
         self._check(self.c.bitnet_hip_kv_fork_dev(_ptr(src_k_ptrs), _ptr(src_v_ptrs), _ptr(dst_k_ptrs), _ptr(dst_v_ptrs), n_layers, n_dst, n_kv, head_dim,
                                                   max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
 
+    def kv_shift_dev(self, k_ptrs, v_ptrs, rope_sin, rope_cos, n_layers: int, n_kv: int, head_dim: int, max_pos: int, keep: int, discard: int,
+                     n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
+        """In place, in one launch: cache slot j of every layer's K and V takes slot j + discard for j in [keep, n_positions - discard), V bit for
+        bit, K re-rotated between RoPE table rows j + discard and j.  *_ptrs: int64 device tensors of n_layers device pointers; rope_sin /
+        rope_cos: [max_pos, 64] f32 on the device."""
+        self._check(self.c.bitnet_hip_kv_shift_dev(_ptr(k_ptrs), _ptr(v_ptrs), _ptr(rope_sin), _ptr(rope_cos), n_layers, n_kv, head_dim, max_pos, keep,
+                                                   discard, n_positions, 2 if kv_f16 else 0, _vp(stream)))
+
     def attention_merge_q_max_keys(self) -> int:
         return int(self.c.bitnet_hip_attention_merge_q_max_keys())
 
@@ -1113,6 +1124,8 @@ class HostDecoder:
         L.bitnet_host_rewind.restype = C.c_int
         L.bitnet_host_fork.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]
         L.bitnet_host_fork.restype = C.c_int
+        L.bitnet_host_shift.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.bitnet_host_shift.restype = C.c_int
         L.bitnet_host_prefill_packed.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.bitnet_host_prefill_packed.restype = C.c_int
         L.bitnet_host_step_wide.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
@@ -1367,6 +1380,16 @@ class HostDecoder:
         """Keep the first n positions (0 <= n <= position()): the next feed() writes at n.  The cache bytes and the sampler state stay."""
         self._check(self.c.bitnet_host_rewind(self.h, n))
         self._fed = min(self._fed, int(n))
+
+    def shift(self, keep: int, discard: int) -> None:
+        """Context shift: keep the first `keep` positions, discard the next `discard`, slide the rest down (keep >= 0, discard >= 1,
+        keep + discard <= position()).  One launch moves every layer's cache slots in place -- V bit for bit, K re-rotated to its new
+        position -- and the position, history, forced count and log-probability records follow; the sampler state, last_logits() and the
+        captured graphs stay.  A sequence at the end of its cache goes on after shift(4, position() // 2) instead of reset() + a prompt
+        forward over what it wants to keep.  Never automatic: the overflow refusals stay."""
+        self._check(self.c.bitnet_host_shift(self.h, int(keep), int(discard)))
+        f, k, d = self._fed, int(keep), int(discard)
+        self._fed = f if f <= k else k if f <= k + d else f - d
 
     def fork_into(self, dsts, n: int) -> None:
         """Every decoder of `dsts` (1..8 of them: this decoder's owner or borrowers of the same weights, the same cache type, in no batch

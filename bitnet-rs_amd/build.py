@@ -32,8 +32,10 @@ COMMON_FLAGS = [
     f"-I{CSRC}",
 ]
 # Per-file extra flags.  kernels_exact.hip and kernels_sample.hip restate the reference's
-# scalar loops bit for bit, and Rust never contracts a*b+c; kernels_logprob.hip's error bound counts its additions one by one.
-EXTRA = {"kernels_exact.hip": ["-ffp-contract=off"], "kernels_sample.hip": ["-ffp-contract=off"], "kernels_logprob.hip": ["-ffp-contract=off"]}
+# scalar loops bit for bit, and Rust never contracts a*b+c; kernels_logprob.hip's error bound counts its additions one by one;
+# kernels_kvshift.hip's re-rotation is specified operation by operation (tests hold it bit for bit to numpy float32).
+EXTRA = {"kernels_exact.hip": ["-ffp-contract=off"], "kernels_sample.hip": ["-ffp-contract=off"], "kernels_logprob.hip": ["-ffp-contract=off"],
+         "kernels_kvshift.hip": ["-ffp-contract=off"]}
 
 
 # The hand-counted `s_waitcnt vmcnt(N)` around the LDS-DMA of k_prefill_attn (and the register / scratch figures DESIGN.md

@@ -1322,6 +1322,38 @@ int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const 
     BH_GUARD_END
 }
 
+/* ---- context shift of a live sequence's KV state (kernels_kvshift.hip) ---- */
+
+int bitnet_hip_kv_shift_dev(void *const *k_ptrs_dev, void *const *v_ptrs_dev, const float *rope_sin_dev, const float *rope_cos_dev, size_t n_layers,
+                            size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t keep, size_t discard, size_t n_positions, int flags, void *stream) {
+    BH_GUARD_BEGIN
+    if (!k_ptrs_dev || !v_ptrs_dev || !rope_sin_dev || !rope_cos_dev)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_shift_dev");
+    if (n_layers == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: n_layers 0");
+    if (n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: num_key_value_heads 0");
+    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: head_dim %zu unsupported (128)", head_dim);
+    if (flags & ~BITNET_HIP_ATTN_KV_F16)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16)", flags);
+    if (discard == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: discard 0 (at least one position must go)");
+    if (n_positions > max_pos)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: n_positions %zu, max_pos %zu", n_positions, max_pos);  // T:1190-1194
+    size_t gone = 0;
+    if (__builtin_add_overflow(keep, discard, &gone) || gone > n_positions)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: keep %zu + discard %zu exceeds n_positions %zu", keep, discard, n_positions);
+    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
+    size_t slots = 0, head_words = 0, cache_bytes = 0, segments = 0;
+    if (max_pos > (size_t)INT32_MAX || __builtin_add_overflow(max_pos, (size_t)63, &slots) || __builtin_mul_overflow(slots / 64 * 64, rows, &head_words) ||
+        __builtin_mul_overflow(head_words, n_kv_heads, &cache_bytes) || __builtin_mul_overflow(cache_bytes, sizeof(uint32_t), &cache_bytes) ||
+        __builtin_mul_overflow(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, (size_t)2, &segments) || segments >= ((size_t)1 << 24))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (kv_shift_dev: n_layers %zu, n_kv_heads %zu, max_pos %zu)",
+                         n_layers, n_kv_heads, max_pos);
+    if (gone == n_positions) return BITNET_HIP_OK;  // nothing moves: valid, and nothing to launch
+    BH_HIP_TRY(launch_kv_shift(k_ptrs_dev, v_ptrs_dev, rope_sin_dev, rope_cos_dev, n_layers, n_kv_heads, rows, head_words, keep, discard, n_positions,
+                               (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 // ---- the generation path's logits tap (kernels_logprob.hip) ----
 size_t bitnet_hip_logprob_scratch_bytes(size_t vocab) { return vocab == 0 || vocab > ((size_t)1 << 20) ? 0 : logprob_scratch_bytes(); }
 

@@ -216,6 +216,10 @@ hipError_t launch_pick_rows(const float *logits, const int *argmax, int n_seq, i
 // position and KV head (128 for f32 caches, 64 for f16), head_words = ceil(max_pos / 64) * 64 * rows
 hipError_t launch_kv_fork(const void *const *src_k, const void *const *src_v, void *const *dst_k, void *const *dst_v, size_t n_layers, size_t n_dst,
                           size_t n_kv, size_t rows, size_t head_words, size_t n, hipStream_t stream);
+// kernels_kvshift.hip: in place, slot j of every layer's K and V takes slot j + discard for j in [keep, n - discard), K re-rotated between the
+// two RoPE table rows; one launch; rows and head_words as above
+hipError_t launch_kv_shift(void *const *k_ptrs, void *const *v_ptrs, const float *rope_sin, const float *rope_cos, size_t n_layers, size_t n_kv, size_t rows,
+                           size_t head_words, size_t keep, size_t discard, size_t n, hipStream_t stream);
 // kernels_logprob.hip: the logits tap after the pick -- one entry (args by value) or a device table of n_slots entries, one launch each
 size_t logprob_scratch_bytes();
 hipError_t launch_logprob(const bitnet_hip_logprob_args &a, size_t vocab, hipStream_t stream);

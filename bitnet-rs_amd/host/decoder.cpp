@@ -1211,6 +1211,66 @@ int Decoder::rewind(int n) {
     return 0;
 }
 
+// The device pointer tables of fork and shift, allocated and filled once: this decoder's K caches [n_layers], its V caches [n_layers], then room for
+// fork's destinations.
+int Decoder::ensure_fork_tables() {
+    if (fork_tables_) return 0;
+    const size_t L = layers_.size(), M = BITNET_HIP_BATCH_MAX;
+    std::vector<void *> t(2 * L, nullptr);
+    void **tables = nullptr;
+    HCHK(hipMalloc((void **)&tables, (2 + 2 * M) * L * sizeof(void *)));
+    for (size_t l = 0; l < L; ++l) t[l] = layers_[l].kcache, t[L + l] = layers_[l].vcache;
+    if (hipError_t e = hipMemcpy(tables, t.data(), 2 * L * sizeof(void *), hipMemcpyHostToDevice)) {
+        (void)hipFree(tables);
+        HCHK(e);
+    }
+    fork_tables_ = tables;
+    return 0;
+}
+
+int Decoder::shift_forced(int forced, int keep, int discard) { return forced <= keep ? forced : forced <= keep + discard ? keep : forced - discard; }
+
+int Decoder::shift(int keep, int discard) {
+    // every refusal comes before the first write
+    const int p = position();
+    if (p < 0) return BITNET_HIP_ERR_GPU;
+    if (keep < 0) return fail_arg("shift: keep must be >= 0");
+    if (discard < 1) return fail_arg("shift: discard must be >= 1");
+    if (keep > p || discard > p - keep) return fail_arg("shift: keep + discard must be <= position()");
+    if (int rc = ensure_fork_tables()) return rc;
+    const size_t L = layers_.size(), n_hist = (size_t)c_.max_pos + 2;
+    hipStream_t s = (hipStream_t)stream_;
+    // the history first (a host round trip of at most 16 KB): a failure here leaves the caches as they were
+    std::vector<int32_t> h(n_hist), nh(n_hist, 0);
+    HCHK(hipMemcpy(h.data(), history_, n_hist * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < keep; ++i) nh[(size_t)i] = h[(size_t)i];
+    // entries [keep + discard, max_pos) move down (entry p, the unconsumed picked or fed token, travels to p - discard); zero beyond
+    for (int i = keep + discard; i < c_.max_pos; ++i) nh[(size_t)(i - discard)] = h[(size_t)i];
+    BCHK(bitnet_hip_kv_shift_dev(fork_tables_, fork_tables_ + L, rope_sin_, rope_cos_, L, (size_t)c_.n_kv_heads, (size_t)c_.head_dim, (size_t)c_.max_pos,
+                                 (size_t)keep, (size_t)discard, (size_t)p, kv_f16_ ? BITNET_HIP_ATTN_KV_F16 : 0, s));
+    HCHK(hipMemcpyAsync(history_, nh.data(), n_hist * 4, hipMemcpyHostToDevice, s));
+    if (lp_records_) {
+        // record q > keep + discard becomes record q - discard, those in (keep, keep + discard] go, everything above the new last one is cleared
+        const size_t rs = sizeof(bitnet_hip_logprob_record), first = (size_t)keep + (size_t)discard + 1, n_move = (size_t)p + 1 > first ? (size_t)p + 1 - first : 0;
+        std::vector<uint8_t> recs(n_move * rs);
+        HCHK(hipStreamSynchronize(s));
+        if (n_move) {
+            HCHK(hipMemcpy(recs.data(), lp_records_ + first, n_move * rs, hipMemcpyDeviceToHost));
+            HCHK(hipMemcpy(lp_records_ + keep + 1, recs.data(), n_move * rs, hipMemcpyHostToDevice));
+        }
+        const size_t tail = (size_t)keep + 1 + n_move;  // = max(p - discard, keep) + 1
+        if (tail < (size_t)c_.max_pos) HCHK(hipMemset(lp_records_ + tail, 0xff, ((size_t)c_.max_pos - tail) * rs));
+    }
+    HCHK(hipStreamSynchronize(s));
+    // the position and the forced count go last: a HIP runtime error above returns with caches and history already moved under the OLD position,
+    // a state only reset() leaves cleanly (as with any HIP error of this class: BITNET_HIP_ERR_GPU, error() names the call)
+    const int32_t np = p - discard;
+    HCHK(hipMemcpy(pos_, &np, 4, hipMemcpyHostToDevice));
+    host_forced_ = shift_forced(host_forced_, keep, discard);
+    HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
 int Decoder::fork(Decoder &src, Decoder *const *dsts, int n_dst, int n) { return src.fork_from_this(dsts, n_dst, n); }
 
 int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
@@ -1235,11 +1295,7 @@ int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
     // one root, hence one Config: every cache has this decoder's geometry
     const size_t L = layers_.size(), M = BITNET_HIP_BATCH_MAX;
     std::vector<void *> t((2 + 2 * M) * L, nullptr);
-    if (!fork_tables_) {
-        HCHK(hipMalloc((void **)&fork_tables_, t.size() * sizeof(void *)));
-        for (size_t l = 0; l < L; ++l) t[l] = layers_[l].kcache, t[L + l] = layers_[l].vcache;
-        HCHK(hipMemcpy(fork_tables_, t.data(), 2 * L * sizeof(void *), hipMemcpyHostToDevice));
-    }
+    if (int rc = ensure_fork_tables()) return rc;
     void **dst_k = fork_tables_ + 2 * L, **dst_v = dst_k + M * L;
     hipStream_t s = (hipStream_t)stream_;
     if (n > 0) {
@@ -2234,6 +2290,10 @@ int bitnet_host_step_wide(void *const *members, int n_members, int n_steps, int 
 int bitnet_host_rewind(void *d, int n) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
     return D->rewind(n);
+}
+int bitnet_host_shift(void *d, int keep, int discard) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->shift(keep, discard);
 }
 int bitnet_host_fork(void *src, void *const *dsts, int n_dst, int n) {
     Decoder *S = live(src);

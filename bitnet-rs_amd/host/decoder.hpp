@@ -213,6 +213,21 @@ class Decoder {
     // continuation attention never reads a slot at or beyond its past length), and so do the sampler's counts and word counter:
     // reset() remains the full clear.
     int rewind(int n);
+    // CONTEXT SHIFT: keep the first `keep` positions, discard the next `discard`, slide the rest down -- the member of the live-sequence family
+    // that drops tokens from the MIDDLE (the reference's KvCacheBuffer::rotate_kv / truncate, crates/bitnet-kernels/src/cuda/kv_cache.rs:305-348,
+    // and WindowedKVCache, crates/bitnet-gpu-hal/src/sliding_window.rs:161-235; llama.cpp's context shift, StreamingLLM's attention sinks).  With
+    // p = position(): cache slot j of every layer takes slot j + discard for j in [keep, p - discard) by ONE bitnet_hip_kv_shift_dev launch (V
+    // bit for bit, K re-rotated between RoPE table rows j + discard and j; slots >= p - discard are stale as after rewind); the position
+    // becomes p - discard on host and device; history entries [keep + discard, max_pos) move down by discard (entry p, the unconsumed picked or
+    // fed token, travels to p - discard, as with rewind) and the history is zero beyond them; the forced count f becomes f if f <= keep, keep if
+    // f <= keep + discard, else f - discard; log-probability record q > keep + discard becomes record q - discard, records in
+    // (keep, keep + discard] are dropped and records above the new last one are cleared to 0xFF.  The sampler's counts and word counter, the
+    // cache type, the attention form, last_logits() and the captured graphs stay (the graphs read the position from device memory);
+    // last_hidden() is unspecified.  A decoder in a BatchDecoder slot may be shifted between steps.  Explicit, never automatic: every overflow
+    // refusal stays.  Synchronises before returning.
+    // Refused, with nothing modified: keep < 0, discard < 1, keep + discard > position().
+    int shift(int keep, int discard);
+    static int shift_forced(int forced, int keep, int discard);  // the forced count after shift(keep, discard)
     // FORK: every one of the n_dst (1..8) destinations takes over the first n positions of `src`, 0 <= n <= src.position() -- the reference's
     // prefix cache (crates/bitnet-inference/src/prefix_cache.rs: lookup :173, insert :212) with the state kept on the device instead of its
     // host-side cached_state bytes.  Afterwards every destination is what src would be after src.rewind(n), and src itself is untouched:
@@ -387,7 +402,8 @@ class Decoder {
     void *lp_scratch_ = nullptr;
     int host_forced_ = 0;
     // fork: device pointer tables, allocated at the first fork FROM this decoder: [0] its own K caches [n_layers], [1] its V caches (built once),
-    // then the destinations' K [8][n_layers] and V [8][n_layers] (uploaded per call)
+    // then the destinations' K [8][n_layers] and V [8][n_layers] (uploaded per call).  shift() uses [0] and [1].
+    int ensure_fork_tables();
     int fork_from_this(Decoder *const *dsts, int n_dst, int n);
     void **fork_tables_ = nullptr;
     // sharded prefill buffers (grown on demand)
@@ -477,6 +493,7 @@ int bitnet_host_prefill_packed(void *const *members, const int32_t *n, int n_mem
 // Decoder::step_wide: members[0] drives and carries the error text
 int bitnet_host_step_wide(void *const *members, int n_members, int n_steps, int digits, float *elapsed_ms);
 int bitnet_host_rewind(void *d, int n);                                                    // Decoder::rewind
+int bitnet_host_shift(void *d, int keep, int discard);                                     // Decoder::shift
 int bitnet_host_fork(void *src, void *const *dsts, int n_dst, int n);                      // Decoder::fork; the error text goes on src
 int bitnet_host_cached_prefix(void *d, const int32_t *tokens, int n);                      // Decoder::cached_prefix; -1 on error
 int bitnet_host_score(void *d, int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms);

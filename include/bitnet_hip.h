@@ -561,6 +561,29 @@ int bitnet_hip_pick_rows_dev(const float *logits_dev, const int32_t *argmax_dev,
 int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const *src_v_ptrs_dev, void *const *dst_k_ptrs_dev,
                            void *const *dst_v_ptrs_dev, size_t n_layers, size_t n_dst, size_t n_kv_heads, size_t head_dim,
                            size_t max_pos, size_t n_positions, int flags, void *stream);
+/* ---- context shift of a live sequence: drop positions from the middle of the KV state, on the device -------------------
+ * The reference has the pieces on the host: KvCacheBuffer::rotate_kv and truncate (crates/bitnet-kernels/src/cuda/kv_cache.rs:305-348) and
+ * WindowedKVCache (crates/bitnet-gpu-hal/src/sliding_window.rs:161-235): keep the first `keep` positions (the attention sinks), discard the
+ * next `discard`, slide the rest down.  This entry does that IN PLACE on the private device layouts, in ONE launch: in every layer and KV
+ * head, for every j in [keep, n_positions - discard),
+ *   - V slot j takes V slot j + discard, BIT FOR BIT (integer loads and stores);
+ *   - K slot j takes the key of slot j + discard RE-ROTATED (K is cached after RoPE).  For every RoPE pair (x0, x1) = dims (i, i + 64), with
+ *     (sa, ca) = table row j + discard and (sb, cb) = table row j, in f32, unfused, in this order:
+ *         c = ca*cb + sa*sb;  s = sa*cb - ca*sb;  x0' = x0*c + x1*s;  x1' = x1*c - x0*s
+ *     -- the two table rows actually involved, not row `discard`: rows built from f32 angles do not compose to f32 accuracy.  An f16 cache
+ *     word is widened exactly, computed in f32 and rounded once (nearest-even) to f16.
+ * Every byte outside those slots keeps its value: slots < keep, slots >= n_positions - discard (stale, as after a rewind), the padding
+ * slots of the last chunk.  No slot is read after it was overwritten although the ranges overlap (kernels_kvshift.hip states the argument).
+ *   - k_ptrs_dev / v_ptrs_dev: DEVICE arrays of n_layers cache pointers; rope_sin_dev / rope_cos_dev: [max_pos, 64] f32;
+ *   - flags: 0 (f32 caches) or BITNET_HIP_ATTN_KV_F16; every cache has the same type, max_pos and n_kv_heads, head_dim 128, and is
+ *     16-byte aligned;
+ *   - asynchronous and capture-safe: no allocation, no synchronisation, no workspace.  n_positions - keep - discard == 0 is valid and
+ *     launches nothing.  NULL tables or RoPE pointers, n_layers == 0, n_kv_heads == 0, head_dim != 128, discard == 0,
+ *     keep + discard > n_positions, n_positions > max_pos ("KV cache overflow"), unknown flag bits and sizes that overflow return
+ *     BITNET_HIP_ERR_INVALID_ARGUMENT before anything launches. */
+int bitnet_hip_kv_shift_dev(void *const *k_ptrs_dev, void *const *v_ptrs_dev, const float *rope_sin_dev, const float *rope_cos_dev,
+                            size_t n_layers, size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t keep, size_t discard,
+                            size_t n_positions, int flags, void *stream);
 /* bitnet_hip_attention_prefill_dev filling f16 decode caches */
 int bitnet_hip_attention_prefill_kv16_dev(const float *qkv_dev, const float *rope_sin_dev, const float *rope_cos_dev,
                                           void *kcache_f16_dev, void *vcache_f16_dev, size_t n_heads, size_t n_kv_heads,

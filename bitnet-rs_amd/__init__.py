@@ -75,6 +75,12 @@ class DeviceInfo(C.Structure):
     ]
 
 
+class GemvQGeometry(C.Structure):
+    """bitnet_hip_gemv_q_geometry_t"""
+    _fields_ = [(n, C.c_int) for n in ("k_split", "blocks", "blocks_per_wave", "ring", "copy_passes", "scale_form", "layernorm", "tiles_per_workgroup",
+                                       "grid", "merge_slots4", "merge_slots1", "merge_records")]
+
+
 def _np(a, dtype):
     if isinstance(a, (bytes, bytearray, memoryview)):
         a = np.frombuffer(a, dtype=np.uint8)
@@ -136,6 +142,7 @@ class HipLib:
         L.bitnet_hip_quantize_act_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp]
         L.bitnet_hip_embed_q_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_gemv_q_supported.argtypes = [C.c_uint64]
+        L.bitnet_hip_gemv_q_geometry.argtypes = [C.c_uint64, C.c_int, C.c_int, _sz, C.POINTER(GemvQGeometry)]
         L.bitnet_hip_gemv_q_dev.argtypes = [C.c_uint64, _vp, _vp, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
         L.bitnet_hip_attention_decode_q_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_int, _vp, _vp, _vp]
         L.bitnet_hip_gemv_attn_merge_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -593,6 +600,12 @@ class HipLib:
 
     def gemv_q_supported(self, h: int) -> bool:
         return bool(self.c.bitnet_hip_gemv_q_supported(h))
+
+    def gemv_q_geometry(self, h: int, flags: int = 0, layernorm: bool = False, merge_records: int = 0) -> dict:
+        """the k_gemv_q instance gemv_q_dev (merge_records 0) / gemv_attn_merge[_rec]_q_dev (4 or 8) would launch; host only"""
+        g = GemvQGeometry()
+        self._check(self.c.bitnet_hip_gemv_q_geometry(h, flags, int(layernorm), merge_records, C.byref(g)))
+        return {n: getattr(g, n) for n, _ in GemvQGeometry._fields_}
 
     def gemv_q_dev(self, h: int, qact_in, y=None, stats_in=None, ln_gamma=None, ln_eps: float = 0.0, residual=None, flags: int = 0, qact_out=None,
                    gamma_out=None, stats_out=None, stream: int = 0) -> None:

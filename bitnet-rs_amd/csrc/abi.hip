@@ -1071,6 +1071,41 @@ int bitnet_hip_gemv_q_supported(bitnet_hip_weights_t h) {
     return w && gemvq_supported(*w) ? 1 : 0;
 }
 
+int bitnet_hip_gemv_q_geometry(bitnet_hip_weights_t h, int flags, int layernorm, size_t merge_records, bitnet_hip_gemv_q_geometry_t *out) {
+    BH_GUARD_BEGIN
+    const WeightsRef w = lookup(h);
+    if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
+    if (!out) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_q_geometry");
+    if (flags & ~BITNET_HIP_FUSE_SILU_MUL) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "gemv_q_geometry: unknown flag bits 0x%x", flags);
+    const bool silu = (flags & BITNET_HIP_FUSE_SILU_MUL) != 0;
+    // the refusals of the launching entries (gemv_q_front, gemv_attn_merge), in their order
+    if (!gemvq_supported(*w))
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_geometry: matrix %zux%zu (block %zu) is not on the QAct path", w->rows, w->cols, w->block_size);
+    if (silu && (!w->paired || w->rows % 32 != 0 || merge_records))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "FUSE_SILU_MUL needs a handle from weights_concat(..., interleave16=1) and no merge");
+    if (layernorm && w->cols > 4096) return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_geometry: LayerNorm input of %zu columns (<= 4096)", w->cols);
+    if (merge_records && (w->cols % 128 != 0 || div_ceil(div_ceil(w->cols, 256), (size_t)8) > 2 || w->cols > 4096 || (merge_records != 4 && w->cols > 2560)))
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_geometry: no merging instance for %zu records and %zu columns", merge_records, w->cols);
+    GemvQInstance q;
+    if (gemv_q_instance(*w, silu, layernorm != 0, (int)merge_records, q) != hipSuccess)
+        return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_q_geometry: no k_gemv_q instance for %zux%zu (LayerNorm %d, %zu merge records)", w->rows, w->cols,
+                         layernorm != 0, merge_records);
+    out->k_split = q.g.ksplit;
+    out->blocks = q.g.nblk;
+    out->blocks_per_wave = q.g.ring;
+    out->ring = q.ring_inst;
+    out->copy_passes = q.ncp;
+    out->scale_form = q.g.sc;
+    out->layernorm = q.ln;
+    out->tiles_per_workgroup = q.g.tiles_per_wg;
+    out->grid = (int)q.g.grid;
+    out->merge_slots4 = q.ne;
+    out->merge_slots1 = q.ne1;
+    out->merge_records = q.nr;
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 // What bitnet_hip_gemv_q_dev and bitnet_hip_gemv_q_batch_dev share behind their own first lines (handle and null pointers, in each entry's
 // order): is the matrix on the QAct path, `io` from the arguments, silu * up pairing, the LayerNorm binding and its column limit.  `entry`
 // names the caller in the messages.

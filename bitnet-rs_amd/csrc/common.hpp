@@ -187,6 +187,15 @@ static_assert(offsetof(GemvQPrefix, qin) == 40 && offsetof(GemvQPrefix, inv_cols
               "the kernels' argument layout: the derived structs' own members begin at 136");
 hipError_t fill_gemv_q_prefix(GemvQPrefix &a, const Weights &w, const GemvQIo &io, const GemvGeom &g);
 hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream);
+// The k_gemv_q instance of one launch (kernels_gemvq.hip): launch_gemv_q picks its kernel from this, bitnet_hip_gemv_q_geometry reports it.
+struct GemvQInstance {
+    GemvGeom g;
+    int nw;              // waves per workgroup
+    int ring_inst, ncp;  // template RING (>= g.ring) and NCP
+    int ln;              // template LN
+    int ne, ne1, nr;     // merging form: float4 slots, tail slots, records (all 0: the plain form)
+};
+hipError_t gemv_q_instance(const Weights &w, bool silu_mul, bool ln, int merge_records, GemvQInstance &q);
 hipError_t launch_quant_act(const float *x, const float *gamma, size_t n, void *qout, double *stats, hipStream_t stream);
 hipError_t launch_embed_q(const void *table, const int *tokens, const int *offset_ptr, int hidden, int vocab, float *x_out,
                           const float *gamma, void *qout, double *stats, hipStream_t stream);

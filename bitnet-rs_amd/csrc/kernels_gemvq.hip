@@ -535,11 +535,41 @@ hipError_t fill_gemv_q_prefix(GemvQPrefix &a, const Weights &w, const GemvQIo &i
     return hipSuccess;
 }
 
-hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream) {
-    if (!w.tiles || !gemvq_supported(w) || (!io.qin && !io.attn_rec)) return hipErrorInvalidValue;
+// Which k_gemv_q instance a launch takes: the K partition (gemv_geometry), the RING that holds a wave's blocks (the first of 2..5 that does),
+// the 8-KiB passes of the QAct copy, and for the merging form (the o-projection shape: K = heads * 128, ring <= 2, one copy pass) the slots per
+// thread: one float4 (K <= 2048), one float4 + one float (K <= 2560), two float4 (beyond; 4 records only).  launch_gemv_q instantiates exactly
+// this; bitnet_hip_gemv_q_geometry reports it without launching.
+hipError_t gemv_q_instance(const Weights &w, bool silu_mul, bool ln, int merge_records, GemvQInstance &q) {
+    if (!gemvq_supported(w)) return hipErrorInvalidValue;
     // (16-wave workgroups -- 4 waves per SIMD, half the K range each -- measured slower in round 2, gate|up 5.46 vs 5.23 us, and were removed)
     const int nw = 8;
-    const GemvGeom g = gemv_geometry(w, io.silu_mul, nw);
+    q.nw = nw;
+    q.g = gemv_geometry(w, silu_mul, nw);
+    q.ln = ln ? 1 : 0;
+    q.ncp = (int)div_ceil((size_t)kQRec * q.g.nblk, (size_t)16 * nw * 64);
+    q.ring_inst = q.g.ring < 2 ? 2 : q.g.ring;
+    q.ne = q.ne1 = 0;
+    q.nr = merge_records;
+    if (q.g.ring > 5 || q.ncp > 3 || (ln && w.cols / 16 > (size_t)nw * 64)) return hipErrorInvalidValue;
+    if (merge_records) {
+        q.ne = w.cols <= 2560 ? 1 : 2;
+        q.ne1 = w.cols > 2048 && w.cols <= 2560 ? 1 : 0;
+        if (ln || q.g.ring > 2 || q.ncp != 1 || w.cols % 128 != 0 || w.cols > 4096 || (merge_records != 4 && merge_records != 8) ||
+            (merge_records == 8 && q.ne == 2))
+            return hipErrorInvalidValue;
+        q.ring_inst = 2;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream) {
+    if (!w.tiles || !gemvq_supported(w) || (!io.qin && !io.attn_rec)) return hipErrorInvalidValue;
+    const bool ln = io.ln_gamma != nullptr;
+    GemvQInstance q;
+    const hipError_t eq = gemv_q_instance(w, io.silu_mul, ln, io.attn_rec ? io.attn_records : 0, q);
+    if (eq != hipSuccess) return eq;
+    const GemvGeom &g = q.g;
+    const int nw = q.nw;
     GemvQArgs a;
     const hipError_t ef = fill_gemv_q_prefix(a, w, io, g);
     if (ef != hipSuccess) return ef;
@@ -549,26 +579,19 @@ hipError_t launch_gemv_q(const Weights &w, const GemvQIo &io, hipStream_t stream
     a.attn_group_log2 = io.attn_group_log2;
     a.attn_chunk_log2 = io.attn_chunk_log2;
     a.stamps = g_mfma_stamps;
-    const bool ln = io.ln_gamma != nullptr;
-    const int ring = g.ring, sc = g.sc;
-    const int ncp = (int)div_ceil((size_t)kQRec * a.nblk, (size_t)16 * nw * 64);
-    if (ring > 5 || ncp > 3 || (ln && a.n_stats > nw * 64)) return hipErrorInvalidValue;
+    const int ring = q.ring_inst, sc = g.sc, ncp = q.ncp;
     void (*kfn)(GemvQArgs) = nullptr;
 #define BH_QPICK2(RINGv, NCPv)                                                                                                        \
-    if (!kfn && ring <= RINGv && ncp == NCPv)                                                                                         \
+    if (!kfn && ring == RINGv && ncp == NCPv)                                                                                         \
         kfn = ln ? (sc == 2 ? k_gemv_q<8, RINGv, 2, 1, NCPv> : sc == 1 ? k_gemv_q<8, RINGv, 1, 1, NCPv> : k_gemv_q<8, RINGv, 0, 1, NCPv>)  \
                  : (sc == 2 ? k_gemv_q<8, RINGv, 2, 0, NCPv> : sc == 1 ? k_gemv_q<8, RINGv, 1, 0, NCPv> : k_gemv_q<8, RINGv, 0, 0, NCPv>);
 #define BH_QPICK(RINGv) BH_QPICK2(RINGv, 1) BH_QPICK2(RINGv, 2) BH_QPICK2(RINGv, 3)
     BH_QPICK(2) BH_QPICK(3) BH_QPICK(4) BH_QPICK(5)
 #undef BH_QPICK
 #undef BH_QPICK2
-    if (io.attn_rec) {  // merging form: the o-projection shape (K = heads * 128: ring <= 2, one copy pass)
-        // slots per thread: one float4 (K <= 2048), one float4 + one float (K <= 2560), two float4 (beyond; 4 records only)
-        const int nr = io.attn_records;
-        const int ne = w.cols <= 2560 ? 1 : 2, ne1 = w.cols > 2048 && w.cols <= 2560 ? 1 : 0;
-        if (ln || nw != 8 || ring > 2 || ncp != 1 || w.cols % 128 != 0 || w.cols > 4096 || !io.attn_pos || io.attn_chunks_max < 1 || (nr != 4 && nr != 8) ||
-            (nr == 8 && ne == 2))
-            return hipErrorInvalidValue;
+    if (io.attn_rec) {  // merging form
+        const int ne = q.ne, ne1 = q.ne1, nr = q.nr;
+        if (nw != 8 || !io.attn_pos || io.attn_chunks_max < 1) return hipErrorInvalidValue;
         // the kernel addresses the records with 32-bit byte offsets
         if (((uint64_t)(w.cols / 128) >> io.attn_group_log2) * (uint64_t)io.attn_chunks_max * kAttnRecFloats * 4u >= (1ull << 32)) return hipErrorInvalidValue;
 #define BH_QMRG(NEv, NE1v, NRv)                     \

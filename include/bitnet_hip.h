@@ -447,6 +447,22 @@ int bitnet_hip_embed_q_dev(const void *table_f16_dev, const int32_t *tokens_dev,
                            size_t hidden, size_t vocab, float *x_out_dev, const float *gamma_dev, void *qact_out,
                            double *stats_out, void *stream);
 int bitnet_hip_gemv_q_supported(bitnet_hip_weights_t w);
+/* Which kernel instance bitnet_hip_gemv_q_dev (merge_records 0) or bitnet_hip_gemv_attn_merge[_rec]_q_dev (merge_records 4 or 8) would launch
+ * for this matrix: flags = 0 or BITNET_HIP_FUSE_SILU_MUL, layernorm != 0 = with ln_gamma_dev.  Host only: nothing is launched and the device
+ * is not touched.  What the launching entry would refuse for the shape is refused here (BITNET_HIP_ERR_UNSUPPORTED / _INVALID_ARGUMENT). */
+typedef struct {
+    int k_split;             /* K ranges per 16-row tile = waves sharing a tile: 1, 2, 4 or 8 */
+    int blocks;              /* 256-column blocks per row */
+    int blocks_per_wave;     /* the longest K range */
+    int ring;                /* blocks per wave the instance holds (2..5, >= blocks_per_wave) */
+    int copy_passes;         /* 8-KiB passes of the activation copy (1..3) */
+    int scale_form;          /* 32-block weight scales: 0 none, 1 f32, 2 f16 */
+    int layernorm;           /* the LayerNorm-after-product instance */
+    int tiles_per_workgroup; /* 8 / k_split */
+    int grid;                /* workgroups */
+    int merge_slots4, merge_slots1, merge_records; /* merging form: float4 / single-float slots per thread, records; 0 otherwise */
+} bitnet_hip_gemv_q_geometry_t;
+int bitnet_hip_gemv_q_geometry(bitnet_hip_weights_t w, int flags, int layernorm, size_t merge_records, bitnet_hip_gemv_q_geometry_t *out);
 /* bitnet_hip_gemv_fused_dev on a QAct input: y = [residual +] W . act  [LayerNorm: ln_gamma_dev bound + stats_in]
  * [FUSE_SILU_MUL]; outputs: y_dev f32 (nullable) and / or qact_out [* gamma_out_dev] [+ stats_out]. */
 int bitnet_hip_gemv_q_dev(bitnet_hip_weights_t w, const void *qact_in, const double *stats_in,

@@ -53,8 +53,11 @@ def slot_vector(rng, kind, cols):
 
 
 KINDS = ["rand", "zeros", "1e4", "tiny", "rand", "rand", "rand", "rand"]  # slot contents differ on purpose: leakage between slots would show
-SHAPES = [(48, 256, False), (272, 512, False), (3840, 2560, False), (2560, 2560, False), (2560, 6912, False), (13824, 2560, True)]
-# (2560, 6912): the longest ring, three copy passes in batch-1, a second copy round for 8 vectors here; (48, 256): fewer row tiles than waves
+SHAPES = [(48, 256, False), (272, 512, False), (3840, 2560, False), (2560, 2560, False), (2560, 6912, False), (13824, 2560, True),
+          (64, 2560, True), (16, 4352, False)]
+# (2560, 6912): four blocks per wave, two copy passes in batch-1, a second copy round for 8 vectors here; (48, 256): fewer row tiles than waves.
+# Ring depths (blocks per wave, bitnet_hip_gemv_q_geometry): 2, 2, 2, 2, 4, 5, and the last two for the one that was missing: (64, 2560) paired =
+# 10 blocks over 4 K parts, (16, 4352) = 17 blocks over 8 K parts: 3 each.
 
 
 @pytest.mark.parametrize("fmt", ["qk256", "f16"])

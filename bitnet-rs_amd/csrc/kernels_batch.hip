@@ -9,8 +9,10 @@
 // CONTRACT: for each vector the arithmetic is the batch-1 kernel's, operation for operation and in its order (k_gemv_q, k_embed_q,
 // k_logits_f16 + k_argmax_final), so every output is BIT-IDENTICAL to the batch-1 entry point called on that vector alone
 // (tests/test_batch_ops_gpu.py compares raw bits).  Where hipcc's contraction decided the batch-1 result (the head's dot product and its
-// variance sum compile to fused multiply-adds) the fused form is written out here.
+// variance sum compile to fused multiply-adds) the fused form is written out here.  The GEMV keeps it BY CONSTRUCTION in the stages both
+// kernels call (gemvq_stages.hpp, qact.hpp); its other stages are restated below, named where they stand, and held by that test alone.
 #include "common.hpp"
+#include "gemvq_stages.hpp"
 #include "qact.hpp"
 #include "wave.hpp"
 
@@ -26,27 +28,9 @@ struct GemvQBatchArgs : GemvQPrefix {  // tiles .. stats_out as k_gemv_q's (comm
 };
 static_assert(sizeof(GemvQBatchArgs) == 152, "the layout k_gemv_q_batch was compiled for: the prefix, then these members");
 
-// LayerNorm row statistics of one vector from its (sum, sum of squares) pairs in LDS: k_gemv_q's epilogue prologue, expression for expression
-__device__ __forceinline__ void ln_row_stats(const uint8_t *cs, int n_stats, int lane, double inv_cols, float ln_eps, double &ln_mean, double &ln_rdenom) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int i = lane; i < n_stats; i += 64) {
-        const double2 pr = *reinterpret_cast<const double2 *>(cs + 16 * i);
-        s1 += pr.x;
-        s2 += pr.y;
-    }
-    s1 = wave64_sum_d_rows_readlane(s1);
-    s2 = wave64_sum_d_rows_readlane(s2);
-    const double mean_d = s1 * inv_cols;
-    const double var_d = s2 * inv_cols - mean_d * mean_d;
-    ln_mean = (double)(float)mean_d;  // the f32 mean the reference subtracts
-    const double denom = (double)sqrtf((float)(var_d > 0.0 ? var_d : 0.0) + ln_eps);
-    double r = __builtin_amdgcn_rcp(denom);
-    r = r * (2.0 - denom * r);
-    ln_rdenom = r * (2.0 - denom * r);
-}
-
 // k_gemv_q (kernels_gemvq.hip) for NB vectors: 8 waves, the same wave -> (row tile, K range) map, the same block order, lane swaps and K-part
-// sum per vector.  A wave loads and expands each weight tile ONCE (the B operand of the int8 MFMA) and multiplies it with every vector's digit
+// sum per vector.  Shared functions: ring_block, gemvq_block_value, sum_kgroups, ln_row_stats -> ln_from_sums, qact_emit.  RESTATED (EXPERIMENTS.md 28):
+// wave map, epilogue operand rows and dummy loads, scale-tile loads, A-operand lane, weight-scale accumulations, K-part sums with LayerNorm and silu * up.  A wave loads and expands each weight tile ONCE (the B operand of the int8 MFMA) and multiplies it with every vector's digit
 // planes (the A operand, from that vector's LDS image).  NB = compile-time vector count (2, 4, 8); slots n_seq .. NB - 1 redo vector
 // n_seq - 1 and are never stored.  LDS: RING zero records, then n_seq whole QAct vectors (the down-projection's 6912 columns: 15.5 KB each),
 // n_seq statistics blocks (LN), NB x 8 x 16 partial sums -- up to 160 KiB (raise_dynamic_lds).
@@ -67,7 +51,7 @@ __global__ __launch_bounds__(512) void k_gemv_q_batch(GemvQBatchArgs p) {
     float *part = reinterpret_cast<float *>(cs + (LN ? stot : 0u));  // [NB][NW][16]
     if (16 * tid < ZB) *reinterpret_cast<v4u *>(zq + 16 * tid) = v4u{0u, 0u, 0u, 0u};
 
-    // ---- wave -> (row tile, K range): k_gemv_q's map ----
+    // ---- wave -> (row tile, K range): k_gemv_q's map, restated ----
     const int ksplit = 1 << p.ks_log2;
     const int tiles_per_wg = NW >> p.ks_log2;
     const int n_tiles = p.rows >> 4;
@@ -77,7 +61,7 @@ __global__ __launch_bounds__(512) void k_gemv_q_batch(GemvQBatchArgs p) {
     if (p.ks_log2 == 3 && wave >= 4) kpart = 11 - wave;
     const int b0 = (kpart * p.nblk) >> p.ks_log2, b1 = ((kpart + 1) * p.nblk) >> p.ks_log2;
 
-    // ---- 1. activations (first round), statistics, epilogue operands: all unconditional, clamped ----
+    // ---- 1. activations (first round), statistics, epilogue operands (k_gemv_q's e_row .. e_gam, restated): all unconditional, clamped ----
     v4u qa[NCP];
 #pragma unroll
     for (int i = 0; i < NCP; ++i) qa[i] = *reinterpret_cast<const v4u *>(p.qin + umin32(16u * (uint32_t)(tid + NT * i), qtot - 16u));
@@ -114,7 +98,7 @@ __global__ __launch_bounds__(512) void k_gemv_q_batch(GemvQBatchArgs p) {
     }
     const float e_gam = (p.gamma_out ? p.gamma_out : reinterpret_cast<const float *>(p.qin))[p.gamma_out ? e_row : 0];
     __builtin_amdgcn_sched_barrier(0);
-    // ---- 2. weight tiles (+ scale tiles): read once by this wave only ----
+    // ---- 2. weight tiles (+ scale tiles, k_gemv_q's loads restated): read once by this wave only ----
     const size_t tb0 = (size_t)tile * p.nblk;
     const uint8_t *wbase = p.tiles + (tb0 * 64 + lane) * 16;
     v4u wt[RING];
@@ -122,7 +106,7 @@ __global__ __launch_bounds__(512) void k_gemv_q_batch(GemvQBatchArgs p) {
     float2 sf[SC == 1 ? RING : 1];
 #pragma unroll
     for (int j = 0; j < RING; ++j) {
-        const int blk = b0 + j < b1 ? b0 + j : b1 - 1;
+        const int blk = ring_block(b0, b1, j);
         wt[j] = load_nt16v(wbase + (size_t)blk * 1024);
         if (SC == 2) sh[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p.stiles) + (tb0 + blk) * 64 + lane);
         if (SC == 1) {
@@ -156,7 +140,7 @@ __global__ __launch_bounds__(512) void k_gemv_q_batch(GemvQBatchArgs p) {
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
-    // A-operand lane (k-group g, selector row c): as k_gemv_q, one image per vector
+    // A-operand lane (k-group g, selector row c): k_gemv_q's ba0 / ba1 / sa restated as offsets, one image per vector
     const int g = lane >> 4, c = lane & 15;
     const bool mine = (c >> 2) == g;
     const bool m0 = mine && (c & 1) == 0, m1 = mine && (c & 1) == 1;
@@ -187,9 +171,7 @@ __global__ __launch_bounds__(512) void k_gemv_q_batch(GemvQBatchArgs p) {
                 v4i acc = {0, 0, 0, 0};
                 acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i *>(pa0[b] + kQRec * j + 32 * pp), w0, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i *>(pa1[b] + kQRec * j + 32 * pp + 16), w1, acc, 0, 0, 0);
-                const int i0 = (int)(((uint32_t)acc[2] << 8) + (uint32_t)acc[0]), i1 = (int)(((uint32_t)acc[3] << 8) + (uint32_t)acc[1]);
-                float t = (float)i0 * (pp ? as.y : as.x);
-                t = fmaf((float)i1, pp ? as.w : as.z, t);
+                const float t = gemvq_block_value(acc, as, pp);
                 if (SC == 2)
                     facc[b] = pp ? fma_mix_hi(t, sh[j], facc[b]) : fma_mix_lo(t, sh[j], facc[b]);
                 else if (SC == 1)
@@ -201,16 +183,11 @@ __global__ __launch_bounds__(512) void k_gemv_q_batch(GemvQBatchArgs p) {
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        float fa = facc[b], fb = facc[b];
-        asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(fa), "+v"(fb));
-        float f = fa + fb;
-        fa = f, fb = f;
-        asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(fa), "+v"(fb));
-        f = fa + fb;
+        const float f = sum_kgroups(facc[b]);
         if (lane < 16) part[(b * NW + ((wave >> p.ks_log2) << p.ks_log2) + kpart) * 16 + lane] = f;
     }
 
-    // ---- 4. epilogue: the storing waves, vector after vector ----
+    // ---- 4. epilogue: the storing waves, vector after vector (k_gemv_q's K-part sums, LayerNorm, silu and stores, restated) ----
     const bool storing = wave * 64 < tiles_per_wg * 16;
     double ln_mean[LN ? NB : 1], ln_rdenom[LN ? NB : 1];
     if (LN && storing) {

@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "gemvq_stages.hpp"
 #include "qact.hpp"
 #include "wave.hpp"
 
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
     float2 sf[SC == 1 ? RING : 1];
 #pragma unroll
     for (int j = 0; j < RING; ++j) {
-        const int blk = b0 + j < b1 ? b0 + j : b1 - 1;  // clamped: a short range re-reads its last tile
+        const int blk = ring_block(b0, b1, j);
         wt[j] = load_nt16v(wbase + (size_t)blk * 1024);
         if (SC == 2) sh[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p.stiles) + (tb0 + blk) * 64 + lane);
         if (SC == 1) {
@@ -286,19 +287,16 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
             const float rl = e < p.cols ? 1.0f / L : 0.0f;
             float v[4] = {a.x * rl, a.y * rl, a.z * rl, a.w * rl};
             if (as_combine && e < p.cols) v[0] = a.x / L, v[1] = a.y / L, v[2] = a.z / L, v[3] = a.w / L;
-            // qact_emit's arithmetic (qact.hpp) with the 16-element group spread over 4 lanes x 4 elements; destination = the
-            // LDS image instead of a global record
+            // qact_emit's format (qact.hpp) with the 16-element group spread over 4 lanes x 4 elements; destination = the LDS image
             uint32_t u = __float_as_uint(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])))), o;
             o = dpp_u<0xB1>(u), u = o > u ? o : u;  // quad_perm [1,0,3,2]
             o = dpp_u<0x4E>(u), u = o > u ? o : u;  // quad_perm [2,3,0,1]: the maximum over the quad = the 16 elements
-            int be = (int)(u >> 23);
-            be = be < 32 ? 32 : be;
-            be = be > 254 ? 254 : be;
-            const float sc = __uint_as_float((uint32_t)(267 - be) << 23), as = __uint_as_float((uint32_t)(be - 13) << 23);
+            float sc, as;
+            qact_scales(u, sc, as);
             uint32_t d0 = 0, d1 = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const uint32_t t = ((uint32_t)qcvt_rpi(v[j] * sc) + 0x80u) ^ 0x80u;
+                const uint32_t t = qact_digits(v[j], sc);
                 d0 |= (t & 0xffu) << (8 * j);
                 d1 |= ((t >> 8) & 0xffu) << (8 * j);
             }
@@ -307,7 +305,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
                 uint8_t *qb = cq + kQRec * rec;
                 *reinterpret_cast<uint32_t *>(qb + 16 * tp + (e & 15)) = d0;
                 *reinterpret_cast<uint32_t *>(qb + 256 + 16 * tp + (e & 15)) = d1;
-                if ((e & 15) == 0) reinterpret_cast<float *>(qb + 512)[4 * (tp >> 2) + 2 * (tp & 1) + ((tp & 3) >> 1)] = as;
+                if ((e & 15) == 0) reinterpret_cast<float *>(qb + 512)[4 * (tp >> 2) + 2 * (tp & 1) + ((tp & 3) >> 1)] = as;  // qact_scale_slot (qact.hpp) restated
             }
         }
 #pragma unroll
@@ -322,18 +320,16 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
             }
             float v = a * (e < p.cols ? 1.0f / L : 0.0f);
             if (as_combine && e < p.cols) v = a / L;
-            // qact_emit's arithmetic with its own layout: one element per lane, the group = a DPP row
-            int be = (int)(__float_as_uint(row16_max_abs(v)) >> 23);
-            be = be < 32 ? 32 : be;
-            be = be > 254 ? 254 : be;
-            const float sc = __uint_as_float((uint32_t)(267 - be) << 23), as = __uint_as_float((uint32_t)(be - 13) << 23);
-            const uint32_t t = ((uint32_t)qcvt_rpi(v * sc) + 0x80u) ^ 0x80u;
+            // qact_emit's format and lane layout (one element per lane, the group = a DPP row); destination = the LDS image
+            float sc, as;
+            qact_scales(__float_as_uint(row16_max_abs(v)), sc, as);
+            const uint32_t t = qact_digits(v, sc);
             if (e < p.cols) {
                 const int grp = e >> 4, rec = grp >> 4, tp = grp & 15, r = e & 15;
                 uint8_t *qb = cq + kQRec * rec;
                 qb[16 * tp + r] = (uint8_t)t;
                 qb[256 + 16 * tp + r] = (uint8_t)(t >> 8);
-                if (r == 0) reinterpret_cast<float *>(qb + 512)[4 * (tp >> 2) + 2 * (tp & 1) + ((tp & 3) >> 1)] = as;
+                if (r == 0) reinterpret_cast<float *>(qb + 512)[4 * (tp >> 2) + 2 * (tp & 1) + ((tp & 3) >> 1)] = as;  // qact_scale_slot (qact.hpp) restated
             }
         }
     }
@@ -365,10 +361,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
                                                         decode16(wd[2 * pp], p.lut), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const v4i *>(ba1 + kQRec * j + 32 * pp + 16),
                                                         decode16(wd[2 * pp + 1], p.lut), acc, 0, 0, 0);
-            // acc[2 d + h]: exact sums over the 16 weights of half h with digit plane d; |.| <= 16 * 2 * 128
-            const int i0 = (int)(((uint32_t)acc[2] << 8) + (uint32_t)acc[0]), i1 = (int)(((uint32_t)acc[3] << 8) + (uint32_t)acc[1]);
-            float t = (float)i0 * (pp ? as.y : as.x);
-            t = fmaf((float)i1, pp ? as.w : as.z, t);
+            const float t = gemvq_block_value(acc, as, pp);
             if (SC == 2)
                 facc = pp ? fma_mix_hi(t, sh[j], facc) : fma_mix_lo(t, sh[j], facc);
             else if (SC == 1)
@@ -377,19 +370,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
                 facc += t;
         }
     }
-    // the four k-groups of a weight row sit in lanes c, c + 16, c + 32, c + 48: two lane swaps (v_permlane16_swap,
-    // v_permlane32_swap) add them up in every wave at once -- (g0 + g1) + (g2 + g3) -- instead of 4 LDS reads per K part
-    // in the one storing wave
-    {
-        // inline asm with the hazard pad inside (a VALU write needs 2 wait states before v_permlane*_swap reads it):
-        // hipcc's __builtin_amdgcn_permlane16_swap folded the two results into one register here (ROCm 7.2)
-        float a = facc, b = facc;
-        asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-        facc = a + b;  // rows (g0 + g1, g0 + g1, g2 + g3, g2 + g3)
-        a = facc, b = facc;
-        asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-        facc = a + b;
-    }
+    facc = sum_kgroups(facc);
     if (lane < 16) part[(((wave >> p.ks_log2) << p.ks_log2) + kpart) * 16 + lane] = facc;
     BH_QSTAMP(3);
 
@@ -405,13 +386,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q(GemvQArgs p) {
         }
         s1 = wave64_sum_d_rows_readlane(s1);
         s2 = wave64_sum_d_rows_readlane(s2);
-        const double mean_d = s1 * p.inv_cols;
-        const double var_d = s2 * p.inv_cols - mean_d * mean_d;
-        ln_mean = (double)(float)mean_d;  // the f32 mean the reference subtracts
-        const double denom = (double)sqrtf((float)(var_d > 0.0 ? var_d : 0.0) + p.ln_eps);
-        double r = __builtin_amdgcn_rcp(denom);
-        r = r * (2.0 - denom * r);
-        ln_rdenom = r * (2.0 - denom * r);
+        ln_from_sums(s1, s2, p.inv_cols, p.ln_eps, &ln_mean, &ln_rdenom);
     }
     __syncthreads();
     BH_QSTAMP(4);

@@ -35,6 +35,7 @@
 #include <unordered_set>
 
 #include "common.hpp"
+#include "gemvq_stages.hpp"
 #include "qact.hpp"
 #include "wave.hpp"
 
@@ -92,14 +93,7 @@ struct MfmaArgs {
 // 30-bit fixed point -> four balanced base-256 digits d0..d3 in [-128, 127], q = sum d_i 256^i.
 // Adding 0x808080 turns the three low digits into the UNSIGNED bytes of the sum (d_i + 128, the carries are the
 // adder's own), the top byte is already d3; flipping the three added bits back gives the signed digits:
-//     bytes of (q + 0x00808080) ^ 0x00808080  =  d0, d1, d2, d3        (two instructions per element)
-// round(v * sc) to the nearest integer in ONE instruction: v_cvt_rpi_i32_f32 = floor(x + 0.5) (ties go up
-// instead of to even; |error| <= 0.5 either way, and the kernel is VALU bound)
-__device__ __forceinline__ int cvt_rpi(float x) {
-    int r;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
+//     bytes of (q + 0x00808080) ^ 0x00808080  =  d0, d1, d2, d3        (two instructions per element; q = cvt_rpi(v * sc), wave.hpp, one more)
 // max(|a|, |b|, m) in one instruction (the source modifiers do the fabs)
 __device__ __forceinline__ float max3_abs(float a, float b, float m) {
     float r;
@@ -495,13 +489,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_mfma(MfmaArgs p) {
             s1 += stat[2 * w];
             s2 += stat[2 * w + 1];
         }
-        const double mean_d = s1 * p.inv_cols;  // 1/cols from the host: no f64 division sequences in the kernel
-        const double var_d = s2 * p.inv_cols - mean_d * mean_d;
-        ln_mean = (double)(float)mean_d;                                              // the f32 mean the prologue form subtracts
-        const double denom = (double)sqrtf((float)(var_d > 0.0 ? var_d : 0.0) + p.ln_eps);
-        double r = __builtin_amdgcn_rcp(denom);  // v_rcp_f64 + two Newton steps: 1/denom to the last bit or so
-        r = r * (2.0 - denom * r);
-        ln_rdenom = r * (2.0 - denom * r);
+        ln_from_sums(s1, s2, p.inv_cols, p.ln_eps, &ln_mean, &ln_rdenom);  // ln_mean: the f32 mean the prologue form subtracts
     }
     if (!p.silu_mul) {
         if (tid < tiles_per_wg * 16) {

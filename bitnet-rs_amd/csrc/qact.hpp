@@ -38,10 +38,20 @@ constexpr int kQRec = 576;  // bytes per 256-column record
 
 __host__ __device__ inline size_t qact_bytes(size_t cols) { return ((cols + 255) / 256) * (size_t)kQRec; }
 
-__device__ __forceinline__ int qcvt_rpi(float x) {  // floor(x + 1/2), one instruction
-    int r;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
+// The format, ONCE (qact_emit; k_gemv_q's merging prologue).  Bits of the group's |maximum| -> sc = 2^(13 - E) to multiply with, as = 2^(E - 13) to store
+__device__ __forceinline__ void qact_scales(uint32_t max_bits, float &sc, float &as) {
+    int be = (int)(max_bits >> 23);  // biased exponent of the group maximum
+    be = be < 32 ? 32 : be;          // keeps both scales normal floats; groups below 2^-95 quantise to zero
+    be = be > 254 ? 254 : be;        // Inf / NaN input: garbage in, finite scale out
+    sc = __uint_as_float((uint32_t)(267 - be) << 23);
+    as = __uint_as_float((uint32_t)(be - 13) << 23);
+}
+// value -> balanced digits: q = floor(u sc + 1/2), |q| <= 2^14; byte 0 of the result = d0, byte 1 = d1
+__device__ __forceinline__ uint32_t qact_digits(float u, float sc) { return ((uint32_t)cvt_rpi(u * sc) + 0x80u) ^ 0x80u; }
+// 16-group tp of a record -> its scale slot (lane group g = tp / 4, MFMA m = tp % 4 = 2 p + h -> 4 g + 2 h + p, see above)
+__device__ __forceinline__ float *qact_scale_slot(uint8_t *rec, int group) {
+    const int tp = group & 15, g = tp >> 2, m = tp & 3;
+    return reinterpret_cast<float *>(rec + 512) + (4 * g + 2 * (m & 1) + (m >> 1));
 }
 
 // One thread per element, the 16 threads of a DPP row = the 16 elements of group `group` (rows 16 group .. + 15 of
@@ -56,22 +66,14 @@ __device__ __forceinline__ void qact_emit(uint8_t *__restrict__ qout, double *__
         const float s1 = row16_sum_f(v), s2 = row16_sum_f(v * v);
         if (r == 0) *reinterpret_cast<double2 *>(stats + 2 * (size_t)group) = double2{(double)s1, (double)s2};
     }
-    const float am = row16_max_abs(u);
-    int be = (int)(__float_as_uint(am) >> 23);  // biased exponent of the group maximum (sign already cleared)
-    be = be < 32 ? 32 : be;                      // keeps both scales normal floats; groups below 2^-95 quantise to zero
-    be = be > 254 ? 254 : be;                    // Inf / NaN input: garbage in, finite scale out
-    const float sc = __uint_as_float((uint32_t)(267 - be) << 23);   // 2^(13 - E)
-    const float as = __uint_as_float((uint32_t)(be - 13) << 23);    // 2^(E - 13)
-    const int q = qcvt_rpi(u * sc);                                  // |q| <= 2^14
-    const uint32_t t = ((uint32_t)q + 0x80u) ^ 0x80u;                // byte 0 = d0, byte 1 = d1 (balanced digits)
+    float sc, as;
+    qact_scales(__float_as_uint(row16_max_abs(u)), sc, as);
+    const uint32_t t = qact_digits(u, sc);
     const int rec = group >> 4, tp = group & 15;
     uint8_t *base = qout + (size_t)rec * kQRec;
     base[16 * tp + r] = (uint8_t)t;
     base[256 + 16 * tp + r] = (uint8_t)(t >> 8);
-    if (r == 0) {
-        const int g = tp >> 2, m = tp & 3;
-        reinterpret_cast<float *>(base + 512)[4 * g + 2 * (m & 1) + (m >> 1)] = as;
-    }
+    if (r == 0) *qact_scale_slot(base, group) = as;
 }
 
 }  // namespace bitnet_hip

@@ -210,6 +210,11 @@ __device__ __forceinline__ uint32_t pack_h2(float lo, float hi) {
     return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
 }
 __device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__device__ __forceinline__ int cvt_rpi(float x) {  // to the nearest integer in ONE instruction: floor(x + 0.5), ties go up (|error| <= 0.5 either way)
+    int r;
+    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
 
 // ---- memory ----
 // Weight bytes are read ONCE per launch by ONE CU: non-temporal loads keep them from displacing the activation vectors in L2 / Infinity

@@ -1,6 +1,8 @@
 // batch_decoder.cpp -- see batch_decoder.hpp.  Owns buffers, the launch order and one captured graph; every launch is a bitnet_hip_* entry point.
 #include "batch_decoder.hpp"
 
+#include "stream_timer.hpp"
+
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -10,12 +12,6 @@
 namespace bitnet_host {
 
 namespace {
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) hipEventDestroy(e);
-    }
-};
 enum { kRowPos = 0, kRowHist, kRowLogits, kRowTok, kRowPickPos, kRowPickHist, kRowForced, kRowLayers };
 }  // namespace
 
@@ -336,10 +332,8 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
             ++captures_;
         }
     }
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
-    HCHK(hipEventRecord(ev0.e, s));
+    StreamTimer timer;
+    HCHK(timer.start(s));
     for (int i = 0; i < n; ++i) {
         if (use_graph) {
             HCHK(hipGraphLaunch((hipGraphExec_t)graph_exec_, s));
@@ -347,11 +341,7 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
             return rc;
         }
     }
-    HCHK(hipEventRecord(ev1.e, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
-    if (elapsed_ms) *elapsed_ms = ms;
+    HCHK(timer.stop(s, elapsed_ms));
     return 0;
 }
 

@@ -3,6 +3,7 @@
 #include "decoder.hpp"
 
 #include "blake3.hpp"
+#include "stream_timer.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -16,15 +17,6 @@
 #include <vector>
 
 namespace bitnet_host {
-
-namespace {
-struct Event {  // RAII: an error return between create and destroy must not leak the event
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) hipEventDestroy(e);
-    }
-};
-}  // namespace
 
 #define HCHK(expr)                                                                     \
     do {                                                                               \
@@ -924,11 +916,8 @@ int Decoder::run(int n, bool with_logits, bool use_graph, float *elapsed_ms) {
             if (rc) return rc;
         }
     }
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
-    hipEvent_t e0 = ev0.e, e1 = ev1.e;
-    HCHK(hipEventRecord(e0, s));
+    StreamTimer timer;
+    HCHK(timer.start(s));
     for (int i = 0; i < n; ++i) {
         if (use_graph) {
             HCHK(hipGraphLaunch((hipGraphExec_t)graph_exec_[2 * form_at(p + i) + (with_logits ? 1 : 0)], s));
@@ -938,11 +927,7 @@ int Decoder::run(int n, bool with_logits, bool use_graph, float *elapsed_ms) {
         }
         if (with_logits) picked(screen_step(false));
     }
-    HCHK(hipEventRecord(e1, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, e0, e1));
-    if (elapsed_ms) *elapsed_ms = ms;
+    HCHK(timer.stop(s, elapsed_ms));
     return 0;
 }
 
@@ -1009,10 +994,13 @@ int Decoder::fp6_flag(int digits) {
 // any length.)  Only for long shares -- where the hidden-row launches of 64-token tiles come to 400 workgroups or more (from 2497 tokens at
 // hidden 2560: 40 token tiles x 10 row blocks): measured, QK256, same box -- 4096 tokens 21.5 -> 20.3 ms, 3072 tokens 17.3 -> 16.4, 8192 tokens 45.3 -> 43.4, but 2048
 // tokens 11.8 -> 12.0 and 1024 tokens (also one rank's share of the 8-GPU prompt) 7.2 -> 7.8 ms.
-bool Decoder::hybrid_applies(size_t n_rows) const {
-    static const int hybrid_env = getenv("BITNET_HOST_PREFILL_HYBRID") ? atoi(getenv("BITNET_HOST_PREFILL_HYBRID")) : 1;
-    if (!hybrid_env || layers_.empty()) return false;
-    if (hybrid_env != 2 && ((size_t)c_.hidden / 256) * ((n_rows + 63) / 64) < 400) return false;
+bool Decoder::hybrid_applies(size_t n_rows) {
+    if (prefill_hybrid_ < 0) {
+        const char *e = getenv("BITNET_HOST_PREFILL_HYBRID");
+        prefill_hybrid_ = !e ? 1 : atoi(e) == 2 ? 2 : atoi(e) != 0 ? 1 : 0;
+    }
+    if (!prefill_hybrid_ || layers_.empty()) return false;
+    if (prefill_hybrid_ != 2 && ((size_t)c_.hidden / 256) * ((n_rows + 63) / 64) < 400) return false;
     for (const auto &L : layers_)
         if (bitnet_hip_matmul_f16_supported(L.o) != 1 || bitnet_hip_matmul_f16_supported(L.down) != 1) return false;
     return true;
@@ -1042,62 +1030,6 @@ int Decoder::ensure_chain_buffers(size_t N) {
     return 0;
 }
 
-// The attention of one layer of a prompt forward over the N rows in pf_qkv_ (all three forms of the layer loop come here): on a fresh
-// sequence the whole-prompt operator, on a live one (pf_past_ cached positions: Decoder::extend) the continuation operator, which reads the
-// past keys from the cache and takes every slot at or beyond pf_past_ from the new rows; with a pack in flight (pack_members_) the packed operator;
-// with a wide step in flight (wide_n_) the decode attention over the rows' own caches.
-int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16) {
-    const size_t NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, D = (size_t)c_.head_dim, MP = (size_t)c_.max_pos;
-    const int flags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
-    if (wide_n_ > 0) {
-        // a wide step in flight (step_wide): the N rows are N members' current tokens, each over its OWN caches of this layer at its own position
-        const size_t li = (size_t)(&L - layers_.data());
-        BCHK(bitnet_hip_attention_decode_rows_dev(pf_qkv_, rope_sin_, rope_cos_, wide_tables_ + (2 * li) * BITNET_HIP_WIDE_MAX,
-                                                  wide_tables_ + (2 * li + 1) * BITNET_HIP_WIDE_MAX,
-                                                  reinterpret_cast<const int32_t *const *>(wide_tables_ + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
-                                                  (size_t)wide_key_bound_, wide_scratch_, flags, out, stream_));
-    } else if (!pack_members_.empty()) {
-        // a pack in flight (prefill_packed): the N rows are several members' segments, each over its OWN caches of this layer
-        const size_t li = (size_t)(&L - layers_.data()), n = pack_members_.size();
-        void *kc[BITNET_HIP_PACK_MAX], *vc[BITNET_HIP_PACK_MAX];
-        for (size_t i = 0; i < n; ++i) kc[i] = pack_members_[i]->layers_[li].kcache, vc[i] = pack_members_[i]->layers_[li].vcache;
-        BCHK(bitnet_hip_attention_packed_dev(pf_qkv_, N, rope_sin_, rope_cos_, n, pack_row0_.data(), pack_len_.data(), pack_past_.data(), kc, vc, NH, NK, D, MP,
-                                             pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
-    } else if (pf_past_ > 0)
-        BCHK(bitnet_hip_attention_extend_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, pf_past_, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
-    else if (out_f16)
-        BCHK(bitnet_hip_attention_prefill_flags_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
-    else if (kv_f16_)
-        BCHK(bitnet_hip_attention_prefill_kv16_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, static_cast<float *>(out), stream_));
-    else
-        BCHK(bitnet_hip_attention_prefill_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, static_cast<float *>(out), stream_));
-    return 0;
-}
-
-int Decoder::prefill_chain_layers(size_t N) {
-    const size_t H = c_.hidden, nst = H / 64;
-    hipStream_t s = (hipStream_t)stream_;
-    {
-        const int rc = ensure_chain_buffers(N);
-        if (rc) return rc;
-    }
-    BCHK(bitnet_hip_rows_to_f16_dev(pf_x_, layers_[0].attn_norm, N, H, pf_xh_, pf_stats_, s));
-    size_t n_stats = 1;
-    for (size_t l = 0; l < layers_.size(); ++l) {
-        auto &L = layers_[l];
-        BCHK(bitnet_hip_matmul_f16_dev(L.qkv, pf_xh_, N, pf_stats_, n_stats, L.attn_norm, c_.eps, pf_qkv_, nullptr, 0, nullptr, nullptr, nullptr, s));
-        if (int rc = prompt_attention(L, N, pf_atth_, true)) return rc;
-        BCHK(bitnet_hip_matmul_f16_dev(L.o, pf_atth_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, pf_xh_, L.ffn_norm, pf_stats_, s));
-        n_stats = nst;
-        BCHK(bitnet_hip_matmul_f16_dev(L.gateup, pf_xh_, N, pf_stats_, n_stats, L.ffn_norm, c_.eps, nullptr, nullptr, BITNET_HIP_FUSE_SILU_MUL, pf_hh_, nullptr,
-                                       nullptr, s));
-        const bool last = l + 1 == layers_.size();
-        BCHK(bitnet_hip_matmul_f16_dev(L.down, pf_hh_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, last ? nullptr : pf_xh_,
-                                       last ? nullptr : layers_[l + 1].attn_norm, last ? nullptr : pf_stats_, s));
-    }
-    return 0;
-}
-
 // The QK256 prompt forward with NO row quantiser launch (round 5): q|k|v and gate|up run the fp6 x fp4 form on QB32 rows -- block-scaled 15-bit
 // fixed point, one exponent per 32 columns of a token -- that the kernel PRODUCING the residual stream wrote: the o- / down-projection (f16 matrix
 // cores, 320-row workgroups: the hybrid forward's launches) leaves x (f32), QB32(gamma_next * x) and the LayerNorm statistics partials in its
@@ -1118,81 +1050,213 @@ bool Decoder::qb32_applies(int digits, size_t n_rows) {
     return true;
 }
 
-int Decoder::prefill_qb32_layers(size_t N) {
-    const size_t H = c_.hidden, nst = H / 64;
-    hipStream_t s = (hipStream_t)stream_;
-    {
-        const int rc = ensure_chain_buffers(N);
-        if (rc) return rc;
+// The form of ONE prompt forward over N rows, decided once, and the only place a forward grows a buffer beyond ensure_prompt_buffers: the
+// f16 hand-over rows (chain, QB32, h16) and the QB32 rows.  RULE: every growth of a buffer happens here or in ensure_prompt_buffers, before
+// the forward's first launch; the repeat after a saturation asks again under force_scaled_, gets the plain digit-plane form, and grows and
+// frees nothing.  sharded: the token-parallel forward's restriction -- never the chain or QB32 forms, no fp6 flag on q|k|v and gate|up, no
+// f6od (and, running no prompt_layers, last_prefill_path_ left as it is).
+int Decoder::prompt_form(size_t N, int digits, bool sharded, PromptForm *out) {
+    PromptForm f;
+    f.digits = digits;
+    f.chain = !sharded && chain_applies(digits);
+    f.qb = !sharded && !f.chain && qb32_applies(digits, N);
+    f.h16 = !f.chain && !f.qb && handover16_applies(digits);
+    // Hybrid (unscaled matrices): the two projections whose inputs ARE f16 rows (the attention output, silu * up) multiply them on the f16
+    // matrix cores as they stand (k_gemm_f16a, 320-row workgroups: one round of the chip at 4096 tokens) -- no quantiser launch, no second
+    // rounding of values that were rounded to f16 already; q|k|v and gate|up keep the faster int8 digit planes behind their LayerNorm.
+    f.hybrid = f.h16 && hybrid_applies(N);
+    if (!sharded) {
+        if (prefill_fp6_od_ < 0) {  // experiment: o / down on the fp6 form too (non-hybrid)
+            const char *e = getenv("BITNET_HOST_PREFILL_FP6_OD");
+            prefill_fp6_od_ = e && atoi(e) != 0 ? 1 : 0;
+        }
+        f.f6 = (f.chain || f.qb) ? 0 : fp6_flag(digits);
+        f.f6od = prefill_fp6_od_ ? f.f6 : 0;
     }
+    if (f.f16_rows())
+        if (int rc = ensure_chain_buffers(N)) return rc;
     const size_t NP = (N + 63) / 64 * 64;
-    if ((int)NP > pf_qb_cap_) {
+    if (f.qb && (int)NP > pf_qb_cap_) {
         if (pf_qb_) (void)hipFree(pf_qb_);
         pf_qb_ = nullptr;
         pf_qb_cap_ = 0;
-        HCHK(hipMalloc(&pf_qb_, bitnet_hip_qb32_bytes(NP, H)));
-        HCHK(hipMemsetAsync(pf_qb_, 0, bitnet_hip_qb32_bytes(NP, H), s));
+        HCHK(hipMalloc(&pf_qb_, bitnet_hip_qb32_bytes(NP, (size_t)c_.hidden)));
+        HCHK(hipMemsetAsync(pf_qb_, 0, bitnet_hip_qb32_bytes(NP, (size_t)c_.hidden), (hipStream_t)stream_));
         pf_qb_cap_ = (int)NP;
     }
-    BCHK(bitnet_hip_rows_to_qb32_dev(pf_x_, layers_[0].attn_norm, N, H, pf_qb_, pf_stats_, s));
-    size_t n_stats = 1;
+    *out = f;
+    return 0;
+}
+
+// The attention of one layer of a prompt forward over the N rows in pf_qkv_, by the operator the driver names: the whole-prompt operator on
+// a fresh sequence; the continuation operator on a live one, which reads the past keys from the cache and takes every slot at or beyond
+// op.past from the new rows; the packed operator over every member's own caches of the layer; the decode attention over the rows' own caches.
+int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16, const AttnOp &op) {
+    const size_t NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, D = (size_t)c_.head_dim, MP = (size_t)c_.max_pos;
+    const int flags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
+    const size_t li = (size_t)(&L - layers_.data());
+    if (op.kind == AttnOp::Rows) {
+        // a wide step (step_wide): the N rows are N members' current tokens, each over its OWN caches of this layer at its own position
+        BCHK(bitnet_hip_attention_decode_rows_dev(pf_qkv_, rope_sin_, rope_cos_, wide_tables_ + (2 * li) * BITNET_HIP_WIDE_MAX,
+                                                  wide_tables_ + (2 * li + 1) * BITNET_HIP_WIDE_MAX,
+                                                  reinterpret_cast<const int32_t *const *>(wide_tables_ + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
+                                                  op.key_bound, wide_scratch_, flags, out, stream_));
+    } else if (op.kind == AttnOp::Pack) {
+        // a pack (prefill_packed): the N rows are several members' segments, each over its OWN caches of this layer
+        void *kc[BITNET_HIP_PACK_MAX], *vc[BITNET_HIP_PACK_MAX];
+        for (size_t i = 0; i < op.n; ++i) kc[i] = op.members[i]->layers_[li].kcache, vc[i] = op.members[i]->layers_[li].vcache;
+        BCHK(bitnet_hip_attention_packed_dev(pf_qkv_, N, rope_sin_, rope_cos_, op.n, op.row0, op.len, op.pasts, kc, vc, NH, NK, D, MP, pf_attn_ws_, pf_attn_ws_bytes_,
+                                             out, flags, stream_));
+    } else if (op.kind == AttnOp::Continue)
+        BCHK(bitnet_hip_attention_extend_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, op.past, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
+    else if (out_f16)
+        BCHK(bitnet_hip_attention_prefill_flags_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
+    else if (kv_f16_)
+        BCHK(bitnet_hip_attention_prefill_kv16_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, static_cast<float *>(out), stream_));
+    else
+        BCHK(bitnet_hip_attention_prefill_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, N, pf_attn_ws_, pf_attn_ws_bytes_, static_cast<float *>(out), stream_));
+    return 0;
+}
+
+// The four projections of a layer, each in the form f names.  The two chains (bitnet_hip_matmul_f16_dev / _qb32_dev) hand rows from kernel to
+// kernel -- the o- / down-projection's epilogue leaves x (f32, the residual stream), f16 or QB32 rows of gamma_next * x and the LayerNorm
+// statistics partials; the attention writes f16 rows; gate|up's epilogue writes f16(silu(gate) * up) -- so no row quantiser / conversion
+// launch sits between two matmuls; the digit planes (bitnet_hip_matmul_fused_dev) quantise their rows themselves, from f32 or, with the f16
+// hand-over, from the f16 rows of the attention and of gate|up.
+// q|k|v of layer l.  In front of the first layer the chains convert the embedded rows once (one statistics partial per row; a producing
+// epilogue leaves hidden / 64 of them).
+int Decoder::project_qkv(size_t l, size_t N, const PromptForm &f) {
+    Layer &L = layers_[l];
+    const size_t H = c_.hidden, n_stats = l == 0 ? 1 : H / 64;
+    if (f.chain) {
+        if (l == 0) BCHK(bitnet_hip_rows_to_f16_dev(pf_x_, L.attn_norm, N, H, pf_xh_, pf_stats_, stream_));
+        BCHK(bitnet_hip_matmul_f16_dev(L.qkv, pf_xh_, N, pf_stats_, n_stats, L.attn_norm, c_.eps, pf_qkv_, nullptr, 0, nullptr, nullptr, nullptr, stream_));
+    } else if (f.qb) {
+        if (l == 0) BCHK(bitnet_hip_rows_to_qb32_dev(pf_x_, L.attn_norm, N, H, pf_qb_, pf_stats_, stream_));
+        BCHK(bitnet_hip_matmul_qb32_dev(L.qkv, pf_qb_, N, pf_stats_, n_stats, L.attn_norm, c_.eps, pf_qkv_, nullptr, 0, nullptr, nullptr, nullptr, stream_));
+    } else
+        BCHK(bitnet_hip_matmul_fused_dev(L.qkv, pf_x_, pf_qkv_, N, L.attn_norm, c_.eps, nullptr, f.f6, f.digits, pf_gemm_ws_, pf_gemm_ws_bytes_, stream_));
+    return 0;
+}
+
+// o and down: rows in (in16 where the form hands f16 rows, else in32), the residual stream pf_x_ in and out.  next_norm: the LayerNorm the
+// chains prepare the next matmul's rows for, or null behind the last layer, which hands over nothing.
+int Decoder::project_residual(bitnet_hip_weights_t w, size_t N, const PromptForm &f, const float *in32, const void *in16, const float *next_norm) {
+    if (f.chain || f.qb || f.hybrid) {
+        void *hand = !next_norm ? nullptr : f.chain ? pf_xh_ : f.qb ? pf_qb_ : nullptr;
+        BCHK(bitnet_hip_matmul_f16_dev(w, in16, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, hand && f.qb ? BITNET_HIP_FUSE_YH_QB32 : 0, hand, hand ? next_norm : nullptr,
+                                       hand ? pf_stats_ : nullptr, stream_));
+    } else
+        BCHK(bitnet_hip_matmul_fused_dev(w, f.h16 ? static_cast<const float *>(in16) : in32, pf_x_, N, nullptr, 0.f, pf_x_, f.h16 ? BITNET_HIP_FUSE_X_F16 | f.f6od : 0,
+                                         f.digits, pf_gemm_ws_, pf_gemm_ws_bytes_, stream_));
+    return 0;
+}
+
+int Decoder::project_o(Layer &L, size_t N, const PromptForm &f) { return project_residual(L.o, N, f, pf_att_, pf_atth_, L.ffn_norm); }
+
+int Decoder::project_down(Layer &L, size_t N, const PromptForm &f, const float *next_norm) { return project_residual(L.down, N, f, pf_h_, pf_hh_, next_norm); }
+
+int Decoder::project_gateup(Layer &L, size_t N, const PromptForm &f) {
+    const size_t n_stats = (size_t)c_.hidden / 64;  // always behind an o-projection's epilogue
+    if (f.chain)
+        BCHK(bitnet_hip_matmul_f16_dev(L.gateup, pf_xh_, N, pf_stats_, n_stats, L.ffn_norm, c_.eps, nullptr, nullptr, BITNET_HIP_FUSE_SILU_MUL, pf_hh_, nullptr, nullptr, stream_));
+    else if (f.qb)
+        BCHK(bitnet_hip_matmul_qb32_dev(L.gateup, pf_qb_, N, pf_stats_, n_stats, L.ffn_norm, c_.eps, nullptr, nullptr, BITNET_HIP_FUSE_SILU_MUL, pf_hh_, nullptr, nullptr, stream_));
+    else
+        BCHK(bitnet_hip_matmul_fused_dev(L.gateup, pf_x_, f.h16 ? static_cast<float *>(pf_hh_) : pf_h_, N, L.ffn_norm, c_.eps, nullptr,
+                                         BITNET_HIP_FUSE_SILU_MUL | (f.h16 ? BITNET_HIP_FUSE_Y_F16 : 0) | f.f6, f.digits, pf_gemm_ws_, pf_gemm_ws_bytes_, stream_));
+    return 0;
+}
+
+// Every layer over the N rows in pf_x_ (embeddings in, residual stream of the last block out) in the form f, with the attention op names.
+int Decoder::prompt_layers(size_t N, const PromptForm &f, const AttnOp &op) {
+    // last_prefill_path(): the plain loop is recorded as it starts, a chain once it went through (one that a launcher refuses at this shape
+    // leaves the record as it was)
+    if (!f.chain && !f.qb) last_prefill_path_ = 0;
     for (size_t l = 0; l < layers_.size(); ++l) {
-        auto &L = layers_[l];
-        BCHK(bitnet_hip_matmul_qb32_dev(L.qkv, pf_qb_, N, pf_stats_, n_stats, L.attn_norm, c_.eps, pf_qkv_, nullptr, 0, nullptr, nullptr, nullptr, s));
-        if (int rc = prompt_attention(L, N, pf_atth_, true)) return rc;
-        BCHK(bitnet_hip_matmul_f16_dev(L.o, pf_atth_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, BITNET_HIP_FUSE_YH_QB32, pf_qb_, L.ffn_norm, pf_stats_, s));
-        n_stats = nst;
-        BCHK(bitnet_hip_matmul_qb32_dev(L.gateup, pf_qb_, N, pf_stats_, n_stats, L.ffn_norm, c_.eps, nullptr, nullptr, BITNET_HIP_FUSE_SILU_MUL, pf_hh_, nullptr,
-                                        nullptr, s));
-        const bool last = l + 1 == layers_.size();
-        if (last)
-            BCHK(bitnet_hip_matmul_f16_dev(L.down, pf_hh_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, nullptr, nullptr, nullptr, s));
-        else
-            BCHK(bitnet_hip_matmul_f16_dev(L.down, pf_hh_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, BITNET_HIP_FUSE_YH_QB32, pf_qb_, layers_[l + 1].attn_norm,
-                                           pf_stats_, s));
+        Layer &L = layers_[l];
+        if (int rc = project_qkv(l, N, f)) return rc;
+        if (int rc = prompt_attention(L, N, f.f16_rows() ? pf_atth_ : pf_att_, f.f16_rows(), op)) return rc;
+        if (int rc = project_o(L, N, f)) return rc;
+        if (int rc = project_gateup(L, N, f)) return rc;
+        if (int rc = project_down(L, N, f, l + 1 < layers_.size() ? layers_[l + 1].attn_norm : nullptr)) return rc;
+    }
+    if (f.chain || f.qb) last_prefill_path_ = f.chain ? 1 : 2;
+    return 0;
+}
+
+// THE SATURATION RULE, for every driver (prompt_forward, packed_forward, wide_forward): f16 hand-over rows carry no row scale, so a value
+// beyond +-65504 (outlier channels x gamma: none in the synthetic models, possible in a real checkpoint) is clamped AND counted
+// (bitnet_hip_f16_saturations).  A forward that clamped anything is repeated -- whole -- on the digit planes: 30-bit fixed point behind a
+// per-row power-of-two scale (digits = 4: a row whose outlier is 10^5 times its typical element still keeps 13 bits of those; the 2-digit and
+// row-scaled f16 forms would flush them), before anything reads its rows (no silent saturation).  fill embeds the rows into
+// pf_x_: the layers overwrite them, so the repeat embeds again; no driver moves a position before this returns, so the repeat rewrites the
+// same cache slots.  force_scaled_ is clear on every return path.
+template <class Fill> int Decoder::forward_with_repeat(size_t N, int digits, const AttnOp &op, const Fill &fill) {
+    struct Clear {
+        bool &b;
+        ~Clear() { b = false; }
+    } clear{force_scaled_};
+    PromptForm f;
+    if (int rc = prompt_form(N, digits, false, &f)) return rc;
+    (void)bitnet_hip_f16_saturations(1);  // a fresh count for this forward
+    if (int rc = fill()) return rc;
+    if (int rc = prompt_layers(N, f, op)) return rc;
+    if (!f.f16_rows()) return 0;
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    if (bitnet_hip_f16_saturations(1) == 0) return 0;
+    force_scaled_ = true;
+    ++saturation_fallbacks_;
+    if (int rc = prompt_form(N, 4, false, &f)) return rc;
+    if (int rc = fill()) return rc;
+    return prompt_layers(N, f, op);
+}
+
+// The span check of a prompt entry on one decoder: tokens [p, p + n) must have been fed and must fit the cache (T:1190-1194).  No p + n: a
+// huge n must not wrap.  positive: a count below 1 reads as tokens nobody fed (score has a refusal of its own for it, after these two).
+// -> the refusal's text, or null.
+const char *Decoder::span_problem(int p, int n, bool positive) const {
+    if ((positive && n <= 0) || n > host_forced_ - p) return "prefill: feed() the prompt tokens first";
+    return overflow_problem(p, n);
+}
+
+const char *Decoder::overflow_problem(int p, int n) const { return n > c_.max_pos - 1 - p ? "KV cache overflow" : nullptr; }  // (step_wide: nothing to be fed)
+
+// The member-set refusals of prefill_packed and step_wide, in their order, the text on the driver under the entry's name; also: a refusal of
+// the entry's own (or null) that ranks between the count and the members.
+int Decoder::check_members(Decoder *const *members, int n_members, int cap, const std::string &entry, const char *also) {
+    Decoder &drv = *members[0];
+    auto refuse = [&](const std::string &what) { return drv.fail_arg((entry + ": " + what).c_str()); };
+    if (n_members < 1 || n_members > cap) return refuse("n_members must be 1.." + std::to_string(cap));
+    if (also) return drv.fail_arg(also);
+    for (int i = 0; i < n_members; ++i) {
+        Decoder *d = members[i];
+        if (!d) return refuse("null member");
+        if (d->dead_) return refuse("dead member");
+        for (int j = 0; j < i; ++j)
+            if (members[j] == d) return refuse("a member is repeated");
+        if (d->root() != drv.root()) return refuse("all members must run on the same weights (an owner and its borrowers)");
+        if (d->kv_f16_ != drv.kv_f16_) return refuse("mixed KV cache types");
+        if (!d->embed_) return drv.fail_arg("model globals not set");
     }
     return 0;
 }
 
 int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
-    if (!embed_) {
-        err_ = "model globals not set";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
+    if (!embed_) return fail_arg("model globals not set");
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
-    if (p != 0) {
-        err_ = "prefill needs a fresh sequence (position 0): reset() first";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (n <= 0 || n > host_forced_) {
-        err_ = "prefill: feed() the prompt tokens first";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (n > c_.max_pos - 1) {
-        err_ = "KV cache overflow";  // T:1190-1194
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
+    if (p != 0) return fail_arg("prefill needs a fresh sequence (position 0): reset() first");
+    if (const char *e = span_problem(0, n)) return fail_arg(e);
     return prompt_forward(0, n, with_logits, digits, elapsed_ms);
 }
 
 int Decoder::extend(int n, bool with_logits, int digits, float *elapsed_ms) {
-    if (!embed_) {
-        err_ = "model globals not set";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
+    if (!embed_) return fail_arg("model globals not set");
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
-    if (n <= 0 || p + n > host_forced_) {
-        err_ = "prefill: feed() the prompt tokens first";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (p + n > c_.max_pos - 1) {
-        err_ = "KV cache overflow";  // T:1190-1194
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (p == 0) return prefill(n, with_logits, digits, elapsed_ms);
-    return prompt_forward(p, n, with_logits, digits, elapsed_ms);
+    if (const char *e = span_problem(p, n)) return fail_arg(e);
+    return prompt_forward(p, n, with_logits, digits, elapsed_ms);  // at p == 0 this IS prefill
 }
 
 int Decoder::rewind(int n) {
@@ -1345,45 +1409,22 @@ int Decoder::cached_prefix(const int32_t *tokens, int n) {
 // History tokens [p, p + n) through every layer as [n, *] matrices; p = the position (0: a fresh sequence and the whole-prompt attention;
 // otherwise the continuation operator over the p cached positions).  The callers hold the guards.
 int Decoder::prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms) {
-    const size_t H = c_.hidden;
-    pf_past_ = (size_t)p;
-    const size_t attn_need = p == 0 ? bitnet_hip_attention_prefill_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)n)
-                                    : bitnet_hip_attention_extend_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)p, (size_t)n);
+    const size_t H = c_.hidden, N = (size_t)n;
+    const size_t attn_need = p == 0 ? bitnet_hip_attention_prefill_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, N)
+                                    : bitnet_hip_attention_extend_workspace_bytes((size_t)c_.n_heads, (size_t)c_.n_kv_heads, (size_t)p, N);
     if (int rc = ensure_prompt_buffers(n, attn_need)) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
-    hipEvent_t e0 = ev0.e, e1 = ev1.e;
-    if (!force_scaled_) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this prompt
-    HCHK(hipEventRecord(e0, s));
-    const size_t N = (size_t)n;
-    BCHK(bitnet_hip_embed_f16_dev(embed_, history_, pos_, N, H, (size_t)c_.vocab, pf_x_, s));  // rows history[*pos_ + i], *pos_ == p
-    bool f16_rows = false;
-    if (int rc = prompt_layers(N, digits, &f16_rows)) return rc;
-    if (f16_rows) {
-        // f16 hand-over rows carry no row scale: a value beyond +-65504 (outlier channels x gamma: none in the synthetic models, possible in a real
-        // checkpoint) is clamped AND counted (bitnet_hip_f16_saturations).  A prompt that clamped anything is repeated on the digit planes --
-        // 30-bit fixed point behind a per-row power-of-two scale (digits = 4: a row whose outlier is 10^5 times its typical element still keeps 13 bits of
-        // those; the 2-digit and row-scaled f16 forms would flush them) -- before its logits are taken (no silent saturation).
-        HCHK(hipStreamSynchronize(s));
-        if (bitnet_hip_f16_saturations(1) > 0) {
-            force_scaled_ = true;
-            ++saturation_fallbacks_;
-            const int rc = prompt_forward(p, n, with_logits, 4, elapsed_ms);  // (a continuation rewrites only the new positions)
-            force_scaled_ = false;
-            return rc;
-        }
-    }
-    {
-        const int rc = finish_prefill(p + n, pf_x_ + (N - 1) * H, with_logits);
-        if (rc) return rc;
-    }
-    HCHK(hipEventRecord(e1, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, e0, e1));
-    if (elapsed_ms) *elapsed_ms = ms;
+    StreamTimer timer;
+    HCHK(timer.start(s));
+    AttnOp op;
+    op.kind = p == 0 ? AttnOp::Whole : AttnOp::Continue, op.past = (size_t)p;
+    const auto fill = [&]() -> int {
+        BCHK(bitnet_hip_embed_f16_dev(embed_, history_, pos_, N, H, (size_t)c_.vocab, pf_x_, s));  // rows history[*pos_ + i], *pos_ == p
+        return 0;
+    };
+    if (int rc = forward_with_repeat(N, digits, op, fill)) return rc;  // (a repeated continuation rewrites only the new positions)
+    if (int rc = finish_prefill(p + n, pf_x_ + (N - 1) * H, with_logits)) return rc;
+    HCHK(timer.stop(s, elapsed_ms));
     return 0;
 }
 
@@ -1391,19 +1432,8 @@ int Decoder::prefill_packed(Decoder *const *members, const int *n, int n_members
     if (!members || !members[0] || members[0]->dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;  // no driver to carry the text
     Decoder &drv = *members[0];
     // every refusal comes before the first write
-    if (n_members < 1 || n_members > BITNET_HIP_PACK_MAX) return drv.fail_arg("prefill_packed: n_members must be 1..64");
-    if (!n) return drv.fail_arg("prefill_packed: null lengths");
+    if (int rc = check_members(members, n_members, BITNET_HIP_PACK_MAX, "prefill_packed", n ? nullptr : "prefill_packed: null lengths")) return rc;
     std::vector<int32_t> past((size_t)n_members), len((size_t)n_members);
-    for (int i = 0; i < n_members; ++i) {
-        Decoder *d = members[i];
-        if (!d) return drv.fail_arg("prefill_packed: null member");
-        if (d->dead_) return drv.fail_arg("prefill_packed: dead member");
-        for (int j = 0; j < i; ++j)
-            if (members[j] == d) return drv.fail_arg("prefill_packed: a member is repeated");
-        if (d->root() != drv.root()) return drv.fail_arg("prefill_packed: all members must run on the same weights (an owner and its borrowers)");
-        if (d->kv_f16_ != drv.kv_f16_) return drv.fail_arg("prefill_packed: mixed KV cache types");
-        if (!d->embed_) return drv.fail_arg("model globals not set");
-    }
     for (int i = 0; i < n_members; ++i) {
         Decoder *d = members[i];
         const int p = d->position();
@@ -1412,8 +1442,7 @@ int Decoder::prefill_packed(Decoder *const *members, const int *n, int n_members
             return BITNET_HIP_ERR_GPU;
         }
         if (n[i] < 1) return drv.fail_arg("prefill_packed: every member takes at least 1 token");
-        if (n[i] > d->host_forced_ - p) return drv.fail_arg("prefill: feed() the prompt tokens first");  // (no p + n: a huge n must not wrap)
-        if (n[i] > drv.c_.max_pos - 1 - p) return drv.fail_arg("KV cache overflow");  // T:1190-1194
+        if (const char *e = d->span_problem(p, n[i])) return drv.fail_arg(e);
         past[(size_t)i] = p, len[(size_t)i] = n[i];
     }
     return drv.packed_forward(members, past, len, with_logits, digits, elapsed_ms);
@@ -1437,38 +1466,24 @@ int Decoder::packed_forward(Decoder *const *members, const std::vector<int32_t> 
     if (attn_need == 0) return fail_arg("prefill_packed: sizes out of range");
     if (int rc = ensure_prompt_buffers((int)N, attn_need)) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
-    if (!force_scaled_) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this pack
-    HCHK(hipEventRecord(ev0.e, s));
-    for (size_t i = 0; i < M; ++i) {
-        Decoder *d = members[i];
-        // rows history[p + r]: the member's tokens, then (up to the next member's first row) what follows them in its history, as far as the history goes
-        const size_t want = i + 1 < M ? (size_t)row0[i + 1] - (size_t)row0[i] : (size_t)len[i], have = (size_t)c_.max_pos + 2 - (size_t)past[i];
-        const size_t rows = want < have ? want : have;
-        float *dst = pf_x_ + (size_t)row0[i] * H;
-        BCHK(bitnet_hip_embed_f16_dev(d->embed_, d->history_, d->pos_, rows, H, (size_t)c_.vocab, dst, s));
-        for (size_t r = rows; r < want; ++r)  // (a member within a tile of the cache's end: its last token again)
-            HCHK(hipMemcpyAsync(dst + r * H, dst + ((size_t)len[i] - 1) * H, H * 4, hipMemcpyDeviceToDevice, s));
-    }
-    pack_members_.assign(members, members + M);
-    pack_row0_ = row0, pack_len_ = len, pack_past_ = past;
-    bool f16_rows = false;
-    const int rc_layers = prompt_layers(N, digits, &f16_rows);
-    pack_members_.clear();
-    if (rc_layers) return rc_layers;
-    if (f16_rows) {
-        // the saturation rule of prompt_forward: if any f16 hand-over value clamped, the WHOLE pack is repeated on the digit planes
-        HCHK(hipStreamSynchronize(s));
-        if (bitnet_hip_f16_saturations(1) > 0) {
-            force_scaled_ = true;
-            ++saturation_fallbacks_;
-            const int rc = packed_forward(members, past, len, with_logits, 4, elapsed_ms);
-            force_scaled_ = false;
-            return rc;
+    StreamTimer timer;
+    HCHK(timer.start(s));
+    const auto fill = [&]() -> int {
+        for (size_t i = 0; i < M; ++i) {
+            Decoder *d = members[i];
+            // rows history[p + r]: the member's tokens, then (up to the next member's first row) what follows them in its history, as far as the history goes
+            const size_t want = i + 1 < M ? (size_t)row0[i + 1] - (size_t)row0[i] : (size_t)len[i], have = (size_t)c_.max_pos + 2 - (size_t)past[i];
+            const size_t rows = want < have ? want : have;
+            float *dst = pf_x_ + (size_t)row0[i] * H;
+            BCHK(bitnet_hip_embed_f16_dev(d->embed_, d->history_, d->pos_, rows, H, (size_t)c_.vocab, dst, s));
+            for (size_t r = rows; r < want; ++r)  // (a member within a tile of the cache's end: its last token again)
+                HCHK(hipMemcpyAsync(dst + r * H, dst + ((size_t)len[i] - 1) * H, H * 4, hipMemcpyDeviceToDevice, s));
         }
-    }
+        return 0;
+    };
+    AttnOp op;  // (its pointers are this frame's vectors: they outlive both attempts)
+    op.kind = AttnOp::Pack, op.members = members, op.n = M, op.row0 = row0.data(), op.len = len.data(), op.pasts = past.data();
+    if (int rc = forward_with_repeat(N, digits, op, fill)) return rc;
     // the hand-over: every member's own head, pick and log-probability record on its own stream, from its last token's row
     HCHK(hipStreamSynchronize(s));
     for (size_t i = 0; i < M; ++i) {
@@ -1479,11 +1494,7 @@ int Decoder::packed_forward(Decoder *const *members, const std::vector<int32_t> 
             return rc;
         }
     }
-    HCHK(hipEventRecord(ev1.e, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
-    if (elapsed_ms) *elapsed_ms = ms;
+    HCHK(timer.stop(s, elapsed_ms));
     return 0;
 }
 
@@ -1491,18 +1502,7 @@ int Decoder::step_wide(Decoder *const *members, int n_members, int n_steps, int 
     if (!members || !members[0] || members[0]->dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;  // no driver to carry the text
     Decoder &drv = *members[0];
     // every refusal comes before the first write
-    if (n_members < 1 || n_members > BITNET_HIP_WIDE_MAX) return drv.fail_arg("step_wide: n_members must be 1..64");
-    if (n_steps < 1) return drv.fail_arg("step_wide: n_steps must be at least 1");
-    for (int i = 0; i < n_members; ++i) {
-        Decoder *d = members[i];
-        if (!d) return drv.fail_arg("step_wide: null member");
-        if (d->dead_) return drv.fail_arg("step_wide: dead member");
-        for (int j = 0; j < i; ++j)
-            if (members[j] == d) return drv.fail_arg("step_wide: a member is repeated");
-        if (d->root() != drv.root()) return drv.fail_arg("step_wide: all members must run on the same weights (an owner and its borrowers)");
-        if (d->kv_f16_ != drv.kv_f16_) return drv.fail_arg("step_wide: mixed KV cache types");
-        if (!d->embed_) return drv.fail_arg("model globals not set");
-    }
+    if (int rc = check_members(members, n_members, BITNET_HIP_WIDE_MAX, "step_wide", n_steps < 1 ? "step_wide: n_steps must be at least 1" : nullptr)) return rc;
     int max_p = 0;
     for (int i = 0; i < n_members; ++i) {
         Decoder *d = members[i];
@@ -1511,13 +1511,13 @@ int Decoder::step_wide(Decoder *const *members, int n_members, int n_steps, int 
             drv.err_ = d->err_;
             return BITNET_HIP_ERR_GPU;
         }
-        if (n_steps > drv.c_.max_pos - 1 - p) return drv.fail_arg("KV cache overflow");  // T:1190-1194 (no p + n_steps: a huge count must not wrap)
+        if (const char *e = d->overflow_problem(p, n_steps)) return drv.fail_arg(e);
         max_p = p > max_p ? p : max_p;
     }
     return drv.wide_forward(members, n_members, n_steps, max_p, digits, elapsed_ms);
 }
 
-// The wide step's chain, n_steps times: gather, layers (prompt_attention takes the rows attention while wide_n_ is set), saturation check, head,
+// The wide step's chain, n_steps times: gather, layers under the rows attention (with the saturation rule: forward_with_repeat), head,
 // hand-over, then the samplers and logits taps member by member.  This decoder is the driver; max_p = the largest position before the call.
 int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms) {
     const size_t H = c_.hidden, V = (size_t)c_.vocab, NL = layers_.size(), W = BITNET_HIP_WIDE_MAX;
@@ -1561,36 +1561,16 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
     }
     void **g = wide_tables_ + 2 * NL * W;
     const int32_t *const *pos_t = reinterpret_cast<const int32_t *const *>(g), *const *hist_t = reinterpret_cast<const int32_t *const *>(g + W);
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
-    HCHK(hipEventRecord(ev0.e, s));
-    struct InFlight {  // an error return must not leave the rows attention or the repeat's matmul forms switched on
-        int &n;
-        bool &scaled;
-        ~InFlight() { n = 0, scaled = false; }
-    } in_flight{wide_n_, force_scaled_};
+    StreamTimer timer;
+    HCHK(timer.start(s));
+    const auto fill = [&]() -> int {
+        BCHK(bitnet_hip_embed_rows_dev(embed_, hist_t, pos_t, (size_t)M, H, V, pf_x_, s));
+        return 0;
+    };
     for (int step = 0; step < n_steps; ++step) {
-        wide_key_bound_ = max_p + step + 1;
-        int dg = digits;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if (attempt == 0) (void)bitnet_hip_f16_saturations(1);  // a fresh count for this step
-            BCHK(bitnet_hip_embed_rows_dev(embed_, hist_t, pos_t, (size_t)M, H, V, pf_x_, s));
-            wide_n_ = M;
-            bool f16_rows = false;
-            const int rc = prompt_layers((size_t)M, dg, &f16_rows);
-            wide_n_ = 0;
-            if (rc) return rc;
-            if (!f16_rows || attempt == 1) break;
-            // the saturation rule of prompt_forward: if any f16 hand-over value clamped, the WHOLE step is repeated on the digit planes.  The
-            // positions move only in the pick below, so the repeat rewrites the same cache slots.
-            HCHK(hipStreamSynchronize(s));
-            if (bitnet_hip_f16_saturations(1) == 0) break;
-            force_scaled_ = true;
-            ++saturation_fallbacks_;
-            dg = 4;
-        }
-        force_scaled_ = false;
+        AttnOp op;  // (the positions move only in the pick below, so a repeated step rewrites the same cache slots)
+        op.kind = AttnOp::Rows, op.n = (size_t)M, op.key_bound = (size_t)(max_p + step + 1);
+        if (int rc = forward_with_repeat((size_t)M, digits, op, fill)) return rc;
         BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, (size_t)M, wide_tgt_, wide_nll_, wide_am_, wide_logits_, (size_t)M, wide_ws_,
                                       wide_ws_bytes_, s));
         BCHK(bitnet_hip_pick_rows_dev(wide_logits_, wide_am_, (size_t)M, V, reinterpret_cast<float *const *>(g + 3 * W), reinterpret_cast<int32_t *const *>(g + 4 * W),
@@ -1608,11 +1588,7 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
             }
         }
     }
-    HCHK(hipEventRecord(ev1.e, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
-    if (elapsed_ms) *elapsed_ms = ms;
+    HCHK(timer.stop(s, elapsed_ms));
     return 0;
 }
 
@@ -1641,120 +1617,31 @@ int Decoder::ensure_prompt_buffers(int n, size_t attn_need) {
     return 0;
 }
 
-// Every layer over the N rows in pf_x_ (embeddings in, residual stream of the last block out), on the matmul chain N rows and `digits` select;
-// *f16_rows: the chain handed f16 rows from kernel to kernel, so the caller owes the saturation check.  prompt_forward and prefill_packed.
-int Decoder::prompt_layers(size_t N, int digits, bool *f16_rows) {
-    hipStream_t s = (hipStream_t)stream_;
-    const bool chain = chain_applies(digits);
-    if (chain) {
-        const int rc = prefill_chain_layers(N);
-        if (rc) return rc;
-    }
-    const bool qb = !chain && qb32_applies(digits, N);
-    if (qb) {
-        const int rc = prefill_qb32_layers(N);
-        if (rc) return rc;
-    }
-    last_prefill_path_ = chain ? 1 : qb ? 2 : 0;
-    const bool h16 = !chain && !qb && handover16_applies(digits);
-    if (h16) {
-        const int rc = ensure_chain_buffers(N);
-        if (rc) return rc;
-    }
-    // Hybrid (unscaled matrices): the two projections whose inputs ARE f16 rows (the attention output, silu * up) multiply them on the f16
-    // matrix cores as they stand (k_gemm_f16a, 320-row workgroups: one round of the chip at 4096 tokens) -- no quantiser launch, no second
-    // rounding of values that were rounded to f16 already; q|k|v and gate|up keep the faster int8 digit planes behind their LayerNorm.
-    const bool hybrid = h16 && hybrid_applies(N);
-    const int f6 = (chain || qb) ? 0 : fp6_flag(digits);
-    static const int f6od_env = getenv("BITNET_HOST_PREFILL_FP6_OD") ? atoi(getenv("BITNET_HOST_PREFILL_FP6_OD")) : 0;  // experiment: o / down on the fp6 form too (non-hybrid)
-    const int f6od = f6od_env ? f6 : 0;
-    for (auto &L : layers_) {
-        if (chain || qb) break;
-        BCHK(bitnet_hip_matmul_fused_dev(L.qkv, pf_x_, pf_qkv_, N, L.attn_norm, c_.eps, nullptr, f6, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
-        if (h16) {
-            if (int rc = prompt_attention(L, N, pf_atth_, true)) return rc;
-            if (hybrid)
-                BCHK(bitnet_hip_matmul_f16_dev(L.o, pf_atth_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, nullptr, nullptr, nullptr, s));
-            else
-                BCHK(bitnet_hip_matmul_fused_dev(L.o, (const float *)pf_atth_, pf_x_, N, nullptr, 0.f, pf_x_, BITNET_HIP_FUSE_X_F16 | f6od, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
-            BCHK(bitnet_hip_matmul_fused_dev(L.gateup, pf_x_, (float *)pf_hh_, N, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL | BITNET_HIP_FUSE_Y_F16 | f6, digits,
-                                             pf_gemm_ws_, pf_gemm_ws_bytes_, s));
-            if (hybrid)
-                BCHK(bitnet_hip_matmul_f16_dev(L.down, pf_hh_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, nullptr, nullptr, nullptr, s));
-            else
-                BCHK(bitnet_hip_matmul_fused_dev(L.down, (const float *)pf_hh_, pf_x_, N, nullptr, 0.f, pf_x_, BITNET_HIP_FUSE_X_F16 | f6od, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
-            continue;
-        }
-        if (int rc = prompt_attention(L, N, pf_att_, false)) return rc;
-        BCHK(bitnet_hip_matmul_fused_dev(L.o, pf_att_, pf_x_, N, nullptr, 0.f, pf_x_, 0, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
-        BCHK(bitnet_hip_matmul_fused_dev(L.gateup, pf_x_, pf_h_, N, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL | f6, digits, pf_gemm_ws_,
-                                         pf_gemm_ws_bytes_, s));
-        BCHK(bitnet_hip_matmul_fused_dev(L.down, pf_h_, pf_x_, N, nullptr, 0.f, pf_x_, 0, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
-    }
-    *f16_rows = chain || qb || h16;
-    return 0;
-}
-
 int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_fn gather, void *gather_ctx, bool with_logits, int digits,
                              bool wire_f16, float *elapsed_ms) {
-    if (!embed_) {
-        err_ = "model globals not set";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
+    if (!embed_) return fail_arg("model globals not set");
     if (sampling_) {
         err_ = "prefill_sharded: not available with sampling on (set_sampling(NULL) first)";
         return BITNET_HIP_ERR_UNSUPPORTED;
     }
-    if (world < 1 || rank < 0 || rank >= world || (world > 1 && !gather)) {
-        err_ = "prefill_sharded: bad rank / world / gather";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
+    if (world < 1 || rank < 0 || rank >= world || (world > 1 && !gather)) return fail_arg("prefill_sharded: bad rank / world / gather");
     if (n <= 0 || n % (2 * world * 64) != 0) {
         char b[128];
         snprintf(b, sizeof(b), "prompt length %d must be a positive multiple of %d (2 * world * 64) for world %d", n, 2 * world * 64, world);
-        err_ = b;
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
+        return fail_arg(b);
     }
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
-    if (p != 0) {
-        err_ = "prefill needs a fresh sequence (position 0): reset() first";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (n > host_forced_) {
-        err_ = "prefill: feed() the prompt tokens first";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (n > c_.max_pos - 1) {
-        err_ = "KV cache overflow";  // T:1190-1194
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    const size_t H = c_.hidden, QD = (size_t)c_.n_heads * c_.head_dim, KD = (size_t)c_.n_kv_heads * c_.head_dim, F = c_.ffn;
+    if (p != 0) return fail_arg("prefill needs a fresh sequence (position 0): reset() first");
+    if (const char *e = span_problem(0, n)) return fail_arg(e);
+    const size_t H = c_.hidden, QD = (size_t)c_.n_heads * c_.head_dim, KD = (size_t)c_.n_kv_heads * c_.head_dim;
     const size_t NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, D = (size_t)c_.head_dim, MP = (size_t)c_.max_pos;
     const int chunk = n / (2 * world), nq = 2 * chunk;
     const size_t N = (size_t)nq, esz = wire_f16 ? 2 : 4;
-    if (nq > pf_cap_) {  // the per-row buffers of the unsharded prefill, sized for this rank's rows
-        for (void *q : {(void *)pf_x_, (void *)pf_qkv_, (void *)pf_att_, (void *)pf_h_, pf_gemm_ws_})
-            if (q) hipFree(q);
-        pf_x_ = pf_qkv_ = pf_att_ = pf_h_ = nullptr;
-        pf_gemm_ws_ = nullptr;
-        pf_cap_ = 0;
-        pf_gemm_ws_bytes_ = bitnet_hip_matmul_workspace_bytes(N, H > F ? H : F, 4);
-        HCHK(dalloc(&pf_x_, N * H));
-        HCHK(dalloc(&pf_qkv_, N * (QD + 2 * KD)));
-        HCHK(dalloc(&pf_att_, N * QD));
-        HCHK(dalloc(&pf_h_, N * F));
-        HCHK(hipMalloc(&pf_gemm_ws_, pf_gemm_ws_bytes_));
-        pf_cap_ = nq;
-    }
-    const size_t awb = bitnet_hip_attention_prefill_sharded_workspace_bytes(NH, NK, N, (size_t)n);
-    if (awb > pf_attn_ws_bytes_) {
-        if (pf_attn_ws_) hipFree(pf_attn_ws_);
-        pf_attn_ws_ = nullptr;
-        pf_attn_ws_bytes_ = 0;
-        HCHK(hipMalloc(&pf_attn_ws_, awb));
-        pf_attn_ws_bytes_ = awb;
-    }
+    // the per-row buffers of the unsharded prefill, sized for this rank's rows, and the form's own: all growth before the first launch
+    if (int rc = ensure_prompt_buffers(nq, bitnet_hip_attention_prefill_sharded_workspace_bytes(NH, NK, N, (size_t)n))) return rc;
+    PromptForm f;
+    if (int rc = prompt_form(N, digits, true, &f)) return rc;
     if (nq > sp_cap_ || n > sp_ctx_) {
         for (void *q : {sp_kv_send_, sp_kv_all_, (void *)sp_block_pos_, (void *)sp_tokens_})
             if (q) hipFree(q);
@@ -1799,9 +1686,6 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
         HCHK(hipMemcpy(sp_tokens_, tok.data(), N * 4, hipMemcpyHostToDevice));
         HCHK(hipMemcpy(sp_block_pos_, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
     }
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
     // optional per-phase timing: 8 events per layer (6 on the compute stream, 2 around the collective on its own stream)
     const bool timing = sp_timing_;
     if (timing && sp_tev_.size() < layers_.size() * 8) {
@@ -1814,20 +1698,18 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
     }
     size_t li = 0;
     auto mark = [&](int idx, hipStream_t st) -> hipError_t { return timing ? hipEventRecord((hipEvent_t)sp_tev_[li * 8 + (size_t)idx], st) : hipSuccess; };
-    HCHK(hipEventRecord(ev0.e, s));
+    StreamTimer timer;
+    HCHK(timer.start(s));
     BCHK(bitnet_hip_embed_f16_dev(embed_, sp_tokens_, nullptr, N, H, (size_t)c_.vocab, pf_x_, s));
     const size_t ld = QD + 2 * KD, per_rank = N * 2 * KD * esz;
-    const bool h16 = handover16_applies(digits);  // f16 hand-over of the attention output and of silu * up (Decoder::prefill explains)
-    if (h16) {
-        const int rc = ensure_chain_buffers(N);
-        if (rc) return rc;
-    }
-    float *att_out = h16 ? static_cast<float *>(pf_atth_) : pf_att_;
-    const bool hybrid = h16 && hybrid_applies(N);  // o / down on the f16 matrix cores, as in the unsharded prefill (long shares only)
-    const int aflags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (h16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
-    for (auto &L : layers_) {
+    // (f.h16: f16 hand-over of the attention output and of silu * up; f.hybrid: o / down on the f16 matrix cores -- long shares only)
+    float *att_out = f.h16 ? static_cast<float *>(pf_atth_) : pf_att_;
+    const int aflags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (f.h16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
+    // its own loop: the attention has two phases around the collective, and the timing marks sit between the launches
+    for (size_t l = 0; l < layers_.size(); ++l) {
+        Layer &L = layers_[l];
         HCHK(mark(0, s));
-        BCHK(bitnet_hip_matmul_fused_dev(L.qkv, pf_x_, pf_qkv_, N, L.attn_norm, c_.eps, nullptr, 0, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
+        if (int rc = project_qkv(l, N, f)) return rc;
         // the raw (pre-RoPE) k|v rows this rank contributes, compact, f32 or f16
         BCHK(bitnet_hip_pack_cols_dev(pf_qkv_, ld, QD, 2 * KD, N, world > 1 ? sp_kv_send_ : sp_kv_all_, wire_f16 ? 1 : 0, s));
         HCHK(mark(1, s));
@@ -1858,18 +1740,9 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
                                                              rope_cos_, L.kcache, L.vcache, aflags, NH, NK, D, MP, pf_attn_ws_, pf_attn_ws_bytes_, att_out,
                                                              world > 1 ? 2 : 0, s));
         HCHK(mark(4, s));
-        const int xf = h16 ? BITNET_HIP_FUSE_X_F16 : 0, yf = h16 ? BITNET_HIP_FUSE_Y_F16 : 0;
-        float *h_buf = h16 ? static_cast<float *>(pf_hh_) : pf_h_;
-        if (hybrid)
-            BCHK(bitnet_hip_matmul_f16_dev(L.o, pf_atth_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, nullptr, nullptr, nullptr, s));
-        else
-            BCHK(bitnet_hip_matmul_fused_dev(L.o, att_out, pf_x_, N, nullptr, 0.f, pf_x_, xf, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
-        BCHK(bitnet_hip_matmul_fused_dev(L.gateup, pf_x_, h_buf, N, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL | yf, digits, pf_gemm_ws_,
-                                         pf_gemm_ws_bytes_, s));
-        if (hybrid)
-            BCHK(bitnet_hip_matmul_f16_dev(L.down, pf_hh_, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, 0, nullptr, nullptr, nullptr, s));
-        else
-            BCHK(bitnet_hip_matmul_fused_dev(L.down, h_buf, pf_x_, N, nullptr, 0.f, pf_x_, xf, digits, pf_gemm_ws_, pf_gemm_ws_bytes_, s));
+        if (int rc = project_o(L, N, f)) return rc;
+        if (int rc = project_gateup(L, N, f)) return rc;
+        if (int rc = project_down(L, N, f, nullptr)) return rc;  // (no chain here: nothing is handed to the next layer)
         HCHK(mark(5, s));
         ++li;
     }
@@ -1893,11 +1766,7 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
         const int rc = finish_prefill(n, last, with_logits);
         if (rc) return rc;
     }
-    HCHK(hipEventRecord(ev1.e, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
-    if (elapsed_ms) *elapsed_ms = ms;
+    HCHK(timer.stop(s, elapsed_ms));
     if (timing) {
         if (comm_stream_) HCHK(hipStreamSynchronize((hipStream_t)comm_stream_));
         std::vector<float> ph[4];
@@ -1921,36 +1790,14 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
 }
 
 int Decoder::score(int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms) {
-    if (!embed_) {
-        err_ = "model globals not set";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (!nll_out || (logits_rows > 0 && !logits_out)) {
-        err_ = "score: null pointer";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (n > host_forced_) {
-        err_ = "prefill: feed() the prompt tokens first";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (n > c_.max_pos - 1) {
-        err_ = "KV cache overflow";  // T:1190-1194
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (n < 2) {
-        err_ = "score: n must be >= 2 (row r is scored against token r + 1)";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
-    if (logits_rows < 0 || logits_rows > n) {
-        err_ = "score: logits_rows must be in [0, n]";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
+    if (!embed_) return fail_arg("model globals not set");
+    if (!nll_out || (logits_rows > 0 && !logits_out)) return fail_arg("score: null pointer");
+    if (const char *e = span_problem(0, n, false)) return fail_arg(e);  // (the position itself is prefill's to check, below)
+    if (n < 2) return fail_arg("score: n must be >= 2 (row r is scored against token r + 1)");
+    if (logits_rows < 0 || logits_rows > n) return fail_arg("score: logits_rows must be in [0, n]");
     const size_t H = c_.hidden, V = (size_t)c_.vocab, N = (size_t)n;
     const size_t need = bitnet_hip_score_workspace_bytes(N, H, V);
-    if (need == 0) {
-        err_ = "score: dimensions too large";
-        return BITNET_HIP_ERR_INVALID_ARGUMENT;
-    }
+    if (need == 0) return fail_arg("score: dimensions too large");
     if (n > sc_cap_ || need > sc_ws_bytes_) {
         for (void *q : {(void *)sc_tgt_, (void *)sc_am_, (void *)sc_nll_, sc_ws_})
             if (q) hipFree(q);
@@ -1974,21 +1821,15 @@ int Decoder::score(int n, int digits, float *nll_out, int32_t *argmax_out, float
         sc_logits_cap_ = logits_rows;
     }
     hipStream_t s = (hipStream_t)stream_;
-    Event ev0, ev1;
-    HCHK(hipEventCreate(&ev0.e));
-    HCHK(hipEventCreate(&ev1.e));
-    HCHK(hipEventRecord(ev0.e, s));
+    StreamTimer timer;
+    HCHK(timer.start(s));
     if (int rc = prefill(n, true, digits, nullptr)) return rc;
     // row r predicts token r + 1 of the history (the prompt); the last row has no target
     HCHK(hipMemcpyAsync(sc_tgt_, history_ + 1, (N - 1) * 4, hipMemcpyDeviceToDevice, s));
     HCHK(hipMemsetAsync(sc_tgt_ + (N - 1), 0xff, 4, s));
     BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, N, sc_tgt_, sc_nll_, argmax_out ? sc_am_ : nullptr,
                                   logits_rows > 0 ? sc_logits_ : nullptr, (size_t)logits_rows, sc_ws_, sc_ws_bytes_, s));
-    HCHK(hipEventRecord(ev1.e, s));
-    HCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
-    if (elapsed_ms) *elapsed_ms = ms;
+    HCHK(timer.stop(s, elapsed_ms));
     HCHK(hipMemcpy(nll_out, sc_nll_, (N - 1) * 4, hipMemcpyDeviceToHost));
     if (argmax_out) HCHK(hipMemcpy(argmax_out, sc_am_, N * 4, hipMemcpyDeviceToHost));
     if (logits_rows > 0) HCHK(hipMemcpy(logits_out, sc_logits_, (size_t)logits_rows * V * 4, hipMemcpyDeviceToHost));
@@ -2106,17 +1947,11 @@ int Decoder::probe_kernel(int kind, int reps, float *us_per_launch, double *byte
     HCHK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
     HCHK(hipGraphLaunch(ex, s));  // warm
     HCHK(hipStreamSynchronize(s));
-    hipEvent_t e0, e1;
-    HCHK(hipEventCreate(&e0));
-    HCHK(hipEventCreate(&e1));
-    HCHK(hipEventRecord(e0, s));
+    StreamTimer timer;
+    HCHK(timer.start(s));
     for (int i = 0; i < reps; ++i) HCHK(hipGraphLaunch(ex, s));
-    HCHK(hipEventRecord(e1, s));
-    HCHK(hipStreamSynchronize(s));
     float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
+    HCHK(timer.stop(s, &ms));
     hipGraphExecDestroy(ex);
     hipGraphDestroy(g);
     (void)p0;

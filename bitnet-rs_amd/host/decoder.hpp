@@ -182,7 +182,8 @@ class Decoder {
     // count of the whole pack selects the matmul tiles and the chain (last_prefill_path() of the driver).
     // members[0] is the DRIVER: the forward runs on its stream and in its prompt buffers (grown for the padded row total), the error text
     // goes on it, and saturation_fallbacks() of the driver counts a pack that clamped an f16 hand-over value and was repeated -- whole --
-    // at 4 digits.  The tail is finish_prefill on each member (its own head on its own stream).  Synchronises before returning.
+    // at 4 digits (elapsed_ms of a repeated forward -- prefill, extend, a pack, a wide step -- covers both attempts).  The tail is
+    // finish_prefill on each member (its own head on its own stream).  Synchronises before returning.
     // Refused, with nothing modified: n_members outside 1..64; a null, dead or repeated member; members with different root() or kv_f16();
     // n[i] < 1; p_i + n[i] beyond the fed tokens; p_i + n[i] > max_pos - 1; model globals not set.  Members may sit in BatchDecoder slots.
     static int prefill_packed(Decoder *const *members, const int *n, int n_members, bool with_logits, int digits, float *elapsed_ms);
@@ -268,14 +269,12 @@ class Decoder {
     int score(int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms);
     bool chain_applies(int digits) const;
     bool handover16_applies(int digits) const;
-    bool hybrid_applies(size_t n_rows) const;
+    bool hybrid_applies(size_t n_rows);
     int last_prefill_path() const { return last_prefill_path_; }
     int saturation_fallbacks() const { return saturation_fallbacks_; }
     int fp6_flag(int digits);  // BITNET_HIP_FUSE_FP6_DIGITS for the q|k|v and gate|up launches of the digit-plane prompt forward, or 0
     int ensure_chain_buffers(size_t N);
-    int prefill_chain_layers(size_t N);
     bool qb32_applies(int digits, size_t n_rows);  // the QK256 prompt forward on QB32 rows (no row quantiser launch): long prompts, digits = 2
-    int prefill_qb32_layers(size_t N);
     void set_phase_timing(bool on) { sp_timing_ = on; }
     void phase_times(float out[4]) const {
         for (int i = 0; i < 4; ++i) out[i] = sp_phase_us_[i];
@@ -341,19 +340,41 @@ class Decoder {
         bool q_ok = false;  // all four matrices take QAct inputs (bitnet_hip_gemv_q_supported)
     };
     int attn_launch(Layer &L, int form, float *out, void *qout);
+    // THE PROMPT FORWARD (DESIGN.md "Prompt forward host").  Which form each projection of one forward takes, decided once by prompt_form:
+    // chain = the f16 activation chain, qb = the QB32 chain, h16 = digit planes with the f16 hand-over of the attention output and silu * up,
+    // hybrid = h16 with o / down on the f16 matrix cores; f6 / f6od = BITNET_HIP_FUSE_FP6_DIGITS for q|k|v, gate|up / for o, down.
+    struct PromptForm {
+        bool chain = false, qb = false, h16 = false, hybrid = false;
+        int f6 = 0, f6od = 0, digits = 2;
+        bool f16_rows() const { return chain || qb || h16; }  // f16 rows travel between kernels: the forward owes the saturation check
+    };
+    // The attention operator of one forward, named by its driver: the whole prompt; the continuation over `past` cached positions; a pack of n
+    // members with their first rows, lengths and pasts (the driver's arrays: they must outlive the forward); n rows, each over its own
+    // member's cache, with the bound of the record grid.
+    struct AttnOp {
+        enum Kind { Whole, Continue, Pack, Rows } kind = Whole;
+        size_t past = 0, n = 0, key_bound = 0;
+        Decoder *const *members = nullptr;
+        const int32_t *row0 = nullptr, *len = nullptr, *pasts = nullptr;
+    };
+    int prompt_form(size_t N, int digits, bool sharded, PromptForm *out);  // the decision, and every buffer growth the form needs
+    int project_qkv(size_t l, size_t N, const PromptForm &f);
+    int project_o(Layer &L, size_t N, const PromptForm &f);
+    int project_gateup(Layer &L, size_t N, const PromptForm &f);
+    int project_down(Layer &L, size_t N, const PromptForm &f, const float *next_norm);  // next layer's attention norm, or null: nothing handed over
+    int project_residual(bitnet_hip_weights_t w, size_t N, const PromptForm &f, const float *in32, const void *in16, const float *next_norm);
+    int prompt_attention(Layer &L, size_t N, void *out, bool out_f16, const AttnOp &op);  // one layer's attention of a prompt forward
+    int prompt_layers(size_t N, const PromptForm &f, const AttnOp &op);                   // every layer over the N rows in pf_x_
+    // the saturation rule: form, fill, layers and -- if an f16 hand-over value clamped -- fill and layers again at 4 digits on the digit planes
+    template <class Fill> int forward_with_repeat(size_t N, int digits, const AttnOp &op, const Fill &fill);  // fill: int(), the driver's lambda
+    const char *span_problem(int p, int n, bool positive = true) const;  // "feed() first" / "KV cache overflow" for tokens [p, p + n), or null
+    const char *overflow_problem(int p, int n) const;
+    static int check_members(Decoder *const *members, int n_members, int cap, const std::string &entry, const char *also);
     int prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms);  // the body of prefill (p == 0) and extend
-    int prompt_attention(Layer &L, size_t N, void *out, bool out_f16);                   // one layer's attention of a prompt forward
-    size_t pf_past_ = 0;  // cached positions under the prompt forward in flight (0: fresh sequence)
     int ensure_prompt_buffers(int n, size_t attn_need);             // the per-row buffers and the attention workspace of a prompt forward of n rows
-    int prompt_layers(size_t N, int digits, bool *f16_rows);        // every layer over the N rows in pf_x_ (prompt_forward, packed_forward)
     int packed_forward(Decoder *const *members, const std::vector<int32_t> &past, const std::vector<int32_t> &len, bool with_logits, int digits,
                        float *elapsed_ms);                          // the body of prefill_packed, on the driver
-    // the pack in flight (empty: none): prompt_attention then calls the packed operator with every member's caches of the layer
-    std::vector<Decoder *> pack_members_;
-    std::vector<int32_t> pack_row0_, pack_len_, pack_past_;
-    // the wide step in flight (wide_n_ == 0: none): prompt_attention then calls the rows attention with the layer's cache pointer tables
     int wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms);  // the body of step_wide, on the driver
-    int wide_n_ = 0, wide_key_bound_ = 0;
     // wide buffers (none before the first call): device pointer tables [2 * n_layers + 6][64] -- per layer K then V caches, then position, history,
     // forced count, logits row, and the pick's token / position tables (NULL for a member that samples) --, the attention scratch of wide_cap_
     // sequences (zero-filled), the head's [wide_cap_, vocab] logits, argmax, nll, targets (-1) and workspace
@@ -438,6 +459,8 @@ class Decoder {
     int last_prefill_path_ = 0;  // what the last prefill() ran: 0 digit planes (+ f16 hand-over / hybrid), 1 the f16 chain, 2 the QB32 chain
     int prefill_qb32_ = -1;   // BITNET_HOST_PREFILL_QB32: -1 not read yet; 1 = the QB32 chain where it applies (opt-in), 0 (default) = quantiser launches
     int prefill_fp6_ = -1;    // BITNET_HOST_PREFILL_FP6: -1 not yet decided, 0 int8 digit planes, 1 the fp6 x fp4 form on resident fp4 images (fp6_flag)
+    int prefill_hybrid_ = -1;  // BITNET_HOST_PREFILL_HYBRID: -1 not read yet; 1 (default) o / down on the f16 matrix cores for long shares, 0 never, 2 at any length
+    int prefill_fp6_od_ = -1;  // BITNET_HOST_PREFILL_FP6_OD: -1 not read yet; 1 = o / down of the non-hybrid f16 hand-over on the fp6 form too (experiment), 0 (default)
     int prefill_chain_ = -1;  // BITNET_HOST_PREFILL_CHAIN: -1 automatic (the block-scaled format, whose matmul runs on f16 activations anyway), 0 off, 1 on
     size_t pf_gemm_ws_bytes_ = 0, pf_attn_ws_bytes_ = 0;
     size_t weight_bytes_ = 0;

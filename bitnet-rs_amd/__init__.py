@@ -224,6 +224,10 @@ class HipLib:
         L.bitnet_hip_sampler_create_ex.restype = C.c_int
         L.bitnet_hip_sampler_configure_ex.argtypes = [_vp, C.POINTER(SamplingConfigEx)]
         L.bitnet_hip_sampler_configure_ex.restype = C.c_int
+        L.bitnet_hip_sampler_set_mirostat.argtypes = [_vp, C.POINTER(MirostatConfig)]
+        L.bitnet_hip_sampler_set_mirostat.restype = C.c_int
+        L.bitnet_hip_sampler_mirostat_state.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        L.bitnet_hip_sampler_mirostat_state.restype = C.c_int
         L.bitnet_hip_sampler_reset.argtypes = [_vp]
         L.bitnet_hip_sampler_draws.argtypes = [_vp, C.POINTER(C.c_uint64)]
         L.bitnet_hip_sample_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -836,6 +840,11 @@ class SamplingConfigEx(C.Structure):
                    float(frequency_penalty), float(presence_penalty))
 
 
+class MirostatConfig(C.Structure):
+    """bitnet_hip_mirostat_config"""
+    _fields_ = [("tau", C.c_float), ("eta", C.c_float)]
+
+
 class Sampler:
     """One bitnet_hip_sampler: state (config, ChaCha20 key, word counter, token counts) in device memory."""
 
@@ -871,6 +880,21 @@ class Sampler:
         d = C.c_uint64(0)
         self.lib._check(self.lib.c.bitnet_hip_sampler_draws(self.h, C.byref(d)))
         return int(d.value)
+
+    def set_mirostat(self, tau: float | None, eta: float = 0.1) -> None:
+        """MirostatSampler::new(tau, eta, ..) in place of the truncation stages: mu = 2 * tau, updated on the device by every sampling
+        launch.  set_mirostat(None): off.  Graphs that captured sample_dev follow it."""
+        if tau is None:
+            self.lib._check(self.lib.c.bitnet_hip_sampler_set_mirostat(self.h, None))
+            return
+        cfg = MirostatConfig(float(tau), float(eta))
+        self.lib._check(self.lib.c.bitnet_hip_sampler_set_mirostat(self.h, C.byref(cfg)))
+
+    def mirostat_state(self) -> tuple[float, int]:
+        """(mu as the f32 the device holds, fallback calls since set_mirostat / reset).  Synchronous."""
+        mu, fb = C.c_float(0.0), C.c_uint64(0)
+        self.lib._check(self.lib.c.bitnet_hip_sampler_mirostat_state(self.h, C.byref(mu), C.byref(fb)))
+        return float(mu.value), int(fb.value)
 
     def sample_host(self, logits, generated=()) -> int:
         """Sampler::sample(&logits, &generated_tokens): the whole generated list on every call."""
@@ -1126,6 +1150,10 @@ class HostDecoder:
         L.bitnet_host_set_sampling_ex.argtypes = [C.c_void_p, C.POINTER(SamplingConfigEx)]
         L.bitnet_host_set_sampling_ex.restype = C.c_int
         L.bitnet_host_sampling_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bitnet_host_set_mirostat.argtypes = [C.c_void_p, C.POINTER(MirostatConfig)]
+        L.bitnet_host_set_mirostat.restype = C.c_int
+        L.bitnet_host_mirostat_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        L.bitnet_host_mirostat_state.restype = C.c_int
         L.bitnet_host_set_logprobs.argtypes = [C.c_void_p, C.c_int]
         L.bitnet_host_set_logprobs.restype = C.c_int
         L.bitnet_host_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -1234,6 +1262,21 @@ class HostDecoder:
             return
         cfg = SamplingConfigEx.make(temperature, top_k, top_p, repetition_penalty, seed, min_p, typical_p, frequency_penalty, presence_penalty)
         self._check(self.c.bitnet_host_set_sampling_ex(self.h, C.byref(cfg)))
+
+    def set_mirostat(self, tau: float | None, eta: float = 0.1) -> None:
+        """Mirostat v2 (MirostatSampler::new(tau, eta, ..)) behind every with-logits step, mu on the device and inside the captured graphs.
+        Needs set_sampling first, with the truncation stages off; set_mirostat(None): off.  Drops no graphs."""
+        if tau is None:
+            self._check(self.c.bitnet_host_set_mirostat(self.h, None))
+            return
+        cfg = MirostatConfig(float(tau), float(eta))
+        self._check(self.c.bitnet_host_set_mirostat(self.h, C.byref(cfg)))
+
+    def mirostat_state(self) -> tuple[float, int]:
+        """(mu, fallback calls since set_mirostat / reset) of the decoder's sampler; (0.0, 0) without one.  Synchronises."""
+        mu, fb = C.c_float(0.0), C.c_uint64(0)
+        self._check(self.c.bitnet_host_mirostat_state(self.h, C.byref(mu), C.byref(fb)))
+        return float(mu.value), int(fb.value)
 
     def sampling_draws(self) -> int:
         """ChaCha20 words the decoder's sampler has consumed since its last reset / set_sampling (one per non-greedy token)."""

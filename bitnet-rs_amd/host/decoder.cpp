@@ -398,6 +398,26 @@ int Decoder::set_sampling_ex(const bitnet_hip_sampling_config_ex *cfg) {
     return 0;
 }
 
+int Decoder::set_mirostat(const bitnet_hip_mirostat_config *cfg) {
+    if (!cfg) {  // off; a decoder that never sampled has nothing to switch off
+        if (sampler_) BCHK(bitnet_hip_sampler_set_mirostat(sampler_, nullptr));
+        return 0;
+    }
+    if (!sampling_ || !sampler_) return fail_arg("set_mirostat: sampling is off (set_sampling first)");
+    // the mode is read from device memory by the sampling launch: the captured graphs follow it and stay
+    BCHK(bitnet_hip_sampler_set_mirostat(sampler_, cfg));
+    return 0;
+}
+
+int Decoder::mirostat_state(float *mu, uint64_t *fallbacks) {
+    if (mu) *mu = 0.0f;
+    if (fallbacks) *fallbacks = 0;
+    if (!sampler_) return 0;
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    BCHK(bitnet_hip_sampler_mirostat_state(sampler_, mu, fallbacks));
+    return 0;
+}
+
 int Decoder::sampling_draws(uint64_t *out) {
     if (!out) {
         err_ = "sampling_draws: null pointer";
@@ -2084,6 +2104,8 @@ int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *fin
 int bitnet_host_reset(void *d) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->reset(); }
 int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_sampling(cfg); }
 int bitnet_host_set_sampling_ex(void *d, const bitnet_hip_sampling_config_ex *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_sampling_ex(cfg); }
+int bitnet_host_set_mirostat(void *d, const bitnet_hip_mirostat_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_mirostat(cfg); }
+int bitnet_host_mirostat_state(void *d, float *mu, uint64_t *fallbacks) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->mirostat_state(mu, fallbacks); }
 int bitnet_host_sampling_draws(void *d, uint64_t *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->sampling_draws(out); }
 int bitnet_host_set_logprobs(void *d, int top_n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_logprobs(top_n); }
 int bitnet_host_logprobs(void *d, int first, int n, void *records_out) {

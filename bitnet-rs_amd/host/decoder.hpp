@@ -120,6 +120,11 @@ class Decoder {
     int set_sampling(const bitnet_hip_sampling_config *cfg);
     // the same with min-p, typical-p and the additive penalties (bitnet_hip_sampling_config_ex); set_sampling is this with neutral values
     int set_sampling_ex(const bitnet_hip_sampling_config_ex *cfg);
+    // Mirostat v2 on this decoder's sampler (bitnet_hip_sampler_set_mirostat): needs sampling on; NULL = off.  Drops no graphs: the launch reads
+    // the mode from device memory.  reset() restores mu = 2 * tau, rewind() and shift() leave it as they leave the counts, fork() resets each
+    // destination's with its sampler.
+    int set_mirostat(const bitnet_hip_mirostat_config *cfg);
+    int mirostat_state(float *mu, uint64_t *fallbacks);  // synchronises; 0 / 0 without a sampler
     int sampling_draws(uint64_t *out);
     // The reference's logits tap on the generation path (GenerationConfig::{logits_tap_steps, logits_topk, logits_cb}, crates/bitnet-inference/src/
     // config.rs:87-93, engine.rs:1182-1210; the CLI's LogitStep records, crates/bitnet-cli/src/main.rs:1337-1373) on the device: top_n = -1 (default)
@@ -498,6 +503,8 @@ int bitnet_host_set_globals(void *d, const uint16_t *embed_f16, const float *fin
 int bitnet_host_reset(void *d);
 int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg);  // NULL = greedy
 int bitnet_host_set_sampling_ex(void *d, const bitnet_hip_sampling_config_ex *cfg);  // NULL = greedy
+int bitnet_host_set_mirostat(void *d, const bitnet_hip_mirostat_config *cfg);  // NULL = off
+int bitnet_host_mirostat_state(void *d, float *mu, uint64_t *fallbacks);
 int bitnet_host_sampling_draws(void *d, uint64_t *out);
 int bitnet_host_set_logprobs(void *d, int top_n);                             // Decoder::set_logprobs: -1 off, 0..20 on
 int bitnet_host_logprobs(void *d, int first, int n, void *records_out);       // Decoder::logprobs: n bitnet_hip_logprob_record

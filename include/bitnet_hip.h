@@ -833,10 +833,34 @@ typedef struct bitnet_hip_sampling_config_ex {
 } bitnet_hip_sampling_config_ex;
 int bitnet_hip_sampler_create_ex(size_t vocab, const bitnet_hip_sampling_config_ex *cfg, bitnet_hip_sampler **out);
 int bitnet_hip_sampler_configure_ex(bitnet_hip_sampler *sampler, const bitnet_hip_sampling_config_ex *cfg);
+/* Mirostat v2 (crates/bitnet-sampling/src/strategies.rs MirostatSampler :109-196, `sample` :131-190): a mode of the sampler that takes
+ * the place of the truncation stages.  Order: counts; additive penalties; repetition penalty; NaN -> -inf; temperature (division);
+ * MIROSTAT.  There is no greedy shortcut: temperature 1 / top_k 0 / top_p 1 runs Mirostat.  On that row, with state mu (2 * tau at first):
+ *   p = softmax_in_place(x) (crates/bitnet-logits/src/lib.rs:180-213; a row with no finite maximum is uniform over all n ids); an entry with
+ *   p_i > 0 and -ln p_i > mu is removed; if nothing is left the FALLBACK runs: no random word, the token is the argmax of the row, the
+ *   HIGHEST index on ties (the reference's max_by keeps the last), surprise = -ln p_token of the unfiltered p; otherwise q = the rest
+ *   renormalised, u = the next word of the sampler's ChaCha20 stream as (w >> 8) * 2^-24 (the reference's type is ChaCha8Rng; the library keeps
+ *   its one stream, as the chain stages did), the token is the first id, ascending, with u <= the running sum (vocab - 1 if none), and
+ *   surprise = -ln q_token, or tau if q_token is 0.  Then mu -= eta * (surprise - tau), two f32 operations, in device memory.
+ * One launch, as every other path: the slice pass of the full-vocabulary path, then three passes of the finishing workgroup.  The filter is
+ * g_i > mu - ln S with g_i = max - x_i, no logarithm per entry; sums are fixed-point, so repeated launches and bitnet_hip_sample_batch_dev
+ * give the same bits.  Equal to the reference except where a comparison lies within the roundings listed in csrc/kernels_sample.hip.
+ * A forced position moves nothing, mu included.  bitnet_hip_sample_host runs the same path on its own counts and shares mu and the stream.
+ * set_mirostat: cfg == NULL: off.  Else on: tau, eta stored, mu = 2 * tau (MirostatSampler::new :120-126), fallback count 0.  Synchronous and
+ *   not capture-safe; graphs captured before it stay valid and follow it (the mode is read from device memory, like the config).
+ *   Invalid, with nothing changed: tau NaN, infinite or <= 0; eta NaN, infinite or negative (both refused before the sampler is looked at);
+ *   a sampler whose current config has top_k != 0, top_p < 1, min_p > 0, typical_p < 1 or temperature == 0.  While Mirostat is on,
+ *   bitnet_hip_sampler_configure[_ex] refuses exactly those configs in the same way; a config it takes leaves mu alone.
+ * mirostat_state: mu and the number of fallback calls since set_mirostat / reset (either pointer may be NULL).  Synchronous. */
+typedef struct bitnet_hip_mirostat_config { float tau; float eta; } bitnet_hip_mirostat_config;
+int bitnet_hip_sampler_set_mirostat(bitnet_hip_sampler *sampler, const bitnet_hip_mirostat_config *cfg);
+int bitnet_hip_sampler_mirostat_state(bitnet_hip_sampler *sampler, float *mu, uint64_t *fallbacks);
 /* Clears the counts (a new generation) and the word counter, and re-arms the launch hand-over (a launch cut short leaves it
- * unbalanced).  Synchronous; call it with no sample_dev / sample_host in flight.  Not capture-safe. */
+ * unbalanced).  With Mirostat on: mu = 2 * tau (MirostatSampler::reset, strategies.rs:192-195) and the fallback count 0.
+ * Synchronous; call it with no sample_dev / sample_host in flight.  Not capture-safe. */
 int bitnet_hip_sampler_reset(bitnet_hip_sampler *sampler);
-/* ChaCha20 words consumed since create / configure / reset (one per non-greedy call).  Synchronous; not capture-safe. */
+/* ChaCha20 words consumed since create / configure / reset (one per non-greedy call; none for a call that took Mirostat's fallback).
+ * Synchronous; not capture-safe. */
 int bitnet_hip_sampler_draws(bitnet_hip_sampler *sampler, uint64_t *draws);
 /* One sampling step on the device, capture-safe (one kernel, no host work).  "Generated" = the tokens this sampler
  * chose since the last reset: the exponent of token t at call c is sum_{i<c, g_i = t} (c - i), the reference's count when

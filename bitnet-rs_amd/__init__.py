@@ -247,6 +247,18 @@ class HipLib:
         L.bitnet_hip_logprob_dev.restype = C.c_int
         L.bitnet_hip_logprob_batch_dev.argtypes = [_vp, _sz, _sz, _vp]
         L.bitnet_hip_logprob_batch_dev.restype = C.c_int
+        # the stop criteria (bitnet_hip_stop_*): bound here with the rest, never lazily
+        _i32p = C.POINTER(C.c_int32)
+        for name, args in (("create", [C.POINTER(StopConfig), C.POINTER(_vp)]), ("configure", [_vp, C.POINTER(StopConfig)]), ("arm", [_vp, C.c_int]),
+                           ("get_state", [_vp, C.POINTER(StopState)]), ("dev", [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+                           ("batch_create", [_sz, C.POINTER(_vp)]), ("batch_set", [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp]), ("batch_dev", [_vp, _vp]),
+                           ("batch_live", [_vp, _i32p])):
+            f = getattr(L, "bitnet_hip_stop_" + name)
+            f.argtypes, f.restype = args, C.c_int
+        L.bitnet_hip_stop_destroy.argtypes = [_vp]
+        L.bitnet_hip_stop_destroy.restype = None
+        L.bitnet_hip_stop_batch_destroy.argtypes = [_vp]
+        L.bitnet_hip_stop_batch_destroy.restype = None
         L.bitnet_hip_score_workspace_bytes.argtypes = [_sz, _sz, _sz]
         L.bitnet_hip_score_workspace_bytes.restype = _sz
         L.bitnet_hip_score_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
@@ -950,6 +962,129 @@ class SampleBatch:
         self.lib._check(self.lib.c.bitnet_hip_sample_batch_dev(self.h, _vp(stream)))
 
 
+STOP_MAX_IDS, STOP_MAX_SEQS, STOP_MAX_SEQ_LEN, STOP_BATCH_MAX = 32, 16, 32, 64
+STOP_NONE, STOP_TOKEN, STOP_EOS, STOP_MAX_TOKENS, STOP_SEQUENCE = 0, 1, 2, 3, 4
+STOP_REASONS = ("none", "stop_token", "eos", "max_tokens", "sequence")
+
+
+class StopConfig(C.Structure):
+    """bitnet_hip_stop_config.  make() keeps the arrays the pointers refer to alive on the object."""
+    _fields_ = [("stop_ids", C.POINTER(C.c_int32)), ("n_stop_ids", _sz), ("eos_id", C.c_int32), ("max_tokens", C.c_int32),
+                ("seq_tokens", C.POINTER(C.c_int32)), ("seq_len", C.POINTER(C.c_int32)), ("n_seqs", _sz)]
+
+    @classmethod
+    def make(cls, stop_ids=(), eos=None, max_tokens: int = 0, sequences=()) -> "StopConfig":
+        """stop_ids: token ids; eos: an id or None; max_tokens: 0 = no budget; sequences: token-id sequences (stop strings as their own
+        tokenisation -- a string the model spells across a token boundary differently from it needs the host's check on the decoded text)."""
+        ids = _np(np.asarray(list(stop_ids), dtype=np.int64).astype(np.int32), np.int32)
+        seqs = [list(map(int, s)) for s in sequences]
+        lens = _np(np.asarray([len(s) for s in seqs], dtype=np.int32), np.int32)
+        toks = _np(np.asarray([t for s in seqs for t in s], dtype=np.int64).astype(np.int32), np.int32)
+        p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
+        cfg = cls(p(ids), ids.size, -1 if eos is None else int(eos), int(max_tokens), p(toks), p(lens), len(seqs))
+        cfg._keep = (ids, lens, toks)
+        return cfg
+
+
+class StopState(C.Structure):
+    """bitnet_hip_stop_state (24 bytes)"""
+    _fields_ = [(n, C.c_int32) for n in ("reason", "index", "token", "position", "generated", "frozen_steps")]
+
+    @property
+    def stopped(self) -> bool:
+        return self.reason != STOP_NONE
+
+    @property
+    def reason_name(self) -> str:
+        return STOP_REASONS[self.reason] if 0 <= self.reason < len(STOP_REASONS) else f"reason {self.reason}"
+
+    def astuple(self) -> tuple:
+        return tuple(int(getattr(self, n)) for n, _ in self._fields_)
+
+    def __repr__(self) -> str:
+        return "StopState(%s)" % ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_)
+
+
+class Stop:
+    """One bitnet_hip_stop: the criteria and the state of one sequence in device memory; launch() is the one launch behind the pick."""
+
+    def __init__(self, lib: HipLib, cfg: "StopConfig | None" = None, **kw):
+        self.lib = lib
+        h = _vp()
+        cfg = StopConfig.make(**kw) if cfg is None else cfg
+        lib._check(lib.c.bitnet_hip_stop_create(C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.c.bitnet_hip_stop_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def configure(self, cfg: "StopConfig | None" = None, **kw) -> None:
+        cfg = StopConfig.make(**kw) if cfg is None else cfg
+        self.lib._check(self.lib.c.bitnet_hip_stop_configure(self.h, C.byref(cfg)))
+
+    def arm(self, keep_generated: bool = False) -> None:
+        self.lib._check(self.lib.c.bitnet_hip_stop_arm(self.h, int(keep_generated)))
+
+    def state(self) -> StopState:
+        st = StopState()
+        self.lib._check(self.lib.c.bitnet_hip_stop_get_state(self.h, C.byref(st)))
+        return st
+
+    def launch(self, pos, history, capacity: int, n_forced, token=None, stream: int = 0) -> None:
+        """One launch on device tensors (int32): asynchronous, capture-safe."""
+        self.lib._check(self.lib.c.bitnet_hip_stop_dev(self.h, _optr(pos), _optr(history), capacity, _optr(n_forced), _optr(token), _vp(stream)))
+
+
+class StopBatch:
+    """One bitnet_hip_stop_batch: up to 64 slots, each binding a Stop and the device tensors launch() would take; launch() serves every
+    bound slot in ONE kernel launch, per slot bit for bit what Stop.launch alone leaves.  Keeps the bound objects and tensors alive."""
+
+    def __init__(self, lib: HipLib, n_slots: int):
+        self.lib, self.n_slots = lib, int(n_slots)
+        h = _vp()
+        lib._check(lib.c.bitnet_hip_stop_batch_create(n_slots, C.byref(h)))
+        self.h = h
+        self._keep = {}
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.c.bitnet_hip_stop_batch_destroy(self.h)
+            self.h = None
+            self._keep = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def set(self, slot: int, stop: "Stop | None", pos=None, history=None, capacity: int = 0, n_forced=None, token=None) -> None:
+        """Bind `stop` and its device tensors to `slot`, or empty the slot (stop None).  Synchronous; no launch may be in flight."""
+        if stop is None:
+            self.lib._check(self.lib.c.bitnet_hip_stop_batch_set(self.h, slot, None, None, None, 0, None, None))
+            self._keep.pop(slot, None)
+            return
+        self.lib._check(self.lib.c.bitnet_hip_stop_batch_set(self.h, slot, stop.h, _optr(pos), _optr(history), capacity, _optr(n_forced), _optr(token)))
+        self._keep[slot] = (stop, pos, history, n_forced, token)
+
+    def launch(self, stream: int = 0) -> None:
+        self.lib._check(self.lib.c.bitnet_hip_stop_batch_dev(self.h, _vp(stream)))
+
+    def live(self) -> int:
+        """Bound slots that have not stopped yet.  Synchronous."""
+        n = C.c_int32(0)
+        self.lib._check(self.lib.c.bitnet_hip_stop_batch_live(self.h, C.byref(n)))
+        return int(n.value)
+
+
 _lib = None
 
 
@@ -1173,6 +1308,16 @@ class HostDecoder:
         L.bitnet_host_step_wide.restype = C.c_int
         L.bitnet_host_cached_prefix.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
         L.bitnet_host_cached_prefix.restype = C.c_int
+        L.bitnet_host_set_stop.argtypes = [C.c_void_p, C.POINTER(StopConfig)]
+        L.bitnet_host_set_stop.restype = C.c_int
+        L.bitnet_host_stop_state.argtypes = [C.c_void_p, C.POINTER(StopState)]
+        L.bitnet_host_stop_state.restype = C.c_int
+        L.bitnet_host_resume.argtypes = [C.c_void_p]
+        L.bitnet_host_resume.restype = C.c_int
+        L.bitnet_host_run_until_stop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.bitnet_host_run_until_stop.restype = C.c_int
+        L.bitnet_host_graph_nodes.argtypes = [C.c_void_p, C.c_int]
+        L.bitnet_host_graph_nodes.restype = C.c_int
         self.cfg = cfg
         self._top_n = -1  # set_logprobs
         self._fed = 0  # tokens fed since the last reset (the default n of score)
@@ -1305,6 +1450,48 @@ class HostDecoder:
         with np.errstate(invalid="ignore"):
             lp = (r["logit"] - r["lse"]).astype(np.float32)
         return Logprobs(r["token"].copy(), r["logit"].copy(), r["lse"].copy(), lp, r["top_id"][:, :top].copy(), r["top_logit"][:, :top].copy())
+
+    def set_stop(self, stop_ids=(), eos=None, max_tokens: int = 0, sequences=(), *, off: bool = False) -> None:
+        """Stop criteria on the device, behind every with-logits step and inside the captured graphs (the reference's StopCriteria /
+        check_stop): stop token ids, an EOS id, a token budget (0 = none; the token that reaches it counts and is the stop token) and stop
+        sequences of TOKEN IDS.  The first that holds, in that order, stops the sequence; from then on every step already queued leaves it
+        frozen -- position, history, cache slots below the stop position, sampler counts, ChaCha20 counter and Mirostat's mu are those of
+        a run that ended on the stop token -- and stop_state() says why and where.  Arms for a new request, as feed() and reset() do.
+        Stop STRINGS stay with whoever owns the tokenizer: pass each string as its own tokenisation; a string the model spells across a
+        token boundary differently from that tokenisation is not seen here and needs the host's check on the decoded text.
+        set_stop(off=True): no criteria, the launch sequence of a decoder that never called this.  An all-default call is the empty config:
+        it counts tokens and never stops.  Switching on or off drops the captured graphs; a new config on top of an old one does not."""
+        if off:
+            self._check(self.c.bitnet_host_set_stop(self.h, None))
+            return
+        cfg = StopConfig.make(stop_ids, eos, max_tokens, sequences)
+        self._check(self.c.bitnet_host_set_stop(self.h, C.byref(cfg)))
+
+    def stop_state(self) -> "StopState":
+        """(reason, index, token, position, generated, frozen_steps) of the decoder's criteria.  Synchronises."""
+        st = StopState()
+        self._check(self.c.bitnet_host_stop_state(self.h, C.byref(st)))
+        return st
+
+    def resume(self) -> None:
+        """Go on after a stop: the criteria are armed again with the token count kept, the next run() consumes the stop token and generates
+        behind it -- the tokens an uninterrupted run would have produced."""
+        self._check(self.c.bitnet_host_resume(self.h))
+
+    def generate(self, max_steps: int, chunk: int = 16) -> tuple[int, float]:
+        """run(chunk) until the criteria stop the sequence or max_steps steps are queued, with ONE 24-byte state read per chunk instead of a
+        token read per step; returns (steps up to and including the stopping one -- max_steps if nothing stopped --, milliseconds).  Up to
+        chunk - 1 queued steps run frozen behind the stop (stop_state().frozen_steps)."""
+        steps, ms = C.c_int(0), C.c_float(0)
+        self._check(self.c.bitnet_host_run_until_stop(self.h, int(max_steps), int(chunk), C.byref(steps), C.byref(ms)))
+        return int(steps.value), float(ms.value)
+
+    def graph_nodes(self, with_logits: bool = True) -> int:
+        """Kernel nodes of the step graph run() would launch at the current position (captured if need be)."""
+        n = int(self.c.bitnet_host_graph_nodes(self.h, int(with_logits)))
+        if n < 0:
+            raise BitNetHipError(n, self.error() or f"bitnet_host_graph_nodes rc={n}")
+        return n
 
     def feed(self, tokens) -> None:
         t = _np(tokens, np.int32)
@@ -1557,6 +1744,10 @@ class HostBatch:
         L.bitnet_host_batch_captures.argtypes = [C.c_void_p]
         L.bitnet_host_batch_graph_nodes.restype = C.c_int
         L.bitnet_host_batch_graph_nodes.argtypes = [C.c_void_p]
+        L.bitnet_host_batch_live.restype = C.c_int
+        L.bitnet_host_batch_live.argtypes = [C.c_void_p]
+        L.bitnet_host_batch_step_until.restype = C.c_int
+        L.bitnet_host_batch_step_until.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
         self.n_slots = n_slots
         self.h = L.bitnet_host_batch_create(n_slots)
         if not self.h:
@@ -1587,6 +1778,20 @@ class HostBatch:
         ms = C.c_float(0.0)
         self._check(self.c.bitnet_host_batch_step(self.h, n, int(use_graph), C.byref(ms)))
         return float(ms.value)
+
+    def live(self) -> int:
+        """Members with stop criteria (HostDecoder.set_stop) that have not stopped yet.  Synchronises."""
+        n = int(self.c.bitnet_host_batch_live(self.h))
+        if n < 0:
+            raise BitNetHipError(n, self.error() or f"bitnet_host_batch_live rc={n}")
+        return n
+
+    def step_until(self, max_steps: int, chunk: int = 16) -> tuple[int, float]:
+        """step(chunk) until no member with stop criteria is live or max_steps steps are queued; one 4-byte read per chunk.  A stopped member
+        stays frozen in its slot.  Returns (steps queued, milliseconds)."""
+        steps, ms = C.c_int(0), C.c_float(0.0)
+        self._check(self.c.bitnet_host_batch_step_until(self.h, int(max_steps), int(chunk), C.byref(steps), C.byref(ms)))
+        return int(steps.value), float(ms.value)
 
     def captures(self) -> int:
         """Graph captures so far: one for a batch's life, two if its first sampling member arrived after an all-greedy capture."""

@@ -74,6 +74,7 @@ BatchDecoder::~BatchDecoder() {
     if (stream_) hipStreamSynchronize((hipStream_t)stream_);
     drop_graph();
     if (sample_tab_) bitnet_hip_sample_batch_destroy(sample_tab_);  // before the members (and their samplers) are released
+    if (stop_tab_) bitnet_hip_stop_batch_destroy(stop_tab_);        // likewise: it takes its live pointer back from every bound object
     for (void *p : {(void *)tables_, (void *)x_, (void *)x2_, (void *)qkv_, (void *)attn_scratch_, qa_x_, qa_x2_, qa_att_, qa_h_, scratch_, (void *)st_x_,
                     (void *)st_x2_, (void *)lp_table_})
         if (p) hipFree(p);
@@ -108,6 +109,7 @@ int BatchDecoder::ensure_buffers() {
     }
     host_tables_.assign(rows * n, nullptr);
     BCHK(bitnet_hip_sample_batch_create((size_t)c.vocab, n, &sample_tab_));
+    BCHK(bitnet_hip_stop_batch_create(n, &stop_tab_));
     // One pass of the chain with every slot idle (all-NULL tables: the gather, the attention and the head touch nothing, the GEMVs run on the
     // zero-filled vectors): every kernel is loaded and its dynamic-LDS limit raised BEFORE the first capture, which must see launches only.
     if (int rc = launches(true)) return rc;
@@ -169,6 +171,10 @@ int BatchDecoder::set_slot(int b, Decoder *d) {
     }
     if (slot_[b]) {
         if (int rc = bind_sampler(b, nullptr)) return rc;  // its sampler leaves the table before the member can be destroyed
+        if (stop_bound_[b]) {
+            BCHK(bitnet_hip_stop_batch_set(stop_tab_, (size_t)b, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
+            stop_bound_[b] = nullptr;
+        }
         slot_[b]->batch_ = nullptr;
         bitnet_host_release(slot_[b]);
         slot_[b] = nullptr;
@@ -195,6 +201,65 @@ int BatchDecoder::bind_sampler(int b, Decoder *d) {
     BCHK(bitnet_hip_sample_batch_set(sample_tab_, (size_t)b, (bitnet_hip_sampler *)bo[2], (const float *)bo[1], nullptr, (int32_t *)g[5], (int32_t *)g[4],
                                      (const int32_t *)bo[0]));
     bound_[b] = bo[2];
+    return 0;
+}
+
+// The stop table follows its members: slot b binds member b's stop object while the member has criteria on.  First every entry whose object
+// goes (an object sits in one slot at a time), then the new ones.  Synchronous copies, between steps.
+int BatchDecoder::bind_stops() {
+    if (!stop_tab_) return 0;
+    bitnet_hip_stop *want[BITNET_HIP_BATCH_MAX] = {};
+    for (int b = 0; b < n_; ++b) want[b] = slot_[b] ? slot_[b]->stop_object() : nullptr;
+    for (int b = 0; b < n_; ++b)
+        if (stop_bound_[b] && stop_bound_[b] != want[b]) {
+            BCHK(bitnet_hip_stop_batch_set(stop_tab_, (size_t)b, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
+            stop_bound_[b] = nullptr;
+        }
+    for (int b = 0; b < n_; ++b) {
+        stop_in_chain_ |= want[b] != nullptr;
+        if (!want[b] || stop_bound_[b] == want[b]) continue;
+        void *g[7], *bo[3];
+        slot_[b]->global_objects(g);
+        slot_[b]->batch_objects(bo);
+        BCHK(bitnet_hip_stop_batch_set(stop_tab_, (size_t)b, want[b], (int32_t *)g[5], (const int32_t *)g[4], (size_t)slot_[b]->config().max_pos,
+                                       (int32_t *)bo[0], nullptr));
+        stop_bound_[b] = want[b];
+    }
+    return 0;
+}
+
+int BatchDecoder::live(int *out) {
+    if (dead_ || !out) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    *out = 0;
+    if (!stop_tab_) return 0;
+    if (int rc = bind_stops()) return rc;
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    int32_t n = 0;
+    BCHK(bitnet_hip_stop_batch_live(stop_tab_, &n));
+    *out = n;
+    return 0;
+}
+
+int BatchDecoder::step_until(int max_steps, int chunk, int *steps, float *elapsed_ms) {
+    if (steps) *steps = 0;
+    if (elapsed_ms) *elapsed_ms = 0.f;
+    if (dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    if (max_steps < 0 || chunk < 1) return fail_arg("batch: step_until takes max_steps >= 0 and chunk >= 1");
+    bool any = false;
+    for (int b = 0; b < n_; ++b) any |= slot_[b] && slot_[b]->stop_object();
+    if (!any) return fail_arg("batch: step_until needs a member with stop criteria (set_stop)");
+    int queued = 0, alive = 0;
+    float total = 0.f;
+    if (int rc = live(&alive)) return rc;
+    while (alive > 0 && queued < max_steps) {
+        const int c = chunk < max_steps - queued ? chunk : max_steps - queued;
+        float ms = 0.f;
+        if (int rc = step(c, true, &ms)) return rc;
+        queued += c, total += ms;
+        if (int rc = live(&alive)) return rc;
+    }
+    if (steps) *steps = queued;
+    if (elapsed_ms) *elapsed_ms = total;
     return 0;
 }
 
@@ -276,6 +341,8 @@ int BatchDecoder::launches(bool warm) {
     if (warm || sample_in_chain_) BCHK(bitnet_hip_sample_batch_dev(sample_tab_, s));
     // the logits tap of every member that has it on, after the pick; in the chain from the first step at which any member has, and in the warm pass
     if (warm || lp_in_chain_) BCHK(bitnet_hip_logprob_batch_dev(lp_table_, n, (size_t)c.vocab, s));
+    // the stop criteria of every member that has them, last; in the chain from the first step at which any member has, and in the warm pass
+    if (warm || stop_in_chain_) BCHK(bitnet_hip_stop_batch_dev(stop_tab_, s));
     return 0;
 }
 
@@ -309,10 +376,12 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
         }
         for (int b = 0; b < n_; ++b) lp_in_chain_ |= lp[b].records_dev != nullptr;
     }
+    if (int rc = bind_stops()) return rc;
     hipStream_t s = (hipStream_t)stream_;
     if (use_graph) {
-        // the first sampling member ever adds the sampling launch to the chain, the first with logprobs on the logprob launch
-        if (graph_exec_ && (sample_in_chain_ != graph_sig_ || lp_in_chain_ != graph_lp_sig_)) drop_graph();
+        // the first sampling member ever adds the sampling launch to the chain, the first with logprobs on the logprob launch, the first with
+        // stop criteria the stop launch
+        if (graph_exec_ && (sample_in_chain_ != graph_sig_ || lp_in_chain_ != graph_lp_sig_ || stop_in_chain_ != graph_stop_sig_)) drop_graph();
         if (!graph_exec_) {
             hipGraph_t gr = nullptr;
             HCHK(hipStreamBeginCapture(s, hipStreamCaptureModeGlobal));
@@ -329,6 +398,7 @@ int BatchDecoder::step(int n, bool use_graph, float *elapsed_ms) {
             graph_exec_ = ex;
             graph_sig_ = sample_in_chain_;
             graph_lp_sig_ = lp_in_chain_;
+            graph_stop_sig_ = stop_in_chain_;
             ++captures_;
         }
     }
@@ -379,6 +449,15 @@ int bitnet_host_batch_set_slot(void *b, int slot, void *decoder) {
 }
 int bitnet_host_batch_step(void *b, int n, int use_graph, float *elapsed_ms) {
     return b ? static_cast<BatchDecoder *>(b)->step(n, use_graph != 0, elapsed_ms) : BITNET_HIP_ERR_INVALID_ARGUMENT;
+}
+int bitnet_host_batch_live(void *b) {
+    int n = 0;
+    if (!b) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    const int rc = static_cast<BatchDecoder *>(b)->live(&n);
+    return rc ? (rc < 0 ? rc : -rc) : n;
+}
+int bitnet_host_batch_step_until(void *b, int max_steps, int chunk, int *steps, float *elapsed_ms) {
+    return b ? static_cast<BatchDecoder *>(b)->step_until(max_steps, chunk, steps, elapsed_ms) : BITNET_HIP_ERR_INVALID_ARGUMENT;
 }
 int bitnet_host_batch_captures(void *b) { return b ? static_cast<BatchDecoder *>(b)->captures() : 0; }
 int bitnet_host_batch_graph_nodes(void *b) { return b ? static_cast<BatchDecoder *>(b)->graph_nodes() : 0; }

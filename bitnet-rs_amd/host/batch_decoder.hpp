@@ -49,6 +49,15 @@ class BatchDecoder {
     // n with-logits steps for every occupied slot.  Refuses with "KV cache overflow" if any member would pass max_pos - 1 (positions are read
     // once, before the first launch).  Synchronises before returning.
     int step(int n, bool use_graph, float *elapsed_ms);
+    // Members with stop criteria (Decoder::set_stop): the batch owns a stop table (bitnet_hip_stop_batch_*), binds each such member's object to
+    // its slot, and the chain gains ONE bitnet_hip_stop_batch_dev launch behind the sampling and logprob launches -- from the first step at which
+    // a member has criteria on, as the sampling launch joins the chain.  A stopped member stays frozen in its slot and keeps costing its row
+    // until the scheduler takes it out.
+    // live(): members with criteria that have not stopped yet (synchronises; 0 when no member has criteria).
+    int live(int *out);
+    // step(chunk) until no member with criteria is live or max_steps steps are queued (the last chunk clipped); one 4-byte read per chunk.
+    // *steps: the steps queued.  Refuses a batch in which no member has criteria.  Members without criteria simply run every queued step.
+    int step_until(int max_steps, int chunk, int *steps, float *elapsed_ms);
     int captures() const { return captures_; }  // graph captures so far
     int graph_nodes() const;                    // kernel nodes of the captured chain, 0 if none is held
 
@@ -58,6 +67,7 @@ class BatchDecoder {
     int ensure_buffers();
     int upload_tables();
     int bind_sampler(int b, Decoder *d);
+    int bind_stops();  // the stop table follows its members' criteria
     int launches(bool warm = false);  // warm: the pass over all-idle tables that ensure_buffers runs once
     int clear_vectors(int b);
     void drop_graph();
@@ -88,6 +98,10 @@ class BatchDecoder {
     bitnet_hip_logprob_args lp_host_[BITNET_HIP_BATCH_MAX] = {};  // what it holds
     bool lp_in_chain_ = false;      // some member has had logprobs on: the logprob launch is part of every step from then on
     bool graph_lp_sig_ = false;     // ... and whether the captured chain has it
+    bitnet_hip_stop_batch *stop_tab_ = nullptr;          // n_ entries, one launch (bitnet_hip_stop_batch_dev)
+    bitnet_hip_stop *stop_bound_[BITNET_HIP_BATCH_MAX] = {};  // the object each of its entries holds
+    bool stop_in_chain_ = false;    // some member has had criteria: the stop launch is part of every step from then on
+    bool graph_stop_sig_ = false;   // ... and whether the captured chain has it
     int captures_ = 0;
 };
 
@@ -99,6 +113,8 @@ void bitnet_host_batch_destroy(void *b);
 const char *bitnet_host_batch_error(void *b);
 int bitnet_host_batch_set_slot(void *b, int slot, void *decoder);  // decoder NULL clears the slot
 int bitnet_host_batch_step(void *b, int n, int use_graph, float *elapsed_ms);
+int bitnet_host_batch_live(void *b);         // BatchDecoder::live, or a negative error code
+int bitnet_host_batch_step_until(void *b, int max_steps, int chunk, int *steps, float *elapsed_ms);  // BatchDecoder::step_until
 int bitnet_host_batch_captures(void *b);     // graph captures so far
 int bitnet_host_batch_graph_nodes(void *b);  // kernel nodes of the captured chain, 0 if none
 }

@@ -212,6 +212,7 @@ void Decoder::batch_objects(void *ptrs[3]) {
 Decoder::~Decoder() {
     drop_graphs();
     if (sampler_) bitnet_hip_sampler_destroy(sampler_);
+    if (stop_) bitnet_hip_stop_destroy(stop_);
     for (void *p : {(void *)lp_records_, lp_scratch_})
         if (p) hipFree(p);
     if (owner_) {  // borrowed objects stay the owner's
@@ -319,9 +320,7 @@ int Decoder::pick_token(void *stream, bool record, bool need_logits) {
         // the full head's token from the int8 screen + the surviving rows of the f16 table; logits_ stays as it is (refresh_logits)
         BCHK(bitnet_hip_logits_screen_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, screen_, screen_ws_, scratch_, (size_t)screen_wgs_, token_, pos_,
                                           history_, n_forced_, s));
-        return 0;
-    }
-    if (!sampling_) {
+    } else if (!sampling_) {
         // greedy token (T:1589, T:1599-1630, sampling.rs:189-202)
         BCHK(bitnet_hip_logits_f16_dev(embed_, x_, final_norm_, c_.eps, H, (size_t)c_.vocab, logits_, scratch_, (size_t)logits_wgs_, token_, pos_,
                                        history_, n_forced_, s));
@@ -336,7 +335,95 @@ int Decoder::pick_token(void *stream, bool record, bool need_logits) {
         logprob_entry(&a);
         BCHK(bitnet_hip_logprob_dev(&a, (size_t)c_.vocab, s));
     }
+    // the stop criteria, last: does the token just placed end the sequence -- and if it ended earlier, hold the sequence where it stopped
+    if (stop_on_) BCHK(bitnet_hip_stop_dev(stop_, pos_, history_, (size_t)c_.max_pos, n_forced_, token_, s));
     return 0;
+}
+
+int Decoder::arm_stop(bool keep_generated) {
+    if (!stop_on_) return 0;
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    BCHK(bitnet_hip_stop_arm(stop_, keep_generated ? 1 : 0));
+    return 0;
+}
+
+int Decoder::set_stop(const bitnet_hip_stop_config *cfg) {
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    if (!cfg) {
+        if (!stop_on_) return 0;
+        drop_graphs();
+        stop_on_ = false;
+        HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));  // a stop may have raised it
+        return 0;
+    }
+    if (!stop_) {
+        BCHK(bitnet_hip_stop_create(cfg, &stop_));
+        // one launch that cannot act (no position lies inside a history of one entry): the kernel is loaded before a capture can meet it
+        BCHK(bitnet_hip_stop_dev(stop_, pos_, history_, 1, n_forced_, nullptr, stream_));
+        HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    } else {
+        BCHK(bitnet_hip_stop_configure(stop_, cfg));
+    }
+    if (!stop_on_) drop_graphs();  // the launch is part of the captured step
+    stop_on_ = true;
+    BCHK(bitnet_hip_stop_arm(stop_, 0));
+    HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int Decoder::stop_state(bitnet_hip_stop_state *out) {
+    if (!out) return fail_arg("stop_state: null output");
+    if (!stop_on_) return fail_arg("stop_state: no stop criteria (set_stop first)");
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    BCHK(bitnet_hip_stop_get_state(stop_, out));
+    return 0;
+}
+
+int Decoder::resume() {
+    if (!stop_on_) return fail_arg("resume: no stop criteria (set_stop first)");
+    if (int rc = arm_stop(true)) return rc;
+    HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int Decoder::run_until_stop(int max_steps, int chunk, int *steps, float *elapsed_ms) {
+    if (steps) *steps = 0;
+    if (elapsed_ms) *elapsed_ms = 0.f;
+    if (!stop_on_) return fail_arg("run_until_stop: no stop criteria (set_stop first)");
+    if (max_steps < 0 || chunk < 1) return fail_arg("run_until_stop: max_steps >= 0 and chunk >= 1 expected");
+    bitnet_hip_stop_state st;
+    if (int rc = stop_state(&st)) return rc;
+    int queued = 0;
+    float total = 0.f;
+    while (st.reason == BITNET_HIP_STOP_NONE && queued < max_steps) {
+        const int c = chunk < max_steps - queued ? chunk : max_steps - queued;
+        float ms = 0.f;
+        if (int rc = run(c, true, true, &ms)) return rc;
+        queued += c, total += ms;
+        BCHK(bitnet_hip_stop_get_state(stop_, &st));  // run() returned synchronised
+    }
+    if (steps) *steps = st.reason != BITNET_HIP_STOP_NONE && queued ? queued - st.frozen_steps : queued;
+    if (elapsed_ms) *elapsed_ms = total;
+    return 0;
+}
+
+int Decoder::graph_nodes(bool with_logits) {
+    if (!embed_) return fail_arg("model globals not set");
+    const int p = position();
+    if (p < 0) return BITNET_HIP_ERR_GPU;
+    const int form = form_at(p);
+    if (int rc = ensure_graph(with_logits, form)) return rc < 0 ? rc : -rc;
+    hipGraph_t g = (hipGraph_t)graph_[2 * form + (with_logits ? 1 : 0)];
+    size_t n = 0;
+    HCHK(hipGraphGetNodes(g, nullptr, &n));
+    std::vector<hipGraphNode_t> nodes(n);
+    if (n) HCHK(hipGraphGetNodes(g, nodes.data(), &n));
+    int kernels = 0;
+    for (size_t i = 0; i < n; ++i) {
+        hipGraphNodeType t;
+        if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) ++kernels;
+    }
+    return kernels;
 }
 
 void Decoder::logprob_entry(bitnet_hip_logprob_args *out) const {
@@ -567,6 +654,7 @@ int Decoder::set_globals(const uint16_t *embed_f16, const float *final_norm) {
 int Decoder::reset() {
     host_forced_ = 0;
     if (sampler_) BCHK(bitnet_hip_sampler_reset(sampler_));
+    if (int rc = arm_stop(false)) return rc;  // a new request
     HCHK(hipMemset(pos_, 0, 4));
     HCHK(hipMemset(n_forced_, 0, 4));
     HCHK(hipMemset(history_, 0, ((size_t)c_.max_pos + 2) * 4));
@@ -599,7 +687,7 @@ int Decoder::feed(const int32_t *tokens, int n) {
     HCHK(hipMemcpy(history_ + base, tokens, (size_t)n * 4, hipMemcpyHostToDevice));
     host_forced_ = base + n;
     HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));
-    return 0;
+    return arm_stop(false);  // new prompt tokens: a new request, and no stop sequence may reach back across them
 }
 
 int Decoder::position() {
@@ -1292,7 +1380,7 @@ int Decoder::rewind(int n) {
     HCHK(hipMemcpy(pos_, &np, 4, hipMemcpyHostToDevice));
     if (host_forced_ > n) host_forced_ = n;
     HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));
-    return 0;
+    return arm_stop(true);  // the stop and the window go (the tokens behind n are no longer the sequence's), the count stays
 }
 
 // The device pointer tables of fork and shift, allocated and filled once: this decoder's K caches [n_layers], its V caches [n_layers], then room for
@@ -1352,7 +1440,7 @@ int Decoder::shift(int keep, int discard) {
     HCHK(hipMemcpy(pos_, &np, 4, hipMemcpyHostToDevice));
     host_forced_ = shift_forced(host_forced_, keep, discard);
     HCHK(hipMemcpy(n_forced_, &host_forced_, 4, hipMemcpyHostToDevice));
-    return 0;
+    return arm_stop(true);  // as rewind: the stop and the window go, the count stays
 }
 
 int Decoder::fork(Decoder &src, Decoder *const *dsts, int n_dst, int n) { return src.fork_from_this(dsts, n_dst, n); }
@@ -1404,6 +1492,7 @@ int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
         if (d->sampler_) BCHK(bitnet_hip_sampler_reset(d->sampler_));
         // a destination's log-probabilities start at the fork point
         if (d->lp_top_n_ >= 0) HCHK(hipMemset(d->lp_records_, 0xff, (size_t)c_.max_pos * sizeof(bitnet_hip_logprob_record)));
+        if (int rc = d->arm_stop(false)) return rc;  // a destination carries no stop state
     }
     return 0;
 }
@@ -1606,6 +1695,11 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
                 d->logprob_entry(&a);
                 if (bitnet_hip_logprob_dev(&a, V, s) != 0) return fail("step_wide: bitnet_hip_logprob_dev");
             }
+        }
+        for (int i = 0; i < M; ++i) {  // the members' stop criteria, behind every sampler and tap launch of the step
+            Decoder *d = members[i];
+            if (d->stop_on_ && bitnet_hip_stop_dev(d->stop_, d->pos_, d->history_, (size_t)c_.max_pos, d->n_forced_, d->token_, s) != 0)
+                return fail("step_wide: bitnet_hip_stop_dev");
         }
     }
     HCHK(timer.stop(s, elapsed_ms));
@@ -2107,6 +2201,14 @@ int bitnet_host_set_sampling_ex(void *d, const bitnet_hip_sampling_config_ex *cf
 int bitnet_host_set_mirostat(void *d, const bitnet_hip_mirostat_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_mirostat(cfg); }
 int bitnet_host_mirostat_state(void *d, float *mu, uint64_t *fallbacks) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->mirostat_state(mu, fallbacks); }
 int bitnet_host_sampling_draws(void *d, uint64_t *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->sampling_draws(out); }
+int bitnet_host_set_stop(void *d, const bitnet_hip_stop_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_stop(cfg); }
+int bitnet_host_stop_state(void *d, bitnet_hip_stop_state *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->stop_state(out); }
+int bitnet_host_resume(void *d) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->resume(); }
+int bitnet_host_run_until_stop(void *d, int max_steps, int chunk, int *steps, float *elapsed_ms) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->run_until_stop(max_steps, chunk, steps, elapsed_ms);
+}
+int bitnet_host_graph_nodes(void *d, int with_logits) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->graph_nodes(with_logits != 0); }
 int bitnet_host_set_logprobs(void *d, int top_n) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_logprobs(top_n); }
 int bitnet_host_logprobs(void *d, int first, int n, void *records_out) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);

@@ -141,6 +141,34 @@ class Decoder {
     int logprobs(int first, int n, bitnet_hip_logprob_record *out);
     // what a batch binds for this member: its bitnet_hip_logprob_args, an empty entry (null records) with logprobs off
     void logprob_entry(bitnet_hip_logprob_args *out) const;
+    // STOP CRITERIA on the device (bitnet_hip_stop_*, include/bitnet_hip.h): stop token ids, EOS, a token budget and stop sequences of token ids,
+    // the reference's StopCriteria / check_stop (crates/bitnet-generation/src/lib.rs:119-144) and should_stop (crates/bitnet-inference/src/
+    // engine.rs:1315-1348).  cfg == NULL: off.  On, pick_token() issues ONE bitnet_hip_stop_dev launch behind the pick and the logits tap -- in
+    // run, prefill, extend, finish_prefill (so a first token that is already EOS stops), step_wide and prefill_packed -- which decides whether the
+    // token just placed ends the sequence and from then on holds the sequence FROZEN through every step already queued: the position goes back
+    // to the stop position, the device's forced count says "everything is forced", so no pick writes the history and the sampler's counts, word
+    // counter and Mirostat's mu stay where the stop token left them.  A frozen step consumes the stop token at slot `position` again and
+    // rewrites that one cache slot with the same bytes; history entries and cache slots beyond `position` keep what they held.
+    // Switching on or off drops the captured graphs, as set_logprobs does; a new config on a decoder that has criteria does not (the launch
+    // reads it from device memory).  Off, the launch sequence is exactly what it was (graph_nodes()).
+    // set_stop, feed and reset arm fully, for a new request (count 0); rewind and shift clear the stop and the window and keep the count; a
+    // fork destination carries no stop state (it is armed fully if it has criteria of its own).
+    // After a stop with frozen_steps > 0, last_logits() and last_hidden() are those of the last frozen step -- the step that consumes the
+    // stop token at slot `position`, under the attention form run() had queued for that step: what the first step of a resumed generation
+    // computes, bit for bit while the form is the same.  With frozen_steps == 0 they are the stopping step's.
+    int set_stop(const bitnet_hip_stop_config *cfg);
+    bool stop_on() const { return stop_on_; }
+    bitnet_hip_stop *stop_object() const { return stop_on_ ? stop_ : nullptr; }  // what a batch binds for this member
+    int stop_state(bitnet_hip_stop_state *out);  // synchronises; refuses a decoder without criteria
+    // Go on after a stop (or re-open the window of a running sequence): arms with the count kept -- a budget then counts the whole request --
+    // and writes the host's forced count back to the device.  The next run() consumes the stop token and generates behind it.
+    int resume();
+    // run(chunk) until the sequence has stopped or max_steps steps are queued (the last chunk is clipped); ONE 24-byte state read per chunk in
+    // place of a token read per step.  *steps: the steps up to and including the stopping one (queued - frozen_steps), or the steps queued if
+    // nothing stopped; elapsed_ms: the sum over the chunks.  A sequence that has stopped already returns at once with 0 steps.
+    int run_until_stop(int max_steps, int chunk, int *steps, float *elapsed_ms);
+    // kernel nodes of the step graph run() would launch at the current position (captured if need be), or a negative error code
+    int graph_nodes(bool with_logits);
     // Put `n` forced tokens at positions [pos, pos+n) of the history (the prompt).
     int feed(const int32_t *tokens, int n);
     // Run `n` single-token steps (T:1482-1504 body each).  with_logits=false skips the
@@ -427,6 +455,9 @@ class Decoder {
     bitnet_hip_logprob_record *lp_records_ = nullptr;  // [max_pos]
     void *lp_scratch_ = nullptr;
     int host_forced_ = 0;
+    bitnet_hip_stop *stop_ = nullptr;  // set_stop: created at the first config, kept until the decoder goes
+    bool stop_on_ = false;
+    int arm_stop(bool keep_generated);  // no-op without criteria
     // fork: device pointer tables, allocated at the first fork FROM this decoder: [0] its own K caches [n_layers], [1] its V caches (built once),
     // then the destinations' K [8][n_layers] and V [8][n_layers] (uploaded per call).  shift() uses [0] and [1].
     int ensure_fork_tables();
@@ -508,6 +539,11 @@ int bitnet_host_mirostat_state(void *d, float *mu, uint64_t *fallbacks);
 int bitnet_host_sampling_draws(void *d, uint64_t *out);
 int bitnet_host_set_logprobs(void *d, int top_n);                             // Decoder::set_logprobs: -1 off, 0..20 on
 int bitnet_host_logprobs(void *d, int first, int n, void *records_out);       // Decoder::logprobs: n bitnet_hip_logprob_record
+int bitnet_host_set_stop(void *d, const bitnet_hip_stop_config *cfg);           // Decoder::set_stop; NULL = off
+int bitnet_host_stop_state(void *d, bitnet_hip_stop_state *out);               // Decoder::stop_state
+int bitnet_host_resume(void *d);                                               // Decoder::resume
+int bitnet_host_run_until_stop(void *d, int max_steps, int chunk, int *steps, float *elapsed_ms);  // Decoder::run_until_stop
+int bitnet_host_graph_nodes(void *d, int with_logits);                         // Decoder::graph_nodes
 int bitnet_host_feed(void *d, const int32_t *tokens, int n);
 int bitnet_host_run(void *d, int n, int with_logits, int use_graph, float *elapsed_ms);
 int bitnet_host_run_reference(void *d, int n, int with_logits);

@@ -943,6 +943,92 @@ size_t bitnet_hip_logprob_scratch_bytes(size_t vocab);
 int bitnet_hip_logprob_dev(const bitnet_hip_logprob_args *args_host, size_t vocab, void *stream);
 int bitnet_hip_logprob_batch_dev(const bitnet_hip_logprob_args *table_dev, size_t n_slots, size_t vocab, void *stream);
 
+/* ---- stop criteria on the device: stop token ids, EOS, a token budget, stop sequences of token ids -----------------
+ * The reference's StopCriteria / StopReason / check_stop (crates/bitnet-generation/src/lib.rs:119-144), InferenceEngine::should_stop
+ * (crates/bitnet-inference/src/engine.rs:1315-1348) and GenerationConfig's stop fields (crates/bitnet-inference/src/config.rs:67-85) as
+ * ONE small launch behind the pick (bitnet_hip_logits_f16_dev's greedy pick, bitnet_hip_sample_dev, and the logits tap if there is one),
+ * inside a captured step: it decides whether the token just placed ends the sequence, and from then on keeps the sequence FROZEN through
+ * every step that is already queued, so a host can queue a chunk of steps and read the state once.
+ * With P = *pos_dev after the pick and t = history_dev[P], one launch does exactly one of:
+ *   ALREADY STOPPED: *pos_dev = the stop position, *token_dev = the stop token, frozen_steps += 1; nothing else.
+ *   NOT STOPPED and P < *n_forced_dev (a prompt token), or P outside [1, capacity): nothing.  Prompt tokens never stop a sequence and are
+ *     never counted.  (A forced position does not clear the window either: a caller that feeds tokens into a running generation arms again,
+ *     as bitnet_host's feed does.)
+ *   OTHERWISE: generated += 1, window += 1, then the first condition that holds, in check_stop's order, sets the reason:
+ *     1. t is one of stop_ids: BITNET_HIP_STOP_TOKEN, index = the lowest matching entry (so an id that is also eos_id reports here);
+ *     2. t == eos_id: BITNET_HIP_STOP_EOS;
+ *     3. max_tokens > 0 and generated >= max_tokens: BITNET_HIP_STOP_MAX_TOKENS.  The current token counts: a budget of n yields n tokens,
+ *        the n-th being the stop token.  The reference's callers differ here -- check_stop compares the length of the list its caller
+ *        hands it, which some callers extend before the call and some after; the engine's own loop bounds its step count instead;
+ *     4. some sequence s of length L <= window with history_dev[P - L + 1 .. P] == s: BITNET_HIP_STOP_SEQUENCE, index = the LOWEST such s,
+ *        not the longest.  window counts the tokens counted since the last arm, so a match never reaches back into prompt tokens or across
+ *        an arm.
+ *     On a stop: reason, index, token = t, position = P, generated are recorded, frozen_steps = 0, 0x7fffffff is stored to *n_forced_dev
+ *     -- every later pick then treats its position as forced: it writes no history entry, and the sampler samples nothing, counts
+ *     nothing, draws no word and leaves Mirostat's mu alone -- and the table's live count, if a table holds the object, goes down by one.
+ * The freeze: a frozen step starts at the stop position again, consumes the stop token there and rewrites that one cache slot with the
+ * same bytes; history entries and cache slots beyond the stop position keep whatever they held.  Every history index is checked against
+ * `capacity` before it is read: a garbage position is a no-op, never a fault.  Stop strings stay with the owner of the tokenizer: the
+ * device takes token-id sequences, and a string that spans a token boundary differently from its own tokenisation needs the host's check.
+ *   create: validates the config, allocates the device state (armed, nothing counted).  Not capture-safe.
+ *   configure: a new config, the state untouched.  Synchronous; graphs captured earlier stay valid and follow it (the config is read from
+ *     device memory).
+ *   arm(stop, keep_generated): reason, index, token, position, frozen_steps and window = 0; generated = 0 unless keep_generated.  It does
+ *     NOT touch *n_forced_dev, which is the caller's word: a caller that goes on after a stop writes its own forced count back.
+ *     Synchronous; no launch on the object in flight.
+ *   get_state: synchronous read-back, no launch on the object in flight.
+ *   stop_dev: exactly one launch, asynchronous and capture-safe.  token_dev may be NULL.
+ *   batch_create / _destroy / _set: a device table of n_slots = 1..BITNET_HIP_STOP_BATCH_MAX entries, each binding one bitnet_hip_stop and
+ *     the pointers stop_dev would take; stop == NULL empties the slot.  set is one synchronous copy of one entry: graphs captured before it
+ *     stay valid and follow it.  An object serves one table slot or stop_dev at a time; destroying it empties its slot.
+ *   batch_dev: exactly one launch, one wave per slot, even when every slot is empty; per bound slot it leaves, bit for bit, what stop_dev on
+ *     that object alone leaves (one kernel body serves both).
+ *   batch_live: synchronous count of bound slots that have not stopped (kept on the device by the launches, recounted by set and arm).
+ * INVALID_ARGUMENT before the GPU is touched: a NULL config or output pointer; n_stop_ids > BITNET_HIP_STOP_MAX_IDS; n_seqs >
+ * BITNET_HIP_STOP_MAX_SEQS; a sequence of length 0 or above BITNET_HIP_STOP_MAX_SEQ_LEN; a negative id in either list; a NULL list with a
+ * non-zero count; eos_id < -1; max_tokens < 0; a table slot out of range; an object already bound to another slot; NULL pos_dev, history_dev
+ * or n_forced_dev; capacity 0 or above 2^31 - 1.  An empty config is valid: it counts tokens and never stops. */
+#define BITNET_HIP_STOP_MAX_IDS 32
+#define BITNET_HIP_STOP_MAX_SEQS 16
+#define BITNET_HIP_STOP_MAX_SEQ_LEN 32
+#define BITNET_HIP_STOP_BATCH_MAX 64
+#define BITNET_HIP_STOP_NONE 0
+#define BITNET_HIP_STOP_TOKEN 1        /* StopReason::StopTokenId(stop_ids[index]) */
+#define BITNET_HIP_STOP_EOS 2          /* StopReason::EosToken */
+#define BITNET_HIP_STOP_MAX_TOKENS 3   /* StopReason::MaxTokens */
+#define BITNET_HIP_STOP_SEQUENCE 4     /* StopReason::StopString, as the token ids of sequence `index` */
+typedef struct bitnet_hip_stop_config {
+    const int32_t *stop_ids; size_t n_stop_ids;   /* StopCriteria::stop_token_ids */
+    int32_t eos_id;                               /* StopCriteria::eos_token_id; -1: none */
+    int32_t max_tokens;                           /* StopCriteria::max_tokens; 0: none */
+    const int32_t *seq_tokens;                    /* the sequences' token ids, concatenated */
+    const int32_t *seq_len;                       /* [n_seqs], each 1..BITNET_HIP_STOP_MAX_SEQ_LEN */
+    size_t n_seqs;
+} bitnet_hip_stop_config;
+typedef struct bitnet_hip_stop_state {
+    int32_t reason;        /* BITNET_HIP_STOP_*; NONE: still running */
+    int32_t index;         /* of the stop id or sequence that matched */
+    int32_t token;         /* the stop token */
+    int32_t position;      /* its history slot */
+    int32_t generated;     /* tokens counted (since the last arm that did not keep the count), the stop token included */
+    int32_t frozen_steps;  /* launches since the stop: the steps that were queued for nothing */
+} bitnet_hip_stop_state;
+typedef struct bitnet_hip_stop bitnet_hip_stop;
+typedef struct bitnet_hip_stop_batch bitnet_hip_stop_batch;
+int bitnet_hip_stop_create(const bitnet_hip_stop_config *cfg, bitnet_hip_stop **out);
+void bitnet_hip_stop_destroy(bitnet_hip_stop *stop);
+int bitnet_hip_stop_configure(bitnet_hip_stop *stop, const bitnet_hip_stop_config *cfg);
+int bitnet_hip_stop_arm(bitnet_hip_stop *stop, int keep_generated);
+int bitnet_hip_stop_get_state(bitnet_hip_stop *stop, bitnet_hip_stop_state *out);
+int bitnet_hip_stop_dev(bitnet_hip_stop *stop, int32_t *pos_dev, const int32_t *history_dev, size_t capacity, int32_t *n_forced_dev,
+                        int32_t *token_dev, void *stream);
+int bitnet_hip_stop_batch_create(size_t n_slots, bitnet_hip_stop_batch **out);
+void bitnet_hip_stop_batch_destroy(bitnet_hip_stop_batch *table);
+int bitnet_hip_stop_batch_set(bitnet_hip_stop_batch *table, size_t slot, bitnet_hip_stop *stop, int32_t *pos_dev, const int32_t *history_dev,
+                              size_t capacity, int32_t *n_forced_dev, int32_t *token_dev);
+int bitnet_hip_stop_batch_dev(bitnet_hip_stop_batch *table, void *stream);
+int bitnet_hip_stop_batch_live(bitnet_hip_stop_batch *table, int32_t *live);
+
 /* ---- measurement aid -------------------------------------------------------
  * Measured HBM read ceiling of the device (quote the roofline fraction against the vendor
  * figure AND a measured stream ceiling): a read-only streaming kernel (non-temporal 16-byte loads, one

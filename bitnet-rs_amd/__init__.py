@@ -1130,6 +1130,15 @@ def blake3_hex(data: bytes) -> str:
     return out.value.decode()
 
 
+def host_device_bytes() -> int:
+    """Bytes of device memory the process's host decoders and batches own right now (host/dev_buffer.hpp; the weight handles are not counted)."""
+    load()
+    L = C.CDLL(HOST_LIB_PATH)
+    L.bitnet_host_device_bytes.argtypes = []
+    L.bitnet_host_device_bytes.restype = C.c_uint64
+    return int(L.bitnet_host_device_bytes())
+
+
 class HostConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("hidden", "n_layers", "n_heads", "n_kv_heads", "head_dim", "ffn", "vocab", "max_pos")] + [
         ("eps", C.c_float),

@@ -75,9 +75,8 @@ BatchDecoder::~BatchDecoder() {
     drop_graph();
     if (sample_tab_) bitnet_hip_sample_batch_destroy(sample_tab_);  // before the members (and their samplers) are released
     if (stop_tab_) bitnet_hip_stop_batch_destroy(stop_tab_);        // likewise: it takes its live pointer back from every bound object
-    for (void *p : {(void *)tables_, (void *)x_, (void *)x2_, (void *)qkv_, (void *)attn_scratch_, qa_x_, qa_x2_, qa_att_, qa_h_, scratch_, (void *)st_x_,
-                    (void *)st_x2_, (void *)lp_table_})
-        if (p) hipFree(p);
+    // the buffers before the stream goes and before the members are let go, as ever (one this line forgot would still be freed, as a member)
+    release_all(tables_, x_, x2_, qkv_, attn_scratch_, qa_x_, qa_x2_, qa_att_, qa_h_, scratch_, st_x_, st_x2_, lp_table_);
     if (stream_) hipStreamDestroy((hipStream_t)stream_);
     for (int b = 0; b < n_; ++b)
         if (slot_[b]) {
@@ -97,16 +96,13 @@ int BatchDecoder::ensure_buffers() {
     const size_t as = bitnet_hip_attention_scratch_bytes((size_t)c.n_kv_heads, (size_t)c.max_pos);
     const size_t rows = kRowLayers + 2 * (size_t)c.n_layers;
     struct {
-        void **p;
+        DevMem *b;
         size_t bytes;
-    } want[] = {{(void **)&x_, n * H * 4}, {(void **)&x2_, n * H * 4}, {(void **)&qkv_, n * (QD + 2 * KD) * 4}, {(void **)&attn_scratch_, n * as},
-                {&qa_x_, n * qh},          {&qa_x2_, n * qh},          {&qa_att_, n * qq},                       {&qa_h_, n * qf},
-                {(void **)&st_x_, n * sb}, {(void **)&st_x2_, n * sb}, {&scratch_, n * 8 * (size_t)logits_wgs_}, {(void **)&tables_, rows * n * sizeof(void *)},
-                {(void **)&lp_table_, n * sizeof(bitnet_hip_logprob_args)}};  // zero-filled: every entry empty
-    for (auto &w : want) {
-        HCHK(hipMalloc(w.p, w.bytes));
-        HCHK(hipMemset(*w.p, 0, w.bytes));
-    }
+    } want[] = {{&x_, n * H * 4},  {&x2_, n * H * 4},  {&qkv_, n * (QD + 2 * KD) * 4},           {&attn_scratch_, n * as},
+                {&qa_x_, n * qh},  {&qa_x2_, n * qh},  {&qa_att_, n * qq},                       {&qa_h_, n * qf},
+                {&st_x_, n * sb},  {&st_x2_, n * sb},  {&scratch_, n * 8 * (size_t)logits_wgs_}, {&tables_, rows * n * sizeof(void *)},
+                {&lp_table_, n * sizeof(bitnet_hip_logprob_args)}};  // zero-filled: every entry empty
+    for (auto &w : want) HCHK(w.b->alloc_zeroed_bytes(w.bytes));
     host_tables_.assign(rows * n, nullptr);
     BCHK(bitnet_hip_sample_batch_create((size_t)c.vocab, n, &sample_tab_));
     BCHK(bitnet_hip_stop_batch_create(n, &stop_tab_));
@@ -330,8 +326,8 @@ int BatchDecoder::launches(bool warm) {
                                                    kv_f16_ ? BITNET_HIP_ATTN_KV_F16 : 0, nullptr, qa_att_, s));
         BCHK(bitnet_hip_gemv_q_batch_dev(h[1], n, qa_att_, nullptr, nullptr, 0.f, x_, 0, x2_, qa_x2_, ffn_norm, st_x2_, s));
         BCHK(bitnet_hip_gemv_q_batch_dev(h[2], n, qa_x2_, st_x2_, ffn_norm, c.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL, nullptr, qa_h_, nullptr, nullptr, s));
-        BCHK(bitnet_hip_gemv_q_batch_dev(h[3], n, qa_h_, nullptr, nullptr, 0.f, x2_, 0, x_, more ? qa_x_ : nullptr, more ? (const float *)pn[0] : nullptr,
-                                         more ? st_x_ : nullptr, s));
+        BCHK(bitnet_hip_gemv_q_batch_dev(h[3], n, qa_h_, nullptr, nullptr, 0.f, x2_, 0, x_, more ? qa_x_.get() : nullptr, more ? (const float *)pn[0] : nullptr,
+                                         more ? st_x_.get() : nullptr, s));
     }
     BCHK(bitnet_hip_logits_f16_batch_dev(g[0], x_, (const float *)g[1], c.eps, H, (size_t)c.vocab, n, (float *const *)row(kRowLogits), scratch_,
                                          (size_t)logits_wgs_, (int32_t *const *)row(kRowTok), (int32_t *const *)row(kRowPickPos),

@@ -80,12 +80,12 @@ class BatchDecoder {
     void *stream_ = nullptr;
     // device pointer tables, [row][n_] pointers each: rows 0..5 = embed/attention positions, histories, logits rows, pick tokens, pick positions,
     // pick histories, forced counts (row 6), then per layer K caches and V caches
-    void **tables_ = nullptr;
+    DevBuf<void *> tables_;
     std::vector<void *> host_tables_;
     bool tables_dirty_ = true;
-    float *x_ = nullptr, *x2_ = nullptr, *qkv_ = nullptr, *attn_scratch_ = nullptr;
-    void *qa_x_ = nullptr, *qa_x2_ = nullptr, *qa_att_ = nullptr, *qa_h_ = nullptr, *scratch_ = nullptr;
-    double *st_x_ = nullptr, *st_x2_ = nullptr;
+    DevBuf<float> x_, x2_, qkv_, attn_scratch_;
+    DevBuf<void> qa_x_, qa_x2_, qa_att_, qa_h_, scratch_;
+    DevBuf<double> st_x_, st_x2_;
     int logits_wgs_ = 512;
     void *graph_ = nullptr, *graph_exec_ = nullptr;
     std::vector<void *> sampling_sig() const;  // per slot the sampler of a sampling member (null: fused greedy pick, or empty) ...
@@ -94,7 +94,7 @@ class BatchDecoder {
     void *bound_[BITNET_HIP_BATCH_MAX] = {};         // the sampler each of its entries holds
     bool sample_in_chain_ = false;  // some member has sampled: the sampling launch is part of every step from then on
     bool graph_sig_ = false;        // ... and whether the captured chain has it
-    bitnet_hip_logprob_args *lp_table_ = nullptr;             // device: [n_] entries, one launch (bitnet_hip_logprob_batch_dev)
+    DevBuf<bitnet_hip_logprob_args> lp_table_;                // device: [n_] entries, one launch (bitnet_hip_logprob_batch_dev)
     bitnet_hip_logprob_args lp_host_[BITNET_HIP_BATCH_MAX] = {};  // what it holds
     bool lp_in_chain_ = false;      // some member has had logprobs on: the logprob launch is part of every step from then on
     bool graph_lp_sig_ = false;     // ... and whether the captured chain has it

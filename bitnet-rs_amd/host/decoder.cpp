@@ -45,11 +45,6 @@ int Decoder::fail(const char *what) {
     return BITNET_HIP_ERR_EXECUTION;
 }
 
-template <class T>
-static hipError_t dalloc(T **p, size_t n) {
-    return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T) ? n * sizeof(T) : 1);
-}
-
 static std::string config_problem(const Config &c) {
     char b[160];
     if (c.hidden <= 0 || c.n_layers <= 0 || c.n_heads <= 0 || c.n_kv_heads <= 0 || c.head_dim <= 0 || c.ffn <= 0 || c.vocab <= 0 || c.max_pos <= 1) {
@@ -65,7 +60,16 @@ static std::string config_problem(const Config &c) {
     return "";
 }
 
-Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n_layers <= 4096 ? (size_t)cfg.n_layers : 0) {
+DecoderStreams::~DecoderStreams() {
+    for (void *e : sp_tev_)
+        if (e) hipEventDestroy((hipEvent_t)e);
+    if (sp_ev_pack_) hipEventDestroy((hipEvent_t)sp_ev_pack_);
+    if (sp_ev_gather_) hipEventDestroy((hipEvent_t)sp_ev_gather_);
+    if (comm_stream_) hipStreamDestroy((hipStream_t)comm_stream_);
+    if (stream_) hipStreamDestroy((hipStream_t)stream_);
+}
+
+Decoder::Decoder(const Config &cfg, bool own_norms) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n_layers <= 4096 ? (size_t)cfg.n_layers : 0) {
     // A rejected configuration or a failed allocation leaves a DEAD object: error() says why, every other entry point
     // returns an error without touching a member (c_ used to keep the rejected n_layers while layers_ was empty).
     dead_ = true;
@@ -100,46 +104,31 @@ Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n
                     (size_t)c_.n_heads * 128 <= 4096;
         merge8_ok_ = merge_ok_ && (size_t)c_.n_heads * 128 <= 2560;  // bitnet_hip_gemv_attn_merge_rec_q_dev with 8 records
     }
-    bool ok = true;
-    ok &= dalloc(&x_, H) == hipSuccess && dalloc(&x2_, H) == hipSuccess;
-    ok &= dalloc(&qkv_, (size_t)(c_.n_heads + 2 * c_.n_kv_heads) * D) == hipSuccess;
-    ok &= dalloc(&att_, (size_t)c_.n_heads * D) == hipSuccess;
-    ok &= dalloc(&h_, (size_t)c_.ffn) == hipSuccess;
-    {
-        // QAct records + LayerNorm statistics pairs of the four vectors that travel between the step's GEMVs (zero-filled
-        // once: bytes past a vector's last group are never written and must read as zero digits)
-        const size_t qh = bitnet_hip_qact_bytes(H), qq = bitnet_hip_qact_bytes((size_t)c_.n_heads * D), qf = bitnet_hip_qact_bytes((size_t)c_.ffn);
-        const size_t sb = bitnet_hip_qact_stats_bytes(H);
-        ok = ok && hipMalloc(&qa_x_, qh) == hipSuccess && hipMalloc(&qa_x2_, qh) == hipSuccess && hipMalloc(&qa_att_, qq) == hipSuccess &&
-             hipMalloc(&qa_h_, qf) == hipSuccess && hipMalloc((void **)&st_x_, sb) == hipSuccess && hipMalloc((void **)&st_x2_, sb) == hipSuccess;
-        ok = ok && hipMemset(qa_x_, 0, qh) == hipSuccess && hipMemset(qa_x2_, 0, qh) == hipSuccess && hipMemset(qa_att_, 0, qq) == hipSuccess &&
-             hipMemset(qa_h_, 0, qf) == hipSuccess && hipMemset(st_x_, 0, sb) == hipSuccess && hipMemset(st_x2_, 0, sb) == hipSuccess;
-    }
-    ok &= dalloc(&ref_n_, H > (size_t)c_.ffn ? H : (size_t)c_.ffn) == hipSuccess && dalloc(&ref_gu_, 2 * (size_t)c_.ffn) == hipSuccess &&
-          dalloc(&ref_t_, H) == hipSuccess;
-    ok &= dalloc(&logits_, (size_t)c_.vocab) == hipSuccess;
-    ok &= hipMalloc(&scratch_, 8 * (size_t)(logits_wgs_ > screen_wgs_ ? logits_wgs_ : screen_wgs_)) == hipSuccess;
+    // Every allocation of a decoder's life that is not grown on demand, on ONE failure path: a hipError_t is true when it is an error, so the
+    // first failure ends the chain, and the members free what they hold.
+    const size_t F = (size_t)c_.ffn, QD = (size_t)c_.n_heads * D;
+    bool bad = x_.alloc(H) || x2_.alloc(H) || qkv_.alloc(QD + 2 * (size_t)c_.n_kv_heads * D) || att_.alloc(QD) || h_.alloc(F);
+    // QAct records + LayerNorm statistics pairs of the four vectors that travel between the step's GEMVs (zero-filled
+    // once: bytes past a vector's last group are never written and must read as zero digits)
+    bad = bad || qa_x_.alloc_zeroed(bitnet_hip_qact_bytes(H)) || qa_x2_.alloc_zeroed(bitnet_hip_qact_bytes(H)) || qa_att_.alloc_zeroed(bitnet_hip_qact_bytes(QD)) ||
+          qa_h_.alloc_zeroed(bitnet_hip_qact_bytes(F)) || st_x_.alloc_zeroed_bytes(bitnet_hip_qact_stats_bytes(H)) || st_x2_.alloc_zeroed_bytes(bitnet_hip_qact_stats_bytes(H));
+    bad = bad || ref_n_.alloc(H > F ? H : F) || ref_gu_.alloc(2 * F) || ref_t_.alloc(H) || logits_.alloc((size_t)c_.vocab);
+    bad = bad || scratch_.alloc(8 * (size_t)(logits_wgs_ > screen_wgs_ ? logits_wgs_ : screen_wgs_));
     if (const size_t wb = bitnet_hip_head_screen_ws_bytes(H, (size_t)c_.vocab, (size_t)screen_wgs_))  // 0: no screened head at this hidden size
-        ok = ok && hipMalloc((void **)&screen_ws_, wb) == hipSuccess && hipMemset(screen_ws_, 0, wb) == hipSuccess;
-    {
-        const size_t sb = bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos);
-        // zero-filled: the merging o-projection reads records of chunks past the context (and gives them zero weight)
-        ok = ok && hipMalloc((void **)&attn_scratch_, sb) == hipSuccess && hipMemset(attn_scratch_, 0, sb) == hipSuccess;
-    }
-    ok &= dalloc(&pos_, 1) == hipSuccess && dalloc(&n_forced_, 1) == hipSuccess && dalloc(&token_, 1) == hipSuccess;
-    ok &= dalloc(&history_, (size_t)c_.max_pos + 2) == hipSuccess;
-    ok &= dalloc(&rope_sin_, (size_t)c_.max_pos * half) == hipSuccess;
-    ok &= dalloc(&rope_cos_, (size_t)c_.max_pos * half) == hipSuccess;
+        bad = bad || screen_ws_.alloc_zeroed_bytes(wb);
+    // zero-filled: the merging o-projection reads records of chunks past the context (and gives them zero weight)
+    bad = bad || attn_scratch_.alloc_zeroed_bytes(bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos));
+    bad = bad || pos_.alloc(1) || n_forced_.alloc(1) || token_.alloc(1) || history_.alloc((size_t)c_.max_pos + 2);
+    bad = bad || rope_sin_.alloc((size_t)c_.max_pos * half) || rope_cos_.alloc((size_t)c_.max_pos * half);
     for (auto &L : layers_) {
         const size_t n = (size_t)c_.n_kv_heads * (((size_t)c_.max_pos + 63) / 64 * 64) * D;  // whole 64-position tiles
-        ok &= dalloc(&L.kcache, n) == hipSuccess && dalloc(&L.vcache, n) == hipSuccess;
         // the decode attention reads whole 64-position tiles and multiplies slots past the context by exact zeros:
         // they must hold finite bit patterns (include/bitnet_hip.h), so the caches start zero-filled
-        ok = ok && hipMemset(L.kcache, 0, n * sizeof(float)) == hipSuccess && hipMemset(L.vcache, 0, n * sizeof(float)) == hipSuccess;
-        ok &= dalloc(&L.attn_norm, H) == hipSuccess && dalloc(&L.ffn_norm, H) == hipSuccess;
+        bad = bad || L.kcache.alloc_zeroed(n) || L.vcache.alloc_zeroed(n);
+        if (own_norms) bad = bad || L.attn_norm.alloc(H) || L.ffn_norm.alloc(H);
     }
-    ok &= dalloc(&final_norm_, H) == hipSuccess;
-    if (!ok) {
+    if (own_norms) bad = bad || final_norm_.alloc(H);
+    if (bad) {
         err_ = "device allocation failed";
         return;
     }
@@ -160,9 +149,9 @@ Decoder::Decoder(const Config &cfg) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n
     reset();
 }
 
-// Borrowing decoder: built as any other (own buffers, caches, stream), then its norm vectors, final norm, weight handles and embedding
-// table are the OWNER's.
-Decoder::Decoder(Decoder &owner, int) : Decoder(owner.c_) {
+// Borrowing decoder: built as any other (own buffers, caches, stream) but for the norm vectors: those, the final norm, the weight handles,
+// the embedding table and its screening image are the OWNER's.
+Decoder::Decoder(Decoder &owner, int) : Decoder(owner.c_, false) {
     if (dead_) return;
     if (owner.dead_ || owner.owner_ || !owner.embed_) {
         dead_ = true;
@@ -178,14 +167,12 @@ Decoder::Decoder(Decoder &owner, int) : Decoder(owner.c_) {
     for (size_t l = 0; l < layers_.size(); ++l) {
         Layer &L = layers_[l];
         const Layer &O = owner.layers_[l];
-        hipFree(L.attn_norm), hipFree(L.ffn_norm);
-        L.attn_norm = O.attn_norm, L.ffn_norm = O.ffn_norm;
+        L.attn_norm.borrow(O.attn_norm), L.ffn_norm.borrow(O.ffn_norm);
         L.qkv = O.qkv, L.o = O.o, L.gateup = O.gateup, L.down = O.down, L.q_ok = O.q_ok;
     }
-    hipFree(final_norm_);
-    final_norm_ = owner.final_norm_;
-    embed_ = owner.embed_;
-    screen_ = owner.screen_;
+    final_norm_.borrow(owner.final_norm_);
+    embed_.borrow(owner.embed_);
+    screen_.borrow(owner.screen_);
     weight_bytes_ = owner.weight_bytes_;
     act_mode_ = owner.act_mode_;
     owner_ = &owner;
@@ -209,38 +196,20 @@ void Decoder::batch_objects(void *ptrs[3]) {
     ptrs[0] = n_forced_, ptrs[1] = logits_, ptrs[2] = sampler_;
 }
 
+// What is not memory, in the order the memory needs: the graphs before the buffers they name, the sampler and the stop object before the
+// buffers they point into.  The members follow -- every DevBuf frees what it owns, a borrowed view nothing -- and the streams go last
+// (DecoderStreams).
 Decoder::~Decoder() {
     drop_graphs();
     if (sampler_) bitnet_hip_sampler_destroy(sampler_);
     if (stop_) bitnet_hip_stop_destroy(stop_);
-    for (void *p : {(void *)lp_records_, lp_scratch_})
-        if (p) hipFree(p);
-    if (owner_) {  // borrowed objects stay the owner's
-        for (auto &L : layers_) L.qkv = L.o = L.gateup = L.down = 0, L.attn_norm = L.ffn_norm = nullptr;
-        embed_ = nullptr, final_norm_ = nullptr, screen_ = nullptr;
+    if (owner_) {  // borrowed handles stay the owner's
         owner_->borrowers_--;
+        return;
     }
-    for (auto &L : layers_) {
+    for (auto &L : layers_)
         for (bitnet_hip_weights_t h : {L.qkv, L.o, L.gateup, L.down})
             if (h) bitnet_hip_weights_free(h);
-        for (float *p : {L.attn_norm, L.ffn_norm, L.kcache, L.vcache})
-            if (p) hipFree(p);
-    }
-    for (void *p : {(void *)embed_, screen_, (void *)screen_ws_, (void *)final_norm_, (void *)rope_sin_, (void *)rope_cos_, (void *)x_, (void *)x2_,
-                    (void *)qkv_, (void *)att_, (void *)h_, (void *)ref_n_, (void *)ref_gu_, (void *)ref_t_, qa_x_, qa_x2_, qa_att_, qa_h_, (void *)st_x_, (void *)st_x2_, (void *)logits_, scratch_, (void *)attn_scratch_, (void *)pos_, (void *)n_forced_,
-                    (void *)history_, (void *)token_})
-        if (p) hipFree(p);
-    for (void *p : {(void *)pf_x_, (void *)pf_qkv_, (void *)pf_att_, (void *)pf_h_, pf_gemm_ws_, pf_attn_ws_, sp_kv_send_, sp_kv_all_,
-                    (void *)sp_block_pos_, (void *)sp_tokens_, pf_xh_, pf_atth_, pf_hh_, (void *)pf_stats_, pf_qb_, (void *)sc_tgt_, (void *)sc_am_,
-                    (void *)sc_nll_, (void *)sc_logits_, sc_ws_, (void *)fork_tables_, (void *)wide_tables_, (void *)wide_scratch_, (void *)wide_logits_,
-                    (void *)wide_nll_, (void *)wide_am_, (void *)wide_tgt_, wide_ws_})
-        if (p) hipFree(p);
-    for (void *e : sp_tev_)
-        if (e) hipEventDestroy((hipEvent_t)e);
-    if (sp_ev_pack_) hipEventDestroy((hipEvent_t)sp_ev_pack_);
-    if (sp_ev_gather_) hipEventDestroy((hipEvent_t)sp_ev_gather_);
-    if (comm_stream_) hipStreamDestroy((hipStream_t)comm_stream_);
-    if (stream_) hipStreamDestroy((hipStream_t)stream_);
 }
 
 // A layer that already holds weights gives them back first, and every captured step graph goes (the graphs
@@ -276,12 +245,12 @@ int Decoder::ensure_screen_image() {
             err_ = owner_->err_;
             return rc;
         }
-        screen_ = owner_->screen_;
+        screen_.borrow(owner_->screen_);
         return 0;
     }
     const size_t H = c_.hidden, V = c_.vocab, bytes = bitnet_hip_head_screen_bytes(H, V);
     if (!bytes || !embed_) return 0;  // no instance for this hidden size, or no table yet (set_globals builds it)
-    if (!screen_) HCHK(hipMalloc(&screen_, bytes));
+    if (!screen_) HCHK(screen_.alloc(bytes));
     BCHK(bitnet_hip_head_screen_build_dev(embed_, H, V, screen_, stream_));
     HCHK(hipStreamSynchronize((hipStream_t)stream_));
     return 0;
@@ -437,13 +406,12 @@ void Decoder::logprob_entry(bitnet_hip_logprob_args *out) const {
 int Decoder::set_logprobs(int top_n) {
     if (top_n < -1 || top_n > BITNET_HIP_LOGPROB_TOP_MAX) return fail_arg("set_logprobs: top_n must be -1 (off) or 0..20");
     if (top_n == lp_top_n_) return 0;
-    if (top_n >= 0 && !lp_records_) {
+    if (top_n >= 0 && (!lp_records_ || !lp_scratch_)) {  // both or neither: a call that failed between the two is made good by the next
         const size_t rb = (size_t)c_.max_pos * sizeof(bitnet_hip_logprob_record), sb = bitnet_hip_logprob_scratch_bytes((size_t)c_.vocab);
         if (!sb) return fail_arg("set_logprobs: vocabulary out of range");
-        HCHK(hipMalloc((void **)&lp_records_, rb));
+        HCHK(lp_records_.alloc((size_t)c_.max_pos));
         HCHK(hipMemset(lp_records_, 0xff, rb));
-        HCHK(hipMalloc(&lp_scratch_, sb));
-        HCHK(hipMemset(lp_scratch_, 0, sb));
+        HCHK(lp_scratch_.alloc_zeroed(sb));
         // one launch of an empty entry: the kernel is loaded before a capture can meet it
         bitnet_hip_logprob_args none{};
         BCHK(bitnet_hip_logprob_dev(&none, (size_t)c_.vocab, stream_));
@@ -644,7 +612,7 @@ int Decoder::set_globals(const uint16_t *embed_f16, const float *final_norm) {
     if (int rc = weights_locked()) return rc;
     if (int rc = refresh_logits()) return rc;  // logits still owed from a screened step belong to the table that is about to go
     const size_t n = (size_t)c_.vocab * c_.hidden * 2;
-    if (!embed_) HCHK(hipMalloc(&embed_, n));
+    if (!embed_) HCHK(embed_.alloc(n));
     HCHK(hipMemcpy(embed_, embed_f16, n, hipMemcpyHostToDevice));
     HCHK(hipMemcpy(final_norm_, final_norm, (size_t)c_.hidden * 4, hipMemcpyHostToDevice));
     if (head_screen_on_ || screen_) return ensure_screen_image();  // the image follows the table
@@ -790,16 +758,16 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
                 if (int rc = attn_launch(L, form, nullptr, nullptr)) return rc;
                 BCHK(bitnet_hip_gemv_attn_merge_rec_q_dev(L.o, attn_scratch_, NH, NK, MP, pos_, x2_, x_, qa_x2_, L.ffn_norm, st_x2_, form == 3 ? 8 : 4, s));
             } else {
-                if (int rc = attn_launch(L, form, tr ? att_ : nullptr, qa_att_)) return rc;
+                if (int rc = attn_launch(L, form, tr ? att_.get() : nullptr, qa_att_)) return rc;
                 TRACE(bp + "attn_out", "attn_out", (int)l, att_, tQD);
                 BCHK(bitnet_hip_gemv_q_dev(L.o, qa_att_, nullptr, nullptr, 0.f, x_, 0, x2_, qa_x2_, L.ffn_norm, st_x2_, s));
             }
             TRACE(bp + "attn_residual", "attn_residual", (int)l, x2_, H);
-            BCHK(bitnet_hip_gemv_q_dev(L.gateup, qa_x2_, st_x2_, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL, tr ? h_ : nullptr, qa_h_, nullptr, nullptr, s));
+            BCHK(bitnet_hip_gemv_q_dev(L.gateup, qa_x2_, st_x2_, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL, tr ? h_.get() : nullptr, qa_h_, nullptr, nullptr, s));
             TRACE(bp + "ffn_hidden", "ffn_hidden", (int)l, h_, (size_t)c_.ffn);
             const bool more = l + 1 < layers_.size();
-            BCHK(bitnet_hip_gemv_q_dev(L.down, qa_h_, nullptr, nullptr, 0.f, x2_, 0, x_, more ? qa_x_ : nullptr, more ? layers_[l + 1].attn_norm : nullptr,
-                                       more ? st_x_ : nullptr, s));
+            BCHK(bitnet_hip_gemv_q_dev(L.down, qa_h_, nullptr, nullptr, 0.f, x2_, 0, x_, more ? qa_x_.get() : nullptr, more ? layers_[l + 1].attn_norm.get() : nullptr,
+                                       more ? st_x_.get() : nullptr, s));
             TRACE(bp + "ffn_out", "ffn_out", (int)l, x_, H);
         }
         if (tr) TRACE("t" + std::to_string(tr->seq) + "_all_layers_out", "all_layers_out", -1, x_, H);
@@ -1119,15 +1087,12 @@ int Decoder::ensure_chain_buffers(size_t N) {
     const size_t NP = (N + 63) / 64 * 64, nst = H / 64;
     hipStream_t s = (hipStream_t)stream_;
     if ((int)NP > pfc_cap_) {
-        for (void *q : {pf_xh_, pf_atth_, pf_hh_, (void *)pf_stats_})
-            if (q) hipFree(q);
-        pf_xh_ = pf_atth_ = pf_hh_ = nullptr;
-        pf_stats_ = nullptr;
+        release_all(pf_xh_, pf_atth_, pf_hh_, pf_stats_);
         pfc_cap_ = 0;
-        HCHK(hipMalloc(&pf_xh_, NP * H * 2));
-        HCHK(hipMalloc(&pf_atth_, NP * QD * 2));
-        HCHK(hipMalloc(&pf_hh_, NP * F * 2));
-        HCHK(hipMalloc((void **)&pf_stats_, nst * NP * 2 * sizeof(float)));
+        HCHK(pf_xh_.alloc(NP * H * 2));
+        HCHK(pf_atth_.alloc(NP * QD * 2));
+        HCHK(pf_hh_.alloc(NP * F * 2));
+        HCHK(pf_stats_.alloc(nst * NP * 2));
         // rows past the prompt are read by the last token tile (never stored): they must hold finite values
         HCHK(hipMemsetAsync(pf_xh_, 0, NP * H * 2, s));
         HCHK(hipMemsetAsync(pf_atth_, 0, NP * QD * 2, s));
@@ -1185,10 +1150,9 @@ int Decoder::prompt_form(size_t N, int digits, bool sharded, PromptForm *out) {
         if (int rc = ensure_chain_buffers(N)) return rc;
     const size_t NP = (N + 63) / 64 * 64;
     if (f.qb && (int)NP > pf_qb_cap_) {
-        if (pf_qb_) (void)hipFree(pf_qb_);
-        pf_qb_ = nullptr;
+        release_all(pf_qb_);
         pf_qb_cap_ = 0;
-        HCHK(hipMalloc(&pf_qb_, bitnet_hip_qb32_bytes(NP, (size_t)c_.hidden)));
+        HCHK(pf_qb_.alloc(bitnet_hip_qb32_bytes(NP, (size_t)c_.hidden)));
         HCHK(hipMemsetAsync(pf_qb_, 0, bitnet_hip_qb32_bytes(NP, (size_t)c_.hidden), (hipStream_t)stream_));
         pf_qb_cap_ = (int)NP;
     }
@@ -1251,9 +1215,9 @@ int Decoder::project_qkv(size_t l, size_t N, const PromptForm &f) {
 // chains prepare the next matmul's rows for, or null behind the last layer, which hands over nothing.
 int Decoder::project_residual(bitnet_hip_weights_t w, size_t N, const PromptForm &f, const float *in32, const void *in16, const float *next_norm) {
     if (f.chain || f.qb || f.hybrid) {
-        void *hand = !next_norm ? nullptr : f.chain ? pf_xh_ : f.qb ? pf_qb_ : nullptr;
+        void *hand = !next_norm ? nullptr : f.chain ? pf_xh_.get() : f.qb ? pf_qb_.get() : nullptr;
         BCHK(bitnet_hip_matmul_f16_dev(w, in16, N, nullptr, 0, nullptr, 0.f, pf_x_, pf_x_, hand && f.qb ? BITNET_HIP_FUSE_YH_QB32 : 0, hand, hand ? next_norm : nullptr,
-                                       hand ? pf_stats_ : nullptr, stream_));
+                                       hand ? pf_stats_.get() : nullptr, stream_));
     } else
         BCHK(bitnet_hip_matmul_fused_dev(w, f.h16 ? static_cast<const float *>(in16) : in32, pf_x_, N, nullptr, 0.f, pf_x_, f.h16 ? BITNET_HIP_FUSE_X_F16 | f.f6od : 0,
                                          f.digits, pf_gemm_ws_, pf_gemm_ws_bytes_, stream_));
@@ -1271,7 +1235,7 @@ int Decoder::project_gateup(Layer &L, size_t N, const PromptForm &f) {
     else if (f.qb)
         BCHK(bitnet_hip_matmul_qb32_dev(L.gateup, pf_qb_, N, pf_stats_, n_stats, L.ffn_norm, c_.eps, nullptr, nullptr, BITNET_HIP_FUSE_SILU_MUL, pf_hh_, nullptr, nullptr, stream_));
     else
-        BCHK(bitnet_hip_matmul_fused_dev(L.gateup, pf_x_, f.h16 ? static_cast<float *>(pf_hh_) : pf_h_, N, L.ffn_norm, c_.eps, nullptr,
+        BCHK(bitnet_hip_matmul_fused_dev(L.gateup, pf_x_, f.h16 ? static_cast<float *>(pf_hh_.get()) : pf_h_, N, L.ffn_norm, c_.eps, nullptr,
                                          BITNET_HIP_FUSE_SILU_MUL | (f.h16 ? BITNET_HIP_FUSE_Y_F16 : 0) | f.f6, f.digits, pf_gemm_ws_, pf_gemm_ws_bytes_, stream_));
     return 0;
 }
@@ -1287,7 +1251,7 @@ int Decoder::prompt_layers(size_t N, const PromptForm &f, const AttnOp &op) {
         if (int rc = prompt_attention(L, N, f.f16_rows() ? pf_atth_ : pf_att_, f.f16_rows(), op)) return rc;
         if (int rc = project_o(L, N, f)) return rc;
         if (int rc = project_gateup(L, N, f)) return rc;
-        if (int rc = project_down(L, N, f, l + 1 < layers_.size() ? layers_[l + 1].attn_norm : nullptr)) return rc;
+        if (int rc = project_down(L, N, f, l + 1 < layers_.size() ? layers_[l + 1].attn_norm.get() : nullptr)) return rc;
     }
     if (f.chain || f.qb) last_prefill_path_ = f.chain ? 1 : 2;
     return 0;
@@ -1389,14 +1353,12 @@ int Decoder::ensure_fork_tables() {
     if (fork_tables_) return 0;
     const size_t L = layers_.size(), M = BITNET_HIP_BATCH_MAX;
     std::vector<void *> t(2 * L, nullptr);
-    void **tables = nullptr;
-    HCHK(hipMalloc((void **)&tables, (2 + 2 * M) * L * sizeof(void *)));
+    HCHK(fork_tables_.alloc((2 + 2 * M) * L));
     for (size_t l = 0; l < L; ++l) t[l] = layers_[l].kcache, t[L + l] = layers_[l].vcache;
-    if (hipError_t e = hipMemcpy(tables, t.data(), 2 * L * sizeof(void *), hipMemcpyHostToDevice)) {
-        (void)hipFree(tables);
+    if (hipError_t e = hipMemcpy(fork_tables_, t.data(), 2 * L * sizeof(void *), hipMemcpyHostToDevice)) {
+        fork_tables_.reset();  // "built once": a table that is held is a table that is filled
         HCHK(e);
     }
-    fork_tables_ = tables;
     return 0;
 }
 
@@ -1633,24 +1595,20 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
     hipStream_t s = (hipStream_t)stream_;
     const size_t ws_need = bitnet_hip_score_workspace_bytes((size_t)M, H, V);
     if (ws_need == 0) return fail_arg("step_wide: dimensions too large");
-    if (!wide_tables_) HCHK(hipMalloc((void **)&wide_tables_, (2 * NL + 6) * W * sizeof(void *)));
+    if (!wide_tables_) HCHK(wide_tables_.alloc((2 * NL + 6) * W));
     if (M > wide_cap_ || ws_need > wide_ws_bytes_) {
         const size_t cap = (size_t)(M > wide_cap_ ? M : wide_cap_), sb = bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos);
-        for (void *q : {(void *)wide_scratch_, (void *)wide_logits_, (void *)wide_nll_, (void *)wide_am_, (void *)wide_tgt_, wide_ws_})
-            if (q) hipFree(q);
-        wide_scratch_ = wide_logits_ = wide_nll_ = nullptr;
-        wide_am_ = wide_tgt_ = nullptr;
-        wide_ws_ = nullptr;
+        release_all(wide_scratch_, wide_logits_, wide_nll_, wide_am_, wide_tgt_, wide_ws_);
         wide_cap_ = 0, wide_ws_bytes_ = 0;
         const size_t wb = bitnet_hip_score_workspace_bytes(cap, H, V);
-        HCHK(hipMalloc((void **)&wide_scratch_, cap * sb));
+        HCHK(wide_scratch_.alloc_bytes(cap * sb));
         HCHK(hipMemsetAsync(wide_scratch_, 0, cap * sb, s));  // the combine requests records past the context (and drops them by index): valid, finite memory
-        HCHK(dalloc(&wide_logits_, cap * V));
-        HCHK(dalloc(&wide_nll_, cap));
-        HCHK(dalloc(&wide_am_, cap));
-        HCHK(dalloc(&wide_tgt_, cap));
+        HCHK(wide_logits_.alloc(cap * V));
+        HCHK(wide_nll_.alloc(cap));
+        HCHK(wide_am_.alloc(cap));
+        HCHK(wide_tgt_.alloc(cap));
         HCHK(hipMemsetAsync(wide_tgt_, 0xff, cap * 4, s));  // target -1: no NLL, the head leaves logits and argmax
-        HCHK(hipMalloc(&wide_ws_, wb));
+        HCHK(wide_ws_.alloc(wb));
         wide_cap_ = (int)cap, wide_ws_bytes_ = wb;
     }
     if (int rc = ensure_prompt_buffers(M, 16)) return rc;
@@ -1664,7 +1622,7 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
             void **g = t.data() + 2 * NL * W;
             if (d->refresh_logits()) return fail("step_wide: refresh_logits");  // the pick writes this row from now on
             g[0 * W + i] = d->pos_, g[1 * W + i] = d->history_, g[2 * W + i] = d->n_forced_, g[3 * W + i] = d->logits_;
-            g[4 * W + i] = d->sampling_ ? nullptr : d->token_, g[5 * W + i] = d->sampling_ ? nullptr : d->pos_;
+            g[4 * W + i] = d->sampling_ ? nullptr : d->token_.get(), g[5 * W + i] = d->sampling_ ? nullptr : d->pos_.get();
         }
         HCHK(hipMemcpy(wide_tables_, t.data(), t.size() * sizeof(void *), hipMemcpyHostToDevice));
     }
@@ -1712,20 +1670,17 @@ int Decoder::ensure_prompt_buffers(int n, size_t attn_need) {
     if (n > pf_cap_ || attn_need > pf_attn_ws_bytes_) {
         const size_t N = (size_t)(n > pf_cap_ ? n : pf_cap_);  // the row buffers never shrink: a short turn at a long context keeps the prompt's
         const size_t attn_bytes = attn_need > pf_attn_ws_bytes_ ? attn_need : pf_attn_ws_bytes_;
-        for (void *q : {(void *)pf_x_, (void *)pf_qkv_, (void *)pf_att_, (void *)pf_h_, pf_gemm_ws_, pf_attn_ws_})
-            if (q) hipFree(q);
-        pf_x_ = pf_qkv_ = pf_att_ = pf_h_ = nullptr;
-        pf_gemm_ws_ = pf_attn_ws_ = nullptr;
+        release_all(pf_x_, pf_qkv_, pf_att_, pf_h_, pf_gemm_ws_, pf_attn_ws_);
         pf_cap_ = 0;
         pf_attn_ws_bytes_ = 0;
         pf_gemm_ws_bytes_ = bitnet_hip_matmul_workspace_bytes(N, H > F ? H : F, 4);
         pf_attn_ws_bytes_ = attn_bytes;
-        HCHK(dalloc(&pf_x_, N * H));
-        HCHK(dalloc(&pf_qkv_, N * (QD + 2 * KD)));
-        HCHK(dalloc(&pf_att_, N * QD));
-        HCHK(dalloc(&pf_h_, N * F));
-        HCHK(hipMalloc(&pf_gemm_ws_, pf_gemm_ws_bytes_));
-        HCHK(hipMalloc(&pf_attn_ws_, pf_attn_ws_bytes_));
+        HCHK(pf_x_.alloc(N * H));
+        HCHK(pf_qkv_.alloc(N * (QD + 2 * KD)));
+        HCHK(pf_att_.alloc(N * QD));
+        HCHK(pf_h_.alloc(N * F));
+        HCHK(pf_gemm_ws_.alloc(pf_gemm_ws_bytes_));
+        HCHK(pf_attn_ws_.alloc(pf_attn_ws_bytes_));
         pf_cap_ = (int)N;
     }
     return 0;
@@ -1757,15 +1712,12 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
     PromptForm f;
     if (int rc = prompt_form(N, digits, true, &f)) return rc;
     if (nq > sp_cap_ || n > sp_ctx_) {
-        for (void *q : {sp_kv_send_, sp_kv_all_, (void *)sp_block_pos_, (void *)sp_tokens_})
-            if (q) hipFree(q);
-        sp_kv_send_ = sp_kv_all_ = nullptr;
-        sp_block_pos_ = sp_tokens_ = nullptr;
+        release_all(sp_kv_send_, sp_kv_all_, sp_block_pos_, sp_tokens_);
         sp_cap_ = sp_ctx_ = 0;
-        HCHK(hipMalloc(&sp_kv_send_, N * 2 * KD * 4));
-        HCHK(hipMalloc(&sp_kv_all_, (size_t)n * 2 * KD * 4));
-        HCHK(dalloc(&sp_block_pos_, N / 64));
-        HCHK(dalloc(&sp_tokens_, N));
+        HCHK(sp_kv_send_.alloc(N * 2 * KD * 4));
+        HCHK(sp_kv_all_.alloc((size_t)n * 2 * KD * 4));
+        HCHK(sp_block_pos_.alloc(N / 64));
+        HCHK(sp_tokens_.alloc(N));
         sp_cap_ = nq;
         sp_ctx_ = n;
     }
@@ -1817,7 +1769,7 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
     BCHK(bitnet_hip_embed_f16_dev(embed_, sp_tokens_, nullptr, N, H, (size_t)c_.vocab, pf_x_, s));
     const size_t ld = QD + 2 * KD, per_rank = N * 2 * KD * esz;
     // (f.h16: f16 hand-over of the attention output and of silu * up; f.hybrid: o / down on the f16 matrix cores -- long shares only)
-    float *att_out = f.h16 ? static_cast<float *>(pf_atth_) : pf_att_;
+    float *att_out = f.h16 ? static_cast<float *>(pf_atth_.get()) : pf_att_;
     const int aflags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (f.h16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
     // its own loop: the attention has two phases around the collective, and the timing marks sit between the launches
     for (size_t l = 0; l < layers_.size(); ++l) {
@@ -1875,7 +1827,7 @@ int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_f
             }
             HCHK(hipEventRecord((hipEvent_t)sp_ev_gather_, (hipStream_t)comm_stream_));
             HCHK(hipStreamWaitEvent(s, (hipEvent_t)sp_ev_gather_, 0));
-            last = static_cast<const float *>(sp_kv_all_);
+            last = static_cast<const float *>(sp_kv_all_.get());
         }
         const int rc = finish_prefill(n, last, with_logits);
         if (rc) return rc;
@@ -1913,25 +1865,20 @@ int Decoder::score(int n, int digits, float *nll_out, int32_t *argmax_out, float
     const size_t need = bitnet_hip_score_workspace_bytes(N, H, V);
     if (need == 0) return fail_arg("score: dimensions too large");
     if (n > sc_cap_ || need > sc_ws_bytes_) {
-        for (void *q : {(void *)sc_tgt_, (void *)sc_am_, (void *)sc_nll_, sc_ws_})
-            if (q) hipFree(q);
-        sc_tgt_ = sc_am_ = nullptr;
-        sc_nll_ = nullptr;
-        sc_ws_ = nullptr;
+        release_all(sc_tgt_, sc_am_, sc_nll_, sc_ws_);
         sc_cap_ = 0;
         sc_ws_bytes_ = 0;
-        HCHK(dalloc(&sc_tgt_, N));
-        HCHK(dalloc(&sc_am_, N));
-        HCHK(dalloc(&sc_nll_, N));
-        HCHK(hipMalloc(&sc_ws_, need));
+        HCHK(sc_tgt_.alloc(N));
+        HCHK(sc_am_.alloc(N));
+        HCHK(sc_nll_.alloc(N));
+        HCHK(sc_ws_.alloc(need));
         sc_cap_ = n;
         sc_ws_bytes_ = need;
     }
     if (logits_rows > sc_logits_cap_) {
-        if (sc_logits_) hipFree(sc_logits_);
-        sc_logits_ = nullptr;
+        release_all(sc_logits_);
         sc_logits_cap_ = 0;
-        HCHK(dalloc(&sc_logits_, (size_t)logits_rows * V));
+        HCHK(sc_logits_.alloc((size_t)logits_rows * V));
         sc_logits_cap_ = logits_rows;
     }
     hipStream_t s = (hipStream_t)stream_;
@@ -1941,8 +1888,8 @@ int Decoder::score(int n, int digits, float *nll_out, int32_t *argmax_out, float
     // row r predicts token r + 1 of the history (the prompt); the last row has no target
     HCHK(hipMemcpyAsync(sc_tgt_, history_ + 1, (N - 1) * 4, hipMemcpyDeviceToDevice, s));
     HCHK(hipMemsetAsync(sc_tgt_ + (N - 1), 0xff, 4, s));
-    BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, N, sc_tgt_, sc_nll_, argmax_out ? sc_am_ : nullptr,
-                                  logits_rows > 0 ? sc_logits_ : nullptr, (size_t)logits_rows, sc_ws_, sc_ws_bytes_, s));
+    BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, N, sc_tgt_, sc_nll_, argmax_out ? sc_am_.get() : nullptr,
+                                  logits_rows > 0 ? sc_logits_.get() : nullptr, (size_t)logits_rows, sc_ws_, sc_ws_bytes_, s));
     HCHK(timer.stop(s, elapsed_ms));
     HCHK(hipMemcpy(nll_out, sc_nll_, (N - 1) * 4, hipMemcpyDeviceToHost));
     if (argmax_out) HCHK(hipMemcpy(argmax_out, sc_am_, N * 4, hipMemcpyDeviceToHost));
@@ -2025,8 +1972,8 @@ int Decoder::probe_kernel(int kind, int reps, float *us_per_launch, double *byte
                 case 3: rc = bitnet_hip_gemv_q_dev(L.gateup, qa_x2_, st_x2_, L.ffn_norm, c_.eps, nullptr, BITNET_HIP_FUSE_SILU_MUL, nullptr, qa_h_, nullptr, nullptr, stream_); break;
                 default:
                     // x_ is both the residual stream's next value and (kind 2) its old one in the real step; here it is only written
-                    rc = bitnet_hip_gemv_q_dev(L.down, qa_h_, nullptr, nullptr, 0.f, x2_, 0, ref_t_, more ? qa_x_ : nullptr, more ? layers_[li + 1].attn_norm : nullptr,
-                                               more ? st_x_ : nullptr, stream_);
+                    rc = bitnet_hip_gemv_q_dev(L.down, qa_h_, nullptr, nullptr, 0.f, x2_, 0, ref_t_, more ? qa_x_.get() : nullptr, more ? layers_[li + 1].attn_norm.get() : nullptr,
+                                               more ? st_x_.get() : nullptr, stream_);
                     break;
             }
             ++launches;
@@ -2339,4 +2286,5 @@ int bitnet_host_probe_kernel(void *d, int kind, int reps, float *us_per_launch, 
     return D->probe_kernel(kind, reps, us_per_launch, bytes_per_launch);
 }
 uint64_t bitnet_host_weight_bytes(void *d) { LIVE(0); return D->weight_bytes(); }
+uint64_t bitnet_host_device_bytes(void) { return bitnet_host::dev_bytes_live.load(); }
 }

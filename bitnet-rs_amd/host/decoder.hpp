@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "bitnet_hip.h"
+#include "dev_buffer.hpp"
 
 extern "C" {
 // The collective of the token-parallel prefill as the host supplies it: gather `bytes_per_rank` bytes from every rank into
@@ -59,9 +60,17 @@ struct ProjSpec {
     int8_t code_map[4] = {-2, -1, 0, 1};
 };
 
-class Decoder {
+// A decoder's streams and events, as a BASE of Decoder: bases go after members, so every DevBuf member is freed before its streams are destroyed.
+struct DecoderStreams {
+    void *stream_ = nullptr;
+    void *comm_stream_ = nullptr, *sp_ev_pack_ = nullptr, *sp_ev_gather_ = nullptr;  // the all-gather's own stream and its two ties to the compute stream
+    std::vector<void *> sp_tev_;                                                     // the sharded prefill's timing events (set_phase_timing)
+    ~DecoderStreams();
+};
+
+class Decoder : private DecoderStreams {
   public:
-    explicit Decoder(const Config &cfg);
+    explicit Decoder(const Config &cfg) : Decoder(cfg, true) {}
     ~Decoder();
     Decoder(const Decoder &) = delete;
     Decoder &operator=(const Decoder &) = delete;
@@ -339,6 +348,7 @@ class Decoder {
   private:
     int fail(const char *what);
     int fail_arg(const char *what);
+    Decoder(const Config &cfg, bool own_norms);  // own_norms false: the borrowing constructor points the norm vectors at the owner's
     bool dead_ = false;
     // attention form of a step: 0 = two kernels, 64-position chunks; 1 = one kernel + merging o-projection (short
     // contexts: 4 records); 2 = two kernels, 128-position chunks (more chunks than CUs); 3 = as 1, 8 records (QAct path)
@@ -365,11 +375,10 @@ class Decoder {
 
     Config c_;
     std::string err_;
-    void *stream_ = nullptr;
     struct Layer {
-        float *attn_norm = nullptr, *ffn_norm = nullptr;
+        DevBuf<float> attn_norm, ffn_norm;  // borrowed from the owner's layer by a borrower, as the four handles are
         bitnet_hip_weights_t qkv = 0, o = 0, gateup = 0, down = 0;
-        float *kcache = nullptr, *vcache = nullptr;
+        DevBuf<float> kcache, vcache;
         bool q_ok = false;  // all four matrices take QAct inputs (bitnet_hip_gemv_q_supported)
     };
     int attn_launch(Layer &L, int form, float *out, void *qout);
@@ -411,11 +420,11 @@ class Decoder {
     // wide buffers (none before the first call): device pointer tables [2 * n_layers + 6][64] -- per layer K then V caches, then position, history,
     // forced count, logits row, and the pick's token / position tables (NULL for a member that samples) --, the attention scratch of wide_cap_
     // sequences (zero-filled), the head's [wide_cap_, vocab] logits, argmax, nll, targets (-1) and workspace
-    void **wide_tables_ = nullptr;
+    DevBuf<void *> wide_tables_;
     int wide_cap_ = 0;
-    float *wide_scratch_ = nullptr, *wide_logits_ = nullptr, *wide_nll_ = nullptr;
-    int32_t *wide_am_ = nullptr, *wide_tgt_ = nullptr;
-    void *wide_ws_ = nullptr;
+    DevBuf<float> wide_scratch_, wide_logits_, wide_nll_;
+    DevBuf<int32_t> wide_am_, wide_tgt_;
+    DevBuf<void> wide_ws_;
     size_t wide_ws_bytes_ = 0;
     void release_layer(Layer &L);  // frees the layer's handles, subtracts their bytes, drops the captured graphs
     void drop_graphs();
@@ -427,33 +436,33 @@ class Decoder {
     int ensure_screen_image();  // the owner's image, built if missing (set_globals, set_head_screen)
     int refresh_logits();       // logits_ stale after a screened step: the full head once on the saved head input
     // the head input the last screened launch saved: behind ub and the lb maxima in the workspace (layout: include/bitnet_hip.h)
-    float *screen_x() const { return screen_ws_ + ((size_t)c_.vocab + 3) / 4 * 4 + ((size_t)screen_wgs_ + 3) / 4 * 4; }
-    void *screen_ = nullptr;        // int8 screening image of embed_ (borrowed with it)
-    float *screen_ws_ = nullptr;    // ub, lb maxima, saved head input, counters, rescored rows (bitnet_hip_head_screen_ws_bytes); own
+    float *screen_x() const { return screen_ws_.get() + ((size_t)c_.vocab + 3) / 4 * 4 + ((size_t)screen_wgs_ + 3) / 4 * 4; }
+    DevBuf<void> screen_;           // int8 screening image of embed_ (borrowed with it)
+    DevBuf<float> screen_ws_;       // ub, lb maxima, saved head input, counters, rescored rows (bitnet_hip_head_screen_ws_bytes); own
     bool head_screen_on_ = true;    // BITNET_HOST_HEAD_SCREEN / set_head_screen
     bool pick_screened_ = false;    // what the last pick_token issued (or captured)
     bool logits_stale_ = false;     // the last executed head was the screened one: logits_ does not hold its logits yet
     int graphs_screened_ = -1;      // screen_step(false) when the live graphs were captured (-1: none captured)
     int adopt_projections(Layer &L, bitnet_hip_weights_t h[7]);
-    std::vector<Layer> layers_;
-    void *embed_ = nullptr;
-    float *final_norm_ = nullptr;
-    float *rope_sin_ = nullptr, *rope_cos_ = nullptr;
-    float *x_ = nullptr, *x2_ = nullptr, *qkv_ = nullptr, *att_ = nullptr, *h_ = nullptr, *logits_ = nullptr;
-    void *qa_x_ = nullptr, *qa_x2_ = nullptr, *qa_att_ = nullptr, *qa_h_ = nullptr;  // QAct records of x, x2, attention output, silu(gate)*up
-    double *st_x_ = nullptr, *st_x2_ = nullptr;                                       // LayerNorm statistics pairs of x, x2
+    std::vector<Layer> layers_;  // sized once, never resized
+    DevBuf<void> embed_;         // borrowed by a borrower, as final_norm_
+    DevBuf<float> final_norm_;
+    DevBuf<float> rope_sin_, rope_cos_;
+    DevBuf<float> x_, x2_, qkv_, att_, h_, logits_;
+    DevBuf<void> qa_x_, qa_x2_, qa_att_, qa_h_;  // QAct records of x, x2, attention output, silu(gate)*up
+    DevBuf<double> st_x_, st_x2_;                // LayerNorm statistics pairs of x, x2
     int act_mode_ = 1;
     bool kv_f16_ = false;
     std::string trace_dir_;  // BITNET_TRACE_DIR at construction
-    float *ref_n_ = nullptr, *ref_gu_ = nullptr, *ref_t_ = nullptr;  // unfused reference step: normalised row, gate|up tiles, projection out
-    void *scratch_ = nullptr;
-    float *attn_scratch_ = nullptr;
-    int32_t *pos_ = nullptr, *n_forced_ = nullptr, *history_ = nullptr, *token_ = nullptr;
+    DevBuf<float> ref_n_, ref_gu_, ref_t_;  // unfused reference step: normalised row, gate|up tiles, projection out
+    DevBuf<void> scratch_;
+    DevBuf<float> attn_scratch_;
+    DevBuf<int32_t> pos_, n_forced_, history_, token_;
     bitnet_hip_sampler *sampler_ = nullptr;
     bool sampling_ = false;
     int lp_top_n_ = -1;  // set_logprobs
-    bitnet_hip_logprob_record *lp_records_ = nullptr;  // [max_pos]
-    void *lp_scratch_ = nullptr;
+    DevBuf<bitnet_hip_logprob_record> lp_records_;  // [max_pos]
+    DevBuf<void> lp_scratch_;
     int host_forced_ = 0;
     bitnet_hip_stop *stop_ = nullptr;  // set_stop: created at the first config, kept until the decoder goes
     bool stop_on_ = false;
@@ -462,35 +471,33 @@ class Decoder {
     // then the destinations' K [8][n_layers] and V [8][n_layers] (uploaded per call).  shift() uses [0] and [1].
     int ensure_fork_tables();
     int fork_from_this(Decoder *const *dsts, int n_dst, int n);
-    void **fork_tables_ = nullptr;
+    DevBuf<void *> fork_tables_;
     // sharded prefill buffers (grown on demand)
     int sp_cap_ = 0, sp_ctx_ = 0;
-    void *sp_kv_send_ = nullptr, *sp_kv_all_ = nullptr;
-    void *comm_stream_ = nullptr, *sp_ev_pack_ = nullptr, *sp_ev_gather_ = nullptr;  // the all-gather's own stream and its two ties to the compute stream
-    int32_t *sp_block_pos_ = nullptr, *sp_tokens_ = nullptr;
+    DevBuf<void> sp_kv_send_, sp_kv_all_;
+    DevBuf<int32_t> sp_block_pos_, sp_tokens_;
     // per-phase timing of the sharded prefill (set_phase_timing): 8 timing events per layer on the compute / comm streams, and the
     // medians over the layers of the last timed call: [0] projections (q|k|v + pack, o, gate|up, down), [1] attention (both phases),
     // [2] the part of the all-gather the compute stream had to wait for, [3] the all-gather itself on its own stream; microseconds
     bool sp_timing_ = false;
-    std::vector<void *> sp_tev_;
     float sp_phase_us_[4] = {0.f, 0.f, 0.f, 0.f};
     // prefill buffers (grown on demand)
     int pf_cap_ = 0;
-    float *pf_x_ = nullptr, *pf_qkv_ = nullptr, *pf_att_ = nullptr, *pf_h_ = nullptr;
-    void *pf_gemm_ws_ = nullptr, *pf_attn_ws_ = nullptr;
+    DevBuf<float> pf_x_, pf_qkv_, pf_att_, pf_h_;
+    DevBuf<void> pf_gemm_ws_, pf_attn_ws_;
     // the f16 activation chain of the prompt forward (prefill_chain): f16 rows handed from kernel to kernel, LayerNorm statistics partials
     int pfc_cap_ = 0;
-    void *pf_xh_ = nullptr, *pf_atth_ = nullptr, *pf_hh_ = nullptr;
-    float *pf_stats_ = nullptr;
-    void *pf_qb_ = nullptr;   // QB32 rows of gamma * x (the input of q|k|v and of gate|up), bitnet_hip_qb32_bytes(pfc_cap_, hidden)
+    DevBuf<void> pf_xh_, pf_atth_, pf_hh_;
+    DevBuf<float> pf_stats_;
+    DevBuf<void> pf_qb_;      // QB32 rows of gamma * x (the input of q|k|v and of gate|up), bitnet_hip_qb32_bytes(pfc_cap_, hidden)
     int pf_qb_cap_ = 0;
     bool force_scaled_ = false;   // the prompt is being repeated on the row-scaled forms after an f16 hand-over value was clamped (prefill)
     int saturation_fallbacks_ = 0;
     // score buffers (grown on demand): targets, nll, argmax, dumped logits, workspace of bitnet_hip_score_f16_dev
     int sc_cap_ = 0, sc_logits_cap_ = 0;
-    int32_t *sc_tgt_ = nullptr, *sc_am_ = nullptr;
-    float *sc_nll_ = nullptr, *sc_logits_ = nullptr;
-    void *sc_ws_ = nullptr;
+    DevBuf<int32_t> sc_tgt_, sc_am_;
+    DevBuf<float> sc_nll_, sc_logits_;
+    DevBuf<void> sc_ws_;
     size_t sc_ws_bytes_ = 0;
     int last_prefill_path_ = 0;  // what the last prefill() ran: 0 digit planes (+ f16 hand-over / hybrid), 1 the f16 chain, 2 the QB32 chain
     int prefill_qb32_ = -1;   // BITNET_HOST_PREFILL_QB32: -1 not read yet; 1 = the QB32 chain where it applies (opt-in), 0 (default) = quantiser launches
@@ -584,4 +591,5 @@ int bitnet_host_blake3_hex(const void *data, size_t len, char *out65);  // the t
 int bitnet_host_probe_gateup(void *d, int reps, float *us_per_launch, double *bytes_per_launch);
 int bitnet_host_probe_kernel(void *d, int kind, int reps, float *us_per_launch, double *bytes_per_launch);
 uint64_t bitnet_host_weight_bytes(void *d);
+uint64_t bitnet_host_device_bytes(void);  // bytes of device memory the process's decoders and batches own now (every DevBuf; not the weight handles)
 }

@@ -228,6 +228,10 @@ class HipLib:
         L.bitnet_hip_sampler_set_mirostat.restype = C.c_int
         L.bitnet_hip_sampler_mirostat_state.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         L.bitnet_hip_sampler_mirostat_state.restype = C.c_int
+        L.bitnet_hip_sampler_set_constraints.argtypes = [_vp, C.POINTER(Constraints)]
+        L.bitnet_hip_sampler_set_constraints.restype = C.c_int
+        L.bitnet_hip_sampler_constraints_state.argtypes = [_vp, C.POINTER(C.c_uint64)]
+        L.bitnet_hip_sampler_constraints_state.restype = C.c_int
         L.bitnet_hip_sampler_reset.argtypes = [_vp]
         L.bitnet_hip_sampler_draws.argtypes = [_vp, C.POINTER(C.c_uint64)]
         L.bitnet_hip_sample_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -857,6 +861,44 @@ class MirostatConfig(C.Structure):
     _fields_ = [("tau", C.c_float), ("eta", C.c_float)]
 
 
+CONSTRAINT_MAX_HOLD, CONSTRAINT_MAX_NGRAM = 32, 8
+
+
+class Constraints(C.Structure):
+    """bitnet_hip_constraints.  make() keeps the arrays the pointers refer to alive on the object."""
+    _fields_ = [("bias_ids", C.POINTER(C.c_int32)), ("bias_values", _f32p), ("n_bias", _sz), ("allowed_ids", C.POINTER(C.c_int32)),
+                ("n_allowed", _sz), ("hold_ids", C.POINTER(C.c_int32)), ("n_hold", _sz), ("min_tokens", C.c_int32), ("no_repeat_ngram", C.c_int32)]
+
+    @classmethod
+    def make(cls, bias=None, allowed=None, hold=(), min_tokens: int = 0, no_repeat_ngram: int = 0) -> "Constraints":
+        """bias: {id: value} or (id, value) pairs, in order (the last entry of a duplicate id wins; -inf bans); allowed: ids, every other id is
+        banned (None or empty: no allowed list); hold: ids banned while fewer than min_tokens tokens were chosen; no_repeat_ngram: 0 = off."""
+        pairs = list(bias.items()) if isinstance(bias, dict) else list(bias if bias is not None else ())
+
+        def i32(xs):  # ids as int32, refused rather than wrapped when they do not fit
+            a = np.asarray(list(xs), dtype=np.int64).reshape(-1)
+            if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+                raise ValueError(f"constraints: token id outside the int32 range: {int(a.min())} .. {int(a.max())}")
+            return _np(a.astype(np.int32), np.int32)
+
+        bi, bv = i32(p[0] for p in pairs), _np(np.asarray([p[1] for p in pairs], dtype=np.float32), np.float32)
+        al, ho = i32(allowed if allowed is not None else ()), i32(hold)
+        p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
+        cfg = cls(p(bi), bv.ctypes.data_as(_f32p) if bv.size else None, bi.size, p(al), al.size, p(ho), ho.size, int(min_tokens), int(no_repeat_ngram))
+        cfg._keep = (bi, bv, al, ho)
+        return cfg
+
+    @classmethod
+    def from_args(cls, bias, allowed, hold, min_tokens, no_repeat_ngram, off, on=False) -> "Constraints | None":
+        """None (= off) for off=True, or for a call that names nothing unless on=True (an empty config: it edits nothing, and the chosen
+        tokens are counted from then on); else make(...)."""
+        n = lambda v: 0 if v is None else len(v)
+        hold = list(hold)
+        allowed = None if allowed is None else list(allowed)
+        nothing = not n(bias) and not n(allowed) and not hold and not min_tokens and not no_repeat_ngram
+        return None if off or (nothing and not on) else cls.make(bias, allowed, hold, min_tokens, no_repeat_ngram)
+
+
 class Sampler:
     """One bitnet_hip_sampler: state (config, ChaCha20 key, word counter, token counts) in device memory."""
 
@@ -907,6 +949,20 @@ class Sampler:
         mu, fb = C.c_float(0.0), C.c_uint64(0)
         self.lib._check(self.lib.c.bitnet_hip_sampler_mirostat_state(self.h, C.byref(mu), C.byref(fb)))
         return float(mu.value), int(fb.value)
+
+    def set_constraints(self, bias=None, allowed=None, hold=(), min_tokens: int = 0, no_repeat_ngram: int = 0, *, off: bool = False, on: bool = False) -> None:
+        """Logit constraints in front of every other stage, inside the same launch (bitnet_hip_sampler_set_constraints): bias {id: value}
+        (-inf bans), allowed ids (every other id banned), hold ids banned until min_tokens tokens were chosen, no_repeat_ngram.  With no
+        arguments, or off=True: constraints off; on=True with no arguments: an empty config, which edits nothing and lets chosen() count every
+        token from then on.  Graphs that captured sample_dev follow it; chosen() stays."""
+        cfg = Constraints.from_args(bias, allowed, hold, min_tokens, no_repeat_ngram, off, on)
+        self.lib._check(self.lib.c.bitnet_hip_sampler_set_constraints(self.h, C.byref(cfg) if cfg is not None else None))
+
+    def chosen(self) -> int:
+        """Tokens chosen by launches that ran with constraints on since the last reset (the hold-off's count).  Synchronous."""
+        g = C.c_uint64(0)
+        self.lib._check(self.lib.c.bitnet_hip_sampler_constraints_state(self.h, C.byref(g)))
+        return int(g.value)
 
     def sample_host(self, logits, generated=()) -> int:
         """Sampler::sample(&logits, &generated_tokens): the whole generated list on every call."""
@@ -1298,6 +1354,10 @@ class HostDecoder:
         L.bitnet_host_set_mirostat.restype = C.c_int
         L.bitnet_host_mirostat_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         L.bitnet_host_mirostat_state.restype = C.c_int
+        L.bitnet_host_set_constraints.argtypes = [C.c_void_p, C.POINTER(Constraints)]
+        L.bitnet_host_set_constraints.restype = C.c_int
+        L.bitnet_host_constraints_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bitnet_host_constraints_state.restype = C.c_int
         L.bitnet_host_set_logprobs.argtypes = [C.c_void_p, C.c_int]
         L.bitnet_host_set_logprobs.restype = C.c_int
         L.bitnet_host_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -1431,6 +1491,20 @@ class HostDecoder:
         mu, fb = C.c_float(0.0), C.c_uint64(0)
         self._check(self.c.bitnet_host_mirostat_state(self.h, C.byref(mu), C.byref(fb)))
         return float(mu.value), int(fb.value)
+
+    def set_constraints(self, bias=None, allowed=None, hold=(), min_tokens: int = 0, no_repeat_ngram: int = 0, *, off: bool = False, on: bool = False) -> None:
+        """Logit constraints behind every with-logits step, on the device and inside the captured graphs and generate()'s queued chunks:
+        bias {id: value} (-inf bans), allowed ids (every other id banned), hold ids banned until min_tokens tokens were chosen (an EOS
+        hold-off), no_repeat_ngram.  Needs set_sampling first (temperature 0 is greedy).  No arguments, or off=True: off; on=True with no
+        arguments: an empty config (nothing is edited, chosen() counts).  Drops no graphs."""
+        cfg = Constraints.from_args(bias, allowed, hold, min_tokens, no_repeat_ngram, off, on)
+        self._check(self.c.bitnet_host_set_constraints(self.h, C.byref(cfg) if cfg is not None else None))
+
+    def chosen(self) -> int:
+        """Tokens the decoder's sampler chose under constraints since its last reset; 0 without a sampler.  Synchronises."""
+        g = C.c_uint64(0)
+        self._check(self.c.bitnet_host_constraints_state(self.h, C.byref(g)))
+        return int(g.value)
 
     def sampling_draws(self) -> int:
         """ChaCha20 words the decoder's sampler has consumed since its last reset / set_sampling (one per non-greedy token)."""

@@ -473,6 +473,24 @@ int Decoder::mirostat_state(float *mu, uint64_t *fallbacks) {
     return 0;
 }
 
+int Decoder::set_constraints(const bitnet_hip_constraints *cfg) {
+    if (!cfg && !sampler_) return 0;  // off on a decoder that never sampled: nothing to switch off
+    if (cfg && (!sampling_ || !sampler_)) return fail_arg("set_constraints: sampling is off (set_sampling first; temperature 0 is greedy)");
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));  // on or off, the config is copied synchronously: no queued step may still read the old one
+    // bias, bans and the hold list are reached through device memory by the sampling launch: the captured graphs follow them and stay
+    BCHK(bitnet_hip_sampler_set_constraints(sampler_, cfg));
+    return 0;
+}
+
+int Decoder::constraints_state(uint64_t *chosen) {
+    if (!chosen) return fail_arg("constraints_state: null pointer");
+    *chosen = 0;
+    if (!sampler_) return 0;
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    BCHK(bitnet_hip_sampler_constraints_state(sampler_, chosen));
+    return 0;
+}
+
 int Decoder::sampling_draws(uint64_t *out) {
     if (!out) {
         err_ = "sampling_draws: null pointer";
@@ -2147,6 +2165,8 @@ int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg) { L
 int bitnet_host_set_sampling_ex(void *d, const bitnet_hip_sampling_config_ex *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_sampling_ex(cfg); }
 int bitnet_host_set_mirostat(void *d, const bitnet_hip_mirostat_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_mirostat(cfg); }
 int bitnet_host_mirostat_state(void *d, float *mu, uint64_t *fallbacks) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->mirostat_state(mu, fallbacks); }
+int bitnet_host_set_constraints(void *d, const bitnet_hip_constraints *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_constraints(cfg); }
+int bitnet_host_constraints_state(void *d, uint64_t *chosen) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->constraints_state(chosen); }
 int bitnet_host_sampling_draws(void *d, uint64_t *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->sampling_draws(out); }
 int bitnet_host_set_stop(void *d, const bitnet_hip_stop_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_stop(cfg); }
 int bitnet_host_stop_state(void *d, bitnet_hip_stop_state *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->stop_state(out); }

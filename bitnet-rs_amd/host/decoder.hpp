@@ -134,6 +134,12 @@ class Decoder : private DecoderStreams {
     // destination's with its sampler.
     int set_mirostat(const bitnet_hip_mirostat_config *cfg);
     int mirostat_state(float *mu, uint64_t *fallbacks);  // synchronises; 0 / 0 without a sampler
+    // Logit constraints on this decoder's sampler (bitnet_hip_sampler_set_constraints: logit bias, bans, an allowed set, an EOS hold-off, an
+    // n-gram block): needs sampling on -- greedy decoding with constraints is set_sampling with temperature 0; NULL = off.  Drops no graphs: the
+    // launch reaches the config through device memory.  The config belongs to this decoder.  reset() zeroes the count of chosen tokens, rewind()
+    // and shift() leave it as they leave the counts, fork() resets each destination's with its sampler.
+    int set_constraints(const bitnet_hip_constraints *cfg);
+    int constraints_state(uint64_t *chosen);  // synchronises; 0 without a sampler
     int sampling_draws(uint64_t *out);
     // The reference's logits tap on the generation path (GenerationConfig::{logits_tap_steps, logits_topk, logits_cb}, crates/bitnet-inference/src/
     // config.rs:87-93, engine.rs:1182-1210; the CLI's LogitStep records, crates/bitnet-cli/src/main.rs:1337-1373) on the device: top_n = -1 (default)
@@ -543,6 +549,8 @@ int bitnet_host_set_sampling(void *d, const bitnet_hip_sampling_config *cfg);  /
 int bitnet_host_set_sampling_ex(void *d, const bitnet_hip_sampling_config_ex *cfg);  // NULL = greedy
 int bitnet_host_set_mirostat(void *d, const bitnet_hip_mirostat_config *cfg);  // NULL = off
 int bitnet_host_mirostat_state(void *d, float *mu, uint64_t *fallbacks);
+int bitnet_host_set_constraints(void *d, const bitnet_hip_constraints *cfg);  // NULL = off
+int bitnet_host_constraints_state(void *d, uint64_t *chosen);
 int bitnet_host_sampling_draws(void *d, uint64_t *out);
 int bitnet_host_set_logprobs(void *d, int top_n);                             // Decoder::set_logprobs: -1 off, 0..20 on
 int bitnet_host_logprobs(void *d, int first, int n, void *records_out);       // Decoder::logprobs: n bitnet_hip_logprob_record

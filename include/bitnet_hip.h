@@ -855,8 +855,44 @@ int bitnet_hip_sampler_configure_ex(bitnet_hip_sampler *sampler, const bitnet_hi
 typedef struct bitnet_hip_mirostat_config { float tau; float eta; } bitnet_hip_mirostat_config;
 int bitnet_hip_sampler_set_mirostat(bitnet_hip_sampler *sampler, const bitnet_hip_mirostat_config *cfg);
 int bitnet_hip_sampler_mirostat_state(bitnet_hip_sampler *sampler, float *mu, uint64_t *fallbacks);
-/* Clears the counts (a new generation) and the word counter, and re-arms the launch hand-over (a launch cut short leaves it
- * unbalanced).  With Mirostat on: mu = 2 * tau (MirostatSampler::reset, strategies.rs:192-195) and the fallback count 0.
+/* Logit constraints: a per-token logit_bias (the reference's llama-compatible front end takes one, crates/bitnet-py/src/llama_compat.py:128,
+ * 161,207), banned tokens, an allowed set, an EOS hold-off (min_tokens) and no_repeat_ngram_size -- element-wise edits of the row in front of
+ * everything else the sampler does, inside the same single launch.  A stage CONSTRAINTS directly behind "counts":
+ *   counts; CONSTRAINTS; additive penalties; repetition penalty; NaN -> -inf; then the rest of the chain, or Mirostat, unchanged.
+ * For entry i with raw logit x:
+ *   bias: x = x + b[i], one f32 addition; b is 0 except at bias_ids, where it is the value of the LAST entry that names the id; -inf bans.
+ *   ban:  x = -inf if i is not in a non-empty allowed list, or i is a hold id and g < min_tokens, or i is n-gram-blocked.  A ban always wins:
+ *     a +inf logit with a -inf bias is NaN, and NaN -> -inf catches it.
+ *   g: the tokens this sampler has chosen, in launches that ran with constraints on, since bitnet_hip_sampler_reset -- a word in device
+ *     memory, advanced by the launch.  A forced position (and so a step frozen by the stop criteria) chooses nothing and does not count.
+ *     reset zeroes it; configure[_ex], set_mirostat and set_constraints leave it alone.  Launches with constraints off do not count (they run
+ *     the bodies that have no such stage): switch constraints on before the first token, with an empty config if need be.
+ *   n-gram block: n = no_repeat_ngram, P = *pos_dev, h = history_dev.  For every j with j + n - 1 <= P and h[j .. j+n-2] == h[P-n+2 .. P],
+ *     token h[j+n-1] is banned.  n = 1 bans every token of h[0..P]; a history of fewer than n tokens bans nothing.  Prompt tokens take part.
+ *     A token id outside [0, vocab) is skipped.  Without pos_dev / history_dev the block is skipped.  Only h[0..P] is read.
+ * bitnet_hip_sample_host applies the same stage with g = n_generated and that call's list as the sequence.  A row on which everything is
+ * banned behaves as a row of -inf logits does on the path at hand.  bitnet_hip_sample_batch_dev shares the kernel body: per slot the result
+ * is bit for bit bitnet_hip_sample_dev's.
+ * The logits tap (bitnet_hip_logprob_*) keeps reading the RAW row: its log-probabilities are those of the unconstrained distribution.
+ * set_constraints: cfg == NULL: off.  The lists are copied; the caller's arrays are not kept.  Synchronous and not capture-safe; graphs
+ *   captured before it stay valid and follow it (bias, bans and the hold list are reached through device memory).  INVALID_ARGUMENT, with
+ *   nothing changed, and before the sampler pointer is looked at: a NULL list with a non-zero count; an id outside [0, vocab) (without a
+ *   sampler: outside [0, 2^20)); a bias value that is NaN or +inf; n_hold > BITNET_HIP_CONSTRAINT_MAX_HOLD; min_tokens < 0; no_repeat_ngram
+ *   outside 0..BITNET_HIP_CONSTRAINT_MAX_NGRAM.
+ * constraints_state: g.  Synchronous. */
+#define BITNET_HIP_CONSTRAINT_MAX_HOLD 32
+#define BITNET_HIP_CONSTRAINT_MAX_NGRAM 8
+typedef struct bitnet_hip_constraints {
+    const int32_t *bias_ids; const float *bias_values; size_t n_bias;  /* x += value; -inf = banned */
+    const int32_t *allowed_ids; size_t n_allowed;   /* n_allowed > 0: every id NOT listed is banned */
+    const int32_t *hold_ids; size_t n_hold;         /* banned while fewer than min_tokens tokens were chosen */
+    int32_t min_tokens;                             /* 0: no hold-off */
+    int32_t no_repeat_ngram;                        /* 0 off; 1..BITNET_HIP_CONSTRAINT_MAX_NGRAM */
+} bitnet_hip_constraints;
+int bitnet_hip_sampler_set_constraints(bitnet_hip_sampler *sampler, const bitnet_hip_constraints *cfg);
+int bitnet_hip_sampler_constraints_state(bitnet_hip_sampler *sampler, uint64_t *chosen);
+/* Clears the counts (a new generation), the word counter and the constraints' count of chosen tokens, and re-arms the launch hand-over (a
+ * launch cut short leaves it unbalanced).  With Mirostat on: mu = 2 * tau (MirostatSampler::reset, strategies.rs:192-195) and the fallback count 0.
  * Synchronous; call it with no sample_dev / sample_host in flight.  Not capture-safe. */
 int bitnet_hip_sampler_reset(bitnet_hip_sampler *sampler);
 /* ChaCha20 words consumed since create / configure / reset (one per non-greedy call; none for a call that took Mirostat's fallback).

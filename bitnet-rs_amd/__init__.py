@@ -18,6 +18,8 @@ import sys
 
 import numpy as np
 
+from . import cproto
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libbitnet_hip.so")
@@ -107,165 +109,7 @@ class HipLib:
             )
         self.path = path
         self.c = C.CDLL(path)
-        L = self.c
-        L.bitnet_hip_init.argtypes = [C.c_int]
-        L.bitnet_hip_cleanup.restype = None
-        L.bitnet_hip_get_last_error.restype = C.c_char_p
-        L.bitnet_hip_get_device_info.argtypes = [C.c_int, C.POINTER(DeviceInfo)]
-        L.bitnet_hip_set_kernel.argtypes = [C.c_int]
-        L.bitnet_hip_gemv_qk256.argtypes = [_u8p, _sz, _f32p, _sz, _f32p, _sz, _sz, _sz, _sz]
-        L.bitnet_hip_i2s_matmul_f32.argtypes = [_f32p, _sz, _u8p, _sz, _f32p, _sz, _f32p, _sz, _sz, _sz, _sz, _sz]
-        L.bitnet_hip_qk256_gemv.argtypes = [_u8p, _sz, _f32p, _sz, _f32p, _sz, _f32p, _sz, _sz, _sz, _sz]
-        L.bitnet_hip_matmul_i2s.argtypes = [_i8p, _sz, _u8p, _sz, _f32p, _sz, _sz, _sz, _sz]
-        L.bitnet_hip_quantize.argtypes = [_f32p, _sz, _u8p, _sz, _f32p, _sz, C.c_int]
-        L.bitnet_hip_dequant_i2s.argtypes = [_u8p, _sz, _sz, _sz, C.c_int, C.c_float, C.c_int, _f32p, _sz]
-        L.bitnet_hip_attention.argtypes = [_f32p, _sz, _f32p, _sz, _f32p, _sz, _f32p, _sz, _sz, _sz, _sz, C.c_int, C.c_float]
-        L.bitnet_hip_qk256_gemv_batch.argtypes = [C.c_void_p, _sz]
-        L.bitnet_hip_weights_upload_qk256.argtypes = [_u8p, _sz, _sz, _sz, _sz, C.POINTER(C.c_uint64)]
-        L.bitnet_hip_weights_upload_i2s.argtypes = [_u8p, _sz, _f32p, _sz, _sz, _sz, _sz, C.POINTER(C.c_uint64)]
-        L.bitnet_hip_weights_upload_coded.argtypes = [_u8p, _sz, _f32p, _sz, _sz, _sz, _sz, _i8p, C.POINTER(C.c_uint64)]
-        L.bitnet_hip_weights_upload_inline_f16.argtypes = [_u8p, _sz, _sz, _sz, _i8p, C.c_int, C.POINTER(C.c_uint64)]
-        L.bitnet_hip_weights_free.argtypes = [C.c_uint64]
-        L.bitnet_hip_weights_info.argtypes = [C.c_uint64, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]
-        L.bitnet_hip_gemv_dev.argtypes = [C.c_uint64, _vp, _vp, _vp]
-        L.bitnet_hip_matmul_dev.argtypes = [C.c_uint64, _vp, _vp, _sz, _vp]
-        L.bitnet_hip_matmul_kernel_dev.argtypes = [C.c_uint64, _vp, _vp, _sz, C.c_int, _vp]
-        L.bitnet_hip_add_dev.argtypes = [_vp, _vp, _vp, _sz, _vp]
-        L.bitnet_hip_silu_mul_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp]
-        L.bitnet_hip_weights_device_bytes.argtypes = [C.c_uint64]
-        L.bitnet_hip_weights_device_bytes.restype = _sz
-        L.bitnet_hip_weights_trim.argtypes = [C.c_uint64]
-        L.bitnet_hip_qact_bytes.argtypes = [_sz]
-        L.bitnet_hip_qact_bytes.restype = _sz
-        L.bitnet_hip_qact_stats_bytes.argtypes = [_sz]
-        L.bitnet_hip_qact_stats_bytes.restype = _sz
-        L.bitnet_hip_quantize_act_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp]
-        L.bitnet_hip_embed_q_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_gemv_q_supported.argtypes = [C.c_uint64]
-        L.bitnet_hip_gemv_q_geometry.argtypes = [C.c_uint64, C.c_int, C.c_int, _sz, C.POINTER(GemvQGeometry)]
-        L.bitnet_hip_gemv_q_dev.argtypes = [C.c_uint64, _vp, _vp, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_attention_decode_q_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_int, _vp, _vp, _vp]
-        L.bitnet_hip_gemv_attn_merge_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-        # the batched decode kernels (n_seq vectors per launch; per-sequence state through device pointer tables)
-        L.bitnet_hip_embed_q_batch_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_embed_q_batch_dev.restype = C.c_int
-        L.bitnet_hip_gemv_q_batch_dev.argtypes = [C.c_uint64, _sz, _vp, _vp, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_gemv_q_batch_dev.restype = C.c_int
-        L.bitnet_hip_attention_decode_batch_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp, _vp]
-        L.bitnet_hip_attention_decode_batch_dev.restype = C.c_int
-        L.bitnet_hip_logits_f16_batch_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_logits_f16_batch_dev.restype = C.c_int
-        # the wide decode step (up to 64 sequences as dense matrix rows; per-sequence state through device pointer tables)
-        L.bitnet_hip_embed_rows_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]
-        L.bitnet_hip_embed_rows_dev.restype = C.c_int
-        L.bitnet_hip_attention_decode_rows_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp]
-        L.bitnet_hip_attention_decode_rows_dev.restype = C.c_int
-        L.bitnet_hip_pick_rows_dev.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_pick_rows_dev.restype = C.c_int
-        # fork of a live sequence's KV state: source tables [n_layers], destination tables [n_dst][n_layers] of device pointers
-        L.bitnet_hip_kv_fork_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]
-        L.bitnet_hip_kv_fork_dev.restype = C.c_int
-        # context shift of a live sequence's KV state, in place: K / V tables [n_layers] of device pointers, the RoPE tables [max_pos, 64]
-        L.bitnet_hip_kv_shift_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp]
-        L.bitnet_hip_kv_shift_dev.restype = C.c_int
-        L.bitnet_hip_gemv_attn_merge_rec_q_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
-        L.bitnet_hip_attention_merge_q_max_keys.restype = _sz
-        L.bitnet_hip_attention_merge_q_max_keys.argtypes = []
-        L.bitnet_hip_matmul_workspace_bytes.argtypes = [_sz, _sz, C.c_int]
-        L.bitnet_hip_matmul_workspace_bytes.restype = _sz
-        L.bitnet_hip_matmul_fused_dev.argtypes = [C.c_uint64, _vp, _vp, _sz, _vp, C.c_float, _vp, C.c_int, C.c_int, _vp, _sz, _vp]
-        L.bitnet_hip_matmul_last_tile.argtypes = [C.POINTER(C.c_int)] * 4
-        L.bitnet_hip_matmul_last_wave_rows.argtypes = []
-        L.bitnet_hip_weights_bind_ln.argtypes = [C.c_uint64, _vp, _vp]
-        L.bitnet_hip_weights_concat.argtypes = [C.POINTER(C.c_uint64), _sz, C.c_int, C.POINTER(C.c_uint64)]
-        L.bitnet_hip_gemv_fused_dev.argtypes = [C.c_uint64, _vp, _vp, _sz, _vp, C.c_float, _vp, C.c_int, _vp]
-        L.bitnet_hip_rmsnorm.argtypes = [_f32p, _sz, _f32p, _sz, _f32p, _sz, _sz, _sz, C.c_float]
-        L.bitnet_hip_norm_rows_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, C.c_float, C.c_int, _vp]
-        L.bitnet_hip_embed_f16_dev.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]
-        L.bitnet_hip_advance_pos_dev.argtypes = [_vp, _vp]
-        L.bitnet_hip_attention_decode_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_attention_decode_wide_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_attention_decode_partial_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp]
-        L.bitnet_hip_gemv_attn_merge_dev.argtypes = [C.c_uint64, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_attention_prefill_workspace_bytes.argtypes = [_sz, _sz, _sz]
-        L.bitnet_hip_attention_prefill_workspace_bytes.restype = _sz
-        L.bitnet_hip_attention_prefill_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp]
-        L.bitnet_hip_attention_extend_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz]
-        L.bitnet_hip_attention_extend_workspace_bytes.restype = _sz
-        L.bitnet_hip_attention_extend_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, C.c_int, _vp]
-        L.bitnet_hip_attention_packed_row_align.argtypes = [_sz, _sz]
-        L.bitnet_hip_attention_packed_row_align.restype = _sz
-        L.bitnet_hip_attention_packed_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.bitnet_hip_attention_packed_workspace_bytes.restype = _sz
-        L.bitnet_hip_attention_packed_dev.argtypes = [_vp, _sz, _vp, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _sz, _sz, _sz, _sz,
-                                                      _vp, _sz, _vp, C.c_int, _vp]
-        L.bitnet_hip_attention_prefill_sharded_workspace_bytes.argtypes = [_sz, _sz, _sz, _sz]
-        L.bitnet_hip_attention_prefill_sharded_workspace_bytes.restype = _sz
-        L.bitnet_hip_attention_prefill_sharded_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp]
-        L.bitnet_hip_attention_scratch_bytes.argtypes = [_sz, _sz]
-        L.bitnet_hip_attention_scratch_bytes.restype = _sz
-        L.bitnet_hip_logits_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_argmax_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _vp]
-        L.bitnet_hip_head_screen_bytes.argtypes = [_sz, _sz]
-        L.bitnet_hip_head_screen_bytes.restype = _sz
-        L.bitnet_hip_head_screen_ws_bytes.argtypes = [_sz, _sz, _sz]
-        L.bitnet_hip_head_screen_ws_bytes.restype = _sz
-        L.bitnet_hip_head_screen_build_dev.argtypes = [_vp, _sz, _sz, _vp, _vp]
-        L.bitnet_hip_head_screen_build_dev.restype = C.c_int
-        L.bitnet_hip_logits_screen_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_logits_screen_dev.restype = C.c_int
-        L.bitnet_hip_hbm_read_ceiling.argtypes = [_sz, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]
-        # the sampler entries are bound here, with the rest, never lazily (a handle bound on first use crashed a process once)
-        L.bitnet_hip_sampler_create.argtypes = [_sz, C.POINTER(SamplingConfig), C.POINTER(_vp)]
-        L.bitnet_hip_sampler_destroy.argtypes = [_vp]
-        L.bitnet_hip_sampler_destroy.restype = None
-        L.bitnet_hip_sampler_configure.argtypes = [_vp, C.POINTER(SamplingConfig)]
-        L.bitnet_hip_sampler_create_ex.argtypes = [_sz, C.POINTER(SamplingConfigEx), C.POINTER(_vp)]
-        L.bitnet_hip_sampler_create_ex.restype = C.c_int
-        L.bitnet_hip_sampler_configure_ex.argtypes = [_vp, C.POINTER(SamplingConfigEx)]
-        L.bitnet_hip_sampler_configure_ex.restype = C.c_int
-        L.bitnet_hip_sampler_set_mirostat.argtypes = [_vp, C.POINTER(MirostatConfig)]
-        L.bitnet_hip_sampler_set_mirostat.restype = C.c_int
-        L.bitnet_hip_sampler_mirostat_state.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
-        L.bitnet_hip_sampler_mirostat_state.restype = C.c_int
-        L.bitnet_hip_sampler_set_constraints.argtypes = [_vp, C.POINTER(Constraints)]
-        L.bitnet_hip_sampler_set_constraints.restype = C.c_int
-        L.bitnet_hip_sampler_constraints_state.argtypes = [_vp, C.POINTER(C.c_uint64)]
-        L.bitnet_hip_sampler_constraints_state.restype = C.c_int
-        L.bitnet_hip_sampler_reset.argtypes = [_vp]
-        L.bitnet_hip_sampler_draws.argtypes = [_vp, C.POINTER(C.c_uint64)]
-        L.bitnet_hip_sample_dev.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_sample_host.argtypes = [_vp, _f32p, _sz, C.POINTER(C.c_uint32), _sz, C.POINTER(C.c_uint32)]
-        L.bitnet_hip_sample_batch_create.argtypes = [_sz, _sz, C.POINTER(_vp)]
-        L.bitnet_hip_sample_batch_create.restype = C.c_int
-        L.bitnet_hip_sample_batch_destroy.argtypes = [_vp]
-        L.bitnet_hip_sample_batch_destroy.restype = None
-        L.bitnet_hip_sample_batch_set.argtypes = [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.bitnet_hip_sample_batch_set.restype = C.c_int
-        L.bitnet_hip_sample_batch_dev.argtypes = [_vp, _vp]
-        L.bitnet_hip_sample_batch_dev.restype = C.c_int
-        # the logits tap (per-token log-probabilities and top-N logits): bound here with the rest, never lazily
-        L.bitnet_hip_logprob_scratch_bytes.argtypes = [_sz]
-        L.bitnet_hip_logprob_scratch_bytes.restype = _sz
-        L.bitnet_hip_logprob_dev.argtypes = [C.POINTER(LogprobArgs), _sz, _vp]
-        L.bitnet_hip_logprob_dev.restype = C.c_int
-        L.bitnet_hip_logprob_batch_dev.argtypes = [_vp, _sz, _sz, _vp]
-        L.bitnet_hip_logprob_batch_dev.restype = C.c_int
-        # the stop criteria (bitnet_hip_stop_*): bound here with the rest, never lazily
-        _i32p = C.POINTER(C.c_int32)
-        for name, args in (("create", [C.POINTER(StopConfig), C.POINTER(_vp)]), ("configure", [_vp, C.POINTER(StopConfig)]), ("arm", [_vp, C.c_int]),
-                           ("get_state", [_vp, C.POINTER(StopState)]), ("dev", [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
-                           ("batch_create", [_sz, C.POINTER(_vp)]), ("batch_set", [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp]), ("batch_dev", [_vp, _vp]),
-                           ("batch_live", [_vp, _i32p])):
-            f = getattr(L, "bitnet_hip_stop_" + name)
-            f.argtypes, f.restype = args, C.c_int
-        L.bitnet_hip_stop_destroy.argtypes = [_vp]
-        L.bitnet_hip_stop_destroy.restype = None
-        L.bitnet_hip_stop_batch_destroy.argtypes = [_vp]
-        L.bitnet_hip_stop_batch_destroy.restype = None
-        L.bitnet_hip_score_workspace_bytes.argtypes = [_sz, _sz, _sz]
-        L.bitnet_hip_score_workspace_bytes.restype = _sz
-        L.bitnet_hip_score_f16_dev.argtypes = [_vp, _vp, _vp, C.c_float, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
+        cproto.bind(self.c, cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_"), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -347,7 +191,6 @@ class HipLib:
     def quantized_matmul_i2s(self, x, packed, scales, block_size: int, m: int, n: int, k: int) -> np.ndarray:
         xa, pa, sa = _np(x, np.float32), _np(packed, np.uint8), _np(scales, np.float32)
         out = np.zeros(m * n, np.float32)
-        self.c.bitnet_hip_quantized_matmul_i2s.argtypes = [_f32p, _sz, _u8p, _sz, _f32p, _sz, _sz, _f32p, _sz, _sz, _sz, _sz]
         self._check(self.c.bitnet_hip_quantized_matmul_i2s(xa.ctypes.data_as(_f32p), xa.size, pa.ctypes.data_as(_u8p), pa.size, sa.ctypes.data_as(_f32p), sa.size,
                                                            block_size, out.ctypes.data_as(_f32p), out.size, m, n, k))
         return out
@@ -429,47 +272,36 @@ class HipLib:
 
     # -- the prompt forward's f16 activation chain (include/bitnet_hip.h) --------------------------------------------------------
     def matmul_f16_supported(self, h: int) -> bool:
-        self.c.bitnet_hip_matmul_f16_supported.argtypes = [C.c_uint64]
         return bool(self.c.bitnet_hip_matmul_f16_supported(h))
 
     def rows_to_f16_dev(self, x, gamma, m: int, cols: int, xh, stats, stream: int = 0) -> None:
-        self.c.bitnet_hip_rows_to_f16_dev.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
         self._check(self.c.bitnet_hip_rows_to_f16_dev(_ptr(x), _optr(gamma), m, cols, _ptr(xh), _optr(stats), _vp(stream)))
 
     def matmul_f16_dev(self, h: int, xh, m: int, stats_in=None, n_stats: int = 0, ln_gamma=None, ln_eps: float = 0.0, y=None, residual=None,
                        flags: int = 0, yh=None, gamma_out=None, stats_out=None, stream: int = 0) -> None:
-        self.c.bitnet_hip_matmul_f16_dev.argtypes = [C.c_uint64, _vp, _sz, _vp, _sz, _vp, C.c_float, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
         self._check(self.c.bitnet_hip_matmul_f16_dev(h, _ptr(xh), m, _optr(stats_in), n_stats, _optr(ln_gamma), ln_eps, _optr(y), _optr(residual), flags,
                                                      _optr(yh), _optr(gamma_out), _optr(stats_out), _vp(stream)))
 
     def f16_saturations(self, reset: bool = True) -> int:
-        self.c.bitnet_hip_f16_saturations.restype = C.c_uint64
-        self.c.bitnet_hip_f16_saturations.argtypes = [C.c_int]
         return int(self.c.bitnet_hip_f16_saturations(1 if reset else 0))
 
     # ---- QB32: producer-quantised rows for the fp6 x fp4 prompt matmul (include/bitnet_hip.h) ----
     def qb32_bytes(self, m: int, cols: int) -> int:
-        self.c.bitnet_hip_qb32_bytes.restype = _sz
-        self.c.bitnet_hip_qb32_bytes.argtypes = [_sz, _sz]
         return int(self.c.bitnet_hip_qb32_bytes(m, cols))
 
     def rows_to_qb32_dev(self, x, gamma, m: int, cols: int, qb, stats, stream: int = 0) -> None:
-        self.c.bitnet_hip_rows_to_qb32_dev.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
         self._check(self.c.bitnet_hip_rows_to_qb32_dev(_ptr(x), _optr(gamma), m, cols, _ptr(qb), _optr(stats), _vp(stream)))
 
     def matmul_qb32_supported(self, h: int) -> bool:
-        self.c.bitnet_hip_matmul_qb32_supported.argtypes = [C.c_uint64]
         return bool(self.c.bitnet_hip_matmul_qb32_supported(h))
 
     def matmul_qb32_dev(self, h: int, qb, m: int, stats_in=None, n_stats: int = 0, ln_gamma=None, ln_eps: float = 0.0, y=None, residual=None,
                         flags: int = 0, yh=None, gamma_out=None, stats_out=None, stream: int = 0) -> None:
-        self.c.bitnet_hip_matmul_qb32_dev.argtypes = [C.c_uint64, _vp, _sz, _vp, _sz, _vp, C.c_float, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
         self._check(self.c.bitnet_hip_matmul_qb32_dev(h, _ptr(qb), m, _optr(stats_in), n_stats, _optr(ln_gamma), ln_eps, _optr(y), _optr(residual), flags,
                                                       _optr(yh), _optr(gamma_out), _optr(stats_out), _vp(stream)))
 
     def attention_prefill_flags_dev(self, qkv, rope_sin, rope_cos, kcache, vcache, n_heads, n_kv, head_dim, max_pos, seq_len, workspace, workspace_bytes,
                                     out, flags: int, stream: int = 0) -> None:
-        self.c.bitnet_hip_attention_prefill_flags_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, C.c_int, _vp]
         self._check(self.c.bitnet_hip_attention_prefill_flags_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kcache), _ptr(vcache), n_heads, n_kv,
                                                                   head_dim, max_pos, seq_len, _ptr(workspace), workspace_bytes, _ptr(out), flags, _vp(stream)))
 
@@ -484,7 +316,6 @@ class HipLib:
         return int(self.c.bitnet_hip_matmul_last_wave_rows())
 
     def matmul_last_resident_fp4(self) -> bool:
-        self.c.bitnet_hip_matmul_last_resident_fp4.restype = C.c_int
         return bool(self.c.bitnet_hip_matmul_last_resident_fp4())
 
     def attention_prefill_workspace_bytes(self, n_heads: int, n_kv: int, seq_len: int) -> int:
@@ -560,8 +391,6 @@ class HipLib:
     def attention_prefill_gathered_dev(self, q, ld_q, q_block_pos, n_q, kv_gathered, n_ctx, world, kv_is_f16, rope_sin, rope_cos, kcache, vcache,
                                        cache_f16, n_heads, n_kv, head_dim, max_pos, workspace, workspace_bytes, out, stream: int = 0) -> None:
         """the k|v rows exactly as an all-gather over `world` ranks left them (rank-major zigzag chunks, f32 or f16)"""
-        self.c.bitnet_hip_attention_prefill_gathered_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _sz, _sz,
-                                                                     _sz, _sz, _vp, _sz, _vp, _vp]
         self._check(self.c.bitnet_hip_attention_prefill_gathered_dev(_ptr(q), ld_q, _ptr(q_block_pos), n_q, _ptr(kv_gathered), n_ctx, world,
                                                                      int(kv_is_f16), _ptr(rope_sin), _ptr(rope_cos), _ptr(kcache), _ptr(vcache),
                                                                      int(cache_f16), n_heads, n_kv, head_dim, max_pos, _ptr(workspace), workspace_bytes,
@@ -598,7 +427,6 @@ class HipLib:
 
     def weights_fp4_image(self, h: int, enable: bool = True, stream: int = 0) -> None:
         """Build (or free) the resident fp4 image the fp6 x fp4 prompt matmul reads (include/bitnet_hip.h)."""
-        self.c.bitnet_hip_weights_fp4_image.argtypes = [C.c_uint64, C.c_int, C.c_void_p]
         self._check(self.c.bitnet_hip_weights_fp4_image(h, 1 if enable else 0, stream))
 
     def weights_trim(self, h: int) -> None:
@@ -796,7 +624,7 @@ class HipLib:
 
     def logprob_batch_dev(self, table, n_slots: int, vocab: int, stream: int = 0) -> None:
         """The same for n_slots entries read from a DEVICE table of LogprobArgs (a uint8 tensor holding them, or a raw pointer), one launch."""
-        self._check(self.c.bitnet_hip_logprob_batch_dev(_optr(table), n_slots, vocab, _vp(stream)))
+        self._check(self.c.bitnet_hip_logprob_batch_dev(C.cast(_optr(table), C.POINTER(LogprobArgs)), n_slots, vocab, _vp(stream)))
 
     def hbm_read_ceiling(self, nbytes: int = 2 << 30, iters: int = 10, stream: int = 0):
         """Measured read-only stream ceiling of the device: (best, mean) GB/s."""
@@ -1161,11 +989,7 @@ def load() -> HipLib:
 
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares (used by the export test)."""
-    import re
-
-    text = open(HEADER_PATH).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(bitnet_hip_[a-z0-9_]+)\s*\(", text)))
+    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_")})
 
 
 # ---------------------------------------------------------------------------
@@ -1173,13 +997,28 @@ def declared_symbols() -> list[str]:
 # ---------------------------------------------------------------------------
 
 HOST_LIB_PATH = os.path.join(HERE, "libbitnet_host.so")
+HOST_HEADER_PATHS = [os.path.join(HERE, "host", f) for f in ("decoder.hpp", "batch_decoder.hpp", "gguf.hpp")]
+_host_libs = {}
+
+
+def host_prototypes() -> list:
+    """Every bitnet_host_* function the extern "C" tails of the host headers declare."""
+    return [p for h in HOST_HEADER_PATHS for p in cproto.prototypes(open(h).read(), "bitnet_host_")]
+
+
+def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
+    """The host library at `path`, loaded and bound from its headers once per process."""
+    if path not in _host_libs:
+        L = C.CDLL(path)
+        cproto.bind(L, host_prototypes(), C_STRUCTS)
+        _host_libs[path] = L
+    return _host_libs[path]
 
 
 def blake3_hex(data: bytes) -> str:
     """BLAKE3 as the trace records carry it (host/blake3.hpp)."""
     load()
-    L = C.CDLL(HOST_LIB_PATH)
-    L.bitnet_host_blake3_hex.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
+    L = _host_lib()
     out = C.create_string_buffer(65)
     if L.bitnet_host_blake3_hex(data, len(data), out) != 0:
         raise BitNetHipError(ERR_INVALID_ARGUMENT, "blake3_hex failed")
@@ -1189,9 +1028,7 @@ def blake3_hex(data: bytes) -> str:
 def host_device_bytes() -> int:
     """Bytes of device memory the process's host decoders and batches own right now (host/dev_buffer.hpp; the weight handles are not counted)."""
     load()
-    L = C.CDLL(HOST_LIB_PATH)
-    L.bitnet_host_device_bytes.argtypes = []
-    L.bitnet_host_device_bytes.restype = C.c_uint64
+    L = _host_lib()
     return int(L.bitnet_host_device_bytes())
 
 
@@ -1201,6 +1038,12 @@ class HostConfig(C.Structure):
         ("rope_theta", C.c_float),
     ]
 
+
+# the structs that cross the C ABI by pointer, by their C names: cproto.bind types such a parameter as POINTER of the class
+C_STRUCTS = {"bitnet_hip_device_info": DeviceInfo, "bitnet_hip_gemv_q_geometry_t": GemvQGeometry, "bitnet_hip_sampling_config": SamplingConfig,
+             "bitnet_hip_sampling_config_ex": SamplingConfigEx, "bitnet_hip_mirostat_config": MirostatConfig,
+             "bitnet_hip_constraints": Constraints, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
+             "bitnet_hip_stop_state": StopState, "bitnet_host_config": HostConfig}
 
 FLAVORS = ("BitNet32F16", "Split32WithSibling", "GgmlQk256NoScale")
 
@@ -1215,23 +1058,7 @@ class GgufFile:
         if not os.path.exists(LIB_PATH):
             raise FileNotFoundError(f"{LIB_PATH} not found: build it with __graft_entry__.build()")
         C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        L = self.c = C.CDLL(lib_path)
-        L.bitnet_host_gguf_open.restype = C.c_void_p
-        L.bitnet_host_gguf_open.argtypes = [C.c_char_p]
-        L.bitnet_host_gguf_from_memory.restype = C.c_void_p
-        L.bitnet_host_gguf_from_memory.argtypes = [_u8p, _sz]
-        L.bitnet_host_gguf_close.argtypes = [C.c_void_p]
-        L.bitnet_host_gguf_error.restype = C.c_char_p
-        L.bitnet_host_gguf_tensor_count.restype = C.c_int64
-        L.bitnet_host_gguf_tensor_count.argtypes = [C.c_void_p]
-        L.bitnet_host_gguf_tensor_info.argtypes = [C.c_void_p, C.c_int64, C.c_char_p, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
-                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.bitnet_host_gguf_data_start.restype = C.c_uint64
-        L.bitnet_host_gguf_data_start.argtypes = [C.c_void_p]
-        L.bitnet_host_gguf_config.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
-        L.bitnet_host_gguf_detect_i2s_flavor.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_int]
-        L.bitnet_host_gguf_loader_is_qk256.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64]
-        L.bitnet_host_gguf_check_projection.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64]
+        L = self.c = _host_lib(lib_path)
         self.h = None
         if path is not None:
             self.h = L.bitnet_host_gguf_open(path.encode())
@@ -1305,88 +1132,7 @@ class HostDecoder:
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not found: build it with __graft_entry__.build() -- there is no fallback path")
         load()  # the kernel library must be loadable first
-        self.c = C.CDLL(path)
-        L = self.c
-        # every binding is set here, at construction, never on first use (a lazily bound pointer argument crashed a process once)
-        L.bitnet_host_create_shared.restype = C.c_void_p
-        L.bitnet_host_create_shared.argtypes = [C.c_void_p]
-        L.bitnet_host_set_attention_form.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_set_attention_form.restype = C.c_int
-        L.bitnet_host_set_head_screen.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_set_head_screen.restype = C.c_int
-        L.bitnet_host_head_screen.argtypes = [C.c_void_p]
-        L.bitnet_host_head_screen.restype = C.c_int
-        L.bitnet_host_head_screen_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-        L.bitnet_host_head_screen_stats.restype = C.c_int
-        L.bitnet_host_release.argtypes = [C.c_void_p]
-        L.bitnet_host_release.restype = None
-        L.bitnet_host_create.restype = C.c_void_p
-        L.bitnet_host_create.argtypes = [C.POINTER(HostConfig)]
-        L.bitnet_host_destroy.argtypes = [C.c_void_p]
-        L.bitnet_host_error.restype = C.c_char_p
-        L.bitnet_host_error.argtypes = [C.c_void_p]
-        L.bitnet_host_set_layer_qk256.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p] + [_u8p] * 7
-        L.bitnet_host_set_layer_i2s.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, C.POINTER(_u8p), C.POINTER(_f32p), _sz]
-        L.bitnet_host_set_globals.argtypes = [C.c_void_p, C.POINTER(C.c_uint16), _f32p]
-        L.bitnet_host_reset.argtypes = [C.c_void_p]
-        L.bitnet_host_feed.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
-        L.bitnet_host_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.bitnet_host_run_reference.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.bitnet_host_prepare_graphs.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_set_act_mode.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_act_mode.argtypes = [C.c_void_p]
-        L.bitnet_host_position.argtypes = [C.c_void_p]
-        L.bitnet_host_form_at.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_last_prefill_path.argtypes = [C.c_void_p]
-        L.bitnet_host_saturation_fallbacks.argtypes = [C.c_void_p]
-        L.bitnet_host_history.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
-        L.bitnet_host_last_logits.argtypes = [C.c_void_p, _f32p]
-        L.bitnet_host_last_hidden.argtypes = [C.c_void_p, _f32p]
-        L.bitnet_host_probe_gateup.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]
-        L.bitnet_host_probe_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]
-        L.bitnet_host_weight_bytes.argtypes = [C.c_void_p]
-        L.bitnet_host_weight_bytes.restype = C.c_uint64
-        L.bitnet_host_set_sampling.argtypes = [C.c_void_p, C.POINTER(SamplingConfig)]
-        L.bitnet_host_set_sampling_ex.argtypes = [C.c_void_p, C.POINTER(SamplingConfigEx)]
-        L.bitnet_host_set_sampling_ex.restype = C.c_int
-        L.bitnet_host_sampling_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        L.bitnet_host_set_mirostat.argtypes = [C.c_void_p, C.POINTER(MirostatConfig)]
-        L.bitnet_host_set_mirostat.restype = C.c_int
-        L.bitnet_host_mirostat_state.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
-        L.bitnet_host_mirostat_state.restype = C.c_int
-        L.bitnet_host_set_constraints.argtypes = [C.c_void_p, C.POINTER(Constraints)]
-        L.bitnet_host_set_constraints.restype = C.c_int
-        L.bitnet_host_constraints_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        L.bitnet_host_constraints_state.restype = C.c_int
-        L.bitnet_host_set_logprobs.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_set_logprobs.restype = C.c_int
-        L.bitnet_host_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.bitnet_host_logprobs.restype = C.c_int
-        L.bitnet_host_score.argtypes = [C.c_void_p, C.c_int, C.c_int, _f32p, C.POINTER(C.c_int32), _f32p, C.c_int, C.POINTER(C.c_float)]
-        L.bitnet_host_extend.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.bitnet_host_extend.restype = C.c_int
-        L.bitnet_host_rewind.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_rewind.restype = C.c_int
-        L.bitnet_host_fork.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]
-        L.bitnet_host_fork.restype = C.c_int
-        L.bitnet_host_shift.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.bitnet_host_shift.restype = C.c_int
-        L.bitnet_host_prefill_packed.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.bitnet_host_prefill_packed.restype = C.c_int
-        L.bitnet_host_step_wide.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.bitnet_host_step_wide.restype = C.c_int
-        L.bitnet_host_cached_prefix.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
-        L.bitnet_host_cached_prefix.restype = C.c_int
-        L.bitnet_host_set_stop.argtypes = [C.c_void_p, C.POINTER(StopConfig)]
-        L.bitnet_host_set_stop.restype = C.c_int
-        L.bitnet_host_stop_state.argtypes = [C.c_void_p, C.POINTER(StopState)]
-        L.bitnet_host_stop_state.restype = C.c_int
-        L.bitnet_host_resume.argtypes = [C.c_void_p]
-        L.bitnet_host_resume.restype = C.c_int
-        L.bitnet_host_run_until_stop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
-        L.bitnet_host_run_until_stop.restype = C.c_int
-        L.bitnet_host_graph_nodes.argtypes = [C.c_void_p, C.c_int]
-        L.bitnet_host_graph_nodes.restype = C.c_int
+        L = self.c = _host_lib(path)
         self.cfg = cfg
         self._top_n = -1  # set_logprobs
         self._fed = 0  # tokens fed since the last reset (the default n of score)
@@ -1440,7 +1186,6 @@ class HostDecoder:
         return int(out[0]), int(out[1]), int(out[2])
 
     def load_gguf(self, gguf: "GgufFile") -> None:
-        self.c.bitnet_host_load_gguf.argtypes = [C.c_void_p, C.c_void_p]
         self._check(self.c.bitnet_host_load_gguf(self.h, gguf.h))
 
     def set_layer_qk256(self, layer: int, w: dict) -> None:
@@ -1588,7 +1333,6 @@ class HostDecoder:
 
     def set_kv_f16(self, on: bool) -> None:
         """Opt-in f16 KV cache (fresh sequence only)."""
-        self.c.bitnet_host_set_kv_f16.argtypes = [C.c_void_p, C.c_int]
         self._check(self.c.bitnet_host_set_kv_f16(self.h, int(on)))
 
     def set_act_mode(self, mode: int) -> None:
@@ -1600,7 +1344,6 @@ class HostDecoder:
 
     def trace_step(self, directory: str, with_logits: bool = True) -> None:
         """One eager step leaving the reference's per-tensor trace records (crates/bitnet-trace) in `directory`."""
-        self.c.bitnet_host_trace_step.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         os.makedirs(directory, exist_ok=True)
         self._check(self.c.bitnet_host_trace_step(self.h, directory.encode(), int(with_logits)))
 
@@ -1621,7 +1364,6 @@ class HostDecoder:
         tests, see prefill_parallel.torch_gather); rccl_comm (an ncclComm_t as int) takes the C entry
         bitnet_host_rccl_allgather instead: the path a Rust host would use, no Python per layer."""
         L = self.c
-        L.bitnet_host_prefill_sharded.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         ms = C.c_float(0)
         if rccl_comm is not None:
             fn = C.cast(L.bitnet_host_rccl_allgather, C.c_void_p)
@@ -1642,18 +1384,15 @@ class HostDecoder:
 
     def set_phase_timing(self, on: bool) -> None:
         """per-phase event timing of the next prefill_sharded calls (8 event records per layer)"""
-        self.c.bitnet_host_set_phase_timing.argtypes = [C.c_void_p, C.c_int]
         self._check(self.c.bitnet_host_set_phase_timing(self.h, int(on)))
 
     def phase_times(self) -> dict:
         """medians over the layers of the last timed prefill_sharded call, microseconds per layer"""
         out = (C.c_float * 4)()
-        self.c.bitnet_host_phase_times.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         self._check(self.c.bitnet_host_phase_times(self.h, out))
         return {"matmul_us": round(out[0], 1), "attention_us": round(out[1], 1), "gather_wait_us": round(out[2], 1), "gather_us": round(out[3], 1)}
 
     def prefill(self, n: int, with_logits: bool = True, digits: int = 4) -> float:
-        self.c.bitnet_host_prefill.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         ms = C.c_float(0)
         self._check(self.c.bitnet_host_prefill(self.h, n, int(with_logits), digits, C.byref(ms)))
         return ms.value
@@ -1811,26 +1550,7 @@ class HostBatch:
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not found: build it with __graft_entry__.build() -- there is no fallback path")
         load()
-        self.c = C.CDLL(path)
-        L = self.c
-        L.bitnet_host_batch_create.restype = C.c_void_p
-        L.bitnet_host_batch_create.argtypes = [C.c_int]
-        L.bitnet_host_batch_destroy.restype = None
-        L.bitnet_host_batch_destroy.argtypes = [C.c_void_p]
-        L.bitnet_host_batch_error.restype = C.c_char_p
-        L.bitnet_host_batch_error.argtypes = [C.c_void_p]
-        L.bitnet_host_batch_set_slot.restype = C.c_int
-        L.bitnet_host_batch_set_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.bitnet_host_batch_step.restype = C.c_int
-        L.bitnet_host_batch_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.bitnet_host_batch_captures.restype = C.c_int
-        L.bitnet_host_batch_captures.argtypes = [C.c_void_p]
-        L.bitnet_host_batch_graph_nodes.restype = C.c_int
-        L.bitnet_host_batch_graph_nodes.argtypes = [C.c_void_p]
-        L.bitnet_host_batch_live.restype = C.c_int
-        L.bitnet_host_batch_live.argtypes = [C.c_void_p]
-        L.bitnet_host_batch_step_until.restype = C.c_int
-        L.bitnet_host_batch_step_until.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L = self.c = _host_lib(path)
         self.n_slots = n_slots
         self.h = L.bitnet_host_batch_create(n_slots)
         if not self.h:

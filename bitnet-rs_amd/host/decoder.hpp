@@ -591,6 +591,8 @@ void bitnet_host_layer_objects(void *d, int layer, uint64_t *handles4, void **pt
 void bitnet_host_global_objects(void *d, void **ptrs7);
 int bitnet_host_position(void *d);
 int bitnet_host_form_at(void *d, int pos);  // attention form (0..3, Decoder::form_at) of a step at position pos; -1 for a dead handle
+int bitnet_host_last_prefill_path(void *d);     // Decoder::last_prefill_path; -1 for a dead handle
+int bitnet_host_saturation_fallbacks(void *d);  // Decoder::saturation_fallbacks; -1 for a dead handle
 int bitnet_host_history(void *d, int32_t *out, int n);
 int bitnet_host_last_logits(void *d, float *out);
 int bitnet_host_last_hidden(void *d, float *out);

@@ -7,6 +7,9 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "bitnet-rs_amd"))
+import cproto  # noqa: E402 -- the one header parser (the ctypes bindings derive from it too)
+
 BASE = {"size_t": "usize", "int": "c_int", "float": "c_float", "double": "f64", "void": "c_void", "char": "c_char", "uint8_t": "u8", "int8_t": "i8",
         "uint16_t": "u16", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "int64_t": "i64", "unsigned long long": "u64", "unsigned": "u32",
         "bitnet_hip_weights_t": "Weights", "bitnet_hip_device_info": "DeviceInfo", "bitnet_hip_gemv_item": "GemvItem", "_Float16": "u16",
@@ -29,18 +32,9 @@ def rust_type(c: str) -> str:
 
 
 def prototypes(header: str):
-    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    text = re.sub(r"//[^\n]*", " ", text)
-    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(bitnet_hip_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
-        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
-        params = []
-        if args and args != "void":
-            for a in args.split(","):
-                a = a.strip()
-                mm = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a)
-                params.append((mm.group(2), rust_type(mm.group(1))))
+    for name, ret, params in cproto.prototypes(header, "bitnet_hip_"):
         r = "" if ret == "void" else " -> " + rust_type(ret)
-        yield name, "pub fn %s(%s)%s;" % (name, ", ".join(f"{n}: {t}" for n, t in params), r)
+        yield name, "pub fn %s(%s)%s;" % (name, ", ".join(f"{n}: {rust_type(t)}" for t, n in params), r)
 
 
 def main():

@@ -83,6 +83,12 @@ class GemvQGeometry(C.Structure):
                                        "grid", "merge_slots4", "merge_slots1", "merge_records")]
 
 
+class GemvGeometry(C.Structure):
+    """bitnet_hip_gemv_geometry_t"""
+    _fields_ = [(n, C.c_int) for n in ("kernel", "unfused", "k_split", "blocks", "blocks_per_wave", "ring", "stat_vectors", "layernorm", "scale_form",
+                                       "wscale", "merge", "tiles_per_workgroup", "grid", "lds_bytes", "lds_raised")]
+
+
 def _np(a, dtype):
     if isinstance(a, (bytes, bytearray, memoryview)):
         a = np.frombuffer(a, dtype=np.uint8)
@@ -448,6 +454,12 @@ class HipLib:
 
     def gemv_q_supported(self, h: int) -> bool:
         return bool(self.c.bitnet_hip_gemv_q_supported(h))
+
+    def gemv_geometry(self, h: int, flags: int = 0, ln_gamma=None, merge: int = 0) -> dict:
+        """the kernel (and k_gemv_mfma instance) gemv_dev / gemv_fused_dev (merge 0) or gemv_attn_merge_dev (merge = query group) would launch; host only"""
+        g = GemvGeometry()
+        self._check(self.c.bitnet_hip_gemv_geometry(h, flags, _optr(ln_gamma), merge, C.byref(g)))
+        return {n: getattr(g, n) for n, _ in GemvGeometry._fields_}
 
     def gemv_q_geometry(self, h: int, flags: int = 0, layernorm: bool = False, merge_records: int = 0) -> dict:
         """the k_gemv_q instance gemv_q_dev (merge_records 0) / gemv_attn_merge[_rec]_q_dev (4 or 8) would launch; host only"""
@@ -1040,7 +1052,7 @@ class HostConfig(C.Structure):
 
 
 # the structs that cross the C ABI by pointer, by their C names: cproto.bind types such a parameter as POINTER of the class
-C_STRUCTS = {"bitnet_hip_device_info": DeviceInfo, "bitnet_hip_gemv_q_geometry_t": GemvQGeometry, "bitnet_hip_sampling_config": SamplingConfig,
+C_STRUCTS = {"bitnet_hip_device_info": DeviceInfo, "bitnet_hip_gemv_q_geometry_t": GemvQGeometry, "bitnet_hip_gemv_geometry_t": GemvGeometry, "bitnet_hip_sampling_config": SamplingConfig,
              "bitnet_hip_sampling_config_ex": SamplingConfigEx, "bitnet_hip_mirostat_config": MirostatConfig,
              "bitnet_hip_constraints": Constraints, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
              "bitnet_hip_stop_state": StopState, "bitnet_host_config": HostConfig}

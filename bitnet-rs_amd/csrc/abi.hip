@@ -1042,6 +1042,60 @@ int bitnet_hip_gemv_attn_merge_rec_q_dev(bitnet_hip_weights_t h, const float *at
                            (int)max_records);
 }
 
+int bitnet_hip_gemv_geometry(bitnet_hip_weights_t h, int flags, const float *ln_gamma_dev, int merge, bitnet_hip_gemv_geometry_t *out) {
+    BH_GUARD_BEGIN
+    const WeightsRef w = lookup(h);
+    if (!w) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "unknown weights handle %llu", (unsigned long long)h);
+    if (!out) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to gemv_geometry");
+    if (flags & ~BITNET_HIP_FUSE_SILU_MUL) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "gemv_geometry: unknown flag bits 0x%x", flags);
+    const bool silu = (flags & BITNET_HIP_FUSE_SILU_MUL) != 0;
+    *out = bitnet_hip_gemv_geometry_t{};
+    int kernel = BITNET_HIP_KERNEL_MFMA;  // gemv_attn_merge names it; the other entries take the process-wide choice
+    if (merge && (silu || ln_gamma_dev))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "gemv_geometry: the merging entry takes neither FUSE_SILU_MUL nor a LayerNorm weight");
+    if (merge) {
+        // gemv_attn_merge's refusals, in its order (cols == n_heads * 128 is the caller's to keep: the entry has no head count of its own)
+        const bool group_ok = merge == 1 || merge == 2 || merge == 4;
+        const size_t n_heads = w->cols / 128, n_kv = group_ok ? n_heads / (size_t)merge : 0;
+        if (!group_ok || w->cols % 128 != 0 || n_kv == 0 || n_kv * (size_t)merge != n_heads)
+            return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_attn_merge_dev: needs cols == n_heads * 128 and a query group of 1, 2 or 4 (got %zu heads / %zu)",
+                             n_heads, n_kv);
+        if (!mfma_supported(*w) || div_ceil(div_ceil(w->cols, 256), (size_t)8) > 2)
+            return set_error(BITNET_HIP_ERR_UNSUPPORTED, "gemv_attn_merge_dev: matrix shape %zux%zu not supported", w->rows, w->cols);
+    } else {
+        // gemv_fused_dev's, then run_gemv's resolution of the kernel choice
+        if (int rc = check_silu_pairing(*w, silu, nullptr)) return rc;
+        kernel = g_kernel.load(std::memory_order_relaxed);
+        if (kernel == BITNET_HIP_KERNEL_AUTO || kernel == BITNET_HIP_KERNEL_MFMA_TILED) kernel = BITNET_HIP_KERNEL_MFMA;
+        if (kernel == BITNET_HIP_KERNEL_MFMA && !mfma_supported(*w)) kernel = BITNET_HIP_KERNEL_VALU;
+        if (kernel == BITNET_HIP_KERNEL_VALU && !valu_supported(*w)) kernel = BITNET_HIP_KERNEL_EXACT;
+    }
+    out->kernel = kernel;
+    if (kernel != BITNET_HIP_KERNEL_MFMA) {
+        out->unfused = (ln_gamma_dev || silu) ? 1 : 0;
+        return BITNET_HIP_OK;
+    }
+    const bool ln = ln_gamma_dev != nullptr, ln2 = ln && w->ln_g && w->ln_gamma_bound == ln_gamma_dev;
+    GemvMfmaInstance q;
+    if (!gemv_mfma_instance(gemv_shape(*w), silu, ln, ln2, merge != 0, 1, q))
+        return set_error(BITNET_HIP_ERR_GPU, "kernel launch failed: %s", hipGetErrorString(hipErrorInvalidValue));  // run_gemv's words for launch_gemv_mfma's refusal
+    out->k_split = q.g.ksplit;
+    out->blocks = q.g.nblk;
+    out->blocks_per_wave = q.g.ring;
+    out->ring = q.ring_inst;
+    out->stat_vectors = q.nv_inst;
+    out->layernorm = q.ln;
+    out->scale_form = q.g.sc;
+    out->wscale = q.wscale;
+    out->merge = q.merge;
+    out->tiles_per_workgroup = q.g.tiles_per_wg;
+    out->grid = (int)q.g.grid;
+    out->lds_bytes = (int)q.lds;
+    out->lds_raised = q.raise_lds ? 1 : 0;
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 /* ---- QAct: activations quantised by their producer (csrc/qact.hpp) ---- */
 
 size_t bitnet_hip_qact_bytes(size_t cols) { return qact_bytes(cols); }

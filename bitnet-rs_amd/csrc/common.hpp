@@ -16,6 +16,7 @@
 #include <string>
 
 #include "bitnet_hip.h"
+#include "gemv_instance.hpp"
 
 namespace bitnet_hip {
 
@@ -148,17 +149,8 @@ bool valu_supported(const Weights &w);
 hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m, const GemvFusion &fu,
                             hipStream_t stream);
 bool mfma_supported(const Weights &w);
-int mfma_pick_ksplit(size_t rows, size_t cols, bool paired, int nw);
-// The K partition of one decode GEMV launch (kernels_mfma.hip, beside mfma_pick_ksplit): launch_gemv_mfma, launch_gemv_q and launch_gemv_q_batch
-// take every one of these numbers from here, so the batched launch cannot choose another partition than batch-1 (its per-vector bit identity).
-struct GemvGeom {
-    int ksplit, ks_log2;  // K ranges per row tile = waves sharing a tile (1, 2, 4 or 8)
-    int nblk;             // 256-column blocks per row
-    int ring, ring_t;     // blocks per wave, and the instantiated RING that holds them (LDS plane stride)
-    int tiles_per_wg;
-    unsigned grid;
-    int sc;               // 32-block weight scales: 0 none, 1 f32 tiles, 2 f16 tiles
-};
+// the K partition (mfma_pick_ksplit, GemvGeom) and the k_gemv_mfma instance of a launch: gemv_instance.hpp; these read them off a handle
+GemvShape gemv_shape(const Weights &w);
 GemvGeom gemv_geometry(const Weights &w, bool silu_mul, int n_waves = 8);
 bool gemvq_supported(const Weights &w);
 // What k_gemv_q's and k_gemv_q_batch's argument structs begin with (they derive from it: the kernels see the members where they always were),

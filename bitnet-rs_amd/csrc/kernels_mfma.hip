@@ -58,8 +58,7 @@ namespace bitnet_hip {
     } while (0)
 #endif
 
-constexpr int kRing = 5;   // weight tiles (1 KiB each) a wave keeps in flight
-constexpr int kNVMAX = 4;  // float4 LayerNorm-statistics vectors per thread (512 threads): K <= 8192
+constexpr int kRing = kGemvRing, kNVMAX = kGemvNVMax;  // gemv_instance.hpp
 
 struct MfmaArgs {
     const uint8_t *tiles;  // [n_tiles][nblk][64 lanes][16 B], fields transposed (k_retile)
@@ -554,43 +553,51 @@ bool mfma_supported(const Weights &w) {
     return true;
 }
 
-int mfma_pick_ksplit(size_t rows, size_t cols, bool paired, int nw) {
-    const size_t n_tiles = div_ceil(rows, 16), nblk = div_ceil(cols, 256);
-    const int ks_max = paired ? 4 : 8;  // K ranges per row tile (<= waves per workgroup)
-    // One round of identical workgroups: the largest K split whose grid still fits the 256 CUs with
-    // one workgroup each (a second workgroup on some CUs makes those the tail: 432 workgroups
-    // for gate|up took 7.4 us against 5.9 us for 216), K range per wave <= kRing blocks.
-    for (int ks = ks_max; ks >= 1; ks >>= 1) {
-        if ((size_t)ks > nblk || div_ceil(nblk, (size_t)ks) > (size_t)kRing) continue;
-        if (div_ceil(n_tiles * ks, (size_t)nw) <= 256) return ks;
-    }
-    // larger matrices need several rounds anyway: spread over the CUs without leaving a wave
-    // fewer than ~2 tiles
-    int ks = 1;
-    while (ks < ks_max && (n_tiles * ks < 8 * 256 || div_ceil(nblk, ks) > (size_t)kRing) && (size_t)ks * 2 <= nblk) ks *= 2;
-    return ks;
+// The shape gemv_instance.hpp selects on, read off a handle.  (The K split follows the LAUNCH's silu_mul, not the handle's pairing.)
+GemvShape gemv_shape(const Weights &w) {
+    GemvShape s;
+    s.rows = w.rows;
+    s.cols = w.cols;
+    s.sc = !(w.scaled && w.block_size == 32) ? 0 : w.scales_f16 ? 2 : 1;
+    s.wscale = w.scaled && w.block_size == 256;
+    return s;
 }
 
-// Everything the three decode GEMV launchers derive from the K split.  nblk and the grid round up: k_gemv_mfma alone takes ragged shapes
-// (the QAct kernels' cols % 256 == 0, rows % 16 == 0 make the rounding a no-op for them).
-GemvGeom gemv_geometry(const Weights &w, bool silu_mul, int n_waves) {
-    GemvGeom g;
-    g.ksplit = mfma_pick_ksplit(w.rows, w.cols, silu_mul, n_waves);
-    g.ks_log2 = g.ksplit == 8 ? 3 : g.ksplit == 4 ? 2 : g.ksplit == 2 ? 1 : 0;
-    g.nblk = (int)div_ceil(w.cols, 256);
-    g.ring = (int)div_ceil((size_t)g.nblk, (size_t)g.ksplit);
-    g.ring_t = g.ring <= 2 ? 2 : g.ring;
-    g.tiles_per_wg = n_waves / g.ksplit;
-    g.grid = (unsigned)div_ceil(div_ceil(w.rows, 16), (size_t)g.tiles_per_wg);
-    g.sc = !(w.scaled && w.block_size == 32) ? 0 : w.scales_f16 ? 2 : 1;
-    return g;
+GemvGeom gemv_geometry(const Weights &w, bool silu_mul, int n_waves) { return gemv_geometry_of(gemv_shape(w), silu_mul, n_waves); }
+
+// The instance table: every (RING, NV, LN, BS32, MERGE) that gemv_mfma_instance can name, nothing else.
+template <int RING, int NV, int LN, int MERGE = 0>
+static void (*mfma_kernel_sc(int sc))(MfmaArgs) {
+    return sc == 2 ? k_gemv_mfma<8, RING, NV, LN, 2, MERGE> : sc == 1 ? k_gemv_mfma<8, RING, NV, LN, 1, MERGE> : k_gemv_mfma<8, RING, NV, LN, 0, MERGE>;
+}
+template <int RING>
+static void (*mfma_kernel_ring(const GemvMfmaInstance &q))(MfmaArgs) {
+    if (q.ln == 0) return q.nv_inst == 1 ? mfma_kernel_sc<RING, 1, 0>(q.g.sc) : nullptr;
+    if (q.nv_inst != 2 && q.nv_inst != 4) return nullptr;
+    if (q.ln == 1) return q.nv_inst == 2 ? mfma_kernel_sc<RING, 2, 1>(q.g.sc) : mfma_kernel_sc<RING, 4, 1>(q.g.sc);
+    return q.nv_inst == 2 ? mfma_kernel_sc<RING, 2, 2>(q.g.sc) : mfma_kernel_sc<RING, 4, 2>(q.g.sc);
+}
+static void (*mfma_kernel(const GemvMfmaInstance &q))(MfmaArgs) {
+    if (q.nw != 8) return nullptr;
+    if (q.merge) return (q.ring_inst == 2 && q.nv_inst == 1 && q.ln == 0) ? mfma_kernel_sc<2, 1, 0, 1>(q.g.sc) : nullptr;
+    switch (q.ring_inst) {
+        case 2: return mfma_kernel_ring<2>(q);
+        case 3: return mfma_kernel_ring<3>(q);
+        case 4: return mfma_kernel_ring<4>(q);
+        case 5: return mfma_kernel_ring<5>(q);
+    }
+    return nullptr;
 }
 
 hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m, const GemvFusion &fu,
                             hipStream_t stream) {
     if (!w.tiles) return hipErrorInvalidValue;
-    const int nw = 8;  // (16-wave workgroups were a round-1 tuning knob that never paid: removed)
-    const GemvGeom g = gemv_geometry(w, fu.silu_mul, nw);
+    // the instance: K partition, RING, NV, LN, scale form, MERGE, LDS -- all of it from gemv_mfma_instance (bitnet_hip_gemv_geometry reports the same)
+    const bool ln = fu.ln_gamma != nullptr, ln2 = ln && w.ln_g && w.ln_gamma_bound == fu.ln_gamma;
+    GemvMfmaInstance q;
+    if (!gemv_mfma_instance(gemv_shape(w), fu.silu_mul, ln, ln2, fu.attn_rec != nullptr, m, q)) return hipErrorInvalidValue;
+    const GemvGeom &g = q.g;
+    const int nw = q.nw;
     MfmaArgs a;
     a.tiles = w.tiles;
     a.rows = (int)w.rows;
@@ -602,7 +609,7 @@ hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m
     a.inv_cols = 1.0 / (double)w.cols;
     a.ln_gamma = fu.ln_gamma;
     a.ln_eps = fu.ln_eps;
-    a.ln_g = (fu.ln_gamma && w.ln_g && w.ln_gamma_bound == fu.ln_gamma) ? w.ln_g : nullptr;
+    a.ln_g = ln2 ? w.ln_g : nullptr;
     a.wscale = (w.scaled && w.block_size == 256) ? w.scales : nullptr;
     if (w.scaled && w.block_size == 256 && !w.scales) return hipErrorInvalidValue;
     a.stiles = g.sc == 1 ? w.scale_tiles : nullptr;
@@ -620,26 +627,11 @@ hipError_t launch_gemv_mfma(const Weights &w, const float *x, float *y, size_t m
     if (fu.qout && (w.rows % 16 != 0 || m != 1 || (fu.silu_mul && w.rows % 32 != 0))) return hipErrorInvalidValue;
     a.stamps = g_mfma_stamps;
     const size_t out_rows = fu.silu_mul ? w.rows / 2 : w.rows;
-    // template selection: RING = blocks per wave, NV = statistics float4 per thread
-    const bool ln = fu.ln_gamma != nullptr, ln2 = a.ln_g != nullptr;
-    const int nv = ln ? (int)div_ceil(w.cols / 4, (size_t)nw * 64) : 1;
-    if (g.ring > kRing || nv > kNVMAX) return hipErrorInvalidValue;
-    void (*kfn)(MfmaArgs) = nullptr;
-#define BH_PICK(NWv, RINGv, NVv)                                                                          \
-    if (nw == NWv && g.ring <= RINGv && nv <= NVv && !kfn)                                                \
-        kfn = ln2 ? (g.sc == 2 ? k_gemv_mfma<NWv, RINGv, NVv, 2, 2> : g.sc == 1 ? k_gemv_mfma<NWv, RINGv, NVv, 2, 1> : k_gemv_mfma<NWv, RINGv, NVv, 2, 0>) \
-              : ln ? (g.sc == 2 ? k_gemv_mfma<NWv, RINGv, NVv, 1, 2> : g.sc == 1 ? k_gemv_mfma<NWv, RINGv, NVv, 1, 1> : k_gemv_mfma<NWv, RINGv, NVv, 1, 0>) \
-                   : (g.sc == 2 ? k_gemv_mfma<NWv, RINGv, 1, 0, 2> : g.sc == 1 ? k_gemv_mfma<NWv, RINGv, 1, 0, 1> : k_gemv_mfma<NWv, RINGv, 1, 0, 0>);
-    if (fu.attn_rec) {  // x merged from the decode attention's chunk records: the o-projection shape only
-        if (ln || m != 1 || nw != 8 || g.ring > 2 || w.cols % 128 != 0 || !fu.attn_pos || fu.attn_chunks_max < 1) return hipErrorInvalidValue;
-        kfn = g.sc == 2 ? k_gemv_mfma<8, 2, 1, 0, 2, 1> : g.sc == 1 ? k_gemv_mfma<8, 2, 1, 0, 1, 1> : k_gemv_mfma<8, 2, 1, 0, 0, 1>;
-    }
-    BH_PICK(8, 2, 2) BH_PICK(8, 2, 4) BH_PICK(8, 3, 2) BH_PICK(8, 3, 4) BH_PICK(8, 4, 2) BH_PICK(8, 4, 4) BH_PICK(8, 5, 2) BH_PICK(8, 5, 4)
-#undef BH_PICK
+    if (fu.attn_rec && (!fu.attn_pos || fu.attn_chunks_max < 1)) return hipErrorInvalidValue;
+    void (*kfn)(MfmaArgs) = mfma_kernel(q);
     if (!kfn) return hipErrorInvalidValue;
-    const size_t lds = (size_t)nw * (g.sc ? 5 : 4) * (g.ring_t * 256 + 16) + 2 * nw * sizeof(double) + nw * 16 * sizeof(float) +
-                       ((ln && !ln2) ? w.cols * sizeof(float) : 0);
-    if (lds > 64 * 1024) {
+    const size_t lds = q.lds;
+    if (q.raise_lds) {
         const hipError_t e = raise_dynamic_lds(kfn, 160 * 1024);
         if (e != hipSuccess) return e;
     }

@@ -424,6 +424,31 @@ size_t bitnet_hip_attention_merge_max_keys(void); /* largest *pos_dev + 1 the me
 int bitnet_hip_gemv_attn_merge_dev(bitnet_hip_weights_t w, const float *attn_scratch_dev, size_t n_heads,
                                    size_t n_kv_heads, size_t max_pos, const int32_t *pos_dev, float *y_dev,
                                    const float *residual_dev, void *stream);
+/* Which kernel bitnet_hip_gemv_dev / bitnet_hip_gemv_fused_dev / a bitnet_hip_matmul_dev row (merge 0) or bitnet_hip_gemv_attn_merge_dev
+ * (merge = query heads per KV head: 1, 2 or 4) would launch for this matrix under the current bitnet_hip_set_kernel choice, and, when that is
+ * the MFMA GEMV, which of its instances: flags = 0 or BITNET_HIP_FUSE_SILU_MUL, ln_gamma_dev = the LayerNorm weight the launch would pass
+ * (NULL: none; the one bound with bitnet_hip_weights_bind_ln selects the LayerNorm-after-product form).  One activation row (m = 1).  Host
+ * only: nothing is launched and the device is not touched.  What the launching entry would refuse for the shape is refused here with its
+ * message.  kernel != BITNET_HIP_KERNEL_MFMA: the matrix leaves the MFMA GEMV (unfused = the LayerNorm / residual / silu * up around it run
+ * as separate launches) and the instance fields are 0. */
+typedef struct {
+    int kernel;              /* BITNET_HIP_KERNEL_MFMA, _VALU or _EXACT: what run_gemv resolves the choice to */
+    int unfused;             /* 1: the fused options run as separate launches around the product (kernel != MFMA only) */
+    int k_split;             /* K ranges per 16-row tile = waves sharing a tile: 1, 2, 4 or 8 */
+    int blocks;              /* 256-column blocks per row (the last one may be ragged) */
+    int blocks_per_wave;     /* the longest K range */
+    int ring;                /* blocks per wave the instance holds (2..5, >= blocks_per_wave) */
+    int stat_vectors;        /* float4 LayerNorm-statistics vectors per thread the instance holds: 1 without LayerNorm, else 2 or 4 */
+    int layernorm;           /* 0 none, 1 prologue on the activations, 2 after the product (the bound gamma) */
+    int scale_form;          /* 32-block weight scales: 0 none, 1 f32, 2 f16 */
+    int wscale;              /* 1: one f32 scale per (row, 256-block), folded at run time */
+    int merge;               /* 1: the activation row is merged from the decode attention's chunk records */
+    int tiles_per_workgroup; /* 8 / k_split */
+    int grid;                /* workgroups per activation row */
+    int lds_bytes;           /* dynamic LDS of the launch */
+    int lds_raised;          /* 1: above 64 KiB, the kernel's dynamic LDS limit is raised before the launch */
+} bitnet_hip_gemv_geometry_t;
+int bitnet_hip_gemv_geometry(bitnet_hip_weights_t w, int flags, const float *ln_gamma_dev, int merge, bitnet_hip_gemv_geometry_t *out);
 /* ---- the decode step on activations quantised by their PRODUCER ("QAct") ---------------------------------------
  * north_star's kernel is "2-bit weight unpack x f16 activation dot product".  The f16-class activation of this
  * library is a QAct: per 16 consecutive elements one power-of-two scale and a 15-bit fixed-point value per element

@@ -38,17 +38,23 @@ TINY = 2.0 ** -126        # what a flushed or denormal f32 result may lose
 
 # ---------------------------------------------------------------- weights
 class Weights:
-    """w int8 [rows, cols] (code values); scale float64 [rows, cols / 32] or None; upload = the arguments of the upload call"""
+    """w int8 [rows, cols] (code values); scale float64 [rows, ceil(cols / block)] or None; block = columns per scale (32, or 256 for the
+    256-block scales only k_gemv_mfma takes); upload = the arguments of the upload call"""
 
-    def __init__(self, kind, w, scale, upload):
-        self.kind, self.w, self.scale, self.upload = kind, w, scale, upload
+    def __init__(self, kind, w, scale, upload, block=32):
+        self.kind, self.w, self.scale, self.upload, self.block = kind, w, scale, upload, block
         self.rows, self.cols = w.shape
 
     def _rows32(self, a, absolute):
         out = np.zeros(self.rows)
+        blk = self.block if self.cols % 32 == 0 else 256  # (ragged columns: k_gemv_mfma's shapes, no scales or 256-block ones)
+        nb = -(-self.cols // blk)
         for r0 in range(0, self.rows, 1024):  # (the largest shapes hold 19 M weights: no whole-matrix float64 copy)
             w = self.w[r0:r0 + 1024].astype(np.float64)
-            t = ((np.abs(w) if absolute else w) * a[None, :]).reshape(-1, self.cols // 32, 32).sum(-1)
+            t = (np.abs(w) if absolute else w) * a[None, :]
+            if nb * blk != self.cols:
+                t = np.concatenate([t, np.zeros((t.shape[0], nb * blk - self.cols))], axis=1)
+            t = t.reshape(-1, nb, blk).sum(-1)
             if self.scale is not None:
                 t = t * (np.abs(self.scale[r0:r0 + 1024]) if absolute else self.scale[r0:r0 + 1024])
             out[r0:r0 + 1024] = t.sum(1)
@@ -63,28 +69,34 @@ class Weights:
         return self._rows32(np.asarray(a, np.float64), False)
 
 
-def make_weights(kind, rows, cols, seed, scales="float"):
+def make_weights(kind, rows, cols, seed, scales="float", any_shape=False):
     """scales: "float" = arbitrary block scales (f16 values for i2s32h); "pow2" = two neighbouring powers of two (no f16 values for i2s32: a matrix
-    whose 32-block scales all are f16 values takes the f16 scale tiles)"""
-    assert kind in KINDS and cols % 256 == 0 and rows % 16 == 0
+    whose 32-block scales all are f16 values takes the f16 scale tiles).  any_shape (k_gemv_mfma): rows of any count, kind "i2s256" (one f32 scale
+    per 256-block), and for qk256 columns of any multiple of 4 -- the row keeps whole 64-byte blocks, the codes past `cols` are random and must
+    not enter the product."""
+    assert kind in KINDS + (("i2s256",) if any_shape else ()) and (any_shape or (cols % 256 == 0 and rows % 16 == 0))
     rng = np.random.default_rng(seed)
     if kind == "qk256":
-        qs = rng.integers(0, 256, (rows, cols // 4), dtype=np.uint8)
-        return Weights(kind, R.QK256_MAP[R.unpack_codes(qs, cols)].astype(np.int8), None, dict(qs=qs, stride=cols // 4))
+        assert cols % 4 == 0
+        stride = -(-cols // 256) * 64
+        qs = rng.integers(0, 256, (rows, stride), dtype=np.uint8)
+        return Weights(kind, R.QK256_MAP[R.unpack_codes(qs, cols)].astype(np.int8), None, dict(qs=qs, stride=stride))
+    assert cols % 256 == 0  # (a scaled matrix of ragged columns has no QK256-shaped rows: it leaves the MFMA kernel)
+    block = 256 if kind == "i2s256" else 32
     codes = rng.choice(np.array([0, 1, 3], np.uint8), size=(rows, cols), p=[0.5, 0.25, 0.25])
     if scales == "pow2":
-        s = np.exp2(-rng.integers(0, 2, (rows, cols // 32)).astype(np.float64) - (30.0 if kind == "i2s32" else 0.0)).astype(np.float32)
+        s = np.exp2(-rng.integers(0, 2, (rows, cols // block)).astype(np.float64) - (30.0 if kind == "i2s32" else 0.0)).astype(np.float32)
     else:
-        s = rng.uniform(0.05, 2.0, (rows, cols // 32)).astype(np.float32)
+        s = rng.uniform(0.05, 2.0, (rows, cols // block)).astype(np.float32)
         if kind == "i2s32h":
             s = s.astype(np.float16).astype(np.float32)
-    return Weights(kind, R.I2S_MAP[codes].astype(np.int8), s.astype(np.float64), dict(packed=R.pack_codes(codes), scales=s, block=32))
+    return Weights(kind, R.I2S_MAP[codes].astype(np.int8), s.astype(np.float64), dict(packed=R.pack_codes(codes), scales=s, block=block), block)
 
 
 def pair(a, b):
     """the (gate, up) handle of weights_concat(.., interleave16=True)"""
     sc = None if a.scale is None else R.interleave16(a.scale, b.scale)
-    return Weights(a.kind, R.interleave16(a.w, b.w), sc, dict(parts=(a, b)))
+    return Weights(a.kind, R.interleave16(a.w, b.w), sc, dict(parts=(a, b)), a.block)
 
 
 # ---------------------------------------------------------------- the activation
@@ -181,8 +193,11 @@ def product(wts, d0, d1, as_, k_split, fault=None, spread=None):
 G_ROUNDINGS = 2 * 2 * 5 + 4 + 7  # see g_rows
 
 
-def g_rows(wts, ln_gamma):
-    """g_r = W[r, :] . gamma as bitnet_hip_weights_bind_ln leaves it: ONE k_gemv_mfma launch on the f32 vector gamma (kernels_mfma.hip) -> g float64
+def g_rows(wts, ln_gamma, bind_k_split=None):
+    """bind_k_split (the K split of the binding launch, where the caller knows it from bitnet_hip_gemv_geometry): the bound of tests/gemv_mfma_ref.py's
+    model of that very launch, which knows the digits and counts the roundings of the partition taken; without it the partition-free bound below.
+
+    g_r = W[r, :] . gamma as bitnet_hip_weights_bind_ln leaves it: ONE k_gemv_mfma launch on the f32 vector gamma (kernels_mfma.hip) -> g float64
     [rows] (the exact dot product) and what the device's f32 g_r may differ from it by.
 
     That kernel holds every element of a wave's K range as q = floor(x 2^(29 - E) + 1/2), E the exponent of the range's maximum (:360-365): off by at
@@ -193,6 +208,10 @@ def g_rows(wts, ln_gamma):
         |g_r - g| <= gamma(31) 1.01 sum_k |W_k| (|gamma_k| + 2^-30 max|gamma|) + 2^-30 max|gamma| sum_k |W_k|
     (1.01: the balanced digits' magnitudes sum_d 256^d |d_d| exceed |q| by at most 128 / 127 per plane).  Exactly g where every gamma_k is one of two
     neighbouring powers of two and the block scales are powers of two: q is 2^29 or 2^28, one digit plane, and every sum stays below 2^24 units."""
+    if bind_k_split is not None:
+        import gemv_mfma_ref  # (imports this module: resolved at call time)
+
+        return gemv_mfma_ref.g_rows(wts, ln_gamma, bind_k_split)
     gm = np.asarray(ln_gamma, np.float32).astype(np.float64)
     g = wts.dot(gm)
     gmax = np.abs(gm).max()
@@ -205,16 +224,22 @@ def g_rows(wts, ln_gamma):
     return g, bg
 
 
-def ln_statistics(stats, cols, eps):
+def ln_statistics(stats, cols, eps, depth=None):
     """:399-415 -- the statistics pairs [cols / 16, 2] (f64) -> the f32 mean (as float64) and the denominator sqrtf(f32(var) + eps) (as float64).
 
     The device adds the pairs in f64 in an order of its own (lane-strided, then across the wave); an order can move either sum by 2^-53 per addition
-    of the magnitudes.  A vector on which that decides an f32 rounding (of the mean, or of the variance) is no reproducible input: asserted."""
+    of the magnitudes.  A vector on which that decides an f32 rounding (of the mean, or of the variance) is no reproducible input: asserted.
+    depth: the additions in sequence on the longest path of the summation, where the caller knows it (default: one per pair, any order at all).
+    A column whose entries are all multiples of one power of two and sum to less than 2^53 of them in magnitude is added exactly in any order."""
     st = np.asarray(stats, np.float64).reshape(-1, 2)
     inv = 1.0 / cols
     s1, s2 = st[:, 0].sum(), st[:, 1].sum()
-    slack = len(st) * 2.0 ** -53
+    slack = (len(st) if depth is None else depth) * 2.0 ** -53
     e1, e2 = slack * np.abs(st[:, 0]).sum(), slack * np.abs(st[:, 1]).sum()
+    if depth is not None:
+        q1, q2 = float(R.quantum(st[:, 0].reshape(1, -1)).min()), float(R.quantum(st[:, 1].reshape(1, -1)).min())
+        e1 = 0.0 if np.abs(st[:, 0]).sum() / q1 < 2.0 ** 53 else e1
+        e2 = 0.0 if np.abs(st[:, 1]).sum() / q2 < 2.0 ** 53 else e2
     mean_d = s1 * inv
     var_d = s2 * inv - mean_d * mean_d
     f32 = lambda v: np.float32(v)
@@ -226,14 +251,14 @@ def ln_statistics(stats, cols, eps):
     return float(f32(mean_d)), float(denom)
 
 
-def layernorm_after(p, stats, cols, eps, g, bg, fault=None):
+def layernorm_after(p, stats, cols, eps, g, bg, fault=None, depth=None):
     """:431, :455-456 -- v = f32(((double)v - mean g_r) r), r = 1 / denom from v_rcp_f64 and two Newton steps (within 2^-51 of 1 / denom).
 
     The target is (v* - mean g) / denom with v* the exact product and g the exact W . gamma.  The kernel's v is within p.bound of v*, its g_r within
     bg of g; the f64 operations (one product, one subtraction, one product, the reciprocal) stay within 2^-50 of the magnitudes; ONE f32 rounding:
         |error| <= (b_v + |mean| b_g) / denom + 2^-50 (|v| + |mean g|) / denom + u |want| + 2^-126
     With an exact product and an exact g_r that is the once-rounded value up to the f64 operations: the exact inputs are held to this."""
-    mean, denom = ln_statistics(stats, cols, eps)
+    mean, denom = ln_statistics(stats, cols, eps, depth)
     if fault == "g_row":
         g = np.roll(g, -16)
     v = np.where(p.bound[0] == 0, p.exact32[0].astype(np.float64), p.want[0])

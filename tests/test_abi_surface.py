@@ -149,6 +149,19 @@ def test_gemv_q_geometry_is_a_host_query(lib, pkg):
     assert lib.c.bitnet_hip_gemv_q_geometry(12345, 0, 0, 0, None) != 0
 
 
+def test_gemv_geometry_is_a_host_query(lib, pkg):
+    """bitnet_hip_gemv_geometry: fifteen ints behind one pointer, no device work -- without a GPU there is no handle to ask about, and it says so."""
+    import ctypes as C
+
+    assert "bitnet_hip_gemv_geometry" in pkg.declared_symbols()
+    assert C.sizeof(pkg.GemvGeometry) == 15 * C.sizeof(C.c_int)
+    assert lib.c.bitnet_hip_gemv_geometry.argtypes == [C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.POINTER(pkg.GemvGeometry)]
+    with pytest.raises(pkg.BitNetHipError, match="unknown weights handle") as e:
+        lib.gemv_geometry(12345)
+    assert e.value.code == pkg.ERR_INVALID_ARGUMENT
+    assert lib.c.bitnet_hip_gemv_geometry(12345, 0, None, 0, None) != 0
+
+
 def test_logits_head_refuses_shapes_it_has_no_instance_for_without_a_gpu(lib, pkg):
     """bitnet_hip_logits_f16_dev: hidden must be one of the kernel's instances (a multiple of 512 up to 8192; 0 is none), the workgroup count a
     grid size.  Refused before the launch."""

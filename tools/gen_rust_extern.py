@@ -14,7 +14,7 @@ BASE = {"size_t": "usize", "int": "c_int", "float": "c_float", "double": "f64", 
         "uint16_t": "u16", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "int64_t": "i64", "unsigned long long": "u64", "unsigned": "u32",
         "bitnet_hip_weights_t": "Weights", "bitnet_hip_device_info": "DeviceInfo", "bitnet_hip_gemv_item": "GemvItem", "_Float16": "u16",
         "bitnet_hip_sampling_config": "SamplingConfig", "bitnet_hip_sampling_config_ex": "SamplingConfigEx", "bitnet_hip_sampler": "Sampler", "bitnet_hip_sample_batch": "SampleBatch", "bitnet_hip_logprob_args": "LogprobArgs",
-        "bitnet_hip_gemv_q_geometry_t": "GemvQGeometry", "bitnet_hip_mirostat_config": "MirostatConfig", "bitnet_hip_stop_config": "StopConfig", "bitnet_hip_stop_state": "StopState", "bitnet_hip_stop": "Stop",
+        "bitnet_hip_gemv_q_geometry_t": "GemvQGeometry", "bitnet_hip_gemv_geometry_t": "GemvGeometry", "bitnet_hip_mirostat_config": "MirostatConfig", "bitnet_hip_stop_config": "StopConfig", "bitnet_hip_stop_state": "StopState", "bitnet_hip_stop": "Stop",
         "bitnet_hip_stop_batch": "StopBatch", "bitnet_hip_constraints": "Constraints"}
 
 

@@ -24,6 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libbitnet_hip.so")
 HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip.h")
+GRAMMAR_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar.h")  # included by HEADER_PATH: the grammar stage's six entry points
 
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_GPU, ERR_UNSUPPORTED, ERR_EXECUTION = -1, -2, -3, -4
@@ -116,6 +117,7 @@ class HipLib:
         self.path = path
         self.c = C.CDLL(path)
         cproto.bind(self.c, cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_"), C_STRUCTS)
+        cproto.bind(self.c, grammar_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -622,6 +624,11 @@ class HipLib:
         return Sampler(self, vocab, SamplingConfigEx.make(temperature, top_k, top_p, repetition_penalty, seed, min_p, typical_p,
                                                           frequency_penalty, presence_penalty))
 
+    def grammar(self, token_class, next_table) -> "Grammar":
+        """A token automaton on the device (bitnet_hip_grammar_*): token_class [vocab], next [n_states, n_classes]; grammar.token_automaton
+        compiles one from a byte-level DFA and the vocabulary's byte strings."""
+        return Grammar(self, token_class, next_table)
+
     def sample_batch(self, vocab: int, n_slots: int) -> "SampleBatch":
         """A table of n_slots sampler bindings served by one launch (bitnet_hip_sample_batch_*)."""
         return SampleBatch(self, vocab, n_slots)
@@ -739,6 +746,71 @@ class Constraints(C.Structure):
         return None if off or (nothing and not on) else cls.make(bias, allowed, hold, min_tokens, no_repeat_ngram)
 
 
+GRAMMAR_MAX_STATES, GRAMMAR_MAX_CLASSES = 65536, 16384
+
+
+class GrammarDesc(C.Structure):
+    """bitnet_hip_grammar_desc.  make() keeps the arrays the pointers refer to alive on the object."""
+    _fields_ = [("token_class", C.POINTER(C.c_uint16)), ("vocab", _sz), ("next", C.POINTER(C.c_int32)), ("n_states", _sz), ("n_classes", _sz)]
+
+    @classmethod
+    def make(cls, token_class, next_table) -> "GrammarDesc":
+        """token_class: [vocab] class ids; next_table: [n_states, n_classes] next states, -1 = the class is not allowed in the state."""
+        tc = np.asarray(token_class)
+        if tc.ndim != 1 or (tc.size and (tc.min() < 0 or tc.max() > 0xffff)):
+            raise ValueError("grammar: token_class must be one-dimensional with every class id in 0..65535")
+        nx = np.asarray(next_table)
+        if nx.ndim != 2:
+            raise ValueError(f"grammar: next must be [n_states, n_classes], got shape {nx.shape}")
+        if nx.size and (nx.min() < -(1 << 31) or nx.max() >= (1 << 31)):
+            raise ValueError("grammar: a next entry is outside the int32 range")
+        tc, nx = _np(tc, np.uint16), _np(nx, np.int32)
+        d = cls(tc.ctypes.data_as(C.POINTER(C.c_uint16)), tc.size, nx.ctypes.data_as(C.POINTER(C.c_int32)), nx.shape[0], nx.shape[1])
+        d._keep = (tc, nx)
+        return d
+
+
+class Grammar:
+    """One bitnet_hip_grammar: a token automaton on the device (token_class [vocab], next [n_states, n_classes]), bound to any number of
+    samplers with Sampler.set_grammar (a decoder's sampler: Decoder::set_grammar, host/grammar_host.hpp).  Keeps the descriptor, so walk() -- host only -- works for its whole life,
+    after close() too.  close() on a bound grammar takes effect when the last sampler lets go of it."""
+
+    def __init__(self, lib: HipLib, token_class, next_table):
+        self.lib = lib
+        self.h = None
+        self.desc = GrammarDesc.make(token_class, next_table)
+        self.vocab, self.n_states, self.n_classes = int(self.desc.vocab), int(self.desc.n_states), int(self.desc.n_classes)
+        h = _vp()
+        lib._check(lib.c.bitnet_hip_grammar_create(C.byref(self.desc), C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.c.bitnet_hip_grammar_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def walk(self, state: int, tokens) -> tuple[int, int]:
+        """(state reached, tokens taken) from `state`: stops in front of the first token that is not allowed or not in the vocabulary."""
+        return grammar_walk(self.lib, self.desc, state, tokens)
+
+
+def grammar_walk(lib: HipLib, desc: GrammarDesc, state: int, tokens) -> tuple[int, int]:
+    """bitnet_hip_grammar_walk on a descriptor: host only, no GPU."""
+    t = np.asarray(list(tokens), dtype=np.int64).reshape(-1)
+    if t.size and (t.min() < -(1 << 31) or t.max() >= (1 << 31)):
+        raise ValueError("grammar: token id outside the int32 range")
+    t = _np(t.astype(np.int32), np.int32)
+    out, taken = C.c_int32(-1), _sz(0)
+    lib._check(lib.c.bitnet_hip_grammar_walk(C.byref(desc), int(state), t.ctypes.data_as(_vp) if t.size else None, t.size, C.byref(out), C.byref(taken)))
+    return int(out.value), int(taken.value)
+
+
 class Sampler:
     """One bitnet_hip_sampler: state (config, ChaCha20 key, word counter, token counts) in device memory."""
 
@@ -803,6 +875,23 @@ class Sampler:
         g = C.c_uint64(0)
         self.lib._check(self.lib.c.bitnet_hip_sampler_constraints_state(self.h, C.byref(g)))
         return int(g.value)
+
+    def set_grammar(self, grammar: "Grammar | None", start_state: int = 0) -> None:
+        """Bind a token automaton (bitnet_hip_sampler_set_grammar): every launch bans the tokens the state does not allow and moves the state
+        with the token it chose, on the device.  None: off.  The state starts at start_state, both counters at 0.  Graphs that captured
+        sample_dev follow it."""
+        self.lib._check(self.lib.c.bitnet_hip_sampler_set_grammar(self.h, grammar.h if grammar is not None else None, int(start_state)))
+        self._grammar = grammar  # the Python object stays alive while bound
+
+    def set_grammar_state(self, state: int) -> None:
+        """Overwrite the state word (the counters stay): what a host calls after a rewind, with Grammar.walk's state."""
+        self.lib._check(self.lib.c.bitnet_hip_sampler_set_grammar_state(self.h, int(state)))
+
+    def grammar_state(self) -> tuple[int, int, int]:
+        """(state, steps, violations) of the bound grammar; (-1, 0, 0) without one.  Synchronous."""
+        s, n, v = C.c_int32(-1), C.c_uint64(0), C.c_uint64(0)
+        self.lib._check(self.lib.c.bitnet_hip_sampler_grammar_state(self.h, C.byref(s), C.byref(n), C.byref(v)))
+        return int(s.value), int(n.value), int(v.value)
 
     def sample_host(self, logits, generated=()) -> int:
         """Sampler::sample(&logits, &generated_tokens): the whole generated list on every call."""
@@ -999,9 +1088,14 @@ def load() -> HipLib:
     return _lib
 
 
+def grammar_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_grammar.h, the header include/bitnet_hip.h includes for the sampler's grammar stage."""
+    return cproto.prototypes(open(GRAMMAR_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def declared_symbols() -> list[str]:
-    """Every function include/bitnet_hip.h declares (used by the export test)."""
-    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_")})
+    """Every function include/bitnet_hip.h declares, the header it includes among them (used by the export test)."""
+    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -1010,6 +1104,7 @@ def declared_symbols() -> list[str]:
 
 HOST_LIB_PATH = os.path.join(HERE, "libbitnet_host.so")
 HOST_HEADER_PATHS = [os.path.join(HERE, "host", f) for f in ("decoder.hpp", "batch_decoder.hpp", "gguf.hpp")]
+HOST_GRAMMAR_HEADER_PATH = os.path.join(HERE, "host", "grammar_host.hpp")  # the decoder's grammar control, bound beside the others
 _host_libs = {}
 
 
@@ -1018,11 +1113,17 @@ def host_prototypes() -> list:
     return [p for h in HOST_HEADER_PATHS for p in cproto.prototypes(open(h).read(), "bitnet_host_")]
 
 
+def host_grammar_prototypes() -> list:
+    """The three exports of host/grammar_host.hpp (Decoder::set_grammar, set_grammar_state, grammar_state), typed at load like the rest."""
+    return cproto.prototypes(open(HOST_GRAMMAR_HEADER_PATH).read(), "bitnet_host_")
+
+
 def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
     """The host library at `path`, loaded and bound from its headers once per process."""
     if path not in _host_libs:
         L = C.CDLL(path)
         cproto.bind(L, host_prototypes(), C_STRUCTS)
+        cproto.bind(L, host_grammar_prototypes(), C_STRUCTS)
         _host_libs[path] = L
     return _host_libs[path]
 
@@ -1054,7 +1155,7 @@ class HostConfig(C.Structure):
 # the structs that cross the C ABI by pointer, by their C names: cproto.bind types such a parameter as POINTER of the class
 C_STRUCTS = {"bitnet_hip_device_info": DeviceInfo, "bitnet_hip_gemv_q_geometry_t": GemvQGeometry, "bitnet_hip_gemv_geometry_t": GemvGeometry, "bitnet_hip_sampling_config": SamplingConfig,
              "bitnet_hip_sampling_config_ex": SamplingConfigEx, "bitnet_hip_mirostat_config": MirostatConfig,
-             "bitnet_hip_constraints": Constraints, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
+             "bitnet_hip_constraints": Constraints, "bitnet_hip_grammar_desc": GrammarDesc, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
              "bitnet_hip_stop_state": StopState, "bitnet_host_config": HostConfig}
 
 FLAVORS = ("BitNet32F16", "Split32WithSibling", "GgmlQk256NoScale")

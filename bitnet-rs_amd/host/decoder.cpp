@@ -1,6 +1,7 @@
 // decoder.cpp -- see decoder.hpp.  Host orchestration only; every device operation is a
 // bitnet_hip_* call (include/bitnet_hip.h) or plain HIP memory / stream / graph plumbing.
 #include "decoder.hpp"
+#include "grammar_host.hpp"
 
 #include "blake3.hpp"
 #include "stream_timer.hpp"
@@ -488,6 +489,32 @@ int Decoder::constraints_state(uint64_t *chosen) {
     if (!sampler_) return 0;
     HCHK(hipStreamSynchronize((hipStream_t)stream_));
     BCHK(bitnet_hip_sampler_constraints_state(sampler_, chosen));
+    return 0;
+}
+
+int Decoder::set_grammar(bitnet_hip_grammar *g, int start) {
+    if (!g && !sampler_) return 0;  // off on a decoder that never sampled: nothing to switch off
+    if (g && (!sampling_ || !sampler_)) return fail_arg("set_grammar: sampling is off (set_sampling first; temperature 0 is greedy)");
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));  // the words are copied synchronously: no queued step may still read the old ones
+    // the mode bit, the table addresses and the state are reached through device memory by the sampling launch: the captured graphs follow and stay
+    BCHK(bitnet_hip_sampler_set_grammar(sampler_, g, start));
+    return 0;
+}
+
+int Decoder::set_grammar_state(int state) {
+    if (!sampling_ || !sampler_) return fail_arg("set_grammar_state: sampling is off (set_sampling and set_grammar first)");
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    BCHK(bitnet_hip_sampler_set_grammar_state(sampler_, state));
+    return 0;
+}
+
+int Decoder::grammar_state(int32_t *state, uint64_t *steps, uint64_t *violations) {
+    if (state) *state = -1;
+    if (steps) *steps = 0;
+    if (violations) *violations = 0;
+    if (!sampler_) return 0;
+    HCHK(hipStreamSynchronize((hipStream_t)stream_));
+    BCHK(bitnet_hip_sampler_grammar_state(sampler_, state, steps, violations));
     return 0;
 }
 
@@ -2167,6 +2194,12 @@ int bitnet_host_set_mirostat(void *d, const bitnet_hip_mirostat_config *cfg) { L
 int bitnet_host_mirostat_state(void *d, float *mu, uint64_t *fallbacks) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->mirostat_state(mu, fallbacks); }
 int bitnet_host_set_constraints(void *d, const bitnet_hip_constraints *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_constraints(cfg); }
 int bitnet_host_constraints_state(void *d, uint64_t *chosen) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->constraints_state(chosen); }
+int bitnet_host_set_grammar(void *d, bitnet_hip_grammar *g, int start_state) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_grammar(g, start_state); }
+int bitnet_host_set_grammar_state(void *d, int state) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_grammar_state(state); }
+int bitnet_host_grammar_state(void *d, int32_t *state, uint64_t *steps, uint64_t *violations) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->grammar_state(state, steps, violations);
+}
 int bitnet_host_sampling_draws(void *d, uint64_t *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->sampling_draws(out); }
 int bitnet_host_set_stop(void *d, const bitnet_hip_stop_config *cfg) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->set_stop(cfg); }
 int bitnet_host_stop_state(void *d, bitnet_hip_stop_state *out) { LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT); return D->stop_state(out); }

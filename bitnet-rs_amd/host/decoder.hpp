@@ -140,6 +140,16 @@ class Decoder : private DecoderStreams {
     // and shift() leave it as they leave the counts, fork() resets each destination's with its sampler.
     int set_constraints(const bitnet_hip_constraints *cfg);
     int constraints_state(uint64_t *chosen);  // synchronises; 0 without a sampler
+    // Grammar-constrained decoding on this decoder's sampler (bitnet_hip_sampler_set_grammar: a token automaton whose state moves with every
+    // chosen token, on the device): needs sampling on -- greedy decoding under a grammar is set_sampling with temperature 0; NULL = off, a no-op
+    // without a sampler.  Synchronises the stream before the copy and drops no graphs: the launch reaches the mode bit, the tables and the state
+    // through device memory.  The handle stays the caller's and may serve many decoders (it counts its bindings).  reset() puts the state back
+    // to `start`; rewind(), fork() and shift() do NOT move a sampler, so the state stays where the tokens since dropped left it: after rewind(n)
+    // the caller sets it with set_grammar_state(the state bitnet_hip_grammar_walk gives for the generated tokens that remain).  C exports:
+    // grammar_host.hpp.
+    int set_grammar(bitnet_hip_grammar *g, int start);
+    int set_grammar_state(int state);
+    int grammar_state(int32_t *state, uint64_t *steps, uint64_t *violations);  // synchronises; -1 / 0 / 0 without a sampler or a grammar
     int sampling_draws(uint64_t *out);
     // The reference's logits tap on the generation path (GenerationConfig::{logits_tap_steps, logits_topk, logits_cb}, crates/bitnet-inference/src/
     // config.rs:87-93, engine.rs:1182-1210; the CLI's LogitStep records, crates/bitnet-cli/src/main.rs:1337-1373) on the device: top_n = -1 (default)
@@ -260,7 +270,7 @@ class Decoder : private DecoderStreams {
     // Keep the first n positions of the sequence, 0 <= n <= position(): the position becomes n and the forced count min(forced, n), on
     // host and device.  The cache bytes stay as they are (the decode attention gives slots beyond the position zero weight, the
     // continuation attention never reads a slot at or beyond its past length), and so do the sampler's counts and word counter:
-    // reset() remains the full clear.
+    // reset() remains the full clear.  A bound grammar's state stays too: set_grammar_state(walk of the tokens that remain) moves it.
     int rewind(int n);
     // CONTEXT SHIFT: keep the first `keep` positions, discard the next `discard`, slide the rest down -- the member of the live-sequence family
     // that drops tokens from the MIDDLE (the reference's KvCacheBuffer::rotate_kv / truncate, crates/bitnet-kernels/src/cuda/kv_cache.rs:305-348,

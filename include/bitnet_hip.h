@@ -916,8 +916,11 @@ typedef struct bitnet_hip_constraints {
 } bitnet_hip_constraints;
 int bitnet_hip_sampler_set_constraints(bitnet_hip_sampler *sampler, const bitnet_hip_constraints *cfg);
 int bitnet_hip_sampler_constraints_state(bitnet_hip_sampler *sampler, uint64_t *chosen);
+/* Grammar-constrained decoding (a token automaton whose state moves with every chosen token; bitnet_hip_grammar_*, bitnet_hip_sampler_set_grammar,
+ * _set_grammar_state, _grammar_state): declared in bitnet_hip_grammar.h, included at the end of this header. */
 /* Clears the counts (a new generation), the word counter and the constraints' count of chosen tokens, and re-arms the launch hand-over (a
  * launch cut short leaves it unbalanced).  With Mirostat on: mu = 2 * tau (MirostatSampler::reset, strategies.rs:192-195) and the fallback count 0.
+ * With a grammar bound: the state word goes back to the bound start state, steps and violations to 0.
  * Synchronous; call it with no sample_dev / sample_host in flight.  Not capture-safe. */
 int bitnet_hip_sampler_reset(bitnet_hip_sampler *sampler);
 /* ChaCha20 words consumed since create / configure / reset (one per non-greedy call; none for a call that took Mirostat's fallback).
@@ -1101,4 +1104,7 @@ int bitnet_hip_hbm_read_ceiling(size_t bytes, int iters, double *best_gbs, doubl
 #ifdef __cplusplus
 }
 #endif
+
+#include "bitnet_hip_grammar.h" /* the sampler's grammar stage: six more entry points of this ABI */
+
 #endif /* BITNET_HIP_H */

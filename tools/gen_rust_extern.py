@@ -15,7 +15,7 @@ BASE = {"size_t": "usize", "int": "c_int", "float": "c_float", "double": "f64", 
         "bitnet_hip_weights_t": "Weights", "bitnet_hip_device_info": "DeviceInfo", "bitnet_hip_gemv_item": "GemvItem", "_Float16": "u16",
         "bitnet_hip_sampling_config": "SamplingConfig", "bitnet_hip_sampling_config_ex": "SamplingConfigEx", "bitnet_hip_sampler": "Sampler", "bitnet_hip_sample_batch": "SampleBatch", "bitnet_hip_logprob_args": "LogprobArgs",
         "bitnet_hip_gemv_q_geometry_t": "GemvQGeometry", "bitnet_hip_gemv_geometry_t": "GemvGeometry", "bitnet_hip_mirostat_config": "MirostatConfig", "bitnet_hip_stop_config": "StopConfig", "bitnet_hip_stop_state": "StopState", "bitnet_hip_stop": "Stop",
-        "bitnet_hip_stop_batch": "StopBatch", "bitnet_hip_constraints": "Constraints"}
+        "bitnet_hip_stop_batch": "StopBatch", "bitnet_hip_constraints": "Constraints", "bitnet_hip_grammar_desc": "GrammarDesc", "bitnet_hip_grammar": "Grammar"}
 
 
 def rust_type(c: str) -> str:
@@ -38,7 +38,7 @@ def prototypes(header: str):
 
 
 def main():
-    header = open(os.path.join(ROOT, "include", "bitnet_hip.h")).read()
+    header = open(os.path.join(ROOT, "include", "bitnet_hip.h")).read() + open(os.path.join(ROOT, "include", "bitnet_hip_grammar.h")).read()
     have = set(re.findall(r"pub fn (bitnet_hip_[a-z0-9_]+)", open(os.path.join(ROOT, "INTEGRATION.md")).read())) if "--missing" in sys.argv else set()
     for name, line in prototypes(header):
         if name not in have:

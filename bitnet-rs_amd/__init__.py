@@ -15,6 +15,7 @@ import ctypes as C
 import importlib.util
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -25,6 +26,7 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libbitnet_hip.so")
 HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip.h")
 GRAMMAR_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar.h")  # included by HEADER_PATH: the grammar stage's six entry points
+KVSNAP_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")  # included by HEADER_PATH: the KV snapshot's three entry points
 
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_GPU, ERR_UNSUPPORTED, ERR_EXECUTION = -1, -2, -3, -4
@@ -118,6 +120,7 @@ class HipLib:
         self.c = C.CDLL(path)
         cproto.bind(self.c, cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_"), C_STRUCTS)
         cproto.bind(self.c, grammar_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, kvsnap_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -523,6 +526,25 @@ class HipLib:
         device tensors of device pointers, the source's [n_layers], the destinations' [n_dst][n_layers]; buffers distinct, 16-byte aligned."""
         self._check(self.c.bitnet_hip_kv_fork_dev(_ptr(src_k_ptrs), _ptr(src_v_ptrs), _ptr(dst_k_ptrs), _ptr(dst_v_ptrs), n_layers, n_dst, n_kv, head_dim,
                                                   max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
+
+    def kv_snapshot_bytes(self, n_layers: int, n_kv: int, head_dim: int, n_positions: int, kv_f16: bool = False) -> int:
+        """Bytes of a snapshot of n_positions: K [n_layers][n_kv][n_positions][128] then V the same, in the cache's element type; 0 for a
+        geometry kv_save_dev / kv_restore_dev refuse."""
+        return int(self.c.bitnet_hip_kv_snapshot_bytes(n_layers, n_kv, head_dim, n_positions, 2 if kv_f16 else 0))
+
+    def kv_save_dev(self, k_ptrs, v_ptrs, n_layers: int, n_kv: int, head_dim: int, max_pos: int, n_positions: int, snapshot, kv_f16: bool = False,
+                    stream: int = 0) -> None:
+        """Cache slots [0, n_positions) of every layer's K and V of one sequence into `snapshot` (kv_snapshot_bytes, 16-byte aligned), position-major,
+        bit for bit, in one launch.  *_ptrs: int64 device tensors of n_layers device pointers."""
+        self._check(self.c.bitnet_hip_kv_save_dev(_ptr(k_ptrs), _ptr(v_ptrs), n_layers, n_kv, head_dim, max_pos, n_positions, 2 if kv_f16 else 0,
+                                                  _ptr(snapshot), _vp(stream)))
+
+    def kv_restore_dev(self, snapshot, snapshot_positions: int, dst_k_ptrs, dst_v_ptrs, n_layers: int, n_dst: int, n_kv: int, head_dim: int,
+                       max_pos: int, n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
+        """Positions [0, n_positions) of a snapshot of snapshot_positions into cache slots [0, n_positions) of n_dst destinations, bit for bit, in
+        one launch; every other cache byte stays.  dst_*_ptrs: int64 device tensors [n_dst][n_layers] of device pointers, as kv_fork_dev takes."""
+        self._check(self.c.bitnet_hip_kv_restore_dev(_ptr(snapshot), snapshot_positions, _ptr(dst_k_ptrs), _ptr(dst_v_ptrs), n_layers, n_dst, n_kv,
+                                                     head_dim, max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
 
     def kv_shift_dev(self, k_ptrs, v_ptrs, rope_sin, rope_cos, n_layers: int, n_kv: int, head_dim: int, max_pos: int, keep: int, discard: int,
                      n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
@@ -1093,9 +1115,14 @@ def grammar_prototypes() -> list:
     return cproto.prototypes(open(GRAMMAR_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def kvsnap_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_kvsnap.h, the header include/bitnet_hip.h includes for the compact KV snapshots."""
+    return cproto.prototypes(open(KVSNAP_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def declared_symbols() -> list[str]:
-    """Every function include/bitnet_hip.h declares, the header it includes among them (used by the export test)."""
-    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes()})
+    """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
+    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + kvsnap_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -1105,6 +1132,7 @@ def declared_symbols() -> list[str]:
 HOST_LIB_PATH = os.path.join(HERE, "libbitnet_host.so")
 HOST_HEADER_PATHS = [os.path.join(HERE, "host", f) for f in ("decoder.hpp", "batch_decoder.hpp", "gguf.hpp")]
 HOST_GRAMMAR_HEADER_PATH = os.path.join(HERE, "host", "grammar_host.hpp")  # the decoder's grammar control, bound beside the others
+HOST_PREFIX_HEADER_PATH = os.path.join(HERE, "host", "prefix_cache.hpp")  # PrefixCache and Decoder::prefill_cached, bound beside the others
 _host_libs = {}
 
 
@@ -1118,12 +1146,18 @@ def host_grammar_prototypes() -> list:
     return cproto.prototypes(open(HOST_GRAMMAR_HEADER_PATH).read(), "bitnet_host_")
 
 
+def host_prefix_prototypes() -> list:
+    """The exports of host/prefix_cache.hpp (PrefixCache, Decoder::prefill_cached), typed at load like the rest."""
+    return cproto.prototypes(open(HOST_PREFIX_HEADER_PATH).read(), "bitnet_host_")
+
+
 def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
     """The host library at `path`, loaded and bound from its headers once per process."""
     if path not in _host_libs:
         L = C.CDLL(path)
         cproto.bind(L, host_prototypes(), C_STRUCTS)
         cproto.bind(L, host_grammar_prototypes(), C_STRUCTS)
+        cproto.bind(L, host_prefix_prototypes(), C_STRUCTS)
         _host_libs[path] = L
     return _host_libs[path]
 
@@ -1145,6 +1179,12 @@ def host_device_bytes() -> int:
     return int(L.bitnet_host_device_bytes())
 
 
+class PrefixStats(C.Structure):
+    """bitnet_host_prefix_stats (host/prefix_cache.hpp): the reference's PrefixCacheStats"""
+    _fields_ = [("hit_rate", C.c_double), ("miss_rate", C.c_double), ("avg_prefix_match_length", C.c_double), ("eviction_count", C.c_uint64),
+                ("memory_usage", C.c_uint64)]
+
+
 class HostConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("hidden", "n_layers", "n_heads", "n_kv_heads", "head_dim", "ffn", "vocab", "max_pos")] + [
         ("eps", C.c_float),
@@ -1156,7 +1196,7 @@ class HostConfig(C.Structure):
 C_STRUCTS = {"bitnet_hip_device_info": DeviceInfo, "bitnet_hip_gemv_q_geometry_t": GemvQGeometry, "bitnet_hip_gemv_geometry_t": GemvGeometry, "bitnet_hip_sampling_config": SamplingConfig,
              "bitnet_hip_sampling_config_ex": SamplingConfigEx, "bitnet_hip_mirostat_config": MirostatConfig,
              "bitnet_hip_constraints": Constraints, "bitnet_hip_grammar_desc": GrammarDesc, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
-             "bitnet_hip_stop_state": StopState, "bitnet_host_config": HostConfig}
+             "bitnet_hip_stop_state": StopState, "bitnet_host_config": HostConfig, "bitnet_host_prefix_stats": PrefixStats}
 
 FLAVORS = ("BitNet32F16", "Split32WithSibling", "GgmlQk256NoScale")
 
@@ -1587,6 +1627,16 @@ class HostDecoder:
         """src.fork_into([self], n)"""
         src.fork_into([self], n)
 
+    def prefill_cached(self, cache: "PrefixCache", n: int, with_logits: bool = True, digits: int = 4) -> int:
+        """prefill(n) through a PrefixCache, on a fresh sequence: with a hit of length m the entry's first min(m, n - 1) positions are restored
+        into this decoder (one launch) and extend() runs over the rest of the prompt -- fork at m, feed, extend, bit for bit; without a hit it
+        is prefill(n, with_logits, digits).  Returns the positions restored (0: no hit).  Never inserts: cache.insert(self, n) does.
+        A hit is a fork: it also resets this decoder's sampler, clears its logprob records and zeroes tokens fed beyond n, which a miss
+        does not (host/decoder.hpp, prefill_cached): feed exactly n tokens and set the sampler up afterwards for one outcome."""
+        hit, ms = C.c_int(0), C.c_float(0)
+        self._check(_prefix_fn(self.c, "bitnet_host_prefill_cached")(self.h, cache.h, int(n), int(with_logits), int(digits), C.byref(hit), C.byref(ms)))
+        return int(hit.value)
+
     def cached_prefix(self, tokens) -> int:
         """Length of the longest common prefix of `tokens` and this sequence's consumed history (the reference's PrefixCache lookup)."""
         t = _np(tokens, np.int32)
@@ -1652,6 +1702,101 @@ class HostDecoder:
 
     def weight_bytes(self) -> int:
         return int(self.c.bitnet_host_weight_bytes(self.h))
+
+
+def _prefix_fn(host: C.CDLL, name: str):
+    """An export of host/prefix_cache.hpp on the bound host library.  By name: these are typed from THAT header at load (host_prefix_prototypes),
+    not from the three headers host_prototypes() reads."""
+    return getattr(host, name)
+
+
+class PrefixCache:
+    """ctypes view of the C++ PrefixCache (host/prefix_cache.hpp): the reference's prompt prefix cache (crates/bitnet-inference/src/
+    prefix_cache.rs: trie, longest-prefix lookup, LRU / LFU / FIFO / TTL eviction under an entry limit and a byte limit, statistics) with each
+    cached state ONE compact device snapshot -- the first n positions of every layer's K and V, nothing of max_pos -- instead of host bytes.
+    insert() saves a prefix of a live decoder (one launch), lookup() is host only, restore() puts an entry into up to 8 decoders (one launch),
+    each left as fork_into from the source at insert time would have left it.  The defaults are the reference's.  No arithmetic here."""
+
+    POLICIES = {"lru": 0, "lfu": 1, "fifo": 2, "ttl": 3}
+
+    def __init__(self, max_entries: int = 1024, max_memory_bytes: int = 512 * 1024 * 1024, policy: str = "lru", min_prefix_length: int = 4,
+                 ttl_seconds: int = 3600, path: str = HOST_LIB_PATH):
+        load()
+        self.c = _host_lib(path)
+        if policy not in self.POLICIES:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, f"PrefixCache: policy must be one of {sorted(self.POLICIES)}, got {policy!r}")
+        self.h = self._f("create")(int(max_entries), int(max_memory_bytes), self.POLICIES[policy], int(min_prefix_length), int(ttl_seconds))
+        if not self.h:
+            raise BitNetHipError(ERR_GPU, "bitnet_host_prefix_cache_create failed")
+
+    def _f(self, name: str):
+        return _prefix_fn(self.c, "bitnet_host_prefix_cache_" + name)
+
+    def error(self) -> str:
+        e = self._f("error")(self.h)
+        return e.decode() if e else ""
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise BitNetHipError(rc, self.error() or f"bitnet_host_prefix_cache rc={rc}")
+
+    def close(self) -> None:
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = None
+
+    def insert(self, dec: "HostDecoder", n: int, now: int | None = None) -> int:
+        """Caches the first n positions of `dec` (0 < n <= position()) under its first n tokens: one save launch into a snapshot of
+        lib.kv_snapshot_bytes.  Evicts by the policy until both limits hold.  now: a monotonic clock in seconds for the TTL policy
+        (default time.monotonic()).  Returns the entry's id."""
+        out = C.c_uint64(0)
+        self._check(self._f("insert")(self.h, dec.h, int(n), int(time.monotonic() if now is None else now), C.byref(out)))
+        return int(out.value)
+
+    def lookup(self, tokens) -> "tuple[int, int] | None":
+        """(matched length, id) of the longest entry whose whole key is a prefix of `tokens`, or None.  Host only."""
+        t = _np(tokens, np.int32)
+        m, i = C.c_int(0), C.c_uint64(0)
+        rc = int(self._f("lookup")(self.h, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, C.byref(m), C.byref(i)))
+        if rc < 0:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, "bitnet_host_prefix_cache_lookup failed")
+        return (int(m.value), int(i.value)) if rc else None
+
+    def restore(self, id: int, dsts, n: int | None = None) -> None:
+        """The first n positions of entry `id` (default: all of them) into every decoder of `dsts` (1..8; the refusals are fork_into's): one
+        restore launch; each ends as fork_into(dsts, n) from the source at insert time would have left it."""
+        dsts = list(dsts)
+        arr = (C.c_void_p * max(len(dsts), 1))(*[d.h if d is not None else None for d in dsts])
+        self._check(self._f("restore")(self.h, int(id), arr, len(dsts), -1 if n is None else int(n)))
+        forced = C.c_int(0)
+        self._f("entry")(self.h, int(id), None, None, C.byref(forced))  # the forced count the entry carries, as the host layer keeps it
+        for d in dsts:
+            d._fed = int(forced.value) if n is None else min(int(forced.value), int(n))
+
+    def entry(self, id: int) -> "tuple[int, int]":
+        """(positions, snapshot bytes) of entry `id`; raises for an id the cache does not hold"""
+        n, b = C.c_int(0), C.c_uint64(0)
+        if self._f("entry")(self.h, int(id), C.byref(n), C.byref(b), None) != 0:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, f"PrefixCache: no entry {id}")
+        return int(n.value), int(b.value)
+
+    def invalidate(self, tokens) -> bool:
+        t = _np(tokens, np.int32)
+        rc = int(self._f("invalidate")(self.h, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size))
+        if rc < 0:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, "bitnet_host_prefix_cache_invalidate failed")
+        return bool(rc)
+
+    def clear(self) -> None:
+        self._check(self._f("clear")(self.h))
+
+    def stats(self) -> dict:
+        s = PrefixStats()
+        self._check(self._f("stats")(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in PrefixStats._fields_}
+
+    def __len__(self) -> int:
+        return int(self._f("len")(self.h))
 
 
 class HostBatch:

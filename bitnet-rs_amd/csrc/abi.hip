@@ -1411,6 +1411,78 @@ int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const 
     BH_GUARD_END
 }
 
+/* ---- compact snapshots of a live sequence's KV state (kernels_kvsnap.hip) ---- */
+
+namespace {
+// bytes of a snapshot of n_positions, or 0: a geometry the launches refuse, or a size that overflows
+size_t kv_snapshot_size(size_t n_layers, size_t n_kv_heads, size_t head_dim, size_t n_positions, int flags) {
+    if (n_layers == 0 || n_kv_heads == 0 || head_dim != 128 || (flags & ~BITNET_HIP_ATTN_KV_F16)) return 0;
+    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
+    size_t segments = 0, bytes = 0;
+    if (__builtin_mul_overflow(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, (size_t)2, &segments) || segments >= ((size_t)1 << 24) ||
+        __builtin_mul_overflow(segments, n_positions, &bytes) || __builtin_mul_overflow(bytes, rows * sizeof(uint32_t), &bytes))
+        return 0;
+    return bytes;
+}
+
+// The refusals save and restore share, fork's wording where the case is fork's; leaves rows and head_words.  `positions`: what the snapshot holds.
+int kv_snapshot_check(const char *entry, size_t n_layers, size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t n_positions, size_t positions, int flags,
+                      const void *snapshot, size_t *rows_out, size_t *head_words_out) {
+    if (n_layers == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_layers 0", entry);
+    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: head_dim %zu unsupported (128)", entry, head_dim);
+    if (n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: num_key_value_heads 0", entry);
+    if (flags & ~BITNET_HIP_ATTN_KV_F16) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16)", entry, flags);
+    if (n_positions > max_pos)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: n_positions %zu, max_pos %zu", n_positions, max_pos);  // T:1190-1194
+    if (n_positions > positions)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_positions %zu exceeds snapshot_positions %zu", entry, n_positions, positions);
+    if ((uintptr_t)snapshot % 16) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: the snapshot must be 16-byte aligned", entry);
+    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
+    size_t slots = 0, head_words = 0, cache_bytes = 0;
+    if (__builtin_add_overflow(max_pos, (size_t)63, &slots) || __builtin_mul_overflow(slots / 64 * 64, rows, &head_words) ||
+        __builtin_mul_overflow(head_words, n_kv_heads, &cache_bytes) || __builtin_mul_overflow(cache_bytes, sizeof(uint32_t), &cache_bytes) ||
+        (positions && !kv_snapshot_size(n_layers, n_kv_heads, head_dim, positions, flags)))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (%s: n_layers %zu, n_kv_heads %zu, max_pos %zu, snapshot of %zu)",
+                         entry, n_layers, n_kv_heads, max_pos, positions);
+    *rows_out = rows, *head_words_out = head_words;
+    return BITNET_HIP_OK;
+}
+}  // namespace
+
+size_t bitnet_hip_kv_snapshot_bytes(size_t n_layers, size_t n_kv_heads, size_t head_dim, size_t n_positions, int flags) {
+    return kv_snapshot_size(n_layers, n_kv_heads, head_dim, n_positions, flags);
+}
+
+int bitnet_hip_kv_save_dev(const void *const *k_ptrs_dev, const void *const *v_ptrs_dev, size_t n_layers, size_t n_kv_heads, size_t head_dim, size_t max_pos,
+                           size_t n_positions, int flags, void *snapshot_dev, void *stream) {
+    BH_GUARD_BEGIN
+    if (!k_ptrs_dev || !v_ptrs_dev || !snapshot_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_save_dev");
+    size_t rows = 0, head_words = 0;
+    if (int rc = kv_snapshot_check("kv_save_dev", n_layers, n_kv_heads, head_dim, max_pos, n_positions, n_positions, flags, snapshot_dev, &rows, &head_words))
+        return rc;
+    if (n_positions == 0) return BITNET_HIP_OK;  // valid, and nothing to launch
+    BH_HIP_TRY(launch_kv_save(k_ptrs_dev, v_ptrs_dev, n_layers, n_kv_heads, rows, head_words, n_positions, snapshot_dev, (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
+int bitnet_hip_kv_restore_dev(const void *snapshot_dev, size_t snapshot_positions, void *const *dst_k_ptrs_dev, void *const *dst_v_ptrs_dev, size_t n_layers,
+                              size_t n_dst, size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t n_positions, int flags, void *stream) {
+    BH_GUARD_BEGIN
+    if (!snapshot_dev || !dst_k_ptrs_dev || !dst_v_ptrs_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_restore_dev");
+    if (n_dst == 0 || n_dst > BITNET_HIP_BATCH_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_restore_dev: n_dst %zu must be 1..%d", n_dst, BITNET_HIP_BATCH_MAX);
+    size_t rows = 0, head_words = 0;
+    if (int rc = kv_snapshot_check("kv_restore_dev", n_layers, n_kv_heads, head_dim, max_pos, n_positions, snapshot_positions, flags, snapshot_dev, &rows,
+                                   &head_words))
+        return rc;
+    if (n_positions == 0) return BITNET_HIP_OK;  // valid, and nothing to launch
+    BH_HIP_TRY(launch_kv_restore(snapshot_dev, snapshot_positions, dst_k_ptrs_dev, dst_v_ptrs_dev, n_layers, n_dst, n_kv_heads, rows, head_words, n_positions,
+                                 (hipStream_t)stream));
+    return BITNET_HIP_OK;
+    BH_GUARD_END
+}
+
 /* ---- context shift of a live sequence's KV state (kernels_kvshift.hip) ---- */
 
 int bitnet_hip_kv_shift_dev(void *const *k_ptrs_dev, void *const *v_ptrs_dev, const float *rope_sin_dev, const float *rope_cos_dev, size_t n_layers,

@@ -221,6 +221,12 @@ hipError_t launch_kv_fork(const void *const *src_k, const void *const *src_v, vo
 // two RoPE table rows; one launch; rows and head_words as above
 hipError_t launch_kv_shift(void *const *k_ptrs, void *const *v_ptrs, const float *rope_sin, const float *rope_cos, size_t n_layers, size_t n_kv, size_t rows,
                            size_t head_words, size_t keep, size_t discard, size_t n, hipStream_t stream);
+// kernels_kvsnap.hip: cache slots [0, n) of one sequence into a position-major snapshot of S = n positions (save); positions [0, n) of a snapshot
+// of S positions into cache slots [0, n) of n_dst destinations (restore); one launch each; rows and head_words as above
+hipError_t launch_kv_save(const void *const *src_k, const void *const *src_v, size_t n_layers, size_t n_kv, size_t rows, size_t head_words, size_t n,
+                          void *snap, hipStream_t stream);
+hipError_t launch_kv_restore(const void *snap, size_t S, void *const *dst_k, void *const *dst_v, size_t n_layers, size_t n_dst, size_t n_kv,
+                             size_t rows, size_t head_words, size_t n, hipStream_t stream);
 // kernels_logprob.hip: the logits tap after the pick -- one entry (args by value) or a device table of n_slots entries, one launch each
 size_t logprob_scratch_bytes();
 hipError_t launch_logprob(const bitnet_hip_logprob_args &a, size_t vocab, hipStream_t stream);

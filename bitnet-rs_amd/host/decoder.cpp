@@ -1452,21 +1452,48 @@ int Decoder::shift(int keep, int discard) {
 
 int Decoder::fork(Decoder &src, Decoder *const *dsts, int n_dst, int n) { return src.fork_from_this(dsts, n_dst, n); }
 
-int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
-    // every refusal comes before the first write
-    if (n_dst < 1 || n_dst > BITNET_HIP_BATCH_MAX) return fail_arg("fork: n_dst must be 1..8");
-    if (!dsts) return fail_arg("fork: null destination");
+const char *Decoder::fork_refusal(Decoder *const *dsts, int n_dst, const Decoder *src, const Decoder *root, bool kv_f16) {
+    if (n_dst < 1 || n_dst > BITNET_HIP_BATCH_MAX) return "n_dst must be 1..8";
+    if (!dsts) return "null destination";
     for (int i = 0; i < n_dst; ++i) {
         Decoder *d = dsts[i];
-        if (!d) return fail_arg("fork: null destination");
-        if (d->dead_) return fail_arg("fork: dead destination");
-        if (d == this) return fail_arg("fork: a destination is the source itself: use rewind");
+        if (!d) return "null destination";
+        if (d->dead_) return "dead destination";
+        if (d == src) return "a destination is the source itself: use rewind";
         for (int j = 0; j < i; ++j)
-            if (dsts[j] == d) return fail_arg("fork: a destination is repeated");
-        if (d->root() != root()) return fail_arg("fork: source and destination must run on the same weights (an owner and its borrowers)");
-        if (d->kv_f16_ != kv_f16_) return fail_arg("fork: mixed KV cache types");
-        if (d->batch_) return fail_arg("fork: a destination sits in a batch slot: leave the batch first");
+            if (dsts[j] == d) return "a destination is repeated";
+        if (d->root() != root) return "source and destination must run on the same weights (an owner and its borrowers)";
+        if (d->kv_f16_ != kv_f16) return "mixed KV cache types";
+        if (d->batch_) return "a destination sits in a batch slot: leave the batch first";
     }
+    return nullptr;
+}
+
+int Decoder::fork_arrive(Decoder *const *dsts, int n_dst, int n, int forced, const int32_t *hist, bool hist_on_device, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < n_dst; ++i) {
+        // history[0 .. n]: entry n is the unconsumed picked or fed token, as rewind(n) leaves it; zero beyond, as after reset() + n steps
+        HCHK(hipMemcpyAsync(dsts[i]->history_, hist, ((size_t)n + 1) * 4, hist_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        HCHK(hipMemsetAsync(dsts[i]->history_ + n + 1, 0, ((size_t)c_.max_pos + 1 - (size_t)n) * 4, s));
+    }
+    HCHK(hipStreamSynchronize(s));
+    const int32_t np = n;
+    for (int i = 0; i < n_dst; ++i) {
+        Decoder *d = dsts[i];
+        HCHK(hipMemcpy(d->pos_, &np, 4, hipMemcpyHostToDevice));
+        d->host_forced_ = forced;
+        HCHK(hipMemcpy(d->n_forced_, &forced, 4, hipMemcpyHostToDevice));
+        if (d->sampler_) BCHK(bitnet_hip_sampler_reset(d->sampler_));
+        // a destination's log-probabilities start at the fork point
+        if (d->lp_top_n_ >= 0) HCHK(hipMemset(d->lp_records_, 0xff, (size_t)c_.max_pos * sizeof(bitnet_hip_logprob_record)));
+        if (int rc = d->arm_stop(false)) return rc;  // a destination carries no stop state
+    }
+    return 0;
+}
+
+int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
+    // every refusal comes before the first write
+    if (const char *why = fork_refusal(dsts, n_dst, this, root(), kv_f16_)) return fail_arg((std::string("fork: ") + why).c_str());
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
     if (n < 0 || n > p) return fail_arg("fork: n must be in [0, position()]");
@@ -1484,24 +1511,7 @@ int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
         BCHK(bitnet_hip_kv_fork_dev(fork_tables_, fork_tables_ + L, dst_k, dst_v, L, (size_t)n_dst, (size_t)c_.n_kv_heads, (size_t)c_.head_dim, (size_t)c_.max_pos,
                                     (size_t)n, kv_f16_ ? BITNET_HIP_ATTN_KV_F16 : 0, s));
     }
-    for (int i = 0; i < n_dst; ++i) {
-        // history[0 .. n]: entry n is the unconsumed picked or fed token, as rewind(n) leaves it; zero beyond, as after reset() + n steps
-        HCHK(hipMemcpyAsync(dsts[i]->history_, history_, ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, s));
-        HCHK(hipMemsetAsync(dsts[i]->history_ + n + 1, 0, ((size_t)c_.max_pos + 1 - (size_t)n) * 4, s));
-    }
-    HCHK(hipStreamSynchronize(s));
-    const int32_t np = n, forced = host_forced_ < n ? host_forced_ : n;
-    for (int i = 0; i < n_dst; ++i) {
-        Decoder *d = dsts[i];
-        HCHK(hipMemcpy(d->pos_, &np, 4, hipMemcpyHostToDevice));
-        d->host_forced_ = forced;
-        HCHK(hipMemcpy(d->n_forced_, &forced, 4, hipMemcpyHostToDevice));
-        if (d->sampler_) BCHK(bitnet_hip_sampler_reset(d->sampler_));
-        // a destination's log-probabilities start at the fork point
-        if (d->lp_top_n_ >= 0) HCHK(hipMemset(d->lp_records_, 0xff, (size_t)c_.max_pos * sizeof(bitnet_hip_logprob_record)));
-        if (int rc = d->arm_stop(false)) return rc;  // a destination carries no stop state
-    }
-    return 0;
+    return fork_arrive(dsts, n_dst, n, host_forced_ < n ? host_forced_ : n, history_, true, s);
 }
 
 int Decoder::cached_prefix(const int32_t *tokens, int n) {

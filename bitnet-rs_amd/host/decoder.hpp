@@ -68,7 +68,11 @@ struct DecoderStreams {
     ~DecoderStreams();
 };
 
+class PrefixCache;  // prefix_cache.hpp
+
 class Decoder : private DecoderStreams {
+    friend class PrefixCache;  // saves from and restores into the caches, history and counters exactly as fork does
+
   public:
     explicit Decoder(const Config &cfg) : Decoder(cfg, true) {}
     ~Decoder();
@@ -304,6 +308,21 @@ class Decoder : private DecoderStreams {
     // Prefix hit: fork at the common length (cached_prefix), then extend's carry-on rule holds as after a rewind: feed() on a fork writes at
     // slot n; feed the rest of the prompt and extend() over it.
     static int fork(Decoder &src, Decoder *const *dsts, int n_dst, int n);
+    // prefill through a PREFIX CACHE (prefix_cache.hpp), on a fresh sequence: the first n fed tokens are looked up; with a hit of length m the
+    // entry's first min(m, n - 1) positions are restored into this decoder (one bitnet_hip_kv_restore_dev launch; at least one token stays
+    // to be computed, its row gives the logits), the rest of the prompt is fed again behind them (restore clears the history beyond its
+    // positions, as fork does) and extend() runs over it -- the explicit sequence fork at m, feed, extend, bit for bit.  Without a hit it IS
+    // prefill(n, with_logits, digits).  *hit (nullable): the positions restored.  elapsed_ms: the prompt forward's.  It never inserts: the
+    // caller decides what is worth keeping (PrefixCache::insert).  The lookup counts in the cache's statistics.
+    // A HIT IS A FORK, and leaves what a fork leaves where a miss leaves what prefill leaves: the cache slots and the logits are the same
+    // arithmetic class either way, but on a hit this decoder's sampler is reset (counts, word counter; config kept), its log-probability
+    // records are cleared, its stop state is re-armed, and history entries beyond n -- tokens fed past the n this call takes in -- are
+    // ZERO (restore clears the history beyond its positions and only [k, n) is fed again); on a miss all of those stay.  A caller that
+    // needs one outcome feeds exactly n tokens and sets its sampler up after the call, or resets the sampler itself on a miss (*hit == 0).
+    // A cache bound to other weights or another cache type holds nothing for this decoder: a miss without a lookup.
+    // Refused as prefill refuses (not fresh, n beyond the fed tokens, "KV cache overflow") and as PrefixCache::restore refuses (this
+    // decoder sits in a BatchDecoder slot).
+    int prefill_cached(PrefixCache &cache, int n, bool with_logits, int digits, int *hit, float *elapsed_ms);
     // The reference's lookup for ONE live sequence: the length of the longest common prefix of tokens[0 .. n) and history[0 .. position()),
     // or -1 on error.  Costs the position read-back and one of min(n, position()) tokens.
     int cached_prefix(const int32_t *tokens, int n);
@@ -487,6 +506,12 @@ class Decoder : private DecoderStreams {
     // then the destinations' K [8][n_layers] and V [8][n_layers] (uploaded per call).  shift() uses [0] and [1].
     int ensure_fork_tables();
     int fork_from_this(Decoder *const *dsts, int n_dst, int n);
+    // The two parts of a fork that PrefixCache::restore shares.  fork_refusal: why this destination set cannot take over a state of `root` and
+    // cache type kv_f16 (src: the live source, or null), or null; the root is compared, never dereferenced.  fork_arrive: behind the cache copy
+    // already queued on `stream`, every destination takes history[0 .. n] (n + 1 entries of `hist`, device or host memory) with zeros beyond,
+    // position n, the forced count, a reset sampler, cleared log-probability records and no stop state; synchronises; the error text on *this.
+    static const char *fork_refusal(Decoder *const *dsts, int n_dst, const Decoder *src, const Decoder *root, bool kv_f16);
+    int fork_arrive(Decoder *const *dsts, int n_dst, int n, int forced, const int32_t *hist, bool hist_on_device, void *stream);
     DevBuf<void *> fork_tables_;
     // sharded prefill buffers (grown on demand)
     int sp_cap_ = 0, sp_ctx_ = 0;

@@ -602,6 +602,9 @@ int bitnet_hip_pick_rows_dev(const float *logits_dev, const int32_t *argmax_dev,
 int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const *src_v_ptrs_dev, void *const *dst_k_ptrs_dev,
                            void *const *dst_v_ptrs_dev, size_t n_layers, size_t n_dst, size_t n_kv_heads, size_t head_dim,
                            size_t max_pos, size_t n_positions, int flags, void *stream);
+/* ---- compact snapshots of a live sequence: bitnet_hip_kv_snapshot_bytes, bitnet_hip_kv_save_dev, bitnet_hip_kv_restore_dev -- the KV state of a
+ * prompt prefix WITHOUT the cache around it, in a public position-major layout: declared in bitnet_hip_kvsnap.h, included at the end of this
+ * header. */
 /* ---- context shift of a live sequence: drop positions from the middle of the KV state, on the device -------------------
  * The reference has the pieces on the host: KvCacheBuffer::rotate_kv and truncate (crates/bitnet-kernels/src/cuda/kv_cache.rs:305-348) and
  * WindowedKVCache (crates/bitnet-gpu-hal/src/sliding_window.rs:161-235): keep the first `keep` positions (the attention sinks), discard the
@@ -1106,5 +1109,6 @@ int bitnet_hip_hbm_read_ceiling(size_t bytes, int iters, double *best_gbs, doubl
 #endif
 
 #include "bitnet_hip_grammar.h" /* the sampler's grammar stage: six more entry points of this ABI */
+#include "bitnet_hip_kvsnap.h"  /* compact KV snapshots: three more */
 
 #endif /* BITNET_HIP_H */

@@ -27,6 +27,7 @@ LIB_PATH = os.path.join(HERE, "libbitnet_hip.so")
 HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip.h")
 GRAMMAR_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar.h")  # included by HEADER_PATH: the grammar stage's six entry points
 KVSNAP_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")  # included by HEADER_PATH: the KV snapshot's three entry points
+WIDETAIL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_widetail.h")  # included by HEADER_PATH: the wide step's 64-entry tail tables, two
 
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_GPU, ERR_UNSUPPORTED, ERR_EXECUTION = -1, -2, -3, -4
@@ -121,6 +122,7 @@ class HipLib:
         cproto.bind(self.c, cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_"), C_STRUCTS)
         cproto.bind(self.c, grammar_prototypes(), C_STRUCTS)
         cproto.bind(self.c, kvsnap_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, widetail_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -651,9 +653,10 @@ class HipLib:
         compiles one from a byte-level DFA and the vocabulary's byte strings."""
         return Grammar(self, token_class, next_table)
 
-    def sample_batch(self, vocab: int, n_slots: int) -> "SampleBatch":
-        """A table of n_slots sampler bindings served by one launch (bitnet_hip_sample_batch_*)."""
-        return SampleBatch(self, vocab, n_slots)
+    def sample_batch(self, vocab: int, n_slots: int, wide: bool = False) -> "SampleBatch":
+        """A table of n_slots sampler bindings served by one launch (bitnet_hip_sample_batch_*): 1..8 slots, or with wide=True 1..64
+        (bitnet_hip_sample_batch_create_wide, the wide step's tail)."""
+        return SampleBatch(self, vocab, n_slots, wide)
 
     def logprob_scratch_bytes(self, vocab: int) -> int:
         """Bytes of the scratch one bitnet_hip_logprob_args entry needs (zeroed once by the caller); 0 for a vocabulary the library refuses."""
@@ -666,6 +669,10 @@ class HipLib:
     def logprob_batch_dev(self, table, n_slots: int, vocab: int, stream: int = 0) -> None:
         """The same for n_slots entries read from a DEVICE table of LogprobArgs (a uint8 tensor holding them, or a raw pointer), one launch."""
         self._check(self.c.bitnet_hip_logprob_batch_dev(C.cast(_optr(table), C.POINTER(LogprobArgs)), n_slots, vocab, _vp(stream)))
+
+    def logprob_rows_dev(self, table, n_slots: int, vocab: int, stream: int = 0) -> None:
+        """logprob_batch_dev for n_slots = 1..64 entries (bitnet_hip_logprob_rows_dev, the wide step's tail), one launch."""
+        self._check(self.c.bitnet_hip_logprob_rows_dev(C.cast(_optr(table), C.POINTER(LogprobArgs)), n_slots, vocab, _vp(stream)))
 
     def hbm_read_ceiling(self, nbytes: int = 2 << 30, iters: int = 10, stream: int = 0):
         """Measured read-only stream ceiling of the device: (best, mean) GB/s."""
@@ -931,14 +938,15 @@ class Sampler:
 
 
 class SampleBatch:
-    """One bitnet_hip_sample_batch: up to 8 slots, each binding a Sampler and the device tensors sample_dev would take; launch() samples for
-    every bound slot in ONE kernel launch, per slot bit for bit what Sampler.sample_dev alone would have left.  Keeps the bound samplers and
-    tensors alive."""
+    """One bitnet_hip_sample_batch: up to 8 slots (up to 64 with wide=True), each binding a Sampler and the device tensors sample_dev would
+    take; launch() samples for every bound slot in ONE kernel launch, per slot bit for bit what Sampler.sample_dev alone would have left.
+    Keeps the bound samplers and tensors alive."""
 
-    def __init__(self, lib: HipLib, vocab: int, n_slots: int):
+    def __init__(self, lib: HipLib, vocab: int, n_slots: int, wide: bool = False):
         self.lib, self.vocab, self.n_slots = lib, int(vocab), int(n_slots)
         h = _vp()
-        lib._check(lib.c.bitnet_hip_sample_batch_create(vocab, n_slots, C.byref(h)))
+        create = lib.c.bitnet_hip_sample_batch_create_wide if wide else lib.c.bitnet_hip_sample_batch_create
+        lib._check(create(vocab, n_slots, C.byref(h)))
         self.h = h
         self._keep = {}
 
@@ -1120,9 +1128,15 @@ def kvsnap_prototypes() -> list:
     return cproto.prototypes(open(KVSNAP_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def widetail_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_widetail.h, the header include/bitnet_hip.h includes for the wide step's 64-entry tail tables."""
+    return cproto.prototypes(open(WIDETAIL_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
-    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + kvsnap_prototypes()})
+    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + kvsnap_prototypes()
+                   + widetail_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -1133,6 +1147,7 @@ HOST_LIB_PATH = os.path.join(HERE, "libbitnet_host.so")
 HOST_HEADER_PATHS = [os.path.join(HERE, "host", f) for f in ("decoder.hpp", "batch_decoder.hpp", "gguf.hpp")]
 HOST_GRAMMAR_HEADER_PATH = os.path.join(HERE, "host", "grammar_host.hpp")  # the decoder's grammar control, bound beside the others
 HOST_PREFIX_HEADER_PATH = os.path.join(HERE, "host", "prefix_cache.hpp")  # PrefixCache and Decoder::prefill_cached, bound beside the others
+HOST_WIDE_HEADER_PATH = os.path.join(HERE, "host", "wide_batch.hpp")  # WideBatch, bound beside the others
 _host_libs = {}
 
 
@@ -1151,6 +1166,11 @@ def host_prefix_prototypes() -> list:
     return cproto.prototypes(open(HOST_PREFIX_HEADER_PATH).read(), "bitnet_host_")
 
 
+def host_wide_prototypes() -> list:
+    """The exports of host/wide_batch.hpp (WideBatch), typed at load like the rest."""
+    return cproto.prototypes(open(HOST_WIDE_HEADER_PATH).read(), "bitnet_host_")
+
+
 def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
     """The host library at `path`, loaded and bound from its headers once per process."""
     if path not in _host_libs:
@@ -1158,6 +1178,7 @@ def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
         cproto.bind(L, host_prototypes(), C_STRUCTS)
         cproto.bind(L, host_grammar_prototypes(), C_STRUCTS)
         cproto.bind(L, host_prefix_prototypes(), C_STRUCTS)
+        cproto.bind(L, host_wide_prototypes(), C_STRUCTS)
         _host_libs[path] = L
     return _host_libs[path]
 
@@ -1403,6 +1424,22 @@ class HostDecoder:
         g = C.c_uint64(0)
         self._check(self.c.bitnet_host_constraints_state(self.h, C.byref(g)))
         return int(g.value)
+
+    def set_grammar(self, grammar: "Grammar | None", start_state: int = 0) -> None:
+        """Decoder::set_grammar: binds a token automaton (lib.grammar(...)) to this decoder's sampler -- sampling must be on; temperature 0 is
+        greedy decoding under the grammar -- with its state at start_state; None switches the stage off.  The handle stays the caller's."""
+        self._check(_host_fn(self.c, "bitnet_host_set_grammar")(self.h, None if grammar is None else grammar.h, int(start_state)))
+        self._grammar = grammar  # kept alive while bound
+
+    def set_grammar_state(self, state: int) -> None:
+        """Decoder::set_grammar_state: after rewind(n), the state bitnet_hip_grammar_walk gives for the generated tokens that remain."""
+        self._check(_host_fn(self.c, "bitnet_host_set_grammar_state")(self.h, int(state)))
+
+    def grammar_state(self) -> tuple[int, int, int]:
+        """(state, steps taken, violations) of the bound grammar; (-1, 0, 0) without a sampler or a grammar.  Synchronises."""
+        st, steps, viol = C.c_int32(-1), C.c_uint64(0), C.c_uint64(0)
+        self._check(_host_fn(self.c, "bitnet_host_grammar_state")(self.h, C.byref(st), C.byref(steps), C.byref(viol)))
+        return int(st.value), int(steps.value), int(viol.value)
 
     def sampling_draws(self) -> int:
         """ChaCha20 words the decoder's sampler has consumed since its last reset / set_sampling (one per non-greedy token)."""
@@ -1704,6 +1741,12 @@ class HostDecoder:
         return int(self.c.bitnet_host_weight_bytes(self.h))
 
 
+def _host_fn(host: C.CDLL, name: str):
+    """An export of host/grammar_host.hpp or host/wide_batch.hpp on the bound host library.  By name, as _prefix_fn: these are typed from
+    THOSE headers at load (host_grammar_prototypes, host_wide_prototypes), not from the three headers host_prototypes() reads."""
+    return getattr(host, name)
+
+
 def _prefix_fn(host: C.CDLL, name: str):
     """An export of host/prefix_cache.hpp on the bound host library.  By name: these are typed from THAT header at load (host_prefix_prototypes),
     not from the three headers host_prototypes() reads."""
@@ -1861,3 +1904,73 @@ class HostBatch:
     def graph_nodes(self) -> int:
         """Kernel nodes of the captured chain, 0 if none is held."""
         return int(self.c.bitnet_host_batch_graph_nodes(self.h))
+
+
+class HostWideBatch:
+    """ctypes view of the C++ WideBatch (host/wide_batch.hpp): up to 64 slots, each holding a HostDecoder -- an owner or decoders from
+    owner.shared() -- stepped TOGETHER through the wide forward (one matrix forward per step) with at most one sampling, one tap and one stop
+    launch per step.  After step(n) every member is bit for bit what HostDecoder.step_wide of the occupied, un-parked slots in slot order
+    leaves on twins.  set_slot() between steps is the scheduler; step_until() parks the members it finds stopped.  Admission: feed() the
+    prompt, ONE prefill_packed of n - 1 tokens without logits over the newcomers, set_slot() -- the next step picks the first token."""
+
+    def __init__(self, n_slots: int, path: str = HOST_LIB_PATH):
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path} not found: build it with __graft_entry__.build() -- there is no fallback path")
+        load()
+        self.c = _host_lib(path)
+        self.n_slots = int(n_slots)
+        self.h = self._w("create")(self.n_slots)
+        if not self.h:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, f"bitnet_host_wide_batch_create: n_slots must be in 1..64, got {n_slots}")
+
+    def _w(self, name: str):
+        return _host_fn(self.c, "bitnet_host_wide_batch_" + name)
+
+    def error(self) -> str:
+        e = self._w("error")(self.h)
+        return e.decode() if e else ""
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise BitNetHipError(rc, self.error() or f"bitnet_host_wide_batch rc={rc}")
+
+    def close(self) -> None:
+        if self.h:
+            self._w("destroy")(self.h)
+            self.h = None
+
+    def set_slot(self, b: int, decoder: "HostDecoder | None") -> None:
+        """Put `decoder` into slot b or clear it (None); clears the slot's parked mark.  A closed decoder is refused (its handle is gone)."""
+        if decoder is not None and not decoder.h:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, "wide batch: null member (a closed decoder)")
+        self._check(self._w("set_slot")(self.h, int(b), None if decoder is None else decoder.h))
+
+    def step(self, n: int = 1, digits: int = 2) -> float:
+        """n wide steps for the occupied, un-parked slots; returns the elapsed milliseconds (HIP events)."""
+        ms = C.c_float(0.0)
+        self._check(self._w("step")(self.h, int(n), int(digits), C.byref(ms)))
+        return float(ms.value)
+
+    def live(self) -> int:
+        """Un-parked members with stop criteria (HostDecoder.set_stop) that have not stopped yet.  Synchronises."""
+        n = int(self._w("live")(self.h))
+        if n < 0:
+            raise BitNetHipError(n, self.error() or f"bitnet_host_wide_batch_live rc={n}")
+        return n
+
+    def step_until(self, max_steps: int, chunk: int = 16, digits: int = 2) -> tuple[int, float]:
+        """step(chunk) until no un-parked member with stop criteria is live or max_steps steps are queued; the members' stop states are read
+        once per chunk and a member found stopped is parked: frozen in its slot, no row in later chunks.  Returns (steps queued, ms)."""
+        steps, ms = C.c_int(0), C.c_float(0.0)
+        self._check(self._w("step_until")(self.h, int(max_steps), int(chunk), int(digits), C.byref(steps), C.byref(ms)))
+        return int(steps.value), float(ms.value)
+
+    def tail_launches(self) -> tuple[int, int, int]:
+        """(sampling, tap, stop) launches the last step() call issued."""
+        out = (C.c_int * 3)()
+        self._check(self._w("tail_launches")(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def table_writes(self) -> int:
+        """Uploads of a tail table or the pointer tables since creation: a step with nothing changed adds none."""
+        return int(self._w("table_writes")(self.h))

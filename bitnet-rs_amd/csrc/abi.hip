@@ -1532,15 +1532,26 @@ int bitnet_hip_logprob_dev(const bitnet_hip_logprob_args *args_host, size_t voca
     BH_GUARD_END
 }
 
-int bitnet_hip_logprob_batch_dev(const bitnet_hip_logprob_args *table_dev, size_t n_slots, size_t vocab, void *stream) {
-    BH_GUARD_BEGIN
-    if (!table_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null table passed to logprob_batch_dev");
+// bitnet_hip_logprob_batch_dev (cap 8) and bitnet_hip_logprob_rows_dev (cap 64): one launch of k_logprob_batch, grid (nwg, n_slots)
+static int logprob_table_dev(const char *who, size_t cap, const bitnet_hip_logprob_args *table_dev, size_t n_slots, size_t vocab, void *stream) {
+    if (!table_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null table passed to %s", who);
     if (vocab == 0 || vocab > ((size_t)1 << 20))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logprob_batch_dev: vocab must be in 1..%d, got %zu", 1 << 20, vocab);
-    if (n_slots == 0 || n_slots > (size_t)BITNET_HIP_BATCH_MAX)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "logprob_batch_dev: n_slots must be in 1..%d, got %zu", BITNET_HIP_BATCH_MAX, n_slots);
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: vocab must be in 1..%d, got %zu", who, 1 << 20, vocab);
+    if (n_slots == 0 || n_slots > cap)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_slots must be in 1..%zu, got %zu", who, cap, n_slots);
     BH_HIP_TRY(launch_logprob_batch(table_dev, n_slots, vocab, (hipStream_t)stream));
     return BITNET_HIP_OK;
+}
+
+int bitnet_hip_logprob_batch_dev(const bitnet_hip_logprob_args *table_dev, size_t n_slots, size_t vocab, void *stream) {
+    BH_GUARD_BEGIN
+    return logprob_table_dev("logprob_batch_dev", BITNET_HIP_BATCH_MAX, table_dev, n_slots, vocab, stream);
+    BH_GUARD_END
+}
+
+int bitnet_hip_logprob_rows_dev(const bitnet_hip_logprob_args *table_dev, size_t n_slots, size_t vocab, void *stream) {
+    BH_GUARD_BEGIN
+    return logprob_table_dev("logprob_rows_dev", BITNET_HIP_WIDE_MAX, table_dev, n_slots, vocab, stream);
     BH_GUARD_END
 }
 

@@ -210,6 +210,8 @@ __global__ __launch_bounds__(kNT) void k_logprob(LogprobArgs a, int vocab, int s
 // Every entry of a batch in one launch: grid (nwg, n_slots), blockIdx.y = the slot, whose LogprobArgs come from a device table (uniform
 // loads: they stay in scalar registers).  An entry with null records is empty: its workgroups return before the first barrier and touch
 // nothing.  Per slot everything is k_logprob's -- slices, the ticket in that entry's own scratch, the last arriver finishing.
+// n_slots: 1..8 through bitnet_hip_logprob_batch_dev, 1..64 through bitnet_hip_logprob_rows_dev; no workgroup waits for another, so the
+// larger grid need not be co-resident.
 __global__ __launch_bounds__(kNT) void k_logprob_batch(const LogprobArgs *__restrict__ table, int vocab, int slice) {
     const LogprobArgs *e = table + blockIdx.y;
     if (!e->records_dev) return;

@@ -1213,11 +1213,13 @@ int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16, const
     const int flags = (kv_f16_ ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
     const size_t li = (size_t)(&L - layers_.data());
     if (op.kind == AttnOp::Rows) {
-        // a wide step (step_wide): the N rows are N members' current tokens, each over its OWN caches of this layer at its own position
-        BCHK(bitnet_hip_attention_decode_rows_dev(pf_qkv_, rope_sin_, rope_cos_, wide_tables_ + (2 * li) * BITNET_HIP_WIDE_MAX,
-                                                  wide_tables_ + (2 * li + 1) * BITNET_HIP_WIDE_MAX,
-                                                  reinterpret_cast<const int32_t *const *>(wide_tables_ + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
-                                                  op.key_bound, wide_scratch_, flags, out, stream_));
+        // a wide step (step_wide, WideBatch::step): the N rows are N members' current tokens, each over its OWN caches of this layer at its own
+        // position; the tables and the cache type are the operator's (the members'), not necessarily this driver's
+        const int rflags = (op.kv_f16 ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
+        BCHK(bitnet_hip_attention_decode_rows_dev(pf_qkv_, rope_sin_, rope_cos_, op.tables + (2 * li) * BITNET_HIP_WIDE_MAX,
+                                                  op.tables + (2 * li + 1) * BITNET_HIP_WIDE_MAX,
+                                                  reinterpret_cast<const int32_t *const *>(op.tables + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
+                                                  op.key_bound, wide_scratch_, rflags, out, stream_));
     } else if (op.kind == AttnOp::Pack) {
         // a pack (prefill_packed): the N rows are several members' segments, each over its OWN caches of this layer
         void *kc[BITNET_HIP_PACK_MAX], *vc[BITNET_HIP_PACK_MAX];
@@ -1645,12 +1647,12 @@ int Decoder::step_wide(Decoder *const *members, int n_members, int n_steps, int 
 
 // The wide step's chain, n_steps times: gather, layers under the rows attention (with the saturation rule: forward_with_repeat), head,
 // hand-over, then the samplers and logits taps member by member.  This decoder is the driver; max_p = the largest position before the call.
-int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms) {
+int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms, WideTail *tail) {
     const size_t H = c_.hidden, V = (size_t)c_.vocab, NL = layers_.size(), W = BITNET_HIP_WIDE_MAX;
     hipStream_t s = (hipStream_t)stream_;
     const size_t ws_need = bitnet_hip_score_workspace_bytes((size_t)M, H, V);
     if (ws_need == 0) return fail_arg("step_wide: dimensions too large");
-    if (!wide_tables_) HCHK(wide_tables_.alloc((2 * NL + 6) * W));
+    if (!tail && !wide_tables_) HCHK(wide_tables_.alloc((2 * NL + 6) * W));
     if (M > wide_cap_ || ws_need > wide_ws_bytes_) {
         const size_t cap = (size_t)(M > wide_cap_ ? M : wide_cap_), sb = bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos);
         release_all(wide_scratch_, wide_logits_, wide_nll_, wide_am_, wide_tgt_, wide_ws_);
@@ -1668,8 +1670,8 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
     }
     if (int rc = ensure_prompt_buffers(M, 16)) return rc;
     // the pointer tables, uploaded once per call: [2 l] / [2 l + 1] layer l's K / V caches, then position, history, forced count, logits row and
-    // the pick's token / position entries (NULL for a member that samples: its sampler does the hand-over)
-    {
+    // the pick's token / position entries (NULL for a member that samples: its sampler does the hand-over); a tail brings its own, uploaded
+    if (!tail) {
         std::vector<void *> t((2 * NL + 6) * W, nullptr);
         for (int i = 0; i < M; ++i) {
             Decoder *d = members[i];
@@ -1681,7 +1683,8 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
         }
         HCHK(hipMemcpy(wide_tables_, t.data(), t.size() * sizeof(void *), hipMemcpyHostToDevice));
     }
-    void **g = wide_tables_ + 2 * NL * W;
+    void *const *const tables = tail ? tail->tables : wide_tables_.get();
+    void *const *g = tables + 2 * NL * W;
     const int32_t *const *pos_t = reinterpret_cast<const int32_t *const *>(g), *const *hist_t = reinterpret_cast<const int32_t *const *>(g + W);
     StreamTimer timer;
     HCHK(timer.start(s));
@@ -1691,13 +1694,28 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
     };
     for (int step = 0; step < n_steps; ++step) {
         AttnOp op;  // (the positions move only in the pick below, so a repeated step rewrites the same cache slots)
-        op.kind = AttnOp::Rows, op.n = (size_t)M, op.key_bound = (size_t)(max_p + step + 1);
+        op.kind = AttnOp::Rows, op.n = (size_t)M, op.key_bound = (size_t)(max_p + step + 1), op.tables = tables, op.kv_f16 = members[0]->kv_f16_;
         if (int rc = forward_with_repeat((size_t)M, digits, op, fill)) return rc;
         BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, (size_t)M, wide_tgt_, wide_nll_, wide_am_, wide_logits_, (size_t)M, wide_ws_,
                                       wide_ws_bytes_, s));
         BCHK(bitnet_hip_pick_rows_dev(wide_logits_, wide_am_, (size_t)M, V, reinterpret_cast<float *const *>(g + 3 * W), reinterpret_cast<int32_t *const *>(g + 4 * W),
                                       reinterpret_cast<int32_t *const *>(g + 5 * W), reinterpret_cast<int32_t *const *>(g + W),
                                       reinterpret_cast<const int32_t *const *>(g + 2 * W), s));
+        if (tail) {  // a WideBatch's tail: every sampling member, every tap, every member with criteria -- one launch each, or none
+            if (tail->sample) {
+                if (bitnet_hip_sample_batch_dev(tail->sample, s) != 0) return fail("wide batch: bitnet_hip_sample_batch_dev");
+                ++tail->launches[0];
+            }
+            if (tail->taps) {
+                if (bitnet_hip_logprob_rows_dev(tail->taps, tail->n_taps, V, s) != 0) return fail("wide batch: bitnet_hip_logprob_rows_dev");
+                ++tail->launches[1];
+            }
+            if (tail->stop) {
+                if (bitnet_hip_stop_batch_dev(tail->stop, s) != 0) return fail("wide batch: bitnet_hip_stop_batch_dev");
+                ++tail->launches[2];
+            }
+            continue;
+        }
         for (int i = 0; i < M; ++i) {  // pick_token's arrangement, on the driver's stream: the member's own sampler, then its own record
             Decoder *d = members[i];
             if (d->sampling_) {

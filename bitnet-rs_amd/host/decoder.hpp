@@ -69,9 +69,23 @@ struct DecoderStreams {
 };
 
 class PrefixCache;  // prefix_cache.hpp
+class WideBatch;    // wide_batch.hpp
+
+// The tail of a wide step when a WideBatch drives it (Decoder::wide_forward): the device pointer tables in wide_forward's own layout, built and
+// uploaded by the batch for its dense member list, and the three tail tables -- each launched ONCE per step behind bitnet_hip_pick_rows_dev, in
+// this order, or not at all when null.  launches[]: the launches issued, counted up by wide_forward.
+struct WideTail {
+    void *const *tables = nullptr;                   // [2 * n_layers + 6][BITNET_HIP_WIDE_MAX]
+    bitnet_hip_sample_batch *sample = nullptr;       // bitnet_hip_sample_batch_dev: some member samples
+    const bitnet_hip_logprob_args *taps = nullptr;   // bitnet_hip_logprob_rows_dev over n_taps entries: some member's tap is on
+    size_t n_taps = 0;
+    bitnet_hip_stop_batch *stop = nullptr;           // bitnet_hip_stop_batch_dev: some member has criteria
+    int launches[3] = {0, 0, 0};
+};
 
 class Decoder : private DecoderStreams {
     friend class PrefixCache;  // saves from and restores into the caches, history and counters exactly as fork does
+    friend class WideBatch;    // holds members in slots and drives wide_forward on their root with a tail of its own
 
   public:
     explicit Decoder(const Config &cfg) : Decoder(cfg, true) {}
@@ -431,6 +445,8 @@ class Decoder : private DecoderStreams {
     struct AttnOp {
         enum Kind { Whole, Continue, Pack, Rows } kind = Whole;
         size_t past = 0, n = 0, key_bound = 0;
+        void *const *tables = nullptr;  // Rows: the device pointer tables (the driver's wide_tables_, or a WideBatch's own)
+        bool kv_f16 = false;            // Rows: the MEMBERS' cache type (a WideBatch drives on the root, whose own type may differ)
         Decoder *const *members = nullptr;
         const int32_t *row0 = nullptr, *len = nullptr, *pasts = nullptr;
     };
@@ -451,7 +467,10 @@ class Decoder : private DecoderStreams {
     int ensure_prompt_buffers(int n, size_t attn_need);             // the per-row buffers and the attention workspace of a prompt forward of n rows
     int packed_forward(Decoder *const *members, const std::vector<int32_t> &past, const std::vector<int32_t> &len, bool with_logits, int digits,
                        float *elapsed_ms);                          // the body of prefill_packed, on the driver
-    int wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms);  // the body of step_wide, on the driver
+    // the body of step_wide, on the driver.  tail == null: the driver builds and uploads the pointer tables and ends every step with one sampling,
+    // tap and stop launch PER MEMBER (step_wide, unchanged).  With a tail (WideBatch): the tables are the tail's and each step ends with at most
+    // one launch of each kind; `this` may then be no member at all (the weights' owner).
+    int wide_forward(Decoder *const *members, int M, int n_steps, int max_p, int digits, float *elapsed_ms, WideTail *tail = nullptr);
     // wide buffers (none before the first call): device pointer tables [2 * n_layers + 6][64] -- per layer K then V caches, then position, history,
     // forced count, logits row, and the pick's token / position tables (NULL for a member that samples) --, the attention scratch of wide_cap_
     // sequences (zero-filled), the head's [wide_cap_, vocab] logits, argmax, nll, targets (-1) and workspace

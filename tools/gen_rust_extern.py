@@ -39,7 +39,7 @@ def prototypes(header: str):
 
 def main():
     header = open(os.path.join(ROOT, "include", "bitnet_hip.h")).read() + open(os.path.join(ROOT, "include", "bitnet_hip_grammar.h")).read()
-    header += open(os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")).read()
+    header += open(os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")).read() + open(os.path.join(ROOT, "include", "bitnet_hip_widetail.h")).read()
     have = set(re.findall(r"pub fn (bitnet_hip_[a-z0-9_]+)", open(os.path.join(ROOT, "INTEGRATION.md")).read())) if "--missing" in sys.argv else set()
     for name, line in prototypes(header):
         if name not in have:

@@ -27,6 +27,7 @@ LIB_PATH = os.path.join(HERE, "libbitnet_hip.so")
 HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip.h")
 GRAMMAR_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar.h")  # included by HEADER_PATH: the grammar stage's six entry points
 KVSNAP_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")  # included by HEADER_PATH: the KV snapshot's three entry points
+BEAM_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_beam.h")  # included by HEADER_PATH: beam search, the select and permute launches and their state
 WIDETAIL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_widetail.h")  # included by HEADER_PATH: the wide step's 64-entry tail tables, two
 
 OK = 0
@@ -123,6 +124,7 @@ class HipLib:
         cproto.bind(self.c, grammar_prototypes(), C_STRUCTS)
         cproto.bind(self.c, kvsnap_prototypes(), C_STRUCTS)
         cproto.bind(self.c, widetail_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, beam_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -528,6 +530,13 @@ class HipLib:
         device tensors of device pointers, the source's [n_layers], the destinations' [n_dst][n_layers]; buffers distinct, 16-byte aligned."""
         self._check(self.c.bitnet_hip_kv_fork_dev(_ptr(src_k_ptrs), _ptr(src_v_ptrs), _ptr(dst_k_ptrs), _ptr(dst_v_ptrs), n_layers, n_dst, n_kv, head_dim,
                                                   max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
+
+    def kv_permute_dev(self, k_ptrs, v_ptrs, beam: "Beam", n_layers: int, n_beams: int, n_kv: int, head_dim: int, max_pos: int, key_bound: int,
+                       kv_f16: bool = False, stream: int = 0) -> None:
+        """In place, in one launch: for every beam b whose parent (read from the beam state on the device) is another beam, cache slots
+        [from[b], n_slots) of every layer's K and V of cache b take the bits of the parent's.  *_ptrs: int64 device tensors [n_beams][n_layers]."""
+        self._check(self.c.bitnet_hip_kv_permute_dev(_ptr(k_ptrs), _ptr(v_ptrs), beam.h, n_layers, n_beams, n_kv, head_dim, max_pos, key_bound,
+                                                     2 if kv_f16 else 0, _vp(stream)))
 
     def kv_snapshot_bytes(self, n_layers: int, n_kv: int, head_dim: int, n_positions: int, kv_f16: bool = False) -> int:
         """Bytes of a snapshot of n_positions: K [n_layers][n_kv][n_positions][128] then V the same, in the cache's element type; 0 for a
@@ -1100,6 +1109,76 @@ class StopBatch:
         return int(n.value)
 
 
+BEAM_MAX = 8
+BEAM_DONE_POOL, BEAM_DONE_BUDGET, BEAM_ERR_RANGE, BEAM_ERR_SHORT = 1, 2, 0x100, 0x200
+
+
+class BeamState(C.Structure):
+    """bitnet_hip_beam_state (624 bytes)"""
+    _fields_ = ([(n, C.c_int32) for n in ("n_beams", "eos", "max_new_tokens", "prompt_pos", "gen_len", "done", "stepped", "n_slots", "pool_n", "pool_seq",
+                                          "frozen_steps", "reserved")]
+                + [("score", C.c_float * BEAM_MAX), ("parent", C.c_int32 * BEAM_MAX), ("from_", C.c_int32 * BEAM_MAX), ("token", C.c_int32 * BEAM_MAX),
+                   ("div", C.c_int32 * BEAM_MAX * BEAM_MAX), ("pool_score", C.c_float * BEAM_MAX), ("pool_key", C.c_float * BEAM_MAX),
+                   ("pool_len", C.c_int32 * BEAM_MAX), ("pool_order", C.c_int32 * BEAM_MAX), ("pool_src", C.c_int32 * BEAM_MAX),
+                   ("pool_last", C.c_int32 * BEAM_MAX)])
+
+    def words(self) -> list:
+        """every 32-bit word of the state in the struct's order, floats as their bits"""
+        raw = bytes(self)
+        signed, unsigned = np.frombuffer(raw, np.int32), np.frombuffer(raw, np.uint32)
+        is_float = lambda i: 12 <= i < 20 or 108 <= i < 124  # score; pool_score and pool_key
+        return [int(unsigned[i]) if is_float(i) else int(signed[i]) for i in range(signed.size)]
+
+
+class BeamMember(C.Structure):
+    """bitnet_hip_beam_member: device pointers as integers"""
+    _fields_ = [("records_dev", C.c_void_p), ("pos_dev", C.c_void_p), ("history_dev", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Beam:
+    """One bitnet_hip_beam: the state of one beam search in device memory.  select() is the launch behind a batched step that picks the next
+    beams and rewrites the histories; HipLib.kv_permute_dev is the launch behind it that moves the caches."""
+
+    def __init__(self, lib: HipLib, n_beams: int, eos: int, max_new_tokens: int, len_weight):
+        self.lib, self.n_beams, self.max_new_tokens = lib, int(n_beams), int(max_new_tokens)
+        w = _np(len_weight, np.float32)
+        if w.size != self.max_new_tokens + 1:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, f"Beam: len_weight holds {w.size} entries, max_new_tokens + 1 = {self.max_new_tokens + 1} needed")
+        h = _vp()
+        lib._check(lib.c.bitnet_hip_beam_create(n_beams, eos, max_new_tokens, w.ctypes.data_as(C.c_void_p), C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.c.bitnet_hip_beam_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def reset(self, prompt_pos: int) -> None:
+        self.lib._check(self.lib.c.bitnet_hip_beam_reset(self.h, int(prompt_pos)))
+
+    def read(self) -> "tuple[BeamState, np.ndarray]":
+        """(state, pool tokens [8][max_new_tokens]); synchronises the device"""
+        st, tok = BeamState(), np.zeros((BEAM_MAX, self.max_new_tokens), np.int32)
+        self.lib._check(self.lib.c.bitnet_hip_beam_read(self.h, C.byref(st), tok.ctypes.data_as(C.c_void_p)))
+        return st, tok
+
+    def done_ptr(self) -> int:
+        """The device address of the state's `done` word (a host loop reads these 4 bytes per chunk of queued steps)."""
+        p = _vp()
+        self.lib._check(self.lib.c.bitnet_hip_beam_done_dev(self.h, C.byref(p)))
+        return int(p.value)
+
+    def select(self, members, stream: int = 0) -> None:
+        """One launch; members: a device table of n_beams BeamMember (a uint8 tensor holding them, or a raw pointer)."""
+        self.lib._check(self.lib.c.bitnet_hip_beam_select_dev(self.h, _optr(members), self.n_beams, _vp(stream)))
+
+
 _lib = None
 
 
@@ -1128,6 +1207,11 @@ def kvsnap_prototypes() -> list:
     return cproto.prototypes(open(KVSNAP_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def beam_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_beam.h, the header include/bitnet_hip.h includes for beam search."""
+    return cproto.prototypes(open(BEAM_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def widetail_prototypes() -> list:
     """The prototypes of include/bitnet_hip_widetail.h, the header include/bitnet_hip.h includes for the wide step's 64-entry tail tables."""
     return cproto.prototypes(open(WIDETAIL_HEADER_PATH).read(), "bitnet_hip_")
@@ -1136,7 +1220,7 @@ def widetail_prototypes() -> list:
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
     return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + kvsnap_prototypes()
-                   + widetail_prototypes()})
+                   + widetail_prototypes() + beam_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -1148,6 +1232,7 @@ HOST_HEADER_PATHS = [os.path.join(HERE, "host", f) for f in ("decoder.hpp", "bat
 HOST_GRAMMAR_HEADER_PATH = os.path.join(HERE, "host", "grammar_host.hpp")  # the decoder's grammar control, bound beside the others
 HOST_PREFIX_HEADER_PATH = os.path.join(HERE, "host", "prefix_cache.hpp")  # PrefixCache and Decoder::prefill_cached, bound beside the others
 HOST_WIDE_HEADER_PATH = os.path.join(HERE, "host", "wide_batch.hpp")  # WideBatch, bound beside the others
+HOST_BEAM_HEADER_PATH = os.path.join(HERE, "host", "beam_search.hpp")  # BeamSearch, bound beside the others
 _host_libs = {}
 
 
@@ -1171,6 +1256,11 @@ def host_wide_prototypes() -> list:
     return cproto.prototypes(open(HOST_WIDE_HEADER_PATH).read(), "bitnet_host_")
 
 
+def host_beam_prototypes() -> list:
+    """The exports of host/beam_search.hpp (BeamSearch), typed at load like the rest."""
+    return cproto.prototypes(open(HOST_BEAM_HEADER_PATH).read(), "bitnet_host_")
+
+
 def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
     """The host library at `path`, loaded and bound from its headers once per process."""
     if path not in _host_libs:
@@ -1179,6 +1269,7 @@ def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
         cproto.bind(L, host_grammar_prototypes(), C_STRUCTS)
         cproto.bind(L, host_prefix_prototypes(), C_STRUCTS)
         cproto.bind(L, host_wide_prototypes(), C_STRUCTS)
+        cproto.bind(L, host_beam_prototypes(), C_STRUCTS)
         _host_libs[path] = L
     return _host_libs[path]
 
@@ -1217,7 +1308,7 @@ class HostConfig(C.Structure):
 C_STRUCTS = {"bitnet_hip_device_info": DeviceInfo, "bitnet_hip_gemv_q_geometry_t": GemvQGeometry, "bitnet_hip_gemv_geometry_t": GemvGeometry, "bitnet_hip_sampling_config": SamplingConfig,
              "bitnet_hip_sampling_config_ex": SamplingConfigEx, "bitnet_hip_mirostat_config": MirostatConfig,
              "bitnet_hip_constraints": Constraints, "bitnet_hip_grammar_desc": GrammarDesc, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
-             "bitnet_hip_stop_state": StopState, "bitnet_host_config": HostConfig, "bitnet_host_prefix_stats": PrefixStats}
+             "bitnet_hip_stop_state": StopState, "bitnet_hip_beam_state": BeamState, "bitnet_host_config": HostConfig, "bitnet_host_prefix_stats": PrefixStats}
 
 FLAVORS = ("BitNet32F16", "Split32WithSibling", "GgmlQk256NoScale")
 
@@ -1742,8 +1833,9 @@ class HostDecoder:
 
 
 def _host_fn(host: C.CDLL, name: str):
-    """An export of host/grammar_host.hpp or host/wide_batch.hpp on the bound host library.  By name, as _prefix_fn: these are typed from
-    THOSE headers at load (host_grammar_prototypes, host_wide_prototypes), not from the three headers host_prototypes() reads."""
+    """An export of host/grammar_host.hpp, host/wide_batch.hpp or host/beam_search.hpp on the bound host library.  By name, as _prefix_fn:
+    these are typed from THOSE headers at load (host_grammar_prototypes, host_wide_prototypes, host_beam_prototypes), not from the three
+    headers host_prototypes() reads."""
     return getattr(host, name)
 
 
@@ -1904,6 +1996,71 @@ class HostBatch:
     def graph_nodes(self) -> int:
         """Kernel nodes of the captured chain, 0 if none is held."""
         return int(self.c.bitnet_host_batch_graph_nodes(self.h))
+
+
+class HostBeamSearch:
+    """ctypes view of the C++ BeamSearch (host/beam_search.hpp): beam search over the first n_beams slots of a HostBatch -- plain greedy members
+    of one owner, brought to one position with identical prefixes (prefill one, fork_into the others).  Per token: the batched step, one select
+    launch (the rule of include/bitnet_hip_beam.h) and one launch that moves the beams' caches in place; the host reads 4 bytes per chunk.
+    After run() the live beams are live sequences: HostBatch.step, run and fork_into go on from them.  No arithmetic here."""
+
+    def __init__(self, batch: "HostBatch", n_beams: int, eos: int, max_new_tokens: int, alpha: float = 0.0):
+        load()
+        self.c, self.batch = batch.c, batch
+        self.n_beams, self.max_new_tokens = int(n_beams), int(max_new_tokens)
+        self.h = self._b("create")(batch.h, int(n_beams), int(eos), int(max_new_tokens), float(alpha))
+        if not self.h:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, "bitnet_host_beam_create failed")
+        err = self.error()
+        if err:
+            self.close()
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, err)
+
+    def _b(self, name: str):
+        return _host_fn(self.c, "bitnet_host_beam_" + name)
+
+    def error(self) -> str:
+        e = self._b("error")(self.h)
+        return e.decode() if e else ""
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise BitNetHipError(rc, self.error() or f"bitnet_host_beam rc={rc}")
+
+    def close(self) -> None:
+        if self.h:
+            self._b("destroy")(self.h)
+            self.h = None
+
+    def start(self) -> None:
+        """A new search from the members' common position; refuses members at different positions or with different prefixes."""
+        self._check(self._b("start")(self.h))
+
+    def run(self, chunk: int = 8) -> "tuple[int, float]":
+        """Queues chunk x {step, select, permute} and reads `done`, until the search is done.  Returns (steps queued, milliseconds of the steps)."""
+        steps, ms = C.c_int(0), C.c_float(0.0)
+        self._check(self._b("run")(self.h, int(chunk), C.byref(steps), C.byref(ms)))
+        return int(steps.value), float(ms.value)
+
+    def state(self) -> BeamState:
+        st = BeamState()
+        self._check(self._b("state")(self.h, C.byref(st)))
+        return st
+
+    def hypotheses(self) -> list:
+        """The pool by descending key, then insertion order: [(tokens, score, key)], score and key as numpy float32."""
+        n = C.c_int(0)
+        lens, tok = np.zeros(BEAM_MAX, np.int32), np.zeros((BEAM_MAX, self.max_new_tokens), np.int32)
+        scores, keys = np.zeros(BEAM_MAX, np.float32), np.zeros(BEAM_MAX, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self._b("hypotheses")(self.h, C.byref(n), p(lens), p(tok), p(scores), p(keys)))
+        return [([int(t) for t in tok[i, :lens[i]]], scores[i], keys[i]) for i in range(int(n.value))]
+
+    def len_weights(self) -> np.ndarray:
+        """The length weights the search passes to the device: [max_new_tokens + 1] float32, len ** -alpha."""
+        out = np.zeros(self.max_new_tokens + 1, np.float32)
+        self._check(self._b("len_weights")(self.h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
 
 
 class HostWideBatch:

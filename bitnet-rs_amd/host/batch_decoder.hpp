@@ -43,6 +43,8 @@ class BatchDecoder {
     const std::string &error() const { return err_; }
     bool dead() const { return dead_; }
     int n_slots() const { return n_; }
+    Decoder *member(int b) const { return b >= 0 && b < n_ ? slot_[b] : nullptr; }  // what slot b holds (BeamSearch binds to the first n_beams)
+    void *stream() const { return stream_; }                                        // the stream every step runs on
     // Puts `d` into slot b (replacing what is there) or clears it (d == nullptr).  Every member: the same owner (or the owner itself), the
     // same KV type, on the QAct path, in no other slot.  Holds a reference on the member until the slot changes.
     int set_slot(int b, Decoder *d);

@@ -1111,5 +1111,6 @@ int bitnet_hip_hbm_read_ceiling(size_t bytes, int iters, double *best_gbs, doubl
 #include "bitnet_hip_grammar.h" /* the sampler's grammar stage: six more entry points of this ABI */
 #include "bitnet_hip_kvsnap.h"  /* compact KV snapshots: three more */
 #include "bitnet_hip_widetail.h" /* the wide step's tail: the sampler and tap tables at 64 entries, two more */
+#include "bitnet_hip_beam.h"    /* beam search: the select launch, the in-place KV permute and their state object, seven more */
 
 #endif /* BITNET_HIP_H */

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "kv_guard.hpp"
 #include "qact.hpp"
 
 namespace bitnet_hip {
@@ -1386,26 +1387,13 @@ int bitnet_hip_kv_fork_dev(const void *const *src_k_ptrs_dev, const void *const 
     BH_GUARD_BEGIN
     if (!src_k_ptrs_dev || !src_v_ptrs_dev || !dst_k_ptrs_dev || !dst_v_ptrs_dev)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_fork_dev");
-    if (n_layers == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: n_layers 0");
-    if (n_dst == 0 || n_dst > BITNET_HIP_BATCH_MAX)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: n_dst %zu must be 1..%d", n_dst, BITNET_HIP_BATCH_MAX);
-    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: head_dim %zu unsupported (128)", head_dim);
-    if (n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: num_key_value_heads 0");
-    if (flags & ~BITNET_HIP_ATTN_KV_F16)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_fork_dev: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16)", flags);
+    if (int rc = kv_guard_shape("kv_fork_dev", n_layers, n_kv_heads, head_dim, flags, "n_dst", n_dst)) return rc;
     if (n_positions > max_pos)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: n_positions %zu, max_pos %zu", n_positions, max_pos);  // T:1190-1194
-    // words (32 bits) per position and KV head, per KV head, per cache; segments = (layer, KV head, K | V) triples the grid is cut into
-    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
-    size_t slots = 0, head_words = 0, cache_bytes = 0, segments = 0;
-    if (__builtin_add_overflow(max_pos, (size_t)63, &slots) || __builtin_mul_overflow(slots / 64 * 64, rows, &head_words) ||
-        __builtin_mul_overflow(head_words, n_kv_heads, &cache_bytes) || __builtin_mul_overflow(cache_bytes, sizeof(uint32_t), &cache_bytes) ||
-        __builtin_mul_overflow(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, (size_t)2, &segments) || segments >= ((size_t)1 << 24) ||
-        __builtin_mul_overflow(n_layers, n_dst, &slots))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (kv_fork_dev: n_layers %zu, n_kv_heads %zu, max_pos %zu)", n_layers,
-                         n_kv_heads, max_pos);
+    KvGeometry g;
+    if (int rc = kv_guard_sizes("kv_fork_dev", n_layers, n_dst, n_kv_heads, head_dim, max_pos, SIZE_MAX, flags, &g)) return rc;
     if (n_positions == 0) return BITNET_HIP_OK;  // valid, and nothing to launch
-    BH_HIP_TRY(launch_kv_fork(src_k_ptrs_dev, src_v_ptrs_dev, dst_k_ptrs_dev, dst_v_ptrs_dev, n_layers, n_dst, n_kv_heads, rows, head_words, n_positions,
+    BH_HIP_TRY(launch_kv_fork(src_k_ptrs_dev, src_v_ptrs_dev, dst_k_ptrs_dev, dst_v_ptrs_dev, n_layers, n_dst, n_kv_heads, g.rows, g.head_words, n_positions,
                               (hipStream_t)stream));
     return BITNET_HIP_OK;
     BH_GUARD_END
@@ -1419,32 +1407,25 @@ size_t kv_snapshot_size(size_t n_layers, size_t n_kv_heads, size_t head_dim, siz
     if (n_layers == 0 || n_kv_heads == 0 || head_dim != 128 || (flags & ~BITNET_HIP_ATTN_KV_F16)) return 0;
     const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
     size_t segments = 0, bytes = 0;
-    if (__builtin_mul_overflow(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, (size_t)2, &segments) || segments >= ((size_t)1 << 24) ||
-        __builtin_mul_overflow(segments, n_positions, &bytes) || __builtin_mul_overflow(bytes, rows * sizeof(uint32_t), &bytes))
+    if (!kv_segments_fit(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, n_positions, &bytes) ||
+        __builtin_mul_overflow(bytes, rows * sizeof(uint32_t), &bytes))
         return 0;
     return bytes;
 }
 
-// The refusals save and restore share, fork's wording where the case is fork's; leaves rows and head_words.  `positions`: what the snapshot holds.
+// The refusals save and restore share beyond kv_guard_shape; leaves rows and head_words.  `positions`: what the snapshot holds.  The sizes are not
+// kv_guard_sizes': a snapshot is refused by ITS size (which holds the segment count) and only when it has one, and the message names it.
 int kv_snapshot_check(const char *entry, size_t n_layers, size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t n_positions, size_t positions, int flags,
-                      const void *snapshot, size_t *rows_out, size_t *head_words_out) {
-    if (n_layers == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_layers 0", entry);
-    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: head_dim %zu unsupported (128)", entry, head_dim);
-    if (n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: num_key_value_heads 0", entry);
-    if (flags & ~BITNET_HIP_ATTN_KV_F16) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16)", entry, flags);
+                      const void *snapshot, KvGeometry *g) {
+    if (int rc = kv_guard_shape(entry, n_layers, n_kv_heads, head_dim, flags)) return rc;
     if (n_positions > max_pos)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: n_positions %zu, max_pos %zu", n_positions, max_pos);  // T:1190-1194
     if (n_positions > positions)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_positions %zu exceeds snapshot_positions %zu", entry, n_positions, positions);
     if ((uintptr_t)snapshot % 16) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: the snapshot must be 16-byte aligned", entry);
-    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
-    size_t slots = 0, head_words = 0, cache_bytes = 0;
-    if (__builtin_add_overflow(max_pos, (size_t)63, &slots) || __builtin_mul_overflow(slots / 64 * 64, rows, &head_words) ||
-        __builtin_mul_overflow(head_words, n_kv_heads, &cache_bytes) || __builtin_mul_overflow(cache_bytes, sizeof(uint32_t), &cache_bytes) ||
-        (positions && !kv_snapshot_size(n_layers, n_kv_heads, head_dim, positions, flags)))
+    if (!kv_cache_fits(n_kv_heads, head_dim, max_pos, flags, g) || (positions && !kv_snapshot_size(n_layers, n_kv_heads, head_dim, positions, flags)))
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (%s: n_layers %zu, n_kv_heads %zu, max_pos %zu, snapshot of %zu)",
                          entry, n_layers, n_kv_heads, max_pos, positions);
-    *rows_out = rows, *head_words_out = head_words;
     return BITNET_HIP_OK;
 }
 }  // namespace
@@ -1457,11 +1438,10 @@ int bitnet_hip_kv_save_dev(const void *const *k_ptrs_dev, const void *const *v_p
                            size_t n_positions, int flags, void *snapshot_dev, void *stream) {
     BH_GUARD_BEGIN
     if (!k_ptrs_dev || !v_ptrs_dev || !snapshot_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_save_dev");
-    size_t rows = 0, head_words = 0;
-    if (int rc = kv_snapshot_check("kv_save_dev", n_layers, n_kv_heads, head_dim, max_pos, n_positions, n_positions, flags, snapshot_dev, &rows, &head_words))
-        return rc;
+    KvGeometry g;
+    if (int rc = kv_snapshot_check("kv_save_dev", n_layers, n_kv_heads, head_dim, max_pos, n_positions, n_positions, flags, snapshot_dev, &g)) return rc;
     if (n_positions == 0) return BITNET_HIP_OK;  // valid, and nothing to launch
-    BH_HIP_TRY(launch_kv_save(k_ptrs_dev, v_ptrs_dev, n_layers, n_kv_heads, rows, head_words, n_positions, snapshot_dev, (hipStream_t)stream));
+    BH_HIP_TRY(launch_kv_save(k_ptrs_dev, v_ptrs_dev, n_layers, n_kv_heads, g.rows, g.head_words, n_positions, snapshot_dev, (hipStream_t)stream));
     return BITNET_HIP_OK;
     BH_GUARD_END
 }
@@ -1472,13 +1452,12 @@ int bitnet_hip_kv_restore_dev(const void *snapshot_dev, size_t snapshot_position
     if (!snapshot_dev || !dst_k_ptrs_dev || !dst_v_ptrs_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_restore_dev");
     if (n_dst == 0 || n_dst > BITNET_HIP_BATCH_MAX)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_restore_dev: n_dst %zu must be 1..%d", n_dst, BITNET_HIP_BATCH_MAX);
-    size_t rows = 0, head_words = 0;
-    if (int rc = kv_snapshot_check("kv_restore_dev", n_layers, n_kv_heads, head_dim, max_pos, n_positions, snapshot_positions, flags, snapshot_dev, &rows,
-                                   &head_words))
+    KvGeometry g;
+    if (int rc = kv_snapshot_check("kv_restore_dev", n_layers, n_kv_heads, head_dim, max_pos, n_positions, snapshot_positions, flags, snapshot_dev, &g))
         return rc;
     if (n_positions == 0) return BITNET_HIP_OK;  // valid, and nothing to launch
-    BH_HIP_TRY(launch_kv_restore(snapshot_dev, snapshot_positions, dst_k_ptrs_dev, dst_v_ptrs_dev, n_layers, n_dst, n_kv_heads, rows, head_words, n_positions,
-                                 (hipStream_t)stream));
+    BH_HIP_TRY(launch_kv_restore(snapshot_dev, snapshot_positions, dst_k_ptrs_dev, dst_v_ptrs_dev, n_layers, n_dst, n_kv_heads, g.rows, g.head_words,
+                                 n_positions, (hipStream_t)stream));
     return BITNET_HIP_OK;
     BH_GUARD_END
 }
@@ -1490,26 +1469,19 @@ int bitnet_hip_kv_shift_dev(void *const *k_ptrs_dev, void *const *v_ptrs_dev, co
     BH_GUARD_BEGIN
     if (!k_ptrs_dev || !v_ptrs_dev || !rope_sin_dev || !rope_cos_dev)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_shift_dev");
-    if (n_layers == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: n_layers 0");
-    if (n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: num_key_value_heads 0");
-    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: head_dim %zu unsupported (128)", head_dim);
-    if (flags & ~BITNET_HIP_ATTN_KV_F16)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16)", flags);
+    // this entry has always named a zero num_key_value_heads before a bad head_dim, the other way round from kv_guard_shape
+    if (n_layers != 0 && n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: num_key_value_heads 0");
+    if (int rc = kv_guard_shape("kv_shift_dev", n_layers, n_kv_heads, head_dim, flags)) return rc;
     if (discard == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: discard 0 (at least one position must go)");
     if (n_positions > max_pos)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: n_positions %zu, max_pos %zu", n_positions, max_pos);  // T:1190-1194
     size_t gone = 0;
     if (__builtin_add_overflow(keep, discard, &gone) || gone > n_positions)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_shift_dev: keep %zu + discard %zu exceeds n_positions %zu", keep, discard, n_positions);
-    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
-    size_t slots = 0, head_words = 0, cache_bytes = 0, segments = 0;
-    if (max_pos > (size_t)INT32_MAX || __builtin_add_overflow(max_pos, (size_t)63, &slots) || __builtin_mul_overflow(slots / 64 * 64, rows, &head_words) ||
-        __builtin_mul_overflow(head_words, n_kv_heads, &cache_bytes) || __builtin_mul_overflow(cache_bytes, sizeof(uint32_t), &cache_bytes) ||
-        __builtin_mul_overflow(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, (size_t)2, &segments) || segments >= ((size_t)1 << 24))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (kv_shift_dev: n_layers %zu, n_kv_heads %zu, max_pos %zu)",
-                         n_layers, n_kv_heads, max_pos);
+    KvGeometry g;  // the kernel holds positions in 32-bit ints
+    if (int rc = kv_guard_sizes("kv_shift_dev", n_layers, 1, n_kv_heads, head_dim, max_pos, (size_t)INT32_MAX, flags, &g)) return rc;
     if (gone == n_positions) return BITNET_HIP_OK;  // nothing moves: valid, and nothing to launch
-    BH_HIP_TRY(launch_kv_shift(k_ptrs_dev, v_ptrs_dev, rope_sin_dev, rope_cos_dev, n_layers, n_kv_heads, rows, head_words, keep, discard, n_positions,
+    BH_HIP_TRY(launch_kv_shift(k_ptrs_dev, v_ptrs_dev, rope_sin_dev, rope_cos_dev, n_layers, n_kv_heads, g.rows, g.head_words, keep, discard, n_positions,
                                (hipStream_t)stream));
     return BITNET_HIP_OK;
     BH_GUARD_END

@@ -9,13 +9,9 @@
 //   k_attn_combine  grid (n_kv): out = sum_c e^(m_c-M) o_c / sum_c e^(m_c-M) l_c.
 // Same value as the reference's softmax(QK^T/sqrt(d)) V up to f32 rounding.
 //
-// Cache layout (private to this library): K transposed in 64-position tiles,
-// kcache[n_kv][ceil(max_pos/64)][D][64] -- one chunk's keys are 32 contiguous KB (a plain
-// [D][max_pos] transpose scatters them over 128 segments of 256 B, which HBM serves badly at
-// long contexts); element (d, pos) at ((pos / 64) * D + d) * 64 + pos % 64 (the score
-// pass reads positions contiguously: lane = position); vcache[n_kv][max_pos][D] (the P.V pass
-// reads dims contiguously: lane = dim).  *pos_ptr = number of cached tokens.
+// The cache layout is kv_layout.hpp's.  *pos_ptr = number of cached tokens.
 #include "common.hpp"
+#include "kv_layout.hpp"
 #include "qact.hpp"
 #include "wave.hpp"
 
@@ -23,14 +19,10 @@ namespace bitnet_hip {
 
 constexpr int kAttnChunk = 64;
 constexpr int kMaxGroup = 4;
-constexpr int kD = 128;
+constexpr int kD = kKvDim;
 // per (kv head, chunk) record in the scratch buffer: (m, l)[4], o[4][128]   (kAttnRecFloats, common.hpp)
 constexpr int kRec = kAttnRecFloats;
 static_assert(kRec == 2 * kMaxGroup + kMaxGroup * kD, "record layout");
-
-// K cache element (dim d, position pos) of one KV head
-__device__ __forceinline__ size_t kidx(int d, int pos) { return ((size_t)(pos >> 6) * kD + d) * 64 + (pos & 63); }
-__host__ __device__ __forceinline__ size_t kv_head_floats(int max_pos) { return (size_t)((max_pos + 63) / 64) * 64 * kD; }
 
 // In-kernel time stamps (s_memrealtime, 100 MHz): diagnostic build only (-DBH_STAMPS; tools/stamp_attn.py), 8 x u64 per workgroup.
 #ifdef BH_STAMPS
@@ -49,9 +41,7 @@ __host__ __device__ __forceinline__ size_t kv_head_floats(int max_pos) { return 
 // records for whoever merges them (the combine kernel, or the o-projection at short contexts) and, at 4k keys, 160
 // workgroups instead of 320 (one per CU instead of 64 CUs with two).
 // KV16: the cache holds f16 (opt-in: half the bytes of the long-context stream; the reference's cache is f32 Tensor::cat,
-// T:1171-1202 -- values rounded ONCE, from the exact f32 k / v, when they are appended).  Layout then:
-// K [kv][chunk][D / 2][64 positions][2 dims] (a lane still reads 4 bytes per load: a dim PAIR of its position),
-// V [kv][pos][D] halves (a thread takes a dim pair of every 4th position).
+// T:1171-1202): a lane still reads 4 bytes per K load, a dim PAIR of its position, and a thread takes a V dim pair of every 4th position.
 // The body is shared by the batch-1 kernel and the batched one (k_attn_partial_batch: the sequence is a third grid dimension and every
 // sequence brings its own caches and position): one source, so a sequence's bits do not depend on which launch computed them.
 // kvh / pc = this workgroup's KV head and record, n_rec = records per KV head in `scratch`.
@@ -159,7 +149,7 @@ __device__ __forceinline__ void attn_partial_body(const float *__restrict__ qkv,
                 }
             } else {
                 _Float16 *k16 = reinterpret_cast<_Float16 *>(kt), *v16 = reinterpret_cast<_Float16 *>(vc);
-                if (t4 < hd) {  // element (d, pos) at ((chunk * 64 + d / 2) * 64 + pos % 64) * 2 + d % 2
+                if (t4 < hd) {  // kidx16(t4, pos) and kidx16(hd + t4, pos) (kv_layout.hpp), restated: the call folds to other instructions
                     const size_t tb = (size_t)(pos >> 6) * (kD / 2), pp = pos & 63;
                     k16[((tb + (t4 >> 1)) * 64 + pp) * 2 + (t4 & 1)] = (_Float16)a;
                     k16[((tb + ((hd + t4) >> 1)) * 64 + pp) * 2 + (t4 & 1)] = (_Float16)b;

@@ -10,7 +10,7 @@
 //
 // k_kv_permute: the same ownership rule on the caches.  All caches of a call share max_pos, so a word offset means the same (layer, head, slot,
 // element) in each; one thread owns a 16-byte vector offset in all B caches, loads the parent's vector for every beam that moves there and only
-// then stores -- at most 8 vectors in registers, no scratch copy, no second launch.  Layouts as kernels_kvfork.hip, from a start slot:
+// then stores -- at most 8 vectors in registers, no scratch copy, no second launch.  In the cache layout (kv_layout.hpp), from a start slot:
 //   K  [kv][C][R][64] words: a vector is 4 neighbouring SLOTS of one row; vectors that straddle from[b] or n are stored dword-wise
 //   V  [kv][C * 64][R] words: a vector lies inside one slot; slots [from[b], n) are one contiguous run
 // Integer loads and stores on pointers typed global: NaN payloads pass, and f32 / f16 caches differ in R alone.
@@ -18,7 +18,8 @@
 #include <new>
 
 #include "beam_rule.hpp"
-#include "common.hpp"
+#include "kv_guard.hpp"
+#include "kv_layout.hpp"
 
 namespace bitnet_hip {
 namespace {
@@ -119,11 +120,6 @@ __global__ __launch_bounds__(kSelThreads) void k_beam_select(BeamState *st, cons
     for (int i = tid; i < kStateWords; i += kSelThreads) reinterpret_cast<uint32_t *>(st)[i] = reinterpret_cast<const uint32_t *>(&s)[i];
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned g_u32;
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-__device__ __forceinline__ g_u32x4 *as_global4(const void *p) { return reinterpret_cast<g_u32x4 *>(reinterpret_cast<uintptr_t>(p)); }
-
 struct KvPermuteArgs {
     void *const *k, *const *v;  // [n_beams][n_layers]
     const BeamState *st;
@@ -140,6 +136,7 @@ __global__ __launch_bounds__(kPermThreads) void k_kv_permute(const KvPermuteArgs
     const BeamState *st = a.st;
     if (!st->stepped) return;  // a frozen step, a range error, a fresh reset: nothing moved
     const int n = min(max(st->n_slots, 0), (int)a.key_bound);
+    // kv_segment (kv_layout.hpp), restated: through the struct the compiler orders this kernel's instructions another way
     const unsigned seg = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
     const unsigned is_v = seg & 1u, kv = (seg >> 1) % a.n_kv, layer = (seg >> 1) / a.n_kv;
     const int B = (int)a.n_beams;
@@ -319,29 +316,20 @@ int bitnet_hip_beam_select_dev(bitnet_hip_beam *bm, const bitnet_hip_beam_member
 int bitnet_hip_kv_permute_dev(void *const *k_ptrs_dev, void *const *v_ptrs_dev, bitnet_hip_beam *bm, size_t n_layers, size_t n_beams, size_t n_kv_heads,
                               size_t head_dim, size_t max_pos, size_t key_bound, int flags, void *stream) {
     if (!k_ptrs_dev || !v_ptrs_dev) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to kv_permute_dev");
-    if (n_layers == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_permute_dev: n_layers 0");
-    if (n_beams == 0 || n_beams > BITNET_HIP_BEAM_MAX)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_permute_dev: n_beams %zu must be 1..%d", n_beams, BITNET_HIP_BEAM_MAX);
-    if (head_dim != 128) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_permute_dev: head_dim %zu unsupported (128)", head_dim);
-    if (n_kv_heads == 0) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_permute_dev: num_key_value_heads 0");
-    if (flags & ~BITNET_HIP_ATTN_KV_F16)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_permute_dev: flags 0x%x (0 or BITNET_HIP_ATTN_KV_F16)", flags);
+    if (int rc = kv_guard_shape("kv_permute_dev", n_layers, n_kv_heads, head_dim, flags, "n_beams", n_beams)) return rc;
     if (key_bound > max_pos)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "KV cache overflow: key_bound %zu, max_pos %zu", key_bound, max_pos);
-    const size_t rows = (flags & BITNET_HIP_ATTN_KV_F16) ? head_dim / 2 : head_dim;
-    size_t slots = 0, head_words = 0, cache_bytes = 0, segments = 0, blocks = 0;
-    if (max_pos > (size_t)0x7fffffff - 63 || __builtin_add_overflow(max_pos, (size_t)63, &slots) || __builtin_mul_overflow(slots / 64 * 64, rows, &head_words) ||
-        __builtin_mul_overflow(head_words, n_kv_heads, &cache_bytes) || __builtin_mul_overflow(cache_bytes, sizeof(uint32_t), &cache_bytes) ||
-        __builtin_mul_overflow(n_layers, n_kv_heads, &segments) || __builtin_mul_overflow(segments, (size_t)2, &segments) || segments >= ((size_t)1 << 24) ||
-        __builtin_mul_overflow(n_layers, n_beams, &slots))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (kv_permute_dev: n_layers %zu, n_kv_heads %zu, max_pos %zu)",
-                         n_layers, n_kv_heads, max_pos);
+    KvGeometry g;  // the kernel rounds slot numbers up to whole chunks in an int
+    if (int rc = kv_guard_sizes("kv_permute_dev", n_layers, n_beams, n_kv_heads, head_dim, max_pos, (size_t)0x7fffffff - 63, flags, &g)) return rc;
+    const size_t rows = g.rows, head_words = g.head_words, segments = g.segments;
+    size_t blocks = 0;
     // the geometry first, the state last: every refusal above names an argument and needs no state to show it
     if (!bm) return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null beam passed to kv_permute_dev");
     if ((int)n_beams != bm->n_beams)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "kv_permute_dev: n_beams %zu, the state was created for %d", n_beams, bm->n_beams);
     if (key_bound == 0) return BITNET_HIP_OK;  // no slot can have moved
-    // a segment's vectors below key_bound (K's whole chunks bound V's run too), in tiles of one workgroup
+    // not kv_parts: a workgroup owns one tile and leaves if nothing of it moves.  A segment's vectors below key_bound (K's whole chunks bound V's
+    // run too), in tiles of one workgroup
     const size_t parts = div_ceil(div_ceil(key_bound, (size_t)64) * rows * 16, kPermTile);
     if (__builtin_mul_overflow(segments, parts, &blocks) || blocks > (size_t)0x7fffffff)
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (kv_permute_dev: %zu segments of %zu workgroups)", segments, parts);

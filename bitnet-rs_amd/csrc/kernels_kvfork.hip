@@ -5,25 +5,18 @@
 // prefix and its opaque cached_state bytes, insert :212 stores one).  Here the state stays on the device, and a prefix hit is a device-to-device copy
 // of cache slots: eight conversations over one system prompt, or eight samples of one prompt, pay one prompt forward.
 //
-// Layouts (kernels_attn.hip), per KV head padded to C = ceil(max_pos / 64) chunks, in 32-bit WORDS (an f16 K word is the (d even, d odd) pair of one
-// position, an f16 V word two neighbouring dims), R = D words-rows per chunk for f32 and D / 2 for f16 -- so one code serves both types:
+// What the first n positions are in the cache layout (kv_layout.hpp), in 32-bit words:
 //   K  [kv][C][R][64]     chunks below n / 64 are one contiguous run of (n / 64) * R * 64 words; in the partial chunk the first n % 64 words of each
 //                         of its R rows
 //   V  [kv][C * 64][R]    the first n rows: one contiguous run of n * R words
 // Both runs are whole 16-byte vectors from a 16-byte aligned start (R is 64 or 128).  A workgroup owns a part of one (layer, KV head, K | V) segment;
 // every source vector is loaded ONCE and stored n_dst times -- the fan-out is why this is a kernel and not 2 * n_layers hipMemcpy2DAsync calls per
 // destination.  Integer loads and stores: NaN payloads and denormals pass through unchanged.  Nothing outside the copied slots is written.
-#include "common.hpp"
+#include "kv_layout.hpp"
 
 namespace bitnet_hip {
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// the cache pointers come out of pointer tables: typed as GLOBAL memory here, or the copy compiles to flat loads and stores
-typedef __attribute__((address_space(1))) unsigned g_u32;
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-__device__ __forceinline__ g_u32 *as_global(const void *p) { return reinterpret_cast<g_u32 *>(reinterpret_cast<uintptr_t>(p)); }
 
 struct KvForkArgs {
     const void *const *src_k, *const *src_v;  // [n_layers]
@@ -34,34 +27,34 @@ struct KvForkArgs {
     size_t n;                                 // positions to copy (>= 1)
 };
 
-constexpr int kForkThreads = 256;
-constexpr int kForkUnroll = 4;  // 16-byte loads in flight per lane before the first store
+constexpr int kForkThreads = kKvCopyThreads;
 
 __global__ __launch_bounds__(kForkThreads) void k_kv_fork(const KvForkArgs a) {
-    const unsigned seg = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
-    const unsigned is_v = seg & 1u, kv = (seg >> 1) % a.n_kv, layer = (seg >> 1) / a.n_kv;
-    const size_t base = (size_t)kv * a.head_words;
-    const g_u32 *src = as_global((is_v ? a.src_v : a.src_k)[layer]) + base;
+    const KvSegment s = kv_segment(blockIdx.x, a.parts, a.n_kv);
+    const unsigned is_v = s.is_v, part = s.part;
+    const size_t base = s.base(a.head_words);
+    const g_u32 *src = as_global((is_v ? a.src_v : a.src_k)[s.layer]) + base;
     g_u32 *dst[kBatchMax];
 #pragma unroll
     for (int d = 0; d < kBatchMax; ++d)
-        dst[d] = (unsigned)d < a.n_dst ? as_global((is_v ? a.dst_v : a.dst_k)[(size_t)d * a.n_layers + layer]) + base : nullptr;
+        dst[d] = (unsigned)d < a.n_dst ? as_global((is_v ? a.dst_v : a.dst_k)[(size_t)d * a.n_layers + s.layer]) + base : nullptr;
 
     // the contiguous run, in 16-byte vectors
     const size_t whole = a.n / 64;
     const size_t run4 = is_v ? a.n * (a.rows / 4) : whole * 16 * a.rows;
+    // kv_copy_run (kv_layout.hpp), restated: called as a function it compiles to other instructions here than this loop always has
     const size_t stride = (size_t)a.parts * kForkThreads;
     const g_u32x4 *s4 = reinterpret_cast<const g_u32x4 *>(src);
     size_t i = (size_t)part * kForkThreads + threadIdx.x;
-    for (; i + (kForkUnroll - 1) * stride < run4; i += kForkUnroll * stride) {
-        u32x4 v[kForkUnroll];
+    for (; i + (kKvCopyUnroll - 1) * stride < run4; i += kKvCopyUnroll * stride) {
+        u32x4 v[kKvCopyUnroll];
 #pragma unroll
-        for (int u = 0; u < kForkUnroll; ++u) v[u] = s4[i + u * stride];
+        for (int u = 0; u < kKvCopyUnroll; ++u) v[u] = s4[i + u * stride];
 #pragma unroll
         for (int d = 0; d < kBatchMax; ++d)
             if ((unsigned)d < a.n_dst) {
 #pragma unroll
-                for (int u = 0; u < kForkUnroll; ++u) reinterpret_cast<g_u32x4 *>(dst[d])[i + u * stride] = v[u];
+                for (int u = 0; u < kKvCopyUnroll; ++u) reinterpret_cast<g_u32x4 *>(dst[d])[i + u * stride] = v[u];
             }
     }
     for (; i < run4; i += stride) {
@@ -96,12 +89,9 @@ hipError_t launch_kv_fork(const void *const *src_k, const void *const *src_v, vo
     a.src_k = src_k, a.src_v = src_v, a.dst_k = dst_k, a.dst_v = dst_v;
     a.n_layers = (unsigned)n_layers, a.n_dst = (unsigned)n_dst, a.n_kv = (unsigned)n_kv, a.rows = (unsigned)rows;
     a.head_words = head_words, a.n = n;
-    // memory-bound: about 2048 workgroups (8 per CU) in all, the rest of a segment is strided; no more parts than the longest run (V's) has
-    // workgroup-wide vectors, and at least one (the partial K chunk is strided by the same parts)
+    // no more parts than the longest run (V's) has workgroup-wide vectors (the partial K chunk is strided by the same parts)
     const size_t segments = 2 * n_layers * n_kv;
-    const size_t want = segments >= 2048 ? 1 : 2048 / segments;
-    const size_t have = div_ceil(n * (rows / 4), (size_t)kForkThreads);
-    a.parts = (unsigned)(want < have ? want : have);
+    a.parts = kv_parts(segments, div_ceil(n * (rows / 4), (size_t)kForkThreads));
     // plain loads and stores: the non-temporal forms measured 3-6 % faster at one destination x 4096 positions, slower at seven destinations and
     // at short prefixes (EXPERIMENTS.md 17)
     hipLaunchKernelGGL(k_kv_fork, dim3((unsigned)(segments * a.parts)), dim3(kForkThreads), 0, stream, a);

@@ -2,18 +2,16 @@
 // every j in [keep, n - discard) -- V bit for bit, K turned back by the RoPE angle between the two positions -- in place, by ONE launch.
 //
 // The reference keeps the pieces on the host: KvCacheBuffer::rotate_kv / truncate (crates/bitnet-kernels/src/cuda/kv_cache.rs:305-348) and
-// WindowedKVCache (crates/bitnet-gpu-hal/src/sliding_window.rs:161-235).  Here the state lives on the device in private layouts (kernels_attn.hip,
-// kernels_kvfork.hip), per KV head padded to C = ceil(max_pos / 64) chunks, in 32-bit WORDS (an f16 K word is the (d even, d odd) pair of one
-// position, an f16 V word two neighbouring dims), R = D word-rows per chunk for f32 and D / 2 for f16:
-//   K  [kv][C][R][64]     word (row, position % 64) of chunk position / 64
-//   V  [kv][C * 64][R]    row j = position j: the move is one contiguous run shifted down by discard * R words (whole 16-byte vectors)
+// WindowedKVCache (crates/bitnet-gpu-hal/src/sliding_window.rs:161-235).  Here the state lives on the device in the private layout
+// (kv_layout.hpp): K moves word by word, row by row; in V, row j = position j, the move is one contiguous run shifted down by discard * R
+// words (whole 16-byte vectors).
 //
 // K is cached AFTER RoPE.  The key of slot j + discard was rotated by table row j + discard (sa, ca) and has to look as if rotated by row j (sb, cb).
 // Per RoPE pair (x0, x1) = dims (i, i + 64), in f32, unfused (this file is built with -ffp-contract=off) and in this order:
 //   c = ca*cb + sa*sb,  s = sa*cb - ca*sb,  x0' = x0*c + x1*s,  x1' = x1*c - x0*s
 // The two table rows actually involved, NOT row `discard`: the tables hold sinf / cosf of the f32 product position * inv_freq, and row j + discard is
 // not row j composed with row discard to f32 accuracy.  An f16 word is widened exactly and rounded once, to nearest-even.
-// In an f32 cache the pair is rows i and i + 64; in an f16 cache dims (2r, 2r + 1) of row r pair with dims (2r + 64, 2r + 65) of row r + 32.
+// Which rows hold a pair: kv_layout.hpp.
 //
 // ORDERING: why no slot is read after it was overwritten.  The move is in place and sources [keep + discard, n) overlap destinations
 // [keep, n - discard) whenever more than `discard` positions move.
@@ -31,21 +29,17 @@
 //       split over `parts` workgroups that take every parts-th tile, as k_kv_fork splits its runs.
 // The table reads are of constant memory and carry no hazard.  Nothing outside slots [keep, n - discard) is written: slots < keep, the stale slots
 // >= n - discard and the padding of the last chunk keep their bytes.
-#include "common.hpp"
+#include "kv_layout.hpp"
 
 namespace bitnet_hip {
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-// the cache pointers come out of pointer tables: typed as GLOBAL memory here, or the move compiles to flat loads and stores
-typedef __attribute__((address_space(1))) unsigned g_u32;
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+// the RoPE tables, typed as global memory as the caches are (kv_layout.hpp)
 typedef __attribute__((address_space(1))) const f32x4 g_cf32x4;
-__device__ __forceinline__ g_u32 *as_global(const void *p) { return reinterpret_cast<g_u32 *>(reinterpret_cast<uintptr_t>(p)); }
-__device__ __forceinline__ g_cf32x4 *as_global4(const float *p) { return reinterpret_cast<g_cf32x4 *>(reinterpret_cast<uintptr_t>(p)); }
+__device__ __forceinline__ g_cf32x4 *table4(const float *p) { return reinterpret_cast<g_cf32x4 *>(reinterpret_cast<uintptr_t>(p)); }
 
 struct KvShiftArgs {
     void *const *k, *const *v;   // [n_layers]
@@ -75,7 +69,7 @@ __device__ __forceinline__ void rotate(float x0, float x1, float c, float s, flo
 // (rows i and i + 64), 16 words of an f16 cache (rows i / 2 and i / 2 + 32).  A row's 64 lanes read and write 64 consecutive words.
 template <bool kF16>
 __device__ __forceinline__ void shift_k(g_u32 *base, const KvShiftArgs &a, unsigned part) {
-    constexpr unsigned R = kF16 ? 64 : 128;
+    constexpr unsigned R = kv_rows(kF16);
     constexpr int P = kF16 ? 8 : 16;  // word pairs per thread
     const unsigned l = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const unsigned row0 = (unsigned)P * w;
@@ -89,8 +83,8 @@ __device__ __forceinline__ void shift_k(g_u32 *base, const KvShiftArgs &a, unsig
             const g_u32 *src = base + (size_t)(js >> 6) * (R * 64) + (js & 63u);
 #pragma unroll
             for (int q = 0; q < P; ++q) lo[q] = src[(row0 + q) * 64], hi[q] = src[(row0 + q + R / 2) * 64];
-            g_cf32x4 *sa4 = as_global4(a.sn + (size_t)js * 64 + 16 * w), *ca4 = as_global4(a.cs + (size_t)js * 64 + 16 * w);
-            g_cf32x4 *sb4 = as_global4(a.sn + (size_t)j * 64 + 16 * w), *cb4 = as_global4(a.cs + (size_t)j * 64 + 16 * w);
+            g_cf32x4 *sa4 = table4(a.sn + (size_t)js * 64 + 16 * w), *ca4 = table4(a.cs + (size_t)js * 64 + 16 * w);
+            g_cf32x4 *sb4 = table4(a.sn + (size_t)j * 64 + 16 * w), *cb4 = table4(a.cs + (size_t)j * 64 + 16 * w);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 sa = sa4[g], ca = ca4[g], sb = sb4[g], cb = cb4[g];
@@ -151,13 +145,12 @@ __device__ __forceinline__ void shift_v(g_u32 *base, const KvShiftArgs &a, unsig
 
 template <bool kF16>
 __global__ __launch_bounds__(kShiftThreads) void k_kv_shift(const KvShiftArgs a) {
-    const unsigned seg = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
-    const unsigned is_v = seg & 1u, kv = (seg >> 1) % a.n_kv, layer = (seg >> 1) / a.n_kv;
-    g_u32 *base = as_global((is_v ? a.v : a.k)[layer]) + (size_t)kv * a.head_words;
-    if (is_v)
-        shift_v(base, a, kF16 ? 64u : 128u, part);
+    const KvSegment s = kv_segment(blockIdx.x, a.parts, a.n_kv);
+    g_u32 *base = as_global((s.is_v ? a.v : a.k)[s.layer]) + s.base(a.head_words);
+    if (s.is_v)
+        shift_v(base, a, kv_rows(kF16), s.part);
     else
-        shift_k<kF16>(base, a, part);
+        shift_k<kF16>(base, a, s.part);
 }
 
 }  // namespace
@@ -172,14 +165,9 @@ hipError_t launch_kv_shift(void *const *k_ptrs, void *const *v_ptrs, const float
     a.head_words = head_words;
     const size_t moved = n - discard - keep;
     const size_t segments = 2 * n_layers * n_kv;
-    // overlapping ranges: one workgroup per segment (ORDERING above).  Disjoint ranges: about 2048 workgroups in all, no more per segment than K
+    // overlapping ranges: one workgroup per segment, whatever kv_parts would give (ORDERING above).  Disjoint ranges: no more per segment than K
     // has chunks to write (a V tile is 64 rows of an f32 cache, 128 of an f16 one: a V part beyond its last tile leaves at once)
-    a.parts = 1;
-    if (moved <= discard) {
-        const size_t want = segments >= 2048 ? 1 : 2048 / segments;
-        const size_t have = (a.end - 1) / 64 - keep / 64 + 1;
-        a.parts = (unsigned)(want < have ? want : have);
-    }
+    a.parts = moved <= discard ? kv_parts(segments, (a.end - 1) / 64 - keep / 64 + 1) : 1;
     const dim3 grid((unsigned)(segments * a.parts)), block(kShiftThreads);
     if (rows == 64)
         hipLaunchKernelGGL(k_kv_shift<true>, grid, block, 0, stream, a);

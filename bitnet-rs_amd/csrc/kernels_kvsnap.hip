@@ -8,12 +8,9 @@
 //
 // The snapshot, PUBLIC (include/bitnet_hip_kvsnap.h), position-major, in the cache's element type, no padding to 64:
 //   K [n_layers][n_kv][S][128]  then  V [n_layers][n_kv][S][128]
-// The caches, private (kernels_kvfork.hip, kernels_attn.hip), per KV head padded to C = ceil(max_pos / 64) chunks, in 32-bit WORDS, R = 128 words
-// per position for f32 and 64 for f16:
-//   K  [kv][C][R][64]     position-fastest inside a chunk
-//   V  [kv][C * 64][R]    dimension-fastest: the snapshot's own order
-// In words the snapshot is [S][R] per (layer, KV head) for both: an f16 K word of the cache is the (d even, d odd) pair of one position, which is
-// also the word a position-major f16 row holds.  So V is fork's contiguous run copy with another head stride on the snapshot side, and K is a
+// The caches are private (kv_layout.hpp): in 32-bit words, R per position, K [kv][C][R][64] position-fastest inside a chunk and V [kv][C * 64][R]
+// dimension-fastest, the snapshot's own order.  In words the snapshot is [S][R] per (layer, KV head) for both: an f16 K word of the cache is the
+// dim pair of one position, which is also the word a position-major f16 row holds.  So V is fork's contiguous run copy with another head stride on the snapshot side, and K is a
 // [R][64] <-> [64][R] transpose of 32-bit words per chunk, the same code for both types.
 //
 // The K transpose goes through LDS in 64 x 64 word tiles (one chunk is R / 64 tiles), so that BOTH global sides move whole 16-byte vectors, 16
@@ -35,17 +32,11 @@
 // Integer loads and stores throughout: NaN payloads and denormals pass.  Nothing outside the named slots is written: save writes S = n positions;
 // restore writes slots < n only -- in a partial last chunk of K the first n % 64 words of each row, by dword stores as k_kv_fork does.  Cache
 // reads stay inside the padded cache, snapshot reads below position n.
-#include "common.hpp"
+#include "kv_layout.hpp"
 
 namespace bitnet_hip {
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// the cache pointers come out of pointer tables: typed as GLOBAL memory here, or the copy compiles to flat loads and stores
-typedef __attribute__((address_space(1))) unsigned g_u32;
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-__device__ __forceinline__ g_u32 *as_global(const void *p) { return reinterpret_cast<g_u32 *>(reinterpret_cast<uintptr_t>(p)); }
 
 struct KvSnapArgs {
     const void *const *cache_k, *const *cache_v;  // save: [n_layers]; restore: [n_dst][n_layers]
@@ -56,8 +47,8 @@ struct KvSnapArgs {
     size_t n, S;                                  // positions to move (>= 1), positions the snapshot holds (>= n; save: == n)
 };
 
-constexpr int kSnapThreads = 256;
-constexpr int kSnapUnroll = 4;  // 16-byte loads in flight per lane before the first store (V), tile rows per lane (K)
+constexpr int kSnapThreads = kKvCopyThreads;
+constexpr int kSnapUnroll = 4;  // tile rows per lane (K)
 constexpr int kTile = 64;       // the K tile: 64 x 64 words, 16 KB of LDS
 
 // LDS word index of element (destination row q, destination word r) of the tile
@@ -105,36 +96,12 @@ __device__ __forceinline__ void transpose_tile(unsigned *tile, const g_u32 *src,
     }
 }
 
-// a contiguous run of run4 16-byte vectors, every vector loaded once and stored n_dst times (k_kv_fork's loop)
-__device__ __forceinline__ void copy_run(const g_u32 *src, g_u32 *const *dst, unsigned n_dst, size_t run4, unsigned part, unsigned parts) {
-    const size_t stride = (size_t)parts * kSnapThreads;
-    const g_u32x4 *s4 = reinterpret_cast<const g_u32x4 *>(src);
-    size_t i = (size_t)part * kSnapThreads + threadIdx.x;
-    for (; i + (kSnapUnroll - 1) * stride < run4; i += kSnapUnroll * stride) {
-        u32x4 x[kSnapUnroll];
-#pragma unroll
-        for (int u = 0; u < kSnapUnroll; ++u) x[u] = s4[i + u * stride];
-#pragma unroll
-        for (int d = 0; d < kBatchMax; ++d)
-            if ((unsigned)d < n_dst) {
-#pragma unroll
-                for (int u = 0; u < kSnapUnroll; ++u) reinterpret_cast<g_u32x4 *>(dst[d])[i + u * stride] = x[u];
-            }
-    }
-    for (; i < run4; i += stride) {
-        const u32x4 x = s4[i];
-#pragma unroll
-        for (int d = 0; d < kBatchMax; ++d)
-            if ((unsigned)d < n_dst) reinterpret_cast<g_u32x4 *>(dst[d])[i] = x;
-    }
-}
-
 template <bool kRestore>
 __global__ __launch_bounds__(kSnapThreads) void k_kv_snap(const KvSnapArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned tile[kTile * kTile];
-    const unsigned seg = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
-    const unsigned is_v = seg & 1u, kv = (seg >> 1) % a.n_kv, layer = (seg >> 1) / a.n_kv;
-    const size_t base = (size_t)kv * a.head_words;
+    const KvSegment s = kv_segment(blockIdx.x, a.parts, a.n_kv);
+    const unsigned is_v = s.is_v, kv = s.kv, layer = s.layer, part = s.part;
+    const size_t base = s.base(a.head_words);
     // this segment's [S][R] words of the snapshot, and its head in every cache of the call
     g_u32 *snap = as_global(a.snap) + (((size_t)is_v * a.n_layers + layer) * a.n_kv + kv) * a.S * a.rows;
     g_u32 *cache[kBatchMax];
@@ -146,8 +113,8 @@ __global__ __launch_bounds__(kSnapThreads) void k_kv_snap(const KvSnapArgs a) {
 
     if (is_v) {
         const size_t run4 = a.n * (a.rows / 4);
-        if (kRestore) copy_run(snap, cache, a.n_dst, run4, part, a.parts);
-        else copy_run(cache[0], one, 1, run4, part, a.parts);
+        if (kRestore) kv_copy_run(snap, cache, a.n_dst, run4, part, a.parts);
+        else kv_copy_run(cache[0], one, 1, run4, part, a.parts);
         return;
     }
     // K: tile t = (chunk t / per, cache rows 64 * (t % per) ..) <-> (snapshot positions 64 * chunk .., words 64 * (t % per) ..)
@@ -176,12 +143,10 @@ hipError_t launch(const void *const *cache_k, const void *const *cache_v, const 
     a.cache_k = cache_k, a.cache_v = cache_v, a.snap = snap;
     a.n_layers = (unsigned)n_layers, a.n_dst = (unsigned)n_dst, a.n_kv = (unsigned)n_kv, a.rows = (unsigned)rows;
     a.head_words = head_words, a.n = n, a.S = S;
-    // memory-bound, as k_kv_fork: about 2048 workgroups in all, a segment's rest is strided.  One round of a workgroup moves 16 KB on either
-    // side (a K tile, or kSnapUnroll vectors per lane of V); no more parts than V has workgroup-wide vector rows, and at least one.
+    // One round of a workgroup moves 16 KB on either side (a K tile, or kKvCopyUnroll vectors per lane of V); no more parts than V has
+    // workgroup-wide vector rows (K's tiles are strided over the same parts)
     const size_t segments = 2 * n_layers * n_kv;
-    const size_t want = segments >= 2048 ? 1 : 2048 / segments;
-    const size_t have = div_ceil(n * (rows / 4), (size_t)kSnapThreads);  // V's vectors in workgroup-wide rows; K's tiles are strided over the same parts
-    a.parts = (unsigned)(want < have ? want : have);
+    a.parts = kv_parts(segments, div_ceil(n * (rows / 4), (size_t)kSnapThreads));
     hipLaunchKernelGGL(k_kv_snap<kRestore>, dim3((unsigned)(segments * a.parts)), dim3(kSnapThreads), 0, stream, a);
     return hipGetLastError();
 }

@@ -27,11 +27,12 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "kv_layout.hpp"
 #include "wave.hpp"
 
 namespace bitnet_hip {
 
-constexpr int kPD = 128;       // head dim
+constexpr int kPD = kKvDim;    // head dim
 constexpr int kQB = 64;        // keys per tile; query rows come in 64-row blocks (q_block_pos)
 constexpr int kQPad = 128;     // query rows are padded to this (the largest workgroup query tile)
 constexpr int kKTile = kQB * kPD * 2;   // one K tile in LDS: 64 keys x 256 bytes, unpadded; 16-byte unit u of key r sits at u ^ (r & 15)
@@ -158,11 +159,11 @@ __global__ __launch_bounds__(256) void k_prefill_prep(PrefillArgs p) {
     } else if (is_k) {
         const int kvh = slot - p.n_heads;
         store_rows_f16(p.kh + ((size_t)kvh * p.Tpad + t0) * kPD);
-        // decode cache: K transposed in 64-position tiles [chunk][128][64] (kernels_attn.hip); t0 is a tile start
-        const size_t head_floats = (size_t)((p.max_pos + 63) / 64) * 64 * kPD;
-        float *kt = p.kcache + (size_t)kvh * head_floats + (size_t)(t0 >> 6) * kPD * 64;
+        // decode cache (kv_layout.hpp): K in 64-position chunks [chunk][128][64]; t0 is a chunk start
+        const size_t head_floats = kv_head_floats(p.max_pos);
+        float *kt = p.kcache + (size_t)kvh * head_floats + kv_chunk_floats(t0);
         if (p.cache_f16) {  // [chunk][D / 2][64][2] halves
-            _Float16 *k16 = reinterpret_cast<_Float16 *>(p.kcache) + (size_t)kvh * head_floats + (size_t)(t0 >> 6) * kPD * 64;
+            _Float16 *k16 = reinterpret_cast<_Float16 *>(p.kcache) + (size_t)kvh * head_floats + kv_chunk_floats(t0);
             for (int i = 0; i < 32 && p.kcache; ++i) {
                 const int idx = tid + 256 * i, d = idx >> 6, tok = idx & 63;
                 if (t0 + tok < p.T) k16[((size_t)(d >> 1) * 64 + tok) * 2 + (d & 1)] = (_Float16)tile[tok][d];
@@ -180,9 +181,9 @@ __global__ __launch_bounds__(256) void k_prefill_prep(PrefillArgs p) {
         }
     } else {
         const int kvh = slot - p.n_heads - p.n_kv;
-        float *vc = p.vcache + (size_t)kvh * ((size_t)((p.max_pos + 63) / 64) * 64 * kPD);  // [max_pos][128]
+        float *vc = p.vcache + (size_t)kvh * kv_head_floats(p.max_pos);  // [max_pos][128]
         if (p.cache_f16) {
-            _Float16 *v16 = reinterpret_cast<_Float16 *>(p.vcache) + (size_t)kvh * ((size_t)((p.max_pos + 63) / 64) * 64 * kPD);
+            _Float16 *v16 = reinterpret_cast<_Float16 *>(p.vcache) + (size_t)kvh * kv_head_floats(p.max_pos);
             for (int i = 0; i < 32 && p.vcache; ++i) {
                 const int idx = tid + 256 * i, tok = idx >> 7, d = idx & 127;
                 if (t0 + tok < p.T) v16[(size_t)(t0 + tok) * kPD + d] = (_Float16)tile[tok][d];
@@ -847,7 +848,7 @@ __device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float 
     const int dp = p.past - t0, dl = p.T - t0;
     const int n_past = dp < 0 ? 0 : dp > kQB ? kQB : dp;  // tile rows [0, n_past) come from the cache,
     const int n_live = dl > kQB ? kQB : dl;               // [n_past, n_live) from the new rows, [n_live, 64) are zeros
-    const size_t head_elems = (size_t)((p.max_pos + 63) / 64) * 64 * kPD;
+    const size_t head_elems = kv_head_floats(p.max_pos);
     float *c32 = static_cast<float *>(is_k ? p.kcache : p.vcache) + (size_t)kvh * head_elems;
     _Float16 *c16 = static_cast<_Float16 *>(is_k ? p.kcache : p.vcache) + (size_t)kvh * head_elems;
     if (n_past < kQB) {
@@ -866,7 +867,7 @@ __device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float 
     }
     if (n_past > 0) {
         if (is_k && !p.cache_f16) {  // [chunk][128][64]: 4 adjacent positions of one dim
-            const float *kt = c32 + (size_t)(t0 >> 6) * kPD * 64;
+            const float *kt = c32 + kv_chunk_floats(t0);
             for (int i = 0; i < 8; ++i) {
                 const int idx = tid + 256 * i, d = idx >> 4, tok = (idx & 15) * 4;
                 if (tok >= n_past) continue;
@@ -877,7 +878,7 @@ __device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float 
                     if (tok + j < n_past) tile[tok + j][d] = e[j];
             }
         } else if (is_k) {  // [chunk][D / 2][64][2]: a dim pair of 2 adjacent positions
-            const _Float16 *k16 = c16 + (size_t)(t0 >> 6) * kPD * 64;
+            const _Float16 *k16 = c16 + kv_chunk_floats(t0);
             for (int i = 0; i < 8; ++i) {
                 const int idx = tid + 256 * i, d2 = idx >> 5, tok = (idx & 31) * 2;
                 if (tok >= n_past) continue;
@@ -918,7 +919,7 @@ __device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float 
     // ---- append the new positions to the decode cache ----
     if (n_past < n_live) {
         if (is_k && !p.cache_f16) {
-            float *kt = c32 + (size_t)(t0 >> 6) * kPD * 64;
+            float *kt = c32 + kv_chunk_floats(t0);
             for (int i = 0; i < 8; ++i) {
                 const int idx = tid + 256 * i, d = idx >> 4, tok = (idx & 15) * 4;
                 if (tok >= n_past && tok + 3 < n_live) {
@@ -929,7 +930,7 @@ __device__ __forceinline__ void extend_prep_tile(const ExtendPrepArgs &p, float 
                 }
             }
         } else if (is_k) {
-            _Float16 *k16 = c16 + (size_t)(t0 >> 6) * kPD * 64;
+            _Float16 *k16 = c16 + kv_chunk_floats(t0);
             for (int i = 0; i < 8; ++i) {
                 const int idx = tid + 256 * i, d2 = idx >> 5, tok = (idx & 31) * 2;
                 const bool lo = tok >= n_past && tok < n_live, hi = tok + 1 >= n_past && tok + 1 < n_live;

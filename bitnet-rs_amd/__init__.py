@@ -28,6 +28,7 @@ HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip.h")
 GRAMMAR_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar.h")  # included by HEADER_PATH: the grammar stage's six entry points
 KVSNAP_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")  # included by HEADER_PATH: the KV snapshot's three entry points
 BEAM_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_beam.h")  # included by HEADER_PATH: beam search, the select and permute launches and their state
+SCORETOPN_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_scoretopn.h")  # included by HEADER_PATH: prompt top-N, two entry points
 WIDETAIL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_widetail.h")  # included by HEADER_PATH: the wide step's 64-entry tail tables, two
 
 OK = 0
@@ -125,6 +126,7 @@ class HipLib:
         cproto.bind(self.c, kvsnap_prototypes(), C_STRUCTS)
         cproto.bind(self.c, widetail_prototypes(), C_STRUCTS)
         cproto.bind(self.c, beam_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, scoretopn_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -630,6 +632,17 @@ class HipLib:
         nll[r] = logsumexp(l_r) - l_r[targets[r]], argmax[r], and the raw logits of rows < logits_rows.  Device pointers / tensors."""
         self._check(self.c.bitnet_hip_score_f16_dev(_optr(table), _optr(x), _optr(gamma), eps, hidden, vocab, n_rows, _optr(targets), _optr(nll),
                                                     _optr(argmax), _optr(logits), logits_rows, _optr(workspace), workspace_bytes, _vp(stream)))
+
+    def score_topn_workspace_bytes(self, n_rows: int, hidden: int, vocab: int) -> int:
+        """Workspace of score_topn_f16_dev: the score workspace plus 36 bytes per (padded row, vocabulary block); 0 where that one is 0."""
+        return int(self.c.bitnet_hip_score_topn_workspace_bytes(n_rows, hidden, vocab))
+
+    def score_topn_f16_dev(self, table, x, gamma, eps: float, hidden: int, vocab: int, n_rows: int, targets, nll, argmax=None, records=None,
+                           top_n: int = 0, workspace=None, workspace_bytes: int = 0, stream: int = 0) -> None:
+        """score_f16_dev with the exact top_n (id, logit) pairs of every row and no logits buffer (include/bitnet_hip.h
+        bitnet_hip_score_topn_f16_dev): records is device memory for n_rows bitnet_hip_logprob_record (LOGPROB_DTYPE)."""
+        self._check(self.c.bitnet_hip_score_topn_f16_dev(_optr(table), _optr(x), _optr(gamma), eps, hidden, vocab, n_rows, _optr(targets), _optr(nll),
+                                                         _optr(argmax), _optr(records), top_n, _optr(workspace), workspace_bytes, _vp(stream)))
 
     def head_screen_bytes(self, hidden: int, vocab: int) -> int:
         """bytes of the screening image of a [vocab, hidden] f16 table; 0: no screened head for this hidden size"""
@@ -1217,10 +1230,15 @@ def widetail_prototypes() -> list:
     return cproto.prototypes(open(WIDETAIL_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def scoretopn_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_scoretopn.h, the header include/bitnet_hip.h includes for prompt top-N."""
+    return cproto.prototypes(open(SCORETOPN_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
     return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + kvsnap_prototypes()
-                   + widetail_prototypes() + beam_prototypes()})
+                   + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -1230,6 +1248,7 @@ def declared_symbols() -> list[str]:
 HOST_LIB_PATH = os.path.join(HERE, "libbitnet_host.so")
 HOST_HEADER_PATHS = [os.path.join(HERE, "host", f) for f in ("decoder.hpp", "batch_decoder.hpp", "gguf.hpp")]
 HOST_GRAMMAR_HEADER_PATH = os.path.join(HERE, "host", "grammar_host.hpp")  # the decoder's grammar control, bound beside the others
+HOST_SCORETOPN_HEADER_PATH = os.path.join(HERE, "host", "score_topn_host.hpp")  # Decoder::score_topn, bound beside the others
 HOST_PREFIX_HEADER_PATH = os.path.join(HERE, "host", "prefix_cache.hpp")  # PrefixCache and Decoder::prefill_cached, bound beside the others
 HOST_WIDE_HEADER_PATH = os.path.join(HERE, "host", "wide_batch.hpp")  # WideBatch, bound beside the others
 HOST_BEAM_HEADER_PATH = os.path.join(HERE, "host", "beam_search.hpp")  # BeamSearch, bound beside the others
@@ -1244,6 +1263,11 @@ def host_prototypes() -> list:
 def host_grammar_prototypes() -> list:
     """The three exports of host/grammar_host.hpp (Decoder::set_grammar, set_grammar_state, grammar_state), typed at load like the rest."""
     return cproto.prototypes(open(HOST_GRAMMAR_HEADER_PATH).read(), "bitnet_host_")
+
+
+def host_scoretopn_prototypes() -> list:
+    """The export of host/score_topn_host.hpp (Decoder::score_topn), typed at load like the rest."""
+    return cproto.prototypes(open(HOST_SCORETOPN_HEADER_PATH).read(), "bitnet_host_")
 
 
 def host_prefix_prototypes() -> list:
@@ -1270,6 +1294,7 @@ def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
         cproto.bind(L, host_prefix_prototypes(), C_STRUCTS)
         cproto.bind(L, host_wide_prototypes(), C_STRUCTS)
         cproto.bind(L, host_beam_prototypes(), C_STRUCTS)
+        cproto.bind(L, host_scoretopn_prototypes(), C_STRUCTS)
         _host_libs[path] = L
     return _host_libs[path]
 
@@ -1401,6 +1426,7 @@ class HostDecoder:
         self.cfg = cfg
         self._top_n = -1  # set_logprobs
         self._fed = 0  # tokens fed since the last reset (the default n of score)
+        self.last_score_topn_ms = 0.0  # prefill + head of the last score_topn
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
         self.h = L.bitnet_host_create(C.byref(hc)) if _owner is None else L.bitnet_host_create_shared(_owner.h)
         if not self.h:
@@ -1788,6 +1814,23 @@ class HostDecoder:
                                              lg.ctypes.data_as(_f32p) if lg is not None else None, logits_rows, C.byref(ms)))
         return ScoreResult(nll, am, lg, ms.value)
 
+    def score_topn(self, tokens_or_n=None, top_n: int = LOGPROB_TOP_MAX) -> np.ndarray:
+        """Prompt log-probabilities: score() whose head also leaves the exact top_n (id, logit) pairs of every row, with no [n, vocab] logits
+        anywhere.  tokens_or_n: a token list (reset, feed, score all of it), a count n of fed tokens, or None (all fed tokens).  Returns n
+        records of LOGPROB_DTYPE, the layout logprob_records() returns: record r holds token r + 1 of the prompt (-1 in the last), its raw
+        logit, the row's lse (logprob = logit - lse), n_top and the top list (larger logit first, lower id on ties).  The decoder ends
+        where score() leaves it; last_score_topn_ms is prefill + head."""
+        if tokens_or_n is not None and not isinstance(tokens_or_n, (int, np.integer)):
+            self.reset()
+            self.feed(tokens_or_n)
+            tokens_or_n = None
+        n = self._fed if tokens_or_n is None else int(tokens_or_n)
+        out = np.zeros(max(n, 0), LOGPROB_DTYPE)
+        ms = C.c_float(0)
+        self._check(_host_fn(self.c, "bitnet_host_score_topn")(self.h, n, 2, int(top_n), out.ctypes.data_as(C.c_void_p), None, C.byref(ms)))
+        self.last_score_topn_ms = ms.value
+        return out
+
     def last_prefill_path(self) -> int:
         """What the last prefill() ran: 0 digit planes (+ f16 hand-over / hybrid o / down), 1 the f16 chain, 2 the QB32 chain."""
         return int(self.c.bitnet_host_last_prefill_path(self.h))
@@ -1833,7 +1876,7 @@ class HostDecoder:
 
 
 def _host_fn(host: C.CDLL, name: str):
-    """An export of host/grammar_host.hpp, host/wide_batch.hpp or host/beam_search.hpp on the bound host library.  By name, as _prefix_fn:
+    """An export of host/grammar_host.hpp, host/wide_batch.hpp, host/beam_search.hpp or host/score_topn_host.hpp on the bound host library.  By name, as _prefix_fn:
     these are typed from THOSE headers at load (host_grammar_prototypes, host_wide_prototypes, host_beam_prototypes), not from the three
     headers host_prototypes() reads."""
     return getattr(host, name)

@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "select.hpp"
 #include "wave.hpp"
 
 namespace bitnet_hip {
@@ -70,6 +71,51 @@ __global__ __launch_bounds__(256) void k_score_rows_f16(const float *__restrict_
     for (int i = tid; i < hidden; i += 256) ar[i] = (_Float16)(gamma ? (xr[i] - mean) / denom * gamma[i] : xr[i]);
 }
 
+// ---- the head's inner product, shared by k_score_head and the escape of k_score_topn ------------------------------------------------
+// One logit is a chain of v_mfma_f32_16x16x32_f16 on one accumulator: K steps of 64 columns in ascending order, two halves per step, and in
+// half kk lane group g (lane >> 4) feeds the 8 columns of 16-byte unit sc_kunit(kk, g) of the step.  Vocabulary rows are the A operand
+// (row = its index mod 16), token rows the B operand.  Both kernels go through these two functions, so a recomputed logit has the head's bits.
+__device__ __forceinline__ int sc_kunit(int kk, int g) { return 4 * kk + g; }
+
+template <int RT, int CT>
+__device__ __forceinline__ void sc_mma(v4f (&acc)[RT][CT], const h8 (&af)[RT], const h8 (&bf)[CT]) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rt], bf[ct], acc[rt][ct], 0, 0, 0);
+}
+
+// ---- the top-K epilogue's lists ----------------------------------------------------------------------------------------------------
+// An entry is one u64: the order-preserving key of the logit (select.hpp fkey, NaN read as -inf) above 0x7fffffff - id, so a larger
+// u64 is the better entry in the project's order (larger value, lower id on equal values).  0 = no entry (below every real one: a
+// real key is >= fkey(-inf) > 0).  A list holds the kSTopK best entries in descending order and, in its last place, the next one: the
+// certificate.  DESIGN.md "Prompt top-N" has the choice of K.
+constexpr int kSTopK = 4;
+constexpr int kSList = kSTopK + 1;
+static_assert(kSList == 5, "sc_list_merge sorts with the 5-input network");
+
+__device__ __forceinline__ uint64_t sc_entry(float l, int v) {
+    return ((uint64_t)fkey(l != l ? -INFINITY : l) << 32) | (uint32_t)(0x7fffffff - v);
+}
+__device__ __forceinline__ void sc_cswap(uint64_t &hi, uint64_t &lo) {
+    const uint64_t a = hi, b = lo;
+    hi = a > b ? a : b;
+    lo = a > b ? b : a;
+}
+// sorted insertion: x sinks through the list, the smallest falls off the end
+__device__ __forceinline__ void sc_list_insert(uint64_t (&L)[kSList], uint64_t x) {
+#pragma unroll
+    for (int i = 0; i < kSList; ++i) sc_cswap(L[i], x);
+}
+// L <- the 5 best of L and O (both descending): max(L[i], O[4 - i]) is that set (the half-cleaner of a bitonic merge), then the
+// 9-comparator sorting network for 5 inputs puts it in order.  A fixed sequence of compares: the same bits on every run.
+__device__ __forceinline__ void sc_list_merge(uint64_t (&L)[kSList], const uint64_t (&O)[kSList]) {
+#pragma unroll
+    for (int i = 0; i < kSList; ++i) L[i] = L[i] > O[kSList - 1 - i] ? L[i] : O[kSList - 1 - i];
+    sc_cswap(L[0], L[1]), sc_cswap(L[3], L[4]), sc_cswap(L[2], L[4]), sc_cswap(L[2], L[3]), sc_cswap(L[1], L[4]);
+    sc_cswap(L[0], L[3]), sc_cswap(L[0], L[2]), sc_cswap(L[1], L[3]), sc_cswap(L[1], L[2]);
+}
+
 struct ScoreArgs {
     const _Float16 *table;  // [vocab, hidden]
     const _Float16 *a;      // [n_pad, hidden]
@@ -80,11 +126,20 @@ struct ScoreArgs {
     int hidden, vocab, n_rows, logits_rows, vb_count, tb_count;
 };
 
+// what the kTopK instance leaves beside the partials (k_score_head's own arguments stay as they were)
+struct TopkOut {
+    uint32_t *ckey;  // [n_pad][vb_count][kSTopK] candidate keys (0: none), descending per block ...
+    int32_t *cid;    // ... their ids (-1: none)
+    uint32_t *cert;  // ... and [n_pad][vb_count] the key of the block's next best entry (0: the block has no more)
+};
+
 __device__ __forceinline__ void sc_glds(const uint8_t *src, uint8_t *lds_dst) {
     __builtin_amdgcn_global_load_lds((glb_void_t *)src, (lds_void_t *)lds_dst, 16, 0, 0);
 }
 
-__global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
+// the body of k_score_head (kTopK false: as it always was) and of k_topn_head (kTopK true: the same pass also leaves each block's list)
+template <bool kTopK>
+__device__ __forceinline__ void score_head_body(const ScoreArgs &p, const TopkOut &tk) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kSLds];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, g = lane >> 4, wv = wave & 1, wt = wave >> 1;
@@ -118,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
     int off_e[2], off_a[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const int u = ((4 * kk + g) ^ ((c >> 1) & 7)) * 16;
+        const int u = (sc_kunit(kk, g) ^ ((c >> 1) & 7)) * 16;
         off_e[kk] = (wv * 64 + c) * 128 + u;
         off_a[kk] = (wt * 64 + c) * 128 + u;
     }
@@ -141,15 +196,13 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
             for (int rt = 0; rt < 4; ++rt) af[rt] = *reinterpret_cast<const h8 *>(eb + off_e[kk] + rt * 16 * 128);
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) bf[ct] = *reinterpret_cast<const h8 *>(ab + off_a[kk] + ct * 16 * 128);
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rt], bf[ct], acc[rt][ct], 0, 0, 0);
+            sc_mma(acc, af, bf);
         }
     }
     // epilogue: acc[rt][ct][j] = logit of vocabulary row v0 + 64 wv + 16 rt + 4 g + j, token t0 + 64 wt + 16 ct + c
     float pm[4], ps[4], pv[4];
     int pi[4];
+    uint64_t pl[kTopK ? 4 : 1][kSList];  // kTopK: per token the list of this wave's 64 vocabulary rows
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
         const int token = t0 + wt * 64 + ct * 16 + c;
@@ -194,13 +247,40 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
             if (sc_better(ov, oi, bv, bi)) bv = ov, bi = oi;
         }
         pm[ct] = m, ps[ct] = s, pv[ct] = bv, pi[ct] = bi;
+        if constexpr (kTopK) {
+            // the lane's 16 rows by insertion, then the four lane groups: g ^ 1, then g ^ 2 (disjoint rows at every merge)
+            uint64_t(&L)[kSList] = pl[ct];
+#pragma unroll
+            for (int i = 0; i < kSList; ++i) L[i] = 0;
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int v = v0 + wv * 64 + rt * 16 + 4 * g + j;
+                    sc_list_insert(L, v < p.vocab ? sc_entry(acc[rt][ct][j], v) : 0);
+                }
+#pragma unroll
+            for (int off = 16; off <= 32; off <<= 1) {
+                uint64_t o[kSList];
+#pragma unroll
+                for (int i = 0; i < kSList; ++i) o[i] = __shfl_xor((unsigned long long)L[i], off, 64);
+                sc_list_merge(L, o);
+            }
+        }
     }
     // merge the two vocabulary halves of the block (wave column wv = 0 holds the lower indices) and write one partial per token
     __syncthreads();  // every wave is done with the staged tiles
     v4f *xch = reinterpret_cast<v4f *>(lds);  // [wt][64 tokens]
+    uint64_t *xls = reinterpret_cast<uint64_t *>(lds + 2 * kST * sizeof(v4f));  // kTopK: [wt][64 tokens][kSList], behind xch
     if (wv == 1 && g == 0) {
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) xch[wt * 64 + ct * 16 + c] = (v4f){pm[ct], ps[ct], pv[ct], __int_as_float(pi[ct])};
+        for (int ct = 0; ct < 4; ++ct) {
+            xch[wt * 64 + ct * 16 + c] = (v4f){pm[ct], ps[ct], pv[ct], __int_as_float(pi[ct])};
+            if constexpr (kTopK) {
+#pragma unroll
+                for (int i = 0; i < kSList; ++i) xls[(wt * 64 + ct * 16 + c) * kSList + i] = pl[ct][i];
+            }
+        }
     }
     __syncthreads();
     if (wv == 0 && g == 0) {
@@ -214,13 +294,36 @@ __global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) {
             sc_merge(m, s, o.x, o.y);
             if (sc_better(o.z, __float_as_int(o.w), bv, bi)) bv = o.z, bi = __float_as_int(o.w);
             p.part[(size_t)token * p.vb_count + vb] = (v4f){m, s, bv, __int_as_float(bi)};
+            if constexpr (kTopK) {
+                uint64_t(&L)[kSList] = pl[ct];
+                uint64_t o[kSList];
+#pragma unroll
+                for (int i = 0; i < kSList; ++i) o[i] = xls[(wt * 64 + ct * 16 + c) * kSList + i];
+                sc_list_merge(L, o);
+                const size_t slot = (size_t)token * p.vb_count + vb;
+                uint32_t *ck = tk.ckey + slot * kSTopK;
+                int32_t *ci = tk.cid + slot * kSTopK;
+#pragma unroll
+                for (int i = 0; i < kSTopK; ++i) {
+                    ck[i] = (uint32_t)(L[i] >> 32);
+                    ci[i] = L[i] ? 0x7fffffff - (int32_t)(uint32_t)L[i] : -1;
+                }
+                tk.cert[slot] = (uint32_t)(L[kSTopK] >> 32);
+            }
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_score_combine(const v4f *__restrict__ part, const float *__restrict__ tlog,
-                                                       const int32_t *__restrict__ targets, int vb_count, int vocab, float *__restrict__ nll,
-                                                       int32_t *__restrict__ argmax) {
+__global__ __launch_bounds__(256, 2) void k_score_head(ScoreArgs p) { score_head_body<false>(p, TopkOut{}); }
+__global__ __launch_bounds__(256, 2) void k_topn_head(ScoreArgs p, TopkOut tk) { score_head_body<true>(p, tk); }
+
+using ScoreRecord = bitnet_hip_logprob_record;
+
+// the body of k_score_combine (kRec false) and of k_topn_combine (kRec true: the row's record gets its token, logit and lse from the same values)
+template <bool kRec>
+__device__ __forceinline__ void score_combine_body(const v4f *__restrict__ part, const float *__restrict__ tlog, const int32_t *__restrict__ targets,
+                                                   int vb_count, int vocab, float *__restrict__ nll, int32_t *__restrict__ argmax,
+                                                   ScoreRecord *__restrict__ rec) {
     __shared__ float sm[256], ss[256], sv[256];
     __shared__ int si[256];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -256,8 +359,132 @@ __global__ __launch_bounds__(256) void k_score_combine(const v4f *__restrict__ p
         }
         nll[row] = r;
         if (argmax) argmax[row] = si[0] == 0x7fffffff ? 0 : si[0];
+        if constexpr (kRec) {
+            rec[row].token = t < 0 ? -1 : t;
+            rec[row].logit = t >= 0 && t < vocab ? tlog[row] : NAN;
+            rec[row].lse = sm[0] == -INFINITY ? NAN : sm[0] + logf(ss[0]);
+        }
     }
 }
+
+__global__ __launch_bounds__(256) void k_score_combine(const v4f *__restrict__ part, const float *__restrict__ tlog,
+                                                       const int32_t *__restrict__ targets, int vb_count, int vocab, float *__restrict__ nll,
+                                                       int32_t *__restrict__ argmax) {
+    score_combine_body<false>(part, tlog, targets, vb_count, vocab, nll, argmax, nullptr);
+}
+__global__ __launch_bounds__(256) void k_topn_combine(const v4f *__restrict__ part, const float *__restrict__ tlog, const int32_t *__restrict__ targets,
+                                                      int vb_count, int vocab, float *__restrict__ nll, int32_t *__restrict__ argmax,
+                                                      ScoreRecord *__restrict__ rec) {
+    score_combine_body<true>(part, tlog, targets, vb_count, vocab, nll, argmax, rec);
+}
+
+// ---- k_score_topn: one workgroup of kNT threads per prompt row ---------------------------------------------------------------------
+//   select   the n_top best of the row's vb_count x kSTopK candidates: select.hpp's radix select on the keys where they lie (array order
+//            is id order among equal keys: blocks ascend, and inside a block equal keys ascend by id), kept into a pool in LDS.
+//   certify  T = the n_top-th best candidate key (0 when there are not that many) is a lower bound of the row's n_top-th best logit; a
+//            block whose certificate is a real key >= T may hide a member (>=: an equal value with a lower id displaces).
+//   escape   per suspect block, in block order: the 8 waves recompute its 128 logits (one 16-row tile each, sc_mma / sc_kunit: the head's
+//            bits, every B column the row), the pool's entries of that block are dropped (the recompute holds them again), and the
+//            n_top + 128 entries are ranked by counting -- (key, id) is a total order, so every entry has its own rank.
+// A last ranking orders the pool; unused places of the record are (-1, 0).  Comparisons and the head's own arithmetic only: exact.
+struct TopnArgs {
+    const _Float16 *table, *a;
+    const uint32_t *ckey;
+    const int32_t *cid;
+    const uint32_t *cert;
+    ScoreRecord *rec;
+    int hidden, vocab, vb_count, top_n;
+};
+
+constexpr int kTopMax = BITNET_HIP_LOGPROB_TOP_MAX;
+constexpr int kPool = kTopMax + kSV;
+constexpr int kNoId = 0x7fffffff;
+
+__global__ __launch_bounds__(kNT) void k_score_topn(TopnArgs p) {
+    __shared__ uint32_t hist[256], bc[2], tmp[16], list[kNT];
+    __shared__ uint32_t uk[2][kPool];
+    __shared__ int32_t ui[2][kPool];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c = lane & 15, g = lane >> 4;
+    const int row = blockIdx.x, n_top = min(p.top_n, p.vocab), ncand = p.vb_count * kSTopK;
+    const uint32_t *keys = p.ckey + (size_t)row * ncand;
+    const int32_t *ids = p.cid + (size_t)row * ncand;
+    const uint32_t *cert = p.cert + (size_t)row * p.vb_count;
+    ScoreRecord *rec = p.rec + row;
+    int cur = 0;
+    if (tid < n_top) uk[0][tid] = 0, ui[0][tid] = kNoId;
+    __syncthreads();
+    uint32_t T = 0;
+    int r = ncand;  // n_top or fewer candidates: all of them, and no bound
+    if (ncand > n_top) block_select(keys, ncand, n_top, hist, bc, &T, &r);
+    block_keep(keys, ncand, T, r, tmp, [&](int i, uint32_t slot) {
+        uk[0][slot] = keys[i];
+        ui[0][slot] = ids[i] < 0 ? kNoId : ids[i];
+    });
+    __syncthreads();
+    const int nk = p.hidden / kSK, np = n_top + kSV;
+    for (int b0 = 0; b0 < p.vb_count; b0 += kNT) {
+        uint32_t f = 0, tot;
+        if (b0 + tid < p.vb_count) {
+            const uint32_t cv = cert[b0 + tid];
+            f = cv != 0 && cv >= T;
+        }
+        const uint32_t slot = block_excl_scan(f, tmp, &tot);
+        if (f) list[slot] = (uint32_t)(b0 + tid);
+        __syncthreads();
+        for (int q = 0; q < (int)tot; ++q) {
+            const int v0 = (int)list[q] * kSV;
+            {  // wave w: rows v0 + 16 w .. + 15, lane (c, g) feeds row c (rows past the vocabulary re-read the last one, masked below)
+                const int vr = min(v0 + 16 * wave + c, p.vocab - 1);
+                const h8 *er = reinterpret_cast<const h8 *>(p.table + (size_t)vr * p.hidden);
+                const h8 *ar = reinterpret_cast<const h8 *>(p.a + (size_t)row * p.hidden);
+                v4f acc[1][1] = {{(v4f){0.f, 0.f, 0.f, 0.f}}};
+                for (int ks = 0; ks < nk; ++ks)
+#pragma unroll
+                    for (int kk = 0; kk < 2; ++kk) {
+                        const h8 af[1] = {er[ks * 8 + sc_kunit(kk, g)]}, bf[1] = {ar[ks * 8 + sc_kunit(kk, g)]};
+                        sc_mma(acc, af, bf);
+                    }
+                if (c == 0) {  // acc[j]: row 4 g + j of the tile (the same in every column)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int o = 16 * wave + 4 * g + j, v = v0 + o;
+                        const uint64_t e = v < p.vocab ? sc_entry(acc[0][0][j], v) : 0;
+                        uk[cur][n_top + o] = (uint32_t)(e >> 32);
+                        ui[cur][n_top + o] = e ? v : kNoId;
+                    }
+                }
+            }
+            if (tid < n_top && ui[cur][tid] >= v0 && ui[cur][tid] < v0 + kSV) uk[cur][tid] = 0, ui[cur][tid] = kNoId;
+            __syncthreads();
+            if (tid < np) {
+                const uint32_t k = uk[cur][tid];
+                const int id = ui[cur][tid];
+                int rank = 0;
+                for (int u = 0; u < np; ++u) {
+                    const uint32_t ku = uk[cur][u];
+                    const int iu = ui[cur][u];
+                    rank += ku > k || (ku == k && (iu < id || (iu == id && u < tid)));
+                }
+                if (rank < n_top) uk[cur ^ 1][rank] = k, ui[cur ^ 1][rank] = id;
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+    }
+    if (tid == 0) rec->n_top = n_top;
+    if (tid < n_top) {  // the pool in order: (key descending, id ascending); the place among equal no-entries does not matter
+        const uint32_t k = uk[cur][tid];
+        const int id = ui[cur][tid];
+        int rank = 0;
+        for (int u = 0; u < n_top; ++u) rank += uk[cur][u] > k || (uk[cur][u] == k && (ui[cur][u] < id || (ui[cur][u] == id && u < tid)));
+        rec->top_id[rank] = id == kNoId ? -1 : id;
+        rec->top_logit[rank] = kval(k);
+    } else if (tid < kTopMax) {
+        rec->top_id[tid] = -1;
+        rec->top_logit[tid] = 0.0f;
+    }
+}
+
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -269,6 +496,72 @@ size_t score_ws_bytes(size_t n_rows, size_t hidden, size_t vocab) {
     if (__builtin_mul_overflow(n_pad, vbc, &pt) || __builtin_mul_overflow(pt, (size_t)16, &pt)) return 0;
     if (__builtin_add_overflow(align256(a), align256(n_pad * 4), &tot) || __builtin_add_overflow(tot, pt, &tot)) return 0;
     return tot;
+}
+
+// the top-N entry's workspace: the score workspace | candidate keys [n_pad][vb_count][kSTopK] u32 | their ids, i32 | certificates
+// [n_pad][vb_count] u32
+size_t topn_extra_bytes(size_t n_rows, size_t vocab) {
+    size_t e = 0;
+    if (__builtin_mul_overflow(div_ceil(n_rows, kST) * kST, div_ceil(vocab, kSV), &e) || __builtin_mul_overflow(e, (size_t)(kSTopK * 8 + 4), &e)) return 0;
+    return e;
+}
+
+// both entries: the refusals, the workspace layout, the launches.  records_dev null: bitnet_hip_score_f16_dev, launch for launch as before.
+int score_launch(const char *who, const void *table_f16_dev, const float *x_dev, const float *gamma_dev, float eps, size_t hidden, size_t vocab,
+                 size_t n_rows, const int32_t *targets_dev, float *nll_dev, int32_t *argmax_dev, float *logits_dev, size_t logits_rows,
+                 ScoreRecord *records_dev, size_t top_n, size_t need, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (hidden == 0 || hidden % kSK != 0)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: hidden must be a positive multiple of 64, got %zu", who, hidden);
+    if (vocab == 0 || n_rows == 0)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: dimensions must be > 0: vocab=%zu, n_rows=%zu", who, vocab, n_rows);
+    if (logits_rows > n_rows)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: logits_rows %zu > n_rows %zu", who, logits_rows, n_rows);
+    size_t dump = 0;
+    const size_t grid = need ? div_ceil(n_rows, kST) * div_ceil(vocab, kSV) : 0;  // need 0: a product overflows
+    if (need == 0 || __builtin_mul_overflow(logits_rows, vocab, &dump) || __builtin_mul_overflow(dump, (size_t)4, &dump) || grid >= (1u << 31))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: dimensions too large for this library (n_rows=%zu, hidden=%zu, vocab=%zu)", who,
+                         n_rows, hidden, vocab);
+    if (workspace_bytes < need)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: workspace too small: %zu bytes needed, %zu given", who, need, workspace_bytes);
+    const size_t n_pad = div_ceil(n_rows, kST) * kST, vbc = div_ceil(vocab, kSV);
+    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);
+    ScoreArgs a;
+    a.table = static_cast<const _Float16 *>(table_f16_dev);
+    a.a = reinterpret_cast<const _Float16 *>(ws);
+    a.tlog = reinterpret_cast<float *>(ws + align256(n_pad * hidden * 2));
+    a.part = reinterpret_cast<v4f *>(ws + align256(n_pad * hidden * 2) + align256(n_pad * 4));
+    uint8_t *extra = ws + score_ws_bytes(n_rows, hidden, vocab);
+    TopkOut tk;
+    tk.ckey = reinterpret_cast<uint32_t *>(extra);
+    tk.cid = reinterpret_cast<int32_t *>(extra + n_pad * vbc * kSTopK * 4);
+    tk.cert = reinterpret_cast<uint32_t *>(extra + n_pad * vbc * kSTopK * 8);
+    a.targets = targets_dev;
+    a.logits = logits_rows ? logits_dev : nullptr;
+    a.hidden = (int)hidden, a.vocab = (int)vocab, a.n_rows = (int)n_rows, a.logits_rows = (int)logits_rows;
+    a.vb_count = (int)vbc, a.tb_count = (int)(n_pad / kST);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_score_rows_f16, dim3((unsigned)n_pad), dim3(256), 0, s, x_dev, gamma_dev, eps, (int)hidden, (int)n_rows,
+                       reinterpret_cast<_Float16 *>(ws));
+    BH_HIP_TRY(hipGetLastError());
+    if (!records_dev) {
+        hipLaunchKernelGGL(k_score_head, dim3((unsigned)grid), dim3(256), 0, s, a);
+        BH_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_score_combine, dim3((unsigned)n_rows), dim3(256), 0, s, a.part, a.tlog, targets_dev, (int)vbc, (int)vocab, nll_dev,
+                           argmax_dev);
+        BH_HIP_TRY(hipGetLastError());
+        return BITNET_HIP_OK;
+    }
+    hipLaunchKernelGGL(k_topn_head, dim3((unsigned)grid), dim3(256), 0, s, a, tk);
+    BH_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_topn_combine, dim3((unsigned)n_rows), dim3(256), 0, s, a.part, a.tlog, targets_dev, (int)vbc, (int)vocab, nll_dev,
+                       argmax_dev, records_dev);
+    BH_HIP_TRY(hipGetLastError());
+    TopnArgs t;
+    t.table = a.table, t.a = a.a, t.ckey = tk.ckey, t.cid = tk.cid, t.cert = tk.cert, t.rec = records_dev;
+    t.hidden = (int)hidden, t.vocab = (int)vocab, t.vb_count = (int)vbc, t.top_n = (int)top_n;
+    hipLaunchKernelGGL(k_score_topn, dim3((unsigned)n_rows), dim3(kNT), 0, s, t);
+    BH_HIP_TRY(hipGetLastError());
+    return BITNET_HIP_OK;
 }
 
 }  // namespace
@@ -288,41 +581,26 @@ int bitnet_hip_score_f16_dev(const void *table_f16_dev, const float *x_dev, cons
                              size_t logits_rows, void *workspace_dev, size_t workspace_bytes, void *stream) {
     if (!table_f16_dev || !x_dev || !targets_dev || !nll_dev || !workspace_dev || (logits_rows && !logits_dev))
         return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to score_f16_dev");
-    if (hidden == 0 || hidden % kSK != 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "score_f16_dev: hidden must be a positive multiple of 64, got %zu", hidden);
-    if (vocab == 0 || n_rows == 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "score_f16_dev: dimensions must be > 0: vocab=%zu, n_rows=%zu", vocab, n_rows);
-    if (logits_rows > n_rows)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "score_f16_dev: logits_rows %zu > n_rows %zu", logits_rows, n_rows);
-    size_t dump = 0;
-    const size_t need = bitnet_hip_score_workspace_bytes(n_rows, hidden, vocab);  // 0: a product overflows
-    const size_t grid = need ? div_ceil(n_rows, kST) * div_ceil(vocab, kSV) : 0;
-    if (need == 0 || __builtin_mul_overflow(logits_rows, vocab, &dump) || __builtin_mul_overflow(dump, (size_t)4, &dump) || grid >= (1u << 31))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "score_f16_dev: dimensions too large for this library (n_rows=%zu, hidden=%zu, vocab=%zu)",
-                         n_rows, hidden, vocab);
-    if (workspace_bytes < need)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "score_f16_dev: workspace too small: %zu bytes needed, %zu given", need, workspace_bytes);
-    const size_t n_pad = div_ceil(n_rows, kST) * kST, vbc = div_ceil(vocab, kSV);
-    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);
-    ScoreArgs a;
-    a.table = static_cast<const _Float16 *>(table_f16_dev);
-    a.a = reinterpret_cast<const _Float16 *>(ws);
-    a.tlog = reinterpret_cast<float *>(ws + align256(n_pad * hidden * 2));
-    a.part = reinterpret_cast<v4f *>(ws + align256(n_pad * hidden * 2) + align256(n_pad * 4));
-    a.targets = targets_dev;
-    a.logits = logits_rows ? logits_dev : nullptr;
-    a.hidden = (int)hidden, a.vocab = (int)vocab, a.n_rows = (int)n_rows, a.logits_rows = (int)logits_rows;
-    a.vb_count = (int)vbc, a.tb_count = (int)(n_pad / kST);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_score_rows_f16, dim3((unsigned)n_pad), dim3(256), 0, s, x_dev, gamma_dev, eps, (int)hidden, (int)n_rows,
-                       reinterpret_cast<_Float16 *>(ws));
-    BH_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_score_head, dim3((unsigned)grid), dim3(256), 0, s, a);
-    BH_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_score_combine, dim3((unsigned)n_rows), dim3(256), 0, s, a.part, a.tlog, targets_dev, (int)vbc, (int)vocab, nll_dev,
-                       argmax_dev);
-    BH_HIP_TRY(hipGetLastError());
-    return BITNET_HIP_OK;
+    return score_launch("score_f16_dev", table_f16_dev, x_dev, gamma_dev, eps, hidden, vocab, n_rows, targets_dev, nll_dev, argmax_dev, logits_dev,
+                        logits_rows, nullptr, 0, bitnet_hip_score_workspace_bytes(n_rows, hidden, vocab), workspace_dev, workspace_bytes, stream);
+}
+
+size_t bitnet_hip_score_topn_workspace_bytes(size_t n_rows, size_t hidden, size_t vocab) {
+    const size_t base = bitnet_hip_score_workspace_bytes(n_rows, hidden, vocab), extra = base ? topn_extra_bytes(n_rows, vocab) : 0;
+    size_t tot = 0;
+    return extra == 0 || __builtin_add_overflow(base, extra, &tot) ? 0 : tot;
+}
+
+int bitnet_hip_score_topn_f16_dev(const void *table_f16_dev, const float *x_dev, const float *gamma_dev, float eps, size_t hidden, size_t vocab,
+                                  size_t n_rows, const int32_t *targets_dev, float *nll_dev, int32_t *argmax_dev, void *records_dev,
+                                  size_t top_n, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (!table_f16_dev || !x_dev || !targets_dev || !nll_dev || !workspace_dev || !records_dev)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to score_topn_f16_dev");
+    if (top_n < 1 || top_n > BITNET_HIP_LOGPROB_TOP_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "score_topn_f16_dev: top_n must be in 1..%d, got %zu", BITNET_HIP_LOGPROB_TOP_MAX, top_n);
+    return score_launch("score_topn_f16_dev", table_f16_dev, x_dev, gamma_dev, eps, hidden, vocab, n_rows, targets_dev, nll_dev, argmax_dev, nullptr, 0,
+                        static_cast<ScoreRecord *>(records_dev), top_n, bitnet_hip_score_topn_workspace_bytes(n_rows, hidden, vocab), workspace_dev,
+                        workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // bitnet_hip_* call (include/bitnet_hip.h) or plain HIP memory / stream / graph plumbing.
 #include "decoder.hpp"
 #include "grammar_host.hpp"
+#include "score_topn_host.hpp"
 
 #include "blake3.hpp"
 #include "stream_timer.hpp"
@@ -1970,6 +1971,47 @@ int Decoder::score(int n, int digits, float *nll_out, int32_t *argmax_out, float
     return 0;
 }
 
+int Decoder::score_topn(int n, int digits, int top_n, bitnet_hip_logprob_record *records_out, float *nll_out, float *elapsed_ms) {
+    if (!embed_) return fail_arg("model globals not set");
+    if (!records_out) return fail_arg("score_topn: null pointer");
+    if (const char *e = span_problem(0, n, false)) return fail_arg(e);  // (the position itself is prefill's to check, below)
+    if (n < 2) return fail_arg("score_topn: n must be >= 2 (row r is scored against token r + 1)");
+    if (top_n < 1 || top_n > BITNET_HIP_LOGPROB_TOP_MAX) return fail_arg("score_topn: top_n must be in 1..BITNET_HIP_LOGPROB_TOP_MAX");
+    const size_t H = c_.hidden, V = (size_t)c_.vocab, N = (size_t)n;
+    const size_t need = bitnet_hip_score_topn_workspace_bytes(N, H, V);
+    if (need == 0) return fail_arg("score_topn: dimensions too large");
+    if (n > sc_cap_ || need > sc_ws_bytes_) {  // score's buffers, with the larger workspace
+        release_all(sc_tgt_, sc_am_, sc_nll_, sc_ws_);
+        sc_cap_ = 0;
+        sc_ws_bytes_ = 0;
+        HCHK(sc_tgt_.alloc(N));
+        HCHK(sc_am_.alloc(N));
+        HCHK(sc_nll_.alloc(N));
+        HCHK(sc_ws_.alloc(need));
+        sc_cap_ = n;
+        sc_ws_bytes_ = need;
+    }
+    if (n > sc_rec_cap_) {
+        release_all(sc_rec_);
+        sc_rec_cap_ = 0;
+        HCHK(sc_rec_.alloc(N));
+        sc_rec_cap_ = n;
+    }
+    hipStream_t s = (hipStream_t)stream_;
+    StreamTimer timer;
+    HCHK(timer.start(s));
+    if (int rc = prefill(n, true, digits, nullptr)) return rc;
+    // row r predicts token r + 1 of the history (the prompt); the last row has no target
+    HCHK(hipMemcpyAsync(sc_tgt_, history_ + 1, (N - 1) * 4, hipMemcpyDeviceToDevice, s));
+    HCHK(hipMemsetAsync(sc_tgt_ + (N - 1), 0xff, 4, s));
+    BCHK(bitnet_hip_score_topn_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, N, sc_tgt_, sc_nll_, sc_am_.get(), sc_rec_.get(), (size_t)top_n, sc_ws_,
+                                       sc_ws_bytes_, s));
+    HCHK(timer.stop(s, elapsed_ms));
+    HCHK(hipMemcpy(records_out, sc_rec_, N * sizeof(bitnet_hip_logprob_record), hipMemcpyDeviceToHost));
+    if (nll_out) HCHK(hipMemcpy(nll_out, sc_nll_, (N - 1) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int Decoder::finish_prefill(int n, const float *last_row, bool with_logits) {
     // hand over to the single-token state: residual stream of the last position, position counter
     if (n <= 0 || n > c_.max_pos - 1) {
@@ -2328,6 +2370,10 @@ int bitnet_host_finish_prefill(void *d, int n, const float *last_row, int with_l
 int bitnet_host_score(void *d, int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms) {
     LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
     return D->score(n, digits, nll_out, argmax_out, logits_out, logits_rows, elapsed_ms);
+}
+int bitnet_host_score_topn(void *d, int n, int digits, int top_n, void *records_out, float *nll_out, float *elapsed_ms) {
+    LIVE(BITNET_HIP_ERR_INVALID_ARGUMENT);
+    return D->score_topn(n, digits, top_n, static_cast<bitnet_hip_logprob_record *>(records_out), nll_out, elapsed_ms);
 }
 void bitnet_host_layer_objects(void *d, int layer, uint64_t *handles4, void **ptrs4) {
     for (int i = 0; i < 4; ++i) handles4[i] = 0, ptrs4[i] = nullptr;

@@ -358,6 +358,11 @@ class Decoder : private DecoderStreams {
     // which can differ from the one prefill picked with the decode head in a near-tie), logits_out[logits_rows * vocab] (nullable).
     // 2 <= n <= fed tokens, n <= max_pos - 1.  Buffers grow on demand (none before the first call); elapsed_ms: prefill + head.
     int score(int n, int digits, float *nll_out, int32_t *argmax_out, float *logits_out, int logits_rows, float *elapsed_ms);
+    // score() with the exact top-N of every row (bitnet_hip_score_topn_f16_dev behind the same prompt forward): records_out[n], record r =
+    // row r's target (token r + 1; -1 in the last), its raw logit, the row's log-sum-exp and the top_n best (id, logit) pairs; nll_out[n - 1]
+    // (nullable) as score's.  The same checks and the same end state as score; top_n in 1..BITNET_HIP_LOGPROB_TOP_MAX.  No [n, vocab] buffer
+    // exists at any point; the records are read back once, behind the timed part.
+    int score_topn(int n, int digits, int top_n, bitnet_hip_logprob_record *records_out, float *nll_out, float *elapsed_ms);
     bool chain_applies(int digits) const;
     bool handover16_applies(int digits) const;
     bool hybrid_applies(size_t n_rows);
@@ -559,6 +564,8 @@ class Decoder : private DecoderStreams {
     DevBuf<float> sc_nll_, sc_logits_;
     DevBuf<void> sc_ws_;
     size_t sc_ws_bytes_ = 0;
+    DevBuf<bitnet_hip_logprob_record> sc_rec_;  // score_topn's records
+    int sc_rec_cap_ = 0;
     int last_prefill_path_ = 0;  // what the last prefill() ran: 0 digit planes (+ f16 hand-over / hybrid), 1 the f16 chain, 2 the QB32 chain
     int prefill_qb32_ = -1;   // BITNET_HOST_PREFILL_QB32: -1 not read yet; 1 = the QB32 chain where it applies (opt-in), 0 (default) = quantiser launches
     int prefill_fp6_ = -1;    // BITNET_HOST_PREFILL_FP6: -1 not yet decided, 0 int8 digit planes, 1 the fp6 x fp4 form on resident fp4 images (fp6_flag)

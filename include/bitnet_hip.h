@@ -797,6 +797,9 @@ size_t bitnet_hip_score_workspace_bytes(size_t n_rows, size_t hidden, size_t voc
 int bitnet_hip_score_f16_dev(const void *table_f16_dev, const float *x_dev, const float *gamma_dev, float eps, size_t hidden, size_t vocab,
                              size_t n_rows, const int32_t *targets_dev, float *nll_dev, int32_t *argmax_dev, float *logits_dev,
                              size_t logits_rows, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* Prompt top-N: the same pass with the exact top-N (id, logit) pairs of every row and no [n_rows, vocab] buffer
+ * (bitnet_hip_score_topn_workspace_bytes, bitnet_hip_score_topn_f16_dev). */
+#include "bitnet_hip_scoretopn.h"
 
 /* ---- sampling on the device: crates/bitnet-cli/src/sampling.rs `Sampler` ---------------------------------------
  * The reference's `Sampler::sample(&logits, &generated_tokens)` in its order: count every entry of the list, repetition

@@ -26,6 +26,7 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libbitnet_hip.so")
 HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip.h")
 GRAMMAR_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar.h")  # included by HEADER_PATH: the grammar stage's six entry points
+GRAMC_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar_compile.h")  # included by HEADER_PATH: the grammar compiler on the device, five
 KVSNAP_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")  # included by HEADER_PATH: the KV snapshot's three entry points
 BEAM_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_beam.h")  # included by HEADER_PATH: beam search, the select and permute launches and their state
 SCORETOPN_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_scoretopn.h")  # included by HEADER_PATH: prompt top-N, two entry points
@@ -123,6 +124,7 @@ class HipLib:
         self.c = C.CDLL(path)
         cproto.bind(self.c, cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_"), C_STRUCTS)
         cproto.bind(self.c, grammar_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, gramc_prototypes(), C_STRUCTS)
         cproto.bind(self.c, kvsnap_prototypes(), C_STRUCTS)
         cproto.bind(self.c, widetail_prototypes(), C_STRUCTS)
         cproto.bind(self.c, beam_prototypes(), C_STRUCTS)
@@ -675,6 +677,25 @@ class HipLib:
         compiles one from a byte-level DFA and the vocabulary's byte strings."""
         return Grammar(self, token_class, next_table)
 
+    def vocab(self, vocab_bytes) -> "Vocab":
+        """The vocabulary's byte strings on the device (bitnet_hip_vocab_create): vocab_bytes[t] is token t's bytes.  Uploaded once, shared by
+        any number of grammar_compile calls."""
+        return Vocab(self, vocab_bytes)
+
+    def grammar_compile(self, vocab: "Vocab", dfa, eos_id: int | None = None) -> "Grammar":
+        """bitnet_hip_grammar_compile: the token automaton of a byte-level DFA (grammar.ByteDFA: .next [n, 256], .start, .accepting) over an
+        uploaded vocabulary, built on the device.  grammar.token_automaton's semantics with classes numbered by their smallest token id; the
+        start state for Sampler.set_grammar is dfa.start."""
+        nx = _np(dfa.next, np.int32)
+        if nx.ndim != 2 or nx.shape[1] != 256:
+            raise ValueError(f"grammar_compile: next must be [n_states, 256], got shape {nx.shape}")
+        acc = np.zeros(nx.shape[0], np.uint8)
+        acc[sorted(int(s) for s in dfa.accepting)] = 1
+        d = DfaDesc(nx.ctypes.data_as(C.POINTER(C.c_int32)), nx.shape[0], int(dfa.start), acc.ctypes.data_as(_u8p))
+        h = _vp()
+        self._check(self.c.bitnet_hip_grammar_compile(vocab.h, C.byref(d), -1 if eos_id is None else int(eos_id), C.byref(h)))
+        return Grammar.from_handle(self, h)
+
     def sample_batch(self, vocab: int, n_slots: int, wide: bool = False) -> "SampleBatch":
         """A table of n_slots sampler bindings served by one launch (bitnet_hip_sample_batch_*): 1..8 slots, or with wide=True 1..64
         (bitnet_hip_sample_batch_create_wide, the wide step's tail)."""
@@ -835,6 +856,28 @@ class Grammar:
         lib._check(lib.c.bitnet_hip_grammar_create(C.byref(self.desc), C.byref(h)))
         self.h = h
 
+    @classmethod
+    def from_handle(cls, lib: HipLib, h) -> "Grammar":
+        """Wraps (and owns) a handle the library made itself (bitnet_hip_grammar_compile): the sizes come from info(), the descriptor walk()
+        needs is read from the device the first time it is asked for."""
+        g = cls.__new__(cls)
+        g.lib, g.h, g.desc = lib, h, None
+        g.vocab, g.n_states, g.n_classes = g.info()
+        return g
+
+    def info(self) -> tuple[int, int, int]:
+        """(vocab, n_states, n_classes) of the handle (bitnet_hip_grammar_info)."""
+        v, s, c = _sz(0), _sz(0), _sz(0)
+        self.lib._check(self.lib.c.bitnet_hip_grammar_info(self.h, C.byref(v), C.byref(s), C.byref(c)))
+        return int(v.value), int(s.value), int(c.value)
+
+    def tables(self) -> tuple[np.ndarray, np.ndarray]:
+        """(token_class [vocab] uint16, next [n_states, n_classes] int32) read from the device (bitnet_hip_grammar_read).  Synchronous."""
+        v, s, c = self.info()
+        tc, nx = np.empty(v, np.uint16), np.empty((s, c), np.int32)
+        self.lib._check(self.lib.c.bitnet_hip_grammar_read(self.h, tc.ctypes.data_as(_vp), nx.ctypes.data_as(_vp)))
+        return tc, nx
+
     def close(self) -> None:
         if self.h:
             self.lib.c.bitnet_hip_grammar_destroy(self.h)
@@ -848,7 +891,40 @@ class Grammar:
 
     def walk(self, state: int, tokens) -> tuple[int, int]:
         """(state reached, tokens taken) from `state`: stops in front of the first token that is not allowed or not in the vocabulary."""
+        if self.desc is None:  # a compiled handle: the tables come from the device once, while the handle is open
+            self.desc = GrammarDesc.make(*self.tables())
         return grammar_walk(self.lib, self.desc, state, tokens)
+
+
+class DfaDesc(C.Structure):
+    """bitnet_hip_dfa_desc: next [n_states][256] int32 (-1: no transition), the start state, one accepting byte per state."""
+    _fields_ = [("next", C.POINTER(C.c_int32)), ("n_states", _sz), ("start", C.c_int32), ("accepting", _u8p)]
+
+
+class Vocab:
+    """One bitnet_hip_vocab: the vocabulary's byte strings in device memory, read by any number of HipLib.grammar_compile calls."""
+
+    def __init__(self, lib: HipLib, vocab_bytes):
+        self.lib, self.h = lib, None
+        toks = [bytes(b) for b in vocab_bytes]
+        off = np.zeros(len(toks) + 1, np.uint64)
+        off[1:] = np.cumsum([len(b) for b in toks], dtype=np.uint64)
+        data = np.frombuffer(b"".join(toks) or b"\0", np.uint8)  # never a NULL pointer: a vocabulary of empty strings still uploads
+        self.n = len(toks)
+        h = _vp()
+        lib._check(lib.c.bitnet_hip_vocab_create(data.ctypes.data_as(_u8p), off.ctypes.data_as(_vp), self.n, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.c.bitnet_hip_vocab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
 
 
 def grammar_walk(lib: HipLib, desc: GrammarDesc, state: int, tokens) -> tuple[int, int]:
@@ -1215,6 +1291,11 @@ def grammar_prototypes() -> list:
     return cproto.prototypes(open(GRAMMAR_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def gramc_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_grammar_compile.h, the header include/bitnet_hip.h includes for the grammar compiler on the device."""
+    return cproto.prototypes(open(GRAMC_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def kvsnap_prototypes() -> list:
     """The prototypes of include/bitnet_hip_kvsnap.h, the header include/bitnet_hip.h includes for the compact KV snapshots."""
     return cproto.prototypes(open(KVSNAP_HEADER_PATH).read(), "bitnet_hip_")
@@ -1237,7 +1318,7 @@ def scoretopn_prototypes() -> list:
 
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
-    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + kvsnap_prototypes()
+    return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + gramc_prototypes() + kvsnap_prototypes()
                    + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes()})
 
 
@@ -1332,7 +1413,7 @@ class HostConfig(C.Structure):
 # the structs that cross the C ABI by pointer, by their C names: cproto.bind types such a parameter as POINTER of the class
 C_STRUCTS = {"bitnet_hip_device_info": DeviceInfo, "bitnet_hip_gemv_q_geometry_t": GemvQGeometry, "bitnet_hip_gemv_geometry_t": GemvGeometry, "bitnet_hip_sampling_config": SamplingConfig,
              "bitnet_hip_sampling_config_ex": SamplingConfigEx, "bitnet_hip_mirostat_config": MirostatConfig,
-             "bitnet_hip_constraints": Constraints, "bitnet_hip_grammar_desc": GrammarDesc, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
+             "bitnet_hip_constraints": Constraints, "bitnet_hip_grammar_desc": GrammarDesc, "bitnet_hip_dfa_desc": DfaDesc, "bitnet_hip_logprob_args": LogprobArgs, "bitnet_hip_stop_config": StopConfig,
              "bitnet_hip_stop_state": StopState, "bitnet_hip_beam_state": BeamState, "bitnet_host_config": HostConfig, "bitnet_host_prefix_stats": PrefixStats}
 
 FLAVORS = ("BitNet32F16", "Split32WithSibling", "GgmlQk256NoScale")

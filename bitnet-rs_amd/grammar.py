@@ -67,7 +67,8 @@ def token_automaton(dfa: ByteDFA, vocab_bytes, eos_id: int | None):
     dfa.n, in which only it is allowed (and which it keeps).  Equal columns share a class.  ValueError when a limit of the library is exceeded.
 
     Cost: a dense [vocab, n_states] int32 array and one row sort of it (np.unique).  That suits tries and small DFAs -- 128 K tokens by 100
-    states is 50 MB -- and not the library's limit of 65536 states; a front end with thousands of states should group tokens as it goes."""
+    states is 50 MB -- and not the library's limit of 65536 states: a DFA with thousands of states goes through compile_on_device, which
+    builds the same automaton on the GPU by partition refinement and never holds that array."""
     V, n = len(vocab_bytes), dfa.n
     if not 1 <= V <= MAX_VOCAB:
         raise ValueError(f"token_automaton: the vocabulary must have 1..{MAX_VOCAB} tokens, got {V}")
@@ -102,3 +103,10 @@ def token_automaton(dfa: ByteDFA, vocab_bytes, eos_id: int | None):
     if S * uniq.shape[0] > MAX_CELLS:
         raise ValueError(f"token_automaton: {S} states * {uniq.shape[0]} classes exceed {MAX_CELLS} table entries")
     return np.ascontiguousarray(inverse.reshape(-1), dtype=np.uint16), np.ascontiguousarray(uniq.T, dtype=np.int32), dfa.start
+
+
+def compile_on_device(lib, dfa: ByteDFA, vocab_handle, eos_id: int | None):
+    """token_automaton on the GPU (bitnet_hip_grammar_compile): (the grammar handle, start) for Sampler.set_grammar.  vocab_handle is
+    lib.vocab(vocab_bytes), uploaded once for any number of DFAs.  The same (state, token) -> next state function and class count as
+    token_automaton; classes are numbered by their smallest token id."""
+    return lib.grammar_compile(vocab_handle, dfa, eos_id), dfa.start

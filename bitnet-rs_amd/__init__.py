@@ -30,6 +30,7 @@ GRAMC_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_grammar_compile.h"
 KVSNAP_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")  # included by HEADER_PATH: the KV snapshot's three entry points
 BEAM_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_beam.h")  # included by HEADER_PATH: beam search, the select and permute launches and their state
 SCORETOPN_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_scoretopn.h")  # included by HEADER_PATH: prompt top-N, two entry points
+PAGED_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_paged.h")  # included by HEADER_PATH: the paged KV cache, seven entry points
 WIDETAIL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_widetail.h")  # included by HEADER_PATH: the wide step's 64-entry tail tables, two
 
 OK = 0
@@ -129,6 +130,7 @@ class HipLib:
         cproto.bind(self.c, widetail_prototypes(), C_STRUCTS)
         cproto.bind(self.c, beam_prototypes(), C_STRUCTS)
         cproto.bind(self.c, scoretopn_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, paged_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -534,6 +536,47 @@ class HipLib:
         device tensors of device pointers, the source's [n_layers], the destinations' [n_dst][n_layers]; buffers distinct, 16-byte aligned."""
         self._check(self.c.bitnet_hip_kv_fork_dev(_ptr(src_k_ptrs), _ptr(src_v_ptrs), _ptr(dst_k_ptrs), _ptr(dst_v_ptrs), n_layers, n_dst, n_kv, head_dim,
                                                   max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
+
+    # ---- the paged KV cache (include/bitnet_hip_paged.h): pools of 64-position pages, sequences as uint32 page tables on the device ----
+    def kv_pool_bytes(self, n_pages: int, n_kv: int, head_dim: int, kv_f16: bool = False) -> int:
+        """Bytes of ONE layer's K pool (its V pool has as many); 0 for a geometry the launches refuse."""
+        return int(self.c.bitnet_hip_kv_pool_bytes(n_pages, n_kv, head_dim, 1 if kv_f16 else 0))
+
+    def attention_paged_splits(self, n_seq: int, n_kv: int, key_bound: int) -> int:
+        """The split count attention_decode_paged_dev chooses for n_splits = 0 (a pure host function)."""
+        return int(self.c.bitnet_hip_attention_paged_splits(n_seq, n_kv, key_bound))
+
+    def attention_paged_scratch_bytes(self, n_seq: int, n_kv: int, n_splits: int) -> int:
+        return int(self.c.bitnet_hip_attention_paged_scratch_bytes(n_seq, n_kv, n_splits))
+
+    def attention_decode_paged_dev(self, qkv, rope_sin, rope_cos, kpool, vpool, n_pages: int, table_ptrs, pos_ptrs, n_seq: int, n_heads, n_kv, head_dim,
+                                   max_pos, key_bound, n_splits: int, scratch, out, kv_f16: bool = False, out_f16: bool = False, stream: int = 0) -> None:
+        """One token of n_seq <= 64 sequences over their page tables, one launch.  table_ptrs / pos_ptrs: int64 device tensors of n_seq device
+        pointers (0 = idle row); scratch: attention_paged_scratch_bytes, zero-filled once; n_splits 0 = the library chooses."""
+        flags = (1 if kv_f16 else 0) | (2 if out_f16 else 0)  # BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16
+        self._check(self.c.bitnet_hip_attention_decode_paged_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kpool), _ptr(vpool), n_pages, _ptr(table_ptrs),
+                                                                 _ptr(pos_ptrs), n_seq, n_heads, n_kv, head_dim, max_pos, key_bound, n_splits, _ptr(scratch), flags,
+                                                                 _ptr(out), _vp(stream)))
+
+    def kv_page_in_dev(self, k_ptrs, v_ptrs, kpool_ptrs, vpool_ptrs, table, n_pages: int, n_layers: int, n_kv: int, head_dim: int, max_pos: int,
+                       n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
+        """Positions [0, n_positions) of one sequence's contiguous caches into the pages `table` (uint32, on the device) names, bit for bit, one
+        launch.  *_ptrs: int64 device tensors of n_layers device pointers."""
+        self._check(self.c.bitnet_hip_kv_page_in_dev(_ptr(k_ptrs), _ptr(v_ptrs), _ptr(kpool_ptrs), _ptr(vpool_ptrs), _ptr(table), n_pages, n_layers, n_kv,
+                                                     head_dim, max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
+
+    def kv_page_out_dev(self, kpool_ptrs, vpool_ptrs, table, n_pages: int, k_ptrs, v_ptrs, n_layers: int, n_kv: int, head_dim: int, max_pos: int,
+                        n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
+        """The way back: the pages `table` names into cache slots [0, n_positions); every other cache byte stays."""
+        self._check(self.c.bitnet_hip_kv_page_out_dev(_ptr(kpool_ptrs), _ptr(vpool_ptrs), _ptr(table), n_pages, _ptr(k_ptrs), _ptr(v_ptrs), n_layers, n_kv,
+                                                      head_dim, max_pos, n_positions, 2 if kv_f16 else 0, _vp(stream)))
+
+    def kv_page_copy_dev(self, kpool_ptrs, vpool_ptrs, n_pages: int, pairs, n_layers: int, n_kv: int, head_dim: int, kv_f16: bool = False,
+                         stream: int = 0) -> None:
+        """Whole pages src -> dst in every layer's K and V pool, one launch.  pairs: up to 64 (src, dst) page ids, host side."""
+        flat = np.ascontiguousarray(np.asarray(pairs, np.uint32).reshape(-1, 2))
+        self._check(self.c.bitnet_hip_kv_page_copy_dev(_ptr(kpool_ptrs), _ptr(vpool_ptrs), n_pages, _vp(flat.ctypes.data), len(flat), n_layers, n_kv, head_dim,
+                                                       2 if kv_f16 else 0, _vp(stream)))
 
     def kv_permute_dev(self, k_ptrs, v_ptrs, beam: "Beam", n_layers: int, n_beams: int, n_kv: int, head_dim: int, max_pos: int, key_bound: int,
                        kv_f16: bool = False, stream: int = 0) -> None:
@@ -1316,10 +1359,15 @@ def scoretopn_prototypes() -> list:
     return cproto.prototypes(open(SCORETOPN_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def paged_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_paged.h, the header include/bitnet_hip.h includes for the paged KV cache."""
+    return cproto.prototypes(open(PAGED_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
     return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + gramc_prototypes() + kvsnap_prototypes()
-                   + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes()})
+                   + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes() + paged_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -1333,6 +1381,7 @@ HOST_SCORETOPN_HEADER_PATH = os.path.join(HERE, "host", "score_topn_host.hpp")  
 HOST_PREFIX_HEADER_PATH = os.path.join(HERE, "host", "prefix_cache.hpp")  # PrefixCache and Decoder::prefill_cached, bound beside the others
 HOST_WIDE_HEADER_PATH = os.path.join(HERE, "host", "wide_batch.hpp")  # WideBatch, bound beside the others
 HOST_BEAM_HEADER_PATH = os.path.join(HERE, "host", "beam_search.hpp")  # BeamSearch, bound beside the others
+HOST_PAGED_HEADER_PATH = os.path.join(HERE, "host", "paged_batch.hpp")  # PagedBatch and the cache-less borrower, bound beside the others
 _host_libs = {}
 
 
@@ -1366,6 +1415,11 @@ def host_beam_prototypes() -> list:
     return cproto.prototypes(open(HOST_BEAM_HEADER_PATH).read(), "bitnet_host_")
 
 
+def host_paged_prototypes() -> list:
+    """The exports of host/paged_batch.hpp (PagedBatch, the cache-less borrower), typed at load like the rest."""
+    return cproto.prototypes(open(HOST_PAGED_HEADER_PATH).read(), "bitnet_host_")
+
+
 def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
     """The host library at `path`, loaded and bound from its headers once per process."""
     if path not in _host_libs:
@@ -1376,6 +1430,7 @@ def _host_lib(path: str = HOST_LIB_PATH) -> C.CDLL:
         cproto.bind(L, host_wide_prototypes(), C_STRUCTS)
         cproto.bind(L, host_beam_prototypes(), C_STRUCTS)
         cproto.bind(L, host_scoretopn_prototypes(), C_STRUCTS)
+        cproto.bind(L, host_paged_prototypes(), C_STRUCTS)
         _host_libs[path] = L
     return _host_libs[path]
 
@@ -1499,7 +1554,7 @@ class HostDecoder:
     """ctypes view of the C++ Decoder (mirror of the reference's Rust-side
     TransformerModel / KVCache / greedy loop).  No arithmetic here."""
 
-    def __init__(self, cfg, path: str = HOST_LIB_PATH, _owner: "HostDecoder | None" = None):
+    def __init__(self, cfg, path: str = HOST_LIB_PATH, _owner: "HostDecoder | None" = None, _no_cache: bool = False, _handle=None):
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not found: build it with __graft_entry__.build() -- there is no fallback path")
         load()  # the kernel library must be loadable first
@@ -1509,10 +1564,15 @@ class HostDecoder:
         self._fed = 0  # tokens fed since the last reset (the default n of score)
         self.last_score_topn_ms = 0.0  # prefill + head of the last score_topn
         hc = HostConfig(**{k: (float(v) if k in ("eps", "rope_theta") else int(v)) for k, v in cfg.asdict().items()})
-        self.h = L.bitnet_host_create(C.byref(hc)) if _owner is None else L.bitnet_host_create_shared(_owner.h)
+        if _handle is not None:  # a PagedBatch member handed out with a reference of its own (HostPagedBatch.member)
+            self.h = _handle
+        elif _no_cache:
+            self.h = _host_fn(L, "bitnet_host_create_shared_no_cache")(_owner.h)
+        else:
+            self.h = L.bitnet_host_create(C.byref(hc)) if _owner is None else L.bitnet_host_create_shared(_owner.h)
         if not self.h:
             raise BitNetHipError(ERR_GPU, "bitnet_host_create failed (allocation)" if _owner is None else "bitnet_host_create_shared: dead or closed owner")
-        err = self.error()
+        err = "" if _handle is not None else self.error()  # (a live member may carry the text of an earlier refusal)
         if err:
             self.close()  # a dead decoder (rejected configuration, failed allocation) is destroyed before the error is raised
             raise BitNetHipError(ERR_GPU, err)
@@ -1535,6 +1595,11 @@ class HostDecoder:
         sampler and stream.  It refuses set_layer_* / set_globals / load_gguf / set_act_mode, and this decoder refuses set_layer_* /
         set_globals while borrowers live.  close() order is free: the library keeps the owner until its last borrower is gone."""
         return HostDecoder(self.cfg, path=self.c._name, _owner=self)
+
+    def shared_no_cache(self) -> "HostDecoder":
+        """shared() WITHOUT KV caches of its own: what a HostPagedBatch creates for its slots.  It keeps history, position, logits row, sampler,
+        tap and stop state; run, prefill*, extend, fork, shift, rewind, the snapshot paths and step_wide refuse it ("owns no KV cache")."""
+        return HostDecoder(self.cfg, path=self.c._name, _owner=self, _no_cache=True)
 
     def set_attention_form(self, form: int) -> None:
         """-1: the attention form follows the position (default); 0: 64-position records + combine at every position, the form a
@@ -2255,3 +2320,72 @@ class HostWideBatch:
     def table_writes(self) -> int:
         """Uploads of a tail table or the pointer tables since creation: a step with nothing changed adds none."""
         return int(self._w("table_writes")(self.h))
+
+
+class HostPagedBatch:
+    """ctypes view of the C++ PagedBatch (host/paged_batch.hpp): up to 64 sequences over ONE pool of 64-position KV pages on `root`'s weights.
+    admit() takes the first n positions of an ordinary, prefilled staging decoder (one page_in launch); fork() shares every page; step() runs
+    the wide forward with the paged attention in every layer, copying a shared page only when a fork appends to it; extract() is the bridge
+    back to an ordinary decoder; member(slot) is the slot's cache-less decoder (sampling, stop criteria, last_logits(), history())."""
+
+    def __init__(self, root: "HostDecoder", n_pages: int, n_slots: int):
+        self.c = root.c
+        self.root = root
+        self.h = self._p("create")(root.h, int(n_pages), int(n_slots))
+        if not self.h:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, "bitnet_host_paged_batch_create: closed root")
+        err = self.error()
+        if err:
+            self.close()
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, err)
+
+    def _p(self, name: str):
+        return _host_fn(self.c, "bitnet_host_paged_batch_" + name)
+
+    def error(self) -> str:
+        e = self._p("error")(self.h)
+        return e.decode() if e else ""
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise BitNetHipError(rc, self.error() or f"bitnet_host_paged_batch rc={rc}")
+
+    def close(self) -> None:
+        if self.h:
+            self._p("destroy")(self.h)
+            self.h = None
+
+    def admit(self, slot: int, src: "HostDecoder", n: int) -> None:
+        self._check(self._p("admit")(self.h, int(slot), src.h, int(n)))
+
+    def fork(self, slot_from: int, slot_to: int) -> None:
+        self._check(self._p("fork")(self.h, int(slot_from), int(slot_to)))
+
+    def release(self, slot: int) -> None:
+        self._check(self._p("release")(self.h, int(slot)))
+
+    def extract(self, slot: int, dst: "HostDecoder") -> None:
+        self._check(self._p("extract")(self.h, int(slot), dst.h))
+
+    def step(self, n: int = 1, digits: int = 2) -> float:
+        """n steps of every member; returns the elapsed milliseconds (HIP events)."""
+        ms = C.c_float(0.0)
+        self._check(self._p("step")(self.h, int(n), int(digits), C.byref(ms)))
+        return float(ms.value)
+
+    def member(self, slot: int) -> "HostDecoder":
+        """The slot's decoder, with a reference of its own: close() it when done (the batch keeps the member)."""
+        h = self._p("member")(self.h, int(slot))
+        if not h:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, "paged batch: the slot is empty")
+        return HostDecoder(self.root.cfg, path=self.c._name, _handle=h)
+
+    def pages_in_use(self) -> int:
+        return int(self._p("pages_in_use")(self.h))
+
+    def pages_free(self) -> int:
+        return int(self._p("pages_free")(self.h))
+
+    def pool_bytes(self) -> int:
+        """Device bytes of all 2 * n_layers pools."""
+        return int(self._p("pool_bytes")(self.h))

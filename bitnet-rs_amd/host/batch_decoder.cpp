@@ -142,6 +142,7 @@ int BatchDecoder::set_slot(int b, Decoder *d) {
     if (b < 0 || b >= n_) return fail_arg("batch: slot index out of range");
     if (d) {
         if (d->dead()) return fail_arg("batch: dead decoder");
+        if (d->no_cache()) return fail_arg("batch: this decoder owns no KV cache (a PagedBatch member)");
         if (d->batch_ && !(d->batch_ == this && slot_[b] == d)) return fail_arg("batch: this decoder already sits in a slot");
         if (d->batch_) return 0;  // the same member into its own slot
         void *g[7];

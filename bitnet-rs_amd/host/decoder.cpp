@@ -71,7 +71,8 @@ DecoderStreams::~DecoderStreams() {
     if (stream_) hipStreamDestroy((hipStream_t)stream_);
 }
 
-Decoder::Decoder(const Config &cfg, bool own_norms) : c_(cfg), layers_(cfg.n_layers > 0 && cfg.n_layers <= 4096 ? (size_t)cfg.n_layers : 0) {
+Decoder::Decoder(const Config &cfg, bool own_norms, bool no_cache)
+    : no_cache_(no_cache), c_(cfg), layers_(cfg.n_layers > 0 && cfg.n_layers <= 4096 ? (size_t)cfg.n_layers : 0) {
     // A rejected configuration or a failed allocation leaves a DEAD object: error() says why, every other entry point
     // returns an error without touching a member (c_ used to keep the rejected n_layers while layers_ was empty).
     dead_ = true;
@@ -119,14 +120,14 @@ Decoder::Decoder(const Config &cfg, bool own_norms) : c_(cfg), layers_(cfg.n_lay
     if (const size_t wb = bitnet_hip_head_screen_ws_bytes(H, (size_t)c_.vocab, (size_t)screen_wgs_))  // 0: no screened head at this hidden size
         bad = bad || screen_ws_.alloc_zeroed_bytes(wb);
     // zero-filled: the merging o-projection reads records of chunks past the context (and gives them zero weight)
-    bad = bad || attn_scratch_.alloc_zeroed_bytes(bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos));
+    if (!no_cache_) bad = bad || attn_scratch_.alloc_zeroed_bytes(bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos));
     bad = bad || pos_.alloc(1) || n_forced_.alloc(1) || token_.alloc(1) || history_.alloc((size_t)c_.max_pos + 2);
     bad = bad || rope_sin_.alloc((size_t)c_.max_pos * half) || rope_cos_.alloc((size_t)c_.max_pos * half);
     for (auto &L : layers_) {
         const size_t n = (size_t)c_.n_kv_heads * (((size_t)c_.max_pos + 63) / 64 * 64) * D;  // whole 64-position tiles
         // the decode attention reads whole 64-position tiles and multiplies slots past the context by exact zeros:
         // they must hold finite bit patterns (include/bitnet_hip.h), so the caches start zero-filled
-        bad = bad || L.kcache.alloc_zeroed(n) || L.vcache.alloc_zeroed(n);
+        if (!no_cache_) bad = bad || L.kcache.alloc_zeroed(n) || L.vcache.alloc_zeroed(n);  // (a PagedBatch member's keys live in the batch's pool)
         if (own_norms) bad = bad || L.attn_norm.alloc(H) || L.ffn_norm.alloc(H);
     }
     if (own_norms) bad = bad || final_norm_.alloc(H);
@@ -153,7 +154,7 @@ Decoder::Decoder(const Config &cfg, bool own_norms) : c_(cfg), layers_(cfg.n_lay
 
 // Borrowing decoder: built as any other (own buffers, caches, stream) but for the norm vectors: those, the final norm, the weight handles,
 // the embedding table and its screening image are the OWNER's.
-Decoder::Decoder(Decoder &owner, int) : Decoder(owner.c_, false) {
+Decoder::Decoder(Decoder &owner, int, bool no_cache) : Decoder(owner.c_, false, no_cache) {
     if (dead_) return;
     if (owner.dead_ || owner.owner_ || !owner.embed_) {
         dead_ = true;
@@ -179,6 +180,11 @@ Decoder::Decoder(Decoder &owner, int) : Decoder(owner.c_, false) {
     act_mode_ = owner.act_mode_;
     owner_ = &owner;
     owner.borrowers_++;
+}
+
+int Decoder::refuse_no_cache(const char *entry) {
+    if (!no_cache_) return 0;
+    return fail_arg((std::string(entry) + ": this decoder owns no KV cache (a PagedBatch member: step it through its batch, extract() it to leave)").c_str());
 }
 
 int Decoder::weights_locked() {
@@ -725,6 +731,7 @@ int Decoder::attn_launch(Layer &L, int form, float *out, void *qout) {
 }
 
 int Decoder::set_kv_f16(bool on) {
+    if (int rc = refuse_no_cache("set_kv_f16")) return rc;
     if (position() != 0 || host_forced_ != 0) {
         err_ = "set_kv_f16: only on a fresh sequence (reset() first): a cache is f16 or f32 for its whole life";
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -869,6 +876,7 @@ int Decoder::step_launches(bool with_logits, int form, Tracer *tr) {
 }
 
 int Decoder::trace_step(const char *dir, bool with_logits) {
+    if (int rc = refuse_no_cache("trace_step")) return rc;
     if (!embed_) {
         err_ = "model globals not set";
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -928,6 +936,7 @@ int Decoder::step_launches_reference(bool with_logits) {
 }
 
 int Decoder::run_reference(int n, bool with_logits) {
+    if (int rc = refuse_no_cache("run_reference")) return rc;
     if (!embed_) {
         err_ = "model globals not set";
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -986,6 +995,7 @@ int Decoder::prepare_graphs(bool with_logits) {
 }
 
 int Decoder::ensure_graph(bool with_logits, int form) {
+    if (int rc = refuse_no_cache("step graph")) return rc;
     const int gi = 2 * form + (with_logits ? 1 : 0);
     if (graphs_screened_ != (int)screen_step(false)) drop_graphs();  // captured under another head (a batch slot taken or left since)
     if (graph_exec_[gi]) return 0;
@@ -1008,6 +1018,7 @@ int Decoder::ensure_graph(bool with_logits, int form) {
 }
 
 int Decoder::run(int n, bool with_logits, bool use_graph, float *elapsed_ms) {
+    if (int rc = refuse_no_cache("run")) return rc;
     if (!embed_) {
         err_ = "model globals not set";
         return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -1221,6 +1232,14 @@ int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16, const
                                                   op.tables + (2 * li + 1) * BITNET_HIP_WIDE_MAX,
                                                   reinterpret_cast<const int32_t *const *>(op.tables + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
                                                   op.key_bound, wide_scratch_, rflags, out, stream_));
+    } else if (op.kind == AttnOp::Paged) {
+        // a PagedBatch step: the rows of a wide step, each over its member's PAGE TABLE in this layer's pools -- one launch, the library's split
+        // count for (N, NK, key_bound); the position pointers are the wide tables' row
+        const PagedAttn &pg = *op.paged;
+        const int rflags = (op.kv_f16 ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
+        BCHK(bitnet_hip_attention_decode_paged_dev(pf_qkv_, rope_sin_, rope_cos_, pg.kpools[li], pg.vpools[li], pg.n_pages, pg.tables,
+                                                   reinterpret_cast<const int32_t *const *>(op.tables + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
+                                                   op.key_bound, 0, pg.scratch, rflags, out, stream_));
     } else if (op.kind == AttnOp::Pack) {
         // a pack (prefill_packed): the N rows are several members' segments, each over its OWN caches of this layer
         void *kc[BITNET_HIP_PACK_MAX], *vc[BITNET_HIP_PACK_MAX];
@@ -1353,6 +1372,7 @@ int Decoder::check_members(Decoder *const *members, int n_members, int cap, cons
         Decoder *d = members[i];
         if (!d) return refuse("null member");
         if (d->dead_) return refuse("dead member");
+        if (d->no_cache_) return refuse("a member owns no KV cache (a PagedBatch member)");
         for (int j = 0; j < i; ++j)
             if (members[j] == d) return refuse("a member is repeated");
         if (d->root() != drv.root()) return refuse("all members must run on the same weights (an owner and its borrowers)");
@@ -1363,6 +1383,7 @@ int Decoder::check_members(Decoder *const *members, int n_members, int cap, cons
 }
 
 int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
+    if (int rc = refuse_no_cache("prefill")) return rc;
     if (!embed_) return fail_arg("model globals not set");
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
@@ -1372,6 +1393,7 @@ int Decoder::prefill(int n, bool with_logits, int digits, float *elapsed_ms) {
 }
 
 int Decoder::extend(int n, bool with_logits, int digits, float *elapsed_ms) {
+    if (int rc = refuse_no_cache("extend")) return rc;
     if (!embed_) return fail_arg("model globals not set");
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
@@ -1380,6 +1402,7 @@ int Decoder::extend(int n, bool with_logits, int digits, float *elapsed_ms) {
 }
 
 int Decoder::rewind(int n) {
+    if (int rc = refuse_no_cache("rewind")) return rc;  // (its pages would stay reserved behind the new position)
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
     if (n < 0 || n > p) {
@@ -1414,6 +1437,7 @@ int Decoder::shift_forced(int forced, int keep, int discard) { return forced <= 
 
 int Decoder::shift(int keep, int discard) {
     // every refusal comes before the first write
+    if (int rc = refuse_no_cache("shift")) return rc;
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
     if (keep < 0) return fail_arg("shift: keep must be >= 0");
@@ -1462,12 +1486,14 @@ const char *Decoder::fork_refusal(Decoder *const *dsts, int n_dst, const Decoder
         Decoder *d = dsts[i];
         if (!d) return "null destination";
         if (d->dead_) return "dead destination";
+        if (d->no_cache_) return "a destination owns no KV cache (a PagedBatch member)";
         if (d == src) return "a destination is the source itself: use rewind";
         for (int j = 0; j < i; ++j)
             if (dsts[j] == d) return "a destination is repeated";
         if (d->root() != root) return "source and destination must run on the same weights (an owner and its borrowers)";
         if (d->kv_f16_ != kv_f16) return "mixed KV cache types";
         if (d->batch_) return "a destination sits in a batch slot: leave the batch first";
+        if (d->no_cache_) return "a destination owns no KV cache (a PagedBatch member)";
     }
     return nullptr;
 }
@@ -1496,6 +1522,7 @@ int Decoder::fork_arrive(Decoder *const *dsts, int n_dst, int n, int forced, con
 
 int Decoder::fork_from_this(Decoder *const *dsts, int n_dst, int n) {
     // every refusal comes before the first write
+    if (int rc = refuse_no_cache("fork")) return rc;
     if (const char *why = fork_refusal(dsts, n_dst, this, root(), kv_f16_)) return fail_arg((std::string("fork: ") + why).c_str());
     const int p = position();
     if (p < 0) return BITNET_HIP_ERR_GPU;
@@ -1654,13 +1681,20 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
     const size_t ws_need = bitnet_hip_score_workspace_bytes((size_t)M, H, V);
     if (ws_need == 0) return fail_arg("step_wide: dimensions too large");
     if (!tail && !wide_tables_) HCHK(wide_tables_.alloc((2 * NL + 6) * W));
-    if (M > wide_cap_ || ws_need > wide_ws_bytes_) {
+    const bool paged = tail && tail->paged;  // a PagedBatch brings its own attention scratch: the rows form's, sized by max_pos, is not made for it
+    if (!paged && M > wide_scratch_cap_) {
         const size_t cap = (size_t)(M > wide_cap_ ? M : wide_cap_), sb = bitnet_hip_attention_scratch_bytes((size_t)c_.n_kv_heads, (size_t)c_.max_pos);
-        release_all(wide_scratch_, wide_logits_, wide_nll_, wide_am_, wide_tgt_, wide_ws_);
-        wide_cap_ = 0, wide_ws_bytes_ = 0;
-        const size_t wb = bitnet_hip_score_workspace_bytes(cap, H, V);
+        wide_scratch_.reset();
+        wide_scratch_cap_ = 0;
         HCHK(wide_scratch_.alloc_bytes(cap * sb));
         HCHK(hipMemsetAsync(wide_scratch_, 0, cap * sb, s));  // the combine requests records past the context (and drops them by index): valid, finite memory
+        wide_scratch_cap_ = (int)cap;
+    }
+    if (M > wide_cap_ || ws_need > wide_ws_bytes_) {
+        const size_t cap = (size_t)(M > wide_cap_ ? M : wide_cap_);
+        release_all(wide_logits_, wide_nll_, wide_am_, wide_tgt_, wide_ws_);
+        wide_cap_ = 0, wide_ws_bytes_ = 0;
+        const size_t wb = bitnet_hip_score_workspace_bytes(cap, H, V);
         HCHK(wide_logits_.alloc(cap * V));
         HCHK(wide_nll_.alloc(cap));
         HCHK(wide_am_.alloc(cap));
@@ -1696,6 +1730,7 @@ int Decoder::wide_forward(Decoder *const *members, int M, int n_steps, int max_p
     for (int step = 0; step < n_steps; ++step) {
         AttnOp op;  // (the positions move only in the pick below, so a repeated step rewrites the same cache slots)
         op.kind = AttnOp::Rows, op.n = (size_t)M, op.key_bound = (size_t)(max_p + step + 1), op.tables = tables, op.kv_f16 = members[0]->kv_f16_;
+        if (paged) op.kind = AttnOp::Paged, op.paged = tail->paged;  // a PagedBatch: the same rows over page tables
         if (int rc = forward_with_repeat((size_t)M, digits, op, fill)) return rc;
         BCHK(bitnet_hip_score_f16_dev(embed_, pf_x_, final_norm_, c_.eps, H, V, (size_t)M, wide_tgt_, wide_nll_, wide_am_, wide_logits_, (size_t)M, wide_ws_,
                                       wide_ws_bytes_, s));
@@ -1762,6 +1797,7 @@ int Decoder::ensure_prompt_buffers(int n, size_t attn_need) {
 
 int Decoder::prefill_sharded(int n, int rank, int world, bitnet_host_allgather_fn gather, void *gather_ctx, bool with_logits, int digits,
                              bool wire_f16, float *elapsed_ms) {
+    if (int rc = refuse_no_cache("prefill_sharded")) return rc;
     if (!embed_) return fail_arg("model globals not set");
     if (sampling_) {
         err_ = "prefill_sharded: not available with sampling on (set_sampling(NULL) first)";
@@ -2013,6 +2049,7 @@ int Decoder::score_topn(int n, int digits, int top_n, bitnet_hip_logprob_record 
 }
 
 int Decoder::finish_prefill(int n, const float *last_row, bool with_logits) {
+    if (int rc = refuse_no_cache("finish_prefill")) return rc;
     // hand over to the single-token state: residual stream of the last position, position counter
     if (n <= 0 || n > c_.max_pos - 1) {
         err_ = "KV cache overflow";
@@ -2068,6 +2105,7 @@ int Decoder::last_hidden(float *out) {
 
 // kind: 0 q|k|v, 1 attention, 2 o_proj, 3 gate|up, 4 down, 5 logits+argmax
 int Decoder::probe_kernel(int kind, int reps, float *us_per_launch, double *bytes_per_launch) {
+    if (int rc = refuse_no_cache("probe_kernel")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     const int p0 = position();
     hipGraph_t g = nullptr;

@@ -70,6 +70,16 @@ struct DecoderStreams {
 
 class PrefixCache;  // prefix_cache.hpp
 class WideBatch;    // wide_batch.hpp
+class PagedBatch;   // paged_batch.hpp
+
+// The paged KV cache a wide step attends over in place of the members' own caches (include/bitnet_hip_paged.h), named by a PagedBatch:
+// kpools / vpools are HOST arrays [n_layers] of device pool pointers; tables is the DEVICE array of the dense members' page tables.
+struct PagedAttn {
+    void *const *kpools = nullptr, *const *vpools = nullptr;
+    size_t n_pages = 0;
+    const uint32_t *const *tables = nullptr;
+    void *scratch = nullptr;  // bitnet_hip_attention_paged_scratch_bytes for the largest split count, zero-filled once
+};
 
 // The tail of a wide step when a WideBatch drives it (Decoder::wide_forward): the device pointer tables in wide_forward's own layout, built and
 // uploaded by the batch for its dense member list, and the three tail tables -- each launched ONCE per step behind bitnet_hip_pick_rows_dev, in
@@ -81,11 +91,13 @@ struct WideTail {
     size_t n_taps = 0;
     bitnet_hip_stop_batch *stop = nullptr;           // bitnet_hip_stop_batch_dev: some member has criteria
     int launches[3] = {0, 0, 0};
+    const PagedAttn *paged = nullptr;                // set: the layers attend through page tables (AttnOp::Paged); tables' cache rows are unused
 };
 
 class Decoder : private DecoderStreams {
     friend class PrefixCache;  // saves from and restores into the caches, history and counters exactly as fork does
     friend class WideBatch;    // holds members in slots and drives wide_forward on their root with a tail of its own
+    friend class PagedBatch;   // creates cache-less members and moves sequence state as fork does
 
   public:
     explicit Decoder(const Config &cfg) : Decoder(cfg, true) {}
@@ -100,7 +112,13 @@ class Decoder : private DecoderStreams {
     // set_layer_*, set_globals (hence load_gguf) and set_act_mode; the owner refuses set_layer_* / set_globals while borrowers exist.  The
     // owner must outlive its borrowers: the C shim's reference count sees to that (bitnet_host_destroy defers).  SINGLE-THREADED USE: an owner,
     // its borrowers and a batch that holds them are driven from one host thread.
-    Decoder(Decoder &owner, int);
+    Decoder(Decoder &owner, int) : Decoder(owner, 0, false) {}
+    // no_cache: a borrower WITHOUT max_pos-sized caches of its own -- a PagedBatch member, whose keys live in the batch's page pool.  It keeps
+    // history, position, logits row, sampler, tap and stop state; every entry that reads or writes a cache of its own (run, run_reference,
+    // trace_step, prefill*, extend, finish_prefill, score*, fork, shift, rewind, set_kv_f16, the prefix-cache paths, step_wide, batch slots)
+    // refuses with "... owns no KV cache".
+    Decoder(Decoder &owner, int, bool no_cache);
+    bool no_cache() const { return no_cache_; }
     Decoder *owner() const { return owner_; }
     Decoder *root() { return owner_ ? owner_ : this; }
     int borrowers() const { return borrowers_; }
@@ -402,8 +420,10 @@ class Decoder : private DecoderStreams {
   private:
     int fail(const char *what);
     int fail_arg(const char *what);
-    Decoder(const Config &cfg, bool own_norms);  // own_norms false: the borrowing constructor points the norm vectors at the owner's
+    Decoder(const Config &cfg, bool own_norms, bool no_cache = false);  // own_norms false: the borrowing constructor points the norm vectors at the owner's
     bool dead_ = false;
+    bool no_cache_ = false;
+    int refuse_no_cache(const char *entry);  // the refusal of a cache-less decoder (PagedBatch member), or 0
     // attention form of a step: 0 = two kernels, 64-position chunks; 1 = one kernel + merging o-projection (short
     // contexts: 4 records); 2 = two kernels, 128-position chunks (more chunks than CUs); 3 = as 1, 8 records (QAct path)
     struct Tracer;
@@ -448,10 +468,11 @@ class Decoder : private DecoderStreams {
     // members with their first rows, lengths and pasts (the driver's arrays: they must outlive the forward); n rows, each over its own
     // member's cache, with the bound of the record grid.
     struct AttnOp {
-        enum Kind { Whole, Continue, Pack, Rows } kind = Whole;
+        enum Kind { Whole, Continue, Pack, Rows, Paged } kind = Whole;
         size_t past = 0, n = 0, key_bound = 0;
         void *const *tables = nullptr;  // Rows: the device pointer tables (the driver's wide_tables_, or a WideBatch's own)
         bool kv_f16 = false;            // Rows: the MEMBERS' cache type (a WideBatch drives on the root, whose own type may differ)
+        const PagedAttn *paged = nullptr;  // Paged: Rows over page tables (tables still carries the position pointers)
         Decoder *const *members = nullptr;
         const int32_t *row0 = nullptr, *len = nullptr, *pasts = nullptr;
     };
@@ -480,7 +501,7 @@ class Decoder : private DecoderStreams {
     // forced count, logits row, and the pick's token / position tables (NULL for a member that samples) --, the attention scratch of wide_cap_
     // sequences (zero-filled), the head's [wide_cap_, vocab] logits, argmax, nll, targets (-1) and workspace
     DevBuf<void *> wide_tables_;
-    int wide_cap_ = 0;
+    int wide_cap_ = 0, wide_scratch_cap_ = 0;  // sequences the head's buffers / the rows attention's scratch are sized for (a paged step makes no scratch)
     DevBuf<float> wide_scratch_, wide_logits_, wide_nll_;
     DevBuf<int32_t> wide_am_, wide_tgt_;
     DevBuf<void> wide_ws_;

@@ -39,6 +39,7 @@ void PrefixCache::drop(const std::vector<uint64_t> &ids) {
 int PrefixCache::insert(Decoder &src, int n, uint64_t now_seconds, uint64_t *id) {
     // every refusal comes before the first allocation and the first change of the index
     if (src.dead()) return refuse("insert: dead decoder");
+    if (src.no_cache()) return refuse("insert: this decoder owns no KV cache (a PagedBatch member: extract() it first)");
     if (bound_ && src.root() != root_) return refuse("insert: the decoder runs on other weights than the cache is bound to");
     if (bound_ && src.kv_f16() != kv_f16_) return refuse("insert: mixed KV cache types");
     const int p = src.position();

@@ -163,6 +163,7 @@ int WideBatch::set_slot(int b, Decoder *d) {
         if (slot_[i] && i != b) others = true, peer = slot_[i];
     if (d) {
         if (d->dead_) return fail_arg("wide batch: dead member");
+        if (d->no_cache_ != (paged_ != nullptr)) return fail_arg(paged_ ? "wide batch: a paged batch takes cache-less members only" : "wide batch: this decoder owns no KV cache (a PagedBatch member)");
         for (int i = 0; i < n_; ++i)
             if (slot_[i] == d && i != b) return fail_arg("wide batch: a member is repeated (this decoder sits in slot " + std::to_string(i) + ")");
         if (others && d->root() != peer->root()) return fail_arg("wide batch: all members must run on the same weights (an owner and its borrowers)");
@@ -245,6 +246,7 @@ int WideBatch::step(int n, int digits, float *elapsed_ms) {
         if (int rc = rebuild(want)) return rc;
     WideTail tail;
     tail.tables = tables_.get();
+    tail.paged = paged_;
     for (int b = 0; b < n_; ++b) {
         const Sig &s = sig_[(size_t)b];
         if (s.sampler) tail.sample = sample_tab_;

@@ -73,8 +73,13 @@ class WideBatch {
     void tail_launches(int out[3]) const;
     // uploads of a tail table or the pointer tables since creation
     int64_t table_writes() const { return table_writes_; }
+    // A PagedBatch's hook (paged_batch.hpp), set before the first member arrives: the layers of every step attend through `p`'s page tables,
+    // whose row i is dense member i (the occupied, un-parked slots in slot order), and only cache-less members are taken.  `p` outlives the batch.
+    void set_paged(const PagedAttn *p) { paged_ = p; }
+    Decoder *member(int b) const { return b >= 0 && b < n_ ? slot_[b] : nullptr; }
 
   private:
+    const PagedAttn *paged_ = nullptr;
     // what the tables were built for, per slot
     struct Sig {
         Decoder *d = nullptr;  // null: empty or parked -- no row, no tail entry

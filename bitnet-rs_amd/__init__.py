@@ -31,6 +31,7 @@ KVSNAP_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_kvsnap.h")  # inc
 BEAM_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_beam.h")  # included by HEADER_PATH: beam search, the select and permute launches and their state
 SCORETOPN_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_scoretopn.h")  # included by HEADER_PATH: prompt top-N, two entry points
 PAGED_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_paged.h")  # included by HEADER_PATH: the paged KV cache, seven entry points
+PAGEDPREFILL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_pagedprefill.h")  # included by HEADER_PATH: prompt attention over page tables, two
 WIDETAIL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_widetail.h")  # included by HEADER_PATH: the wide step's 64-entry tail tables, two
 
 OK = 0
@@ -131,6 +132,7 @@ class HipLib:
         cproto.bind(self.c, beam_prototypes(), C_STRUCTS)
         cproto.bind(self.c, scoretopn_prototypes(), C_STRUCTS)
         cproto.bind(self.c, paged_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, pagedprefill_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -557,6 +559,27 @@ class HipLib:
         self._check(self.c.bitnet_hip_attention_decode_paged_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kpool), _ptr(vpool), n_pages, _ptr(table_ptrs),
                                                                  _ptr(pos_ptrs), n_seq, n_heads, n_kv, head_dim, max_pos, key_bound, n_splits, _ptr(scratch), flags,
                                                                  _ptr(out), _vp(stream)))
+
+    def attention_paged_prefill_workspace_bytes(self, n_heads: int, n_kv: int, n_rows: int) -> int:
+        """Workspace of attention_paged_prefill_dev: the query image and the block records of n_rows packed rows, whatever the pasts; 0 for sizes it refuses."""
+        return int(self.c.bitnet_hip_attention_paged_prefill_workspace_bytes(n_heads, n_kv, n_rows))
+
+    def attention_paged_prefill_dev(self, qkv, n_rows, rope_sin, rope_cos, row0, len_, past, tables, kpool, vpool, n_pages: int, n_heads, n_kv, head_dim, max_pos,
+                                    workspace, workspace_bytes, out, flags: int = 0, stream: int = 0, n_seq: int | None = None) -> None:
+        """attention_packed_dev over page tables: segment s owns packed rows row0[s] .. row0[s] + len_[s] - 1 at positions past[s] .., reads its keys
+        through tables[s] (uint32 device tensors or raw device pointers) and appends the new ones into its pages of kpool / vpool.  row0 / len_ / past
+        are host arrays.  flags: ATTN_CACHE_F16 (1) | ATTN_OUT_F16 (2)."""
+        ra, rp = self._i32_table(row0)
+        la, lp = self._i32_table(len_)
+        pa, pp = self._i32_table(past)
+        tb = None
+        if tables is not None:
+            vals = [None if t is None else (t if isinstance(t, int) else t.data_ptr()) for t in tables]
+            tb = (_vp * max(len(vals), 1))(*vals)
+        n = (ra.size if ra is not None else 0) if n_seq is None else n_seq
+        self._check(self.c.bitnet_hip_attention_paged_prefill_dev(_optr(qkv), n_rows, _optr(rope_sin), _optr(rope_cos), n, rp, lp, pp, tb, _optr(kpool), _optr(vpool),
+                                                                  n_pages, n_heads, n_kv, head_dim, max_pos, _optr(workspace), workspace_bytes, _optr(out), flags,
+                                                                  _vp(stream)))
 
     def kv_page_in_dev(self, k_ptrs, v_ptrs, kpool_ptrs, vpool_ptrs, table, n_pages: int, n_layers: int, n_kv: int, head_dim: int, max_pos: int,
                        n_positions: int, kv_f16: bool = False, stream: int = 0) -> None:
@@ -1364,10 +1387,15 @@ def paged_prototypes() -> list:
     return cproto.prototypes(open(PAGED_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def pagedprefill_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_pagedprefill.h, the header include/bitnet_hip.h includes for the prompt attention over page tables."""
+    return cproto.prototypes(open(PAGEDPREFILL_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
     return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + gramc_prototypes() + kvsnap_prototypes()
-                   + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes() + paged_prototypes()})
+                   + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes() + paged_prototypes() + pagedprefill_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -2371,6 +2399,21 @@ class HostPagedBatch:
         """n steps of every member; returns the elapsed milliseconds (HIP events)."""
         ms = C.c_float(0.0)
         self._check(self._p("step")(self.h, int(n), int(digits), C.byref(ms)))
+        return float(ms.value)
+
+    def open(self, slot: int) -> None:
+        """Seat an empty cache-less member (position 0, no pages): feed its prompt through member(slot), then prefill()."""
+        self._check(self._p("open")(self.h, int(slot)))
+
+    def prefill(self, slots, n, with_logits: bool = True, digits: int = 2) -> float:
+        """n[i] fed tokens of member slots[i] in ONE packed prompt forward straight into pages, at any position (a fresh prompt, a chunk of one,
+        the continuation of a fork); all or nothing when the pool is too small.  Returns the elapsed milliseconds (HIP events)."""
+        sa, na = _np(slots, np.int32), _np(n, np.int32)
+        if sa.size != na.size:
+            raise BitNetHipError(ERR_INVALID_ARGUMENT, "paged batch: prefill: slots and n differ in length")
+        ms = C.c_float(0.0)
+        self._check(self._p("prefill")(self.h, sa.ctypes.data_as(C.POINTER(C.c_int32)), na.ctypes.data_as(C.POINTER(C.c_int32)), int(sa.size), 1 if with_logits else 0,
+                                       int(digits), C.byref(ms)))
         return float(ms.value)
 
     def member(self, slot: int) -> "HostDecoder":

@@ -1246,6 +1246,12 @@ int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16, const
         for (size_t i = 0; i < op.n; ++i) kc[i] = op.members[i]->layers_[li].kcache, vc[i] = op.members[i]->layers_[li].vcache;
         BCHK(bitnet_hip_attention_packed_dev(pf_qkv_, N, rope_sin_, rope_cos_, op.n, op.row0, op.len, op.pasts, kc, vc, NH, NK, D, MP, pf_attn_ws_, pf_attn_ws_bytes_,
                                              out, flags, stream_));
+    } else if (op.kind == AttnOp::PagedPack) {
+        // a pack over page tables (PagedBatch::prefill): the segments' keys are read from, and appended into, this layer's pools
+        const PagedAttn &pg = *op.paged;
+        const int pflags = (op.kv_f16 ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
+        BCHK(bitnet_hip_attention_paged_prefill_dev(pf_qkv_, N, rope_sin_, rope_cos_, op.n, op.row0, op.len, op.pasts, op.seg_tables, pg.kpools[li], pg.vpools[li],
+                                                    pg.n_pages, NH, NK, D, MP, pf_attn_ws_, pf_attn_ws_bytes_, out, pflags, stream_));
     } else if (op.kind == AttnOp::Continue)
         BCHK(bitnet_hip_attention_extend_dev(pf_qkv_, rope_sin_, rope_cos_, L.kcache, L.vcache, NH, NK, D, MP, op.past, N, pf_attn_ws_, pf_attn_ws_bytes_, out, flags, stream_));
     else if (out_f16)
@@ -1608,7 +1614,7 @@ int Decoder::prefill_packed(Decoder *const *members, const int *n, int n_members
 // last token and the next member's first are padding (the embeddings of the history entries that follow -- fed, picked or zero: valid tokens --
 // so every matmul row is finite and of a token's scale; the attention neither reads nor caches them).  This decoder is the driver.
 int Decoder::packed_forward(Decoder *const *members, const std::vector<int32_t> &past, const std::vector<int32_t> &len, bool with_logits, int digits,
-                            float *elapsed_ms) {
+                            float *elapsed_ms, const PagedAttn *paged, const uint32_t *const *seg_tables) {
     const size_t H = c_.hidden, NH = (size_t)c_.n_heads, NK = (size_t)c_.n_kv_heads, M = past.size();
     const size_t align = bitnet_hip_attention_packed_row_align(NH, NK);
     if (align == 0) return fail_arg("prefill_packed: head counts out of range");
@@ -1618,7 +1624,7 @@ int Decoder::packed_forward(Decoder *const *members, const std::vector<int32_t> 
         row0[i] = (int32_t)((N + align - 1) / align * align);
         N = (size_t)row0[i] + (size_t)len[i];
     }
-    const size_t attn_need = bitnet_hip_attention_packed_workspace_bytes(NH, NK, N, M, past.data(), len.data());
+    const size_t attn_need = paged ? bitnet_hip_attention_paged_prefill_workspace_bytes(NH, NK, N) : bitnet_hip_attention_packed_workspace_bytes(NH, NK, N, M, past.data(), len.data());
     if (attn_need == 0) return fail_arg("prefill_packed: sizes out of range");
     if (int rc = ensure_prompt_buffers((int)N, attn_need)) return rc;
     hipStream_t s = (hipStream_t)stream_;
@@ -1639,12 +1645,14 @@ int Decoder::packed_forward(Decoder *const *members, const std::vector<int32_t> 
     };
     AttnOp op;  // (its pointers are this frame's vectors: they outlive both attempts)
     op.kind = AttnOp::Pack, op.members = members, op.n = M, op.row0 = row0.data(), op.len = len.data(), op.pasts = past.data();
+    if (paged) op.kind = AttnOp::PagedPack, op.paged = paged, op.seg_tables = seg_tables, op.kv_f16 = members[0]->kv_f16_;
     if (int rc = forward_with_repeat(N, digits, op, fill)) return rc;
     // the hand-over: every member's own head, pick and log-probability record on its own stream, from its last token's row
     HCHK(hipStreamSynchronize(s));
     for (size_t i = 0; i < M; ++i) {
         Decoder *d = members[i];
-        const int rc = d->finish_prefill(past[i] + len[i], pf_x_ + ((size_t)row0[i] + (size_t)len[i] - 1) * H, with_logits);
+        const float *last_row = pf_x_ + ((size_t)row0[i] + (size_t)len[i] - 1) * H;
+        const int rc = paged ? d->finish_prefill_state(past[i] + len[i], last_row, with_logits) : d->finish_prefill(past[i] + len[i], last_row, with_logits);
         if (rc) {
             if (d != this) err_ = d->err_;
             return rc;
@@ -2050,6 +2058,10 @@ int Decoder::score_topn(int n, int digits, int top_n, bitnet_hip_logprob_record 
 
 int Decoder::finish_prefill(int n, const float *last_row, bool with_logits) {
     if (int rc = refuse_no_cache("finish_prefill")) return rc;
+    return finish_prefill_state(n, last_row, with_logits);
+}
+
+int Decoder::finish_prefill_state(int n, const float *last_row, bool with_logits) {
     // hand over to the single-token state: residual stream of the last position, position counter
     if (n <= 0 || n > c_.max_pos - 1) {
         err_ = "KV cache overflow";

@@ -468,13 +468,14 @@ class Decoder : private DecoderStreams {
     // members with their first rows, lengths and pasts (the driver's arrays: they must outlive the forward); n rows, each over its own
     // member's cache, with the bound of the record grid.
     struct AttnOp {
-        enum Kind { Whole, Continue, Pack, Rows, Paged } kind = Whole;
+        enum Kind { Whole, Continue, Pack, Rows, Paged, PagedPack } kind = Whole;
         size_t past = 0, n = 0, key_bound = 0;
         void *const *tables = nullptr;  // Rows: the device pointer tables (the driver's wide_tables_, or a WideBatch's own)
         bool kv_f16 = false;            // Rows: the MEMBERS' cache type (a WideBatch drives on the root, whose own type may differ)
         const PagedAttn *paged = nullptr;  // Paged: Rows over page tables (tables still carries the position pointers)
         Decoder *const *members = nullptr;
         const int32_t *row0 = nullptr, *len = nullptr, *pasts = nullptr;
+        const uint32_t *const *seg_tables = nullptr;  // PagedPack: a Pack over page tables (host array of the members' device tables; pools in `paged`)
     };
     int prompt_form(size_t N, int digits, bool sharded, PromptForm *out);  // the decision, and every buffer growth the form needs
     int project_qkv(size_t l, size_t N, const PromptForm &f);
@@ -491,8 +492,11 @@ class Decoder : private DecoderStreams {
     static int check_members(Decoder *const *members, int n_members, int cap, const std::string &entry, const char *also);
     int prompt_forward(int p, int n, bool with_logits, int digits, float *elapsed_ms);  // the body of prefill (p == 0) and extend
     int ensure_prompt_buffers(int n, size_t attn_need);             // the per-row buffers and the attention workspace of a prompt forward of n rows
+    // the body of prefill_packed, on the driver.  With paged (PagedBatch::prefill): the members are cache-less, seg_tables[i] is member i's device
+    // page table, and every layer attends through bitnet_hip_attention_paged_prefill_dev; `this` may then be no member at all (the weights' owner).
     int packed_forward(Decoder *const *members, const std::vector<int32_t> &past, const std::vector<int32_t> &len, bool with_logits, int digits,
-                       float *elapsed_ms);                          // the body of prefill_packed, on the driver
+                       float *elapsed_ms, const PagedAttn *paged = nullptr, const uint32_t *const *seg_tables = nullptr);
+    int finish_prefill_state(int n, const float *last_row, bool with_logits);  // finish_prefill behind its refusals
     // the body of step_wide, on the driver.  tail == null: the driver builds and uploads the pointer tables and ends every step with one sampling,
     // tap and stop launch PER MEMBER (step_wide, unchanged).  With a tail (WideBatch): the tables are the tail's and each step ends with at most
     // one launch of each kind; `this` may then be no member at all (the weights' owner).

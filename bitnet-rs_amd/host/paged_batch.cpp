@@ -234,6 +234,67 @@ int PagedBatch::extract(int slot, Decoder &dst) {
     return arrive(d, p, *m);
 }
 
+int PagedBatch::open(int slot) {
+    if (int rc = check_slot(slot, false)) return rc;
+    Decoder *m = new_member();
+    if (!m) return BITNET_HIP_ERR_GPU;
+    return seat(slot, m, pool_->create());
+}
+
+int PagedBatch::prefill(const int *slots, const int *n, int count, bool with_logits, int digits, float *elapsed_ms) {
+    if (elapsed_ms) *elapsed_ms = 0.f;
+    if (dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    // every refusal comes before the first write, the page count included (as step() counts: fresh pages up to the last new position, and a
+    // private copy of the page of the first append for every sharer but the last)
+    if (!slots || !n || count < 1 || count > BITNET_HIP_PACK_MAX) return fail_arg("paged batch: prefill: 1.." + std::to_string(BITNET_HIP_PACK_MAX) + " listed members");
+    std::vector<Decoder *> members((size_t)count);
+    std::vector<int32_t> past((size_t)count), len((size_t)count);
+    std::vector<const uint32_t *> tabs((size_t)count);
+    size_t need = 0;
+    std::map<uint32_t, uint32_t> sharers;
+    for (int i = 0; i < count; ++i) {
+        if (int rc = check_slot(slots[i], true)) return rc;
+        for (int j = 0; j < i; ++j)
+            if (slots[j] == slots[i]) return fail_arg("paged batch: prefill: a slot is listed twice");
+        Decoder *m = members[(size_t)i] = slot_[slots[i]];
+        const int p = m->position();
+        if (p < 0) {
+            err_ = m->err_;
+            return BITNET_HIP_ERR_GPU;
+        }
+        if (n[i] < 1) return fail_arg("paged batch: prefill: every member takes at least 1 token");
+        if (const char *e = m->span_problem(p, n[i])) return fail_arg(e);
+        past[(size_t)i] = p, len[(size_t)i] = n[i], tabs[(size_t)i] = tables_ + (size_t)slots[i] * chunks_;
+        const std::vector<uint32_t> &pg = pool_->find(seq_[slots[i]])->pages;
+        const size_t want = (size_t)(p + n[i] - 1) / 64 + 1;
+        need += want > pg.size() ? want - pg.size() : 0;
+        if ((size_t)p / 64 < pg.size() && pool_->ref_count(pg[(size_t)p / 64]) > 1) {
+            uint32_t &left = sharers.emplace(pg[(size_t)p / 64], pool_->ref_count(pg[(size_t)p / 64])).first->second;
+            if (left > 1) ++need, --left;
+        }
+    }
+    if (need > pool_->pages_free())
+        return fail_arg("paged batch: the pool has too few free pages for this prefill (" + std::to_string(pool_->pages_free()) + " free, " + std::to_string(need) + " needed)");
+    std::vector<uint32_t> pairs;
+    std::vector<int> changed;
+    for (int i = 0; i < count; ++i) {
+        const PagePool::Reserve first = pool_->reserve(seq_[slots[i]], past[(size_t)i]), rest = pool_->reserve(seq_[slots[i]], past[(size_t)i] + len[(size_t)i] - 1);
+        if (first.copy) pairs.push_back(first.src), pairs.push_back(first.dst);
+        if (first.grew || rest.grew) changed.push_back(slots[i]);
+    }
+    const Config &c = root_->c_;
+    const size_t NL = root_->layers_.size();
+    if (!pairs.empty())
+        BCHK(bitnet_hip_kv_page_copy_dev(pool_dev_, pool_dev_ + NL, n_pages_, pairs.data(), pairs.size() / 2, NL, (size_t)c.n_kv_heads, (size_t)c.head_dim,
+                                         kv_f16_ ? BITNET_HIP_ATTN_KV_F16 : 0, root_->stream_));
+    for (int b : changed)
+        if (int rc = upload_table(b)) return rc;
+    // the root drives: its prompt buffers, its stream; the members bring history, position and their own heads
+    const int rc = root_->packed_forward(members.data(), past, len, with_logits, digits, elapsed_ms, &attn_, tabs.data());
+    if (rc) err_ = root_->err_;
+    return rc;
+}
+
 int PagedBatch::step(int n, int digits, float *elapsed_ms) {
     if (elapsed_ms) *elapsed_ms = 0.f;
     if (dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -323,6 +384,10 @@ int bitnet_host_paged_batch_extract(void *b, int slot, void *dst) {
 }
 int bitnet_host_paged_batch_step(void *b, int n, int digits, float *elapsed_ms) {
     return b ? static_cast<PagedBatch *>(b)->step(n, digits, elapsed_ms) : BITNET_HIP_ERR_INVALID_ARGUMENT;
+}
+int bitnet_host_paged_batch_open(void *b, int slot) { return b ? static_cast<PagedBatch *>(b)->open(slot) : BITNET_HIP_ERR_INVALID_ARGUMENT; }
+int bitnet_host_paged_batch_prefill(void *b, const int32_t *slots, const int32_t *n, int count, int with_logits, int digits, float *elapsed_ms) {
+    return b ? static_cast<PagedBatch *>(b)->prefill(slots, n, count, with_logits != 0, digits, elapsed_ms) : BITNET_HIP_ERR_INVALID_ARGUMENT;
 }
 void *bitnet_host_paged_batch_member(void *b, int slot) {
     Decoder *m = b ? static_cast<PagedBatch *>(b)->member(slot) : nullptr;

@@ -16,11 +16,17 @@
 //   release(slot)         the member goes; pages nobody else names return to the pool.
 //   extract(slot, dst)    ONE bitnet_hip_kv_page_out_dev launch into the ordinary decoder dst plus the state, as fork: the bridge back to
 //                         PrefixCache, BeamSearch, shift and run().  The member stays.
+//   open(slot)            seats an EMPTY member (position 0, no pages): the caller feeds its prompt through member(slot).
+//   prefill(slots, n, ..) the listed members take n[i] of their fed tokens in ONE packed prompt forward whose every layer attends through
+//                         bitnet_hip_attention_paged_prefill_dev: the new keys go straight into pages, the past is read from its pages.  Pages are
+//                         reserved for all listed members or for none; at most ONE bitnet_hip_kv_page_copy_dev launch for members whose last page
+//                         is shared; only changed tables are uploaded.  Each member ends as Decoder::prefill_packed leaves a member.  At position
+//                         0 it is a prompt's prefill, later a chunk of one or the continuation of a fork.
 //   step(n, digits)       reserves pages for n appends of every member (refused as a whole, nothing changed, when the pool is too small), at
 //                         most ONE bitnet_hip_kv_page_copy_dev launch for the forks that diverge, a table upload only for tables that changed,
 //                         then WideBatch's step: Decoder::wide_forward with AttnOp::Paged in every layer -- bitnet_hip_attention_decode_paged_dev
 //                         in place of the rows attention -- and WideBatch's one-launch tails.
-// Not here: prompt forwards that write straight into pages, eviction, paged forms of shift / beam / the snapshot movers (extract is the bridge),
+// Not here: eviction, paged forms of shift / beam / the snapshot movers (extract is the bridge),
 // reading a shared page once for several sequences.  SINGLE-THREADED USE, as every batch of this layer.
 #pragma once
 
@@ -47,6 +53,8 @@ class PagedBatch {
     int release(int slot);
     int extract(int slot, Decoder &dst);  // dst as a destination of Decoder::fork
     int step(int n, int digits, float *elapsed_ms);
+    int open(int slot);
+    int prefill(const int *slots, const int *n, int count, bool with_logits, int digits, float *elapsed_ms);
     Decoder *member(int slot) const { return slot >= 0 && slot < n_ ? slot_[slot] : nullptr; }
     size_t pages_in_use() const { return pool_ ? pool_->pages_in_use() : 0; }
     size_t pages_free() const { return pool_ ? pool_->pages_free() : 0; }
@@ -92,6 +100,8 @@ int bitnet_host_paged_batch_fork(void *b, int from, int to);
 int bitnet_host_paged_batch_release(void *b, int slot);
 int bitnet_host_paged_batch_extract(void *b, int slot, void *dst);
 int bitnet_host_paged_batch_step(void *b, int n, int digits, float *elapsed_ms);
+int bitnet_host_paged_batch_open(void *b, int slot);
+int bitnet_host_paged_batch_prefill(void *b, const int32_t *slots, const int32_t *n, int count, int with_logits, int digits, float *elapsed_ms);
 void *bitnet_host_paged_batch_member(void *b, int slot);  // the slot's decoder with one reference MORE (bitnet_host_destroy drops it), or NULL
 int64_t bitnet_host_paged_batch_pages_in_use(void *b);
 int64_t bitnet_host_paged_batch_pages_free(void *b);

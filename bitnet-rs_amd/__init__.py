@@ -32,6 +32,7 @@ BEAM_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_beam.h")  # include
 SCORETOPN_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_scoretopn.h")  # included by HEADER_PATH: prompt top-N, two entry points
 PAGED_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_paged.h")  # included by HEADER_PATH: the paged KV cache, seven entry points
 PAGEDPREFILL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_pagedprefill.h")  # included by HEADER_PATH: prompt attention over page tables, two
+PAGEDSHARED_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_pagedshared.h")  # included by HEADER_PATH: shared pages read once per fork group, three
 WIDETAIL_HEADER_PATH = os.path.join(ROOT, "include", "bitnet_hip_widetail.h")  # included by HEADER_PATH: the wide step's 64-entry tail tables, two
 
 OK = 0
@@ -133,6 +134,7 @@ class HipLib:
         cproto.bind(self.c, scoretopn_prototypes(), C_STRUCTS)
         cproto.bind(self.c, paged_prototypes(), C_STRUCTS)
         cproto.bind(self.c, pagedprefill_prototypes(), C_STRUCTS)
+        cproto.bind(self.c, pagedshared_prototypes(), C_STRUCTS)
 
     # -- helpers ---------------------------------------------------------
     def last_error(self) -> str:
@@ -559,6 +561,25 @@ class HipLib:
         self._check(self.c.bitnet_hip_attention_decode_paged_dev(_ptr(qkv), _ptr(rope_sin), _ptr(rope_cos), _ptr(kpool), _ptr(vpool), n_pages, _ptr(table_ptrs),
                                                                  _ptr(pos_ptrs), n_seq, n_heads, n_kv, head_dim, max_pos, key_bound, n_splits, _ptr(scratch), flags,
                                                                  _ptr(out), _vp(stream)))
+
+    def attention_paged_shared_splits(self, n_groups: int, n_kv: int, shared_pages: int) -> int:
+        """The shared split count attention_decode_paged_shared_dev chooses for n_shared_splits = 0 (a pure host function)."""
+        return int(self.c.bitnet_hip_attention_paged_shared_splits(n_groups, n_kv, shared_pages))
+
+    def attention_paged_shared_scratch_bytes(self, n_seq: int, n_kv: int, n_splits: int, n_shared_splits: int) -> int:
+        return int(self.c.bitnet_hip_attention_paged_shared_scratch_bytes(n_seq, n_kv, n_splits, n_shared_splits))
+
+    def attention_decode_paged_shared_dev(self, qkv, rope_sin, rope_cos, kpool, vpool, n_pages: int, table_ptrs, pos_ptrs, n_seq: int, n_heads, n_kv, head_dim,
+                                          max_pos, key_bound, n_splits: int, scratch, out, leader, shared_pages, n_shared_splits: int = 0,
+                                          kv_f16: bool = False, out_f16: bool = False, stream: int = 0) -> None:
+        """attention_decode_paged_dev for fork groups: leader / shared_pages are host int sequences [n_seq] (leader[b]: the row whose table names row
+        b's shared run, shared_pages[b]: its length in pages, 0 = ungrouped).  The shared pages are read once per group (MFMA), the rest per row."""
+        flags = (1 if kv_f16 else 0) | (2 if out_f16 else 0)
+        _, lp = self._i32_table(leader)
+        _, sp = self._i32_table(shared_pages)
+        self._check(self.c.bitnet_hip_attention_decode_paged_shared_dev(_optr(qkv), _optr(rope_sin), _optr(rope_cos), _optr(kpool), _optr(vpool), n_pages,
+                                                                        _optr(table_ptrs), _optr(pos_ptrs), n_seq, n_heads, n_kv, head_dim, max_pos, key_bound, n_splits,
+                                                                        _optr(scratch), flags, _optr(out), lp, sp, n_shared_splits, _vp(stream)))
 
     def attention_paged_prefill_workspace_bytes(self, n_heads: int, n_kv: int, n_rows: int) -> int:
         """Workspace of attention_paged_prefill_dev: the query image and the block records of n_rows packed rows, whatever the pasts; 0 for sizes it refuses."""
@@ -1392,10 +1413,15 @@ def pagedprefill_prototypes() -> list:
     return cproto.prototypes(open(PAGEDPREFILL_HEADER_PATH).read(), "bitnet_hip_")
 
 
+def pagedshared_prototypes() -> list:
+    """The prototypes of include/bitnet_hip_pagedshared.h, the header include/bitnet_hip.h includes for the fork groups' paged decode attention."""
+    return cproto.prototypes(open(PAGEDSHARED_HEADER_PATH).read(), "bitnet_hip_")
+
+
 def declared_symbols() -> list[str]:
     """Every function include/bitnet_hip.h declares, the headers it includes among them (used by the export test)."""
     return sorted({name for name, _, _ in cproto.prototypes(open(HEADER_PATH).read(), "bitnet_hip_") + grammar_prototypes() + gramc_prototypes() + kvsnap_prototypes()
-                   + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes() + paged_prototypes() + pagedprefill_prototypes()})
+                   + widetail_prototypes() + beam_prototypes() + scoretopn_prototypes() + paged_prototypes() + pagedprefill_prototypes() + pagedshared_prototypes()})
 
 
 # ---------------------------------------------------------------------------
@@ -2400,6 +2426,15 @@ class HostPagedBatch:
         ms = C.c_float(0.0)
         self._check(self._p("step")(self.h, int(n), int(digits), C.byref(ms)))
         return float(ms.value)
+
+    def set_share(self, min_pages: int) -> None:
+        """0: step as ever.  >= 1: step finds fork groups (the same leading pages, at least min_pages of them) and reads their shared pages once per
+        group in every layer (attention_decode_paged_shared_dev)."""
+        self._check(self._p("set_share")(self.h, int(min_pages)))
+
+    def shared_rows(self) -> int:
+        """Rows x layers the last step() sent through the shared pass (0: the default route ran)."""
+        return int(self._p("shared_rows")(self.h))
 
     def open(self, slot: int) -> None:
         """Seat an empty cache-less member (position 0, no pages): feed its prompt through member(slot), then prefill()."""

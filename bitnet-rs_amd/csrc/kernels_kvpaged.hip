@@ -16,12 +16,15 @@
 //                  writes the output row and re-arms the counter.
 //     The query group has at most 4 rows: a 16- or 32-row MFMA tile would run three-quarters empty, and the kernel is a memory stream whose VALU
 //     dot products hide under the loads.
+//   k_attn_paged_suffix<KV16>  the same body (attn_paged_body) behind the shared-page pass of kernels_pagedshared.hip: sequence b starts at its first
+//                       private chunk and its merge takes the shared pass's records first (paged_attn.hpp: AttnPagedLead).
 //   k_kv_page_move      one workgroup per (layer, KV head, K | V, chunk) tile, 16-byte integer loads and stores, both directions.
 //   k_kv_page_copy      one workgroup per (layer, KV head, K | V, pair) tile.
 #include "common.hpp"
 #include "kv_guard.hpp"
 #include "kv_layout.hpp"
 #include "kv_paged.hpp"
+#include "paged_attn.hpp"
 #include "paged_splits.hpp"
 #include "select.hpp"
 #include "wave.hpp"
@@ -30,32 +33,15 @@ namespace bitnet_hip {
 
 namespace {
 
-constexpr int kPgMaxGroup = 4;
-constexpr int kPgD = kKvDim;
-constexpr int kPgRec = kAttnRecFloats;  // (m, l)[4], o[4][128]
 // own page ids kept in LDS: 16384 positions per split.  A workgroup that owns more reads the id of page >= kPgIdCap again from the table -- a
 // line the validation pass of this same workgroup has just read (it walks the whole table), so a cache hit, not a second trip to memory;
 // the library's own split rule reaches it only beyond 32768 positions
 constexpr int kPgIdCap = 256;
-constexpr size_t kPgTicketWords = (size_t)kWideMax;  // arrival counters per KV head, whatever n_seq is: one scratch serves every batch size
-static_assert(kPgRec == 2 * kPgMaxGroup + kPgMaxGroup * kPgD, "record layout");
-static_assert(kPgRec * sizeof(float) % 16 == 0, "records stay 16-byte aligned");
 
-struct AttnPagedArgs {
-    const float *qkv, *rope_sin, *rope_cos;
-    uint32_t *kpool, *vpool;
-    const uint32_t *const *tables;
-    const int *const *pos_ptrs;
-    uint32_t *tickets;  // [kWideMax][n_kv]
-    float *records;     // [n_seq][n_kv][n_splits][kPgRec]
-    float *out;         // one of the two
-    _Float16 *out_h;
-    unsigned n_pages;
-    int n_heads, n_kv, group, key_bound, n_splits;
-};
-
-template <bool KV16>
-__global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
+// The ONE body of the paged decode attention.  LEAD = false is k_attn_paged as the head comment has it.  LEAD = true is the suffix pass of the shared
+// entry (kernels_pagedshared.hip): the walk starts at the sequence's first private chunk and the merge takes the shared pass's records first.
+template <bool KV16, bool LEAD>
+__device__ __forceinline__ void attn_paged_body(const AttnPagedArgs &a, const AttnPagedLead *ld) {
     constexpr int R = KV16 ? kPgD / 2 : kPgD;  // words per position and head
     constexpr int NL = KV16 ? 16 : 32;         // K dwords, and V dwords, per thread and page
     constexpr int NPQ = KV16 ? 4 : 2;          // position classes of the P.V pass
@@ -66,6 +52,8 @@ __global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
     const int pos = *pp;
     if (pos < 0 || pos >= a.key_bound) return;  // block-uniform: beyond the caller's bound = idle
     const int t_k = pos + 1, last_chunk = pos >> 6, n_chunks = last_chunk + 1, n_splits = a.n_splits;
+    const int first = LEAD ? (ld->first[b] < last_chunk ? ld->first[b] : last_chunk) : 0;  // the first chunk of the walk; the page of pos is always walked
+    const int n_lead = LEAD && ld->first[b] > 0 ? ld->n_lead : 0;
 
     __shared__ uint32_t ids[kPgIdCap];
     __shared__ __attribute__((aligned(16))) float qs[kPgMaxGroup * kPgD];
@@ -87,7 +75,7 @@ __global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
     for (int i = tid; i < n_chunks; i += 256) {
         const uint32_t pg = tbl[i];
         bad |= pg >= a.n_pages;
-        const int own = i - sp;
+        const int own = i - first - sp;
         if (own >= 0 && own % n_splits == 0 && own / n_splits < kPgIdCap) ids[own / n_splits] = pg;
     }
     {
@@ -113,10 +101,10 @@ __global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
     }
     if (__syncthreads_or(bad)) return;  // block-uniform, and the same in every workgroup of the sequence: a page id outside the pool = idle
 
-    const int n_own = sp < n_chunks ? (n_chunks - sp + n_splits - 1) / n_splits : 0;
+    const int n_own = first + sp < n_chunks ? (n_chunks - first - sp + n_splits - 1) / n_splits : 0;
     const uint32_t *kpool = a.kpool, *vpool = a.vpool;
     const int n_kv = a.n_kv;
-    auto page_of = [&](int it) -> uint32_t { return it < kPgIdCap ? ids[it] : tbl[sp + it * n_splits]; };  // (every id passed the check above)
+    auto page_of = [&](int it) -> uint32_t { return it < kPgIdCap ? ids[it] : tbl[first + sp + it * n_splits]; };  // (every id passed the check above)
     auto load = [&](uint32_t pg, uint32_t(&k)[NL], uint32_t(&v)[NL]) __attribute__((always_inline)) {
         const size_t tile = kv_page_tile_words(pg, kvh, n_kv, R);
         const uint32_t *kp = kpool + tile + (size_t)(NL * wave) * 64 + lane;  // word (row NL * wave + i, position lane)
@@ -134,7 +122,7 @@ __global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
     // one page: the next page's loads first, then scores -> softmax pieces -> P.V on the tiles in k / v
     auto step = [&](int it, uint32_t(&k)[NL], uint32_t(&v)[NL], uint32_t(&kx)[NL], uint32_t(&vx)[NL]) __attribute__((always_inline)) {
         if (it + 1 < n_own) load(page_of(it + 1), kx, vx);
-        const int chunk = sp + it * n_splits, j0 = chunk * kKvChunk;
+        const int chunk = first + sp + it * n_splits, j0 = chunk * kKvChunk;
         const bool last = chunk == last_chunk;  // the page of the new token, the only partial one (block-uniform)
         // ---- scores: lane = position, wave = 32-dim slice
         if (KV16) {
@@ -274,7 +262,7 @@ __global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
     }
 
     // ---- append: the share that holds the new token's page, after its last page (whole words: f16 pairs packed by one thread) ----
-    if (n_own > 0 && sp + (n_own - 1) * n_splits == last_chunk) {
+    if (n_own > 0 && first + sp + (n_own - 1) * n_splits == last_chunk) {
         const size_t tile = kv_page_tile_words(page_of(n_own - 1), kvh, n_kv, R);
         const int slot = pos & 63;
         if (KV16) {
@@ -323,31 +311,34 @@ __global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
     }
     {
         const int g = tid >> 6, d2 = 2 * lane;  // head g, dims d2 and d2 + 1
-        const float *base = a.records + ((size_t)b * n_kv + kvh) * n_splits * kPgRec;
         float m = -INFINITY, l = 0.0f;
         float2 o = {0.0f, 0.0f};
-        for (int s0 = 0; s0 < n_splits; s0 += 4) {
-            float mc[4], lc[4];
-            float2 oc[4];
+        auto merge_run = [&](const float *base, int n) __attribute__((always_inline)) {
+            for (int s0 = 0; s0 < n; s0 += 4) {
+                float mc[4], lc[4];
+                float2 oc[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float *r = base + (size_t)(s0 + u < n_splits ? s0 + u : s0) * kPgRec;  // past the end: this trip's first record again, dropped below
-                mc[u] = r[2 * g];
-                lc[u] = r[2 * g + 1];
-                oc[u] = *reinterpret_cast<const float2 *>(r + 2 * kPgMaxGroup + g * kPgD + d2);
-            }
+                for (int u = 0; u < 4; ++u) {
+                    const float *r = base + (size_t)(s0 + u < n ? s0 + u : s0) * kPgRec;  // past the end: this trip's first record again, dropped below
+                    mc[u] = r[2 * g];
+                    lc[u] = r[2 * g + 1];
+                    oc[u] = *reinterpret_cast<const float2 *>(r + 2 * kPgMaxGroup + g * kPgD + d2);
+                }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (s0 + u < n_splits) {  // split 0 holds page 0: m is finite from the first step on; an empty share has e^(-inf) = 0
-                    const float m_new = fmaxf(m, mc[u]);
-                    const float s_old = expf(m - m_new), s_c = expf(mc[u] - m_new);
-                    l = fmaf(l, s_old, lc[u] * s_c);
-                    o.x = fmaf(o.x, s_old, oc[u].x * s_c);
-                    o.y = fmaf(o.y, s_old, oc[u].y * s_c);
-                    m = m_new;
+                for (int u = 0; u < 4; ++u) {
+                    if (s0 + u < n) {  // the first record holds page 0 (or, in a suffix pass, a shared page): m is finite from the first step on; an empty share has e^(-inf) = 0
+                        const float m_new = fmaxf(m, mc[u]);
+                        const float s_old = expf(m - m_new), s_c = expf(mc[u] - m_new);
+                        l = fmaf(l, s_old, lc[u] * s_c);
+                        o.x = fmaf(o.x, s_old, oc[u].x * s_c);
+                        o.y = fmaf(o.y, s_old, oc[u].y * s_c);
+                        m = m_new;
+                    }
                 }
             }
-        }
+        };
+        if (LEAD) merge_run(ld->records + ((size_t)b * n_kv + kvh) * ld->n_lead * kPgRec, n_lead);  // shared records first, in shared-split order
+        merge_run(a.records + ((size_t)b * n_kv + kvh) * n_splits * kPgRec, n_splits);
         if (g < group) {
             const size_t col = (size_t)b * a.n_heads * kPgD + (size_t)(kvh * group + g) * kPgD + d2;
             const float x = o.x / l, y = o.y / l;
@@ -359,6 +350,16 @@ __global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
             }
         }
     }
+}
+
+template <bool KV16>
+__global__ __launch_bounds__(256) void k_attn_paged(const AttnPagedArgs a) {
+    attn_paged_body<KV16, false>(a, nullptr);
+}
+
+template <bool KV16>
+__global__ __launch_bounds__(256) void k_attn_paged_suffix(const AttnPagedArgs a, const AttnPagedLead ld) {
+    attn_paged_body<KV16, true>(a, &ld);
 }
 
 // ---- the movers -----------------------------------------------------------------------------------------------------------------------------
@@ -469,6 +470,53 @@ int page_move(const char *entry, bool to_pages, const void *const *k_ptrs, const
 
 }  // namespace
 
+// ---- the front and the launch kernels_pagedshared.hip borrows (paged_attn.hpp) ----
+int attn_paged_front(const char *entry, const float *qkv, const float *rope_sin, const float *rope_cos, void *kpool, void *vpool, size_t n_pages,
+                     const uint32_t *const *table_ptrs_dev, const int32_t *const *pos_ptrs_dev, size_t n_seq, size_t n_heads, size_t n_kv_heads, size_t head_dim,
+                     size_t max_pos, size_t key_bound, size_t *n_splits, void *scratch, int flags, void *out, AttnPagedArgs *a) {
+    if (n_seq == 0 || n_seq > BITNET_HIP_WIDE_MAX)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_seq %zu must be 1..%d", entry, n_seq, BITNET_HIP_WIDE_MAX);
+    if (!qkv || !rope_sin || !rope_cos || !kpool || !vpool || !table_ptrs_dev || !pos_ptrs_dev || !scratch || !out)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to %s", entry);
+    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x (BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)", entry, flags);
+    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
+    if (head_dim != 128 || n_heads / n_kv_heads > 4 || n_heads == 0)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: head_dim %zu / group %zu unsupported (head_dim 128, group 1..4)", entry, head_dim, n_heads / n_kv_heads);
+    const bool f16 = (flags & BITNET_HIP_ATTN_CACHE_F16) != 0;
+    if (int rc = check_pool(entry, n_pages, n_kv_heads, head_dim, f16)) return rc;
+    // positions are ints in the kernel, the grid's x takes the KV heads
+    if (max_pos == 0 || max_pos > ((size_t)1 << 24) || n_heads > 65535)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (%s: n_heads %zu, max_pos %zu)", entry, n_heads, max_pos);
+    if (key_bound == 0 || key_bound > max_pos)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: key_bound %zu must be 1..max_pos %zu", entry, key_bound, max_pos);
+    const size_t pages = div_ceil(key_bound, (size_t)64);
+    if (*n_splits > pages || *n_splits > 65535)
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_splits %zu above the %zu pages of key_bound %zu", entry, *n_splits, pages, key_bound);
+    if (*n_splits == 0) *n_splits = attn_paged_auto_splits(n_seq, n_kv_heads, key_bound);
+    if (!bitnet_hip_attention_paged_scratch_bytes(n_seq, n_kv_heads, *n_splits))
+        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (%s: n_seq %zu, n_kv_heads %zu, n_splits %zu)", entry, n_seq, n_kv_heads,
+                         *n_splits);
+    a->qkv = qkv, a->rope_sin = rope_sin, a->rope_cos = rope_cos;
+    a->kpool = static_cast<uint32_t *>(kpool), a->vpool = static_cast<uint32_t *>(vpool);
+    a->tables = table_ptrs_dev, a->pos_ptrs = reinterpret_cast<const int *const *>(pos_ptrs_dev);
+    a->tickets = static_cast<uint32_t *>(scratch);
+    a->records = reinterpret_cast<float *>(a->tickets + kPgTicketWords * n_kv_heads);
+    a->out = (flags & BITNET_HIP_ATTN_OUT_F16) ? nullptr : static_cast<float *>(out);
+    a->out_h = (flags & BITNET_HIP_ATTN_OUT_F16) ? static_cast<_Float16 *>(out) : nullptr;
+    a->n_pages = (unsigned)n_pages, a->n_heads = (int)n_heads, a->n_kv = (int)n_kv_heads, a->group = (int)(n_heads / n_kv_heads);
+    a->key_bound = (int)key_bound, a->n_splits = (int)*n_splits;
+    return BITNET_HIP_OK;
+}
+
+hipError_t attn_paged_launch(bool f16, const AttnPagedArgs &a, const AttnPagedLead *lead, size_t n_seq, hipStream_t stream) {
+    const dim3 grid((unsigned)a.n_kv, (unsigned)a.n_splits, (unsigned)n_seq);
+    if (lead) hipLaunchKernelGGL(f16 ? k_attn_paged_suffix<true> : k_attn_paged_suffix<false>, grid, dim3(256), 0, stream, a, *lead);
+    else hipLaunchKernelGGL(f16 ? k_attn_paged<true> : k_attn_paged<false>, grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 }  // namespace bitnet_hip
 
 using namespace bitnet_hip;
@@ -493,43 +541,11 @@ int bitnet_hip_attention_decode_paged_dev(const float *qkv, const float *rope_si
                                           size_t n_kv_heads, size_t head_dim, size_t max_pos, size_t key_bound, size_t n_splits, void *scratch, int flags,
                                           void *out, void *stream) {
     const char *entry = "attention_decode_paged_dev";
-    if (n_seq == 0 || n_seq > BITNET_HIP_WIDE_MAX)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_seq %zu must be 1..%d", entry, n_seq, BITNET_HIP_WIDE_MAX);
-    if (!qkv || !rope_sin || !rope_cos || !kpool || !vpool || !table_ptrs_dev || !pos_ptrs_dev || !scratch || !out)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "Null pointer passed to %s", entry);
-    if (flags & ~(BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x (BITNET_HIP_ATTN_CACHE_F16 | BITNET_HIP_ATTN_OUT_F16)", entry, flags);
-    if (n_kv_heads == 0 || n_heads % n_kv_heads != 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "num_heads %zu must be divisible by num_key_value_heads %zu", n_heads, n_kv_heads);
-    if (head_dim != 128 || n_heads / n_kv_heads > 4 || n_heads == 0)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: head_dim %zu / group %zu unsupported (head_dim 128, group 1..4)", entry, head_dim, n_heads / n_kv_heads);
-    const bool f16 = (flags & BITNET_HIP_ATTN_CACHE_F16) != 0;
-    if (int rc = check_pool(entry, n_pages, n_kv_heads, head_dim, f16)) return rc;
-    // positions are ints in the kernel, the grid's x takes the KV heads
-    if (max_pos == 0 || max_pos > ((size_t)1 << 24) || n_heads > 65535)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (%s: n_heads %zu, max_pos %zu)", entry, n_heads, max_pos);
-    if (key_bound == 0 || key_bound > max_pos)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: key_bound %zu must be 1..max_pos %zu", entry, key_bound, max_pos);
-    const size_t pages = div_ceil(key_bound, (size_t)64);
-    if (n_splits > pages || n_splits > 65535)
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "%s: n_splits %zu above the %zu pages of key_bound %zu", entry, n_splits, pages, key_bound);
-    if (n_splits == 0) n_splits = attn_paged_auto_splits(n_seq, n_kv_heads, key_bound);
-    if (!bitnet_hip_attention_paged_scratch_bytes(n_seq, n_kv_heads, n_splits))
-        return set_error(BITNET_HIP_ERR_INVALID_ARGUMENT, "dimensions too large for this library (%s: n_seq %zu, n_kv_heads %zu, n_splits %zu)", entry, n_seq, n_kv_heads,
-                         n_splits);
     AttnPagedArgs a;
-    a.qkv = qkv, a.rope_sin = rope_sin, a.rope_cos = rope_cos;
-    a.kpool = static_cast<uint32_t *>(kpool), a.vpool = static_cast<uint32_t *>(vpool);
-    a.tables = table_ptrs_dev, a.pos_ptrs = reinterpret_cast<const int *const *>(pos_ptrs_dev);
-    a.tickets = static_cast<uint32_t *>(scratch);
-    a.records = reinterpret_cast<float *>(a.tickets + kPgTicketWords * n_kv_heads);
-    a.out = (flags & BITNET_HIP_ATTN_OUT_F16) ? nullptr : static_cast<float *>(out);
-    a.out_h = (flags & BITNET_HIP_ATTN_OUT_F16) ? static_cast<_Float16 *>(out) : nullptr;
-    a.n_pages = (unsigned)n_pages, a.n_heads = (int)n_heads, a.n_kv = (int)n_kv_heads, a.group = (int)(n_heads / n_kv_heads);
-    a.key_bound = (int)key_bound, a.n_splits = (int)n_splits;
-    hipLaunchKernelGGL(f16 ? k_attn_paged<true> : k_attn_paged<false>, dim3((unsigned)n_kv_heads, (unsigned)n_splits, (unsigned)n_seq), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    BH_HIP_TRY(hipGetLastError());
+    if (int rc = attn_paged_front(entry, qkv, rope_sin, rope_cos, kpool, vpool, n_pages, table_ptrs_dev, pos_ptrs_dev, n_seq, n_heads, n_kv_heads, head_dim, max_pos,
+                                  key_bound, &n_splits, scratch, flags, out, &a))
+        return rc;
+    BH_HIP_TRY(attn_paged_launch((flags & BITNET_HIP_ATTN_CACHE_F16) != 0, a, nullptr, n_seq, (hipStream_t)stream));
     return BITNET_HIP_OK;
 }
 

@@ -31,6 +31,7 @@
 #include "common.hpp"
 #include "kv_layout.hpp"
 #include "kv_paged.hpp"
+#include "paged_stage.hpp"
 #include "wave.hpp"
 
 namespace bitnet_hip {
@@ -41,8 +42,7 @@ constexpr int kPpD = kKvDim, kPpT = kKvChunk;
 constexpr int kPpMax = BITNET_HIP_PACK_MAX;
 constexpr int kPpQPad = 128;                   // query rows are padded to the largest workgroup query tile
 constexpr int kPpIdCap = 256;                  // page ids of the walk kept in LDS (16384 positions); beyond: read again from the (checked) table
-constexpr int kPpTileBytes = kPpT * kPpD * 2;  // one f16 operand tile in LDS
-constexpr int kPpBufBytes = 2 * kPpTileBytes;  // K tile | V^T tile; the kernel keeps two
+constexpr int kPpTileBytes = kPgTileBytes, kPpBufBytes = kPgBufBytes;  // paged_stage.hpp: one f16 operand tile; K tile | V^T tile, the kernel keeps two
 
 // the host arrays of a call, as kernel arguments: no upload, the call stays asynchronous
 struct PagedSegs {
@@ -192,23 +192,12 @@ __global__ __launch_bounds__(256) void k_paged_prefill_prep(const PagedPrepArgs 
     }
 }
 
-// max over the four lanes (c, g = 0..3) that hold one query's keys, in every lane (kernels_prefill_attn.hip: the VALU swaps of gfx950)
-__device__ __forceinline__ float paged_max_over_g(float v) {
-    const unsigned u = __float_as_uint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const float m1 = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const unsigned w = __float_as_uint(m1);
-    const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
 template <int HW, bool KV16>
 // One workgroup per CU: at two the f16 instance spilled (148 bytes of scratch per lane at the 256-register budget); the staging registers of the
 // next tile live beside 64 output and 32 score accumulators.  Bringing it back to two workgroups is tuning left open.
 __global__ __launch_bounds__(256) void k_prefill_attn_paged(const PagedAttnArgs p) {
     constexpr int NQ = 2, QG = 32 * (4 / HW);  // query groups of 16 per wave, query rows per workgroup
     constexpr int R = KV16 ? kPpD / 2 : kPpD;  // pool words per position and head
-    constexpr int KN = KV16 ? 4 : 8;           // 16-byte K loads per thread and tile
     extern __shared__ __attribute__((aligned(16))) uint8_t kv_lds[];  // [2][K tile | V^T tile]
     __shared__ uint32_t ids[kPpIdCap];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c = lane & 15, g = lane >> 4;
@@ -258,86 +247,14 @@ __global__ __launch_bounds__(256) void k_prefill_attn_paged(const PagedAttnArgs 
     for (int q = 0; q < NQ; ++q) qlim[q] = bpos + 16 * q + c < T ? bpos + 16 * q + c : T - 1;
     const int qmin = __builtin_amdgcn_readfirstlane(bpos < T ? bpos : T - 1);
 
-    // ---- tile staging: page -> registers (requested a tile ahead), registers -> LDS (behind the arithmetic of the tile before) ----
-    // K: 16-byte unit idx = tid + 256 i = (dim pair row idx >> 4, positions 4 (idx & 15) ..); f32 pools: the two dims' rows, paired on the way in.
-    // V: step i takes positions 4 (wave + 4 i) .. + 3 of word `lane` (f32 pools: the float2 of dims 2 lane, 2 lane + 1).
-    u32x4 kraw[KN];
-    uint32_t vraw[KV16 ? 16 : 32];
+    // ---- tile staging (paged_stage.hpp): page -> registers (requested a tile ahead), registers -> LDS (behind the arithmetic of the tile before).
+    //      n_live = T - kt * 64: positions of the tile below the key count (>= 1) ----
+    PagedTileStage<KV16> st;
     auto page_of = [&](int kt) -> uint32_t { return kt < kPpIdCap ? ids[kt] : tbl[kt]; };  // (every id passed the check above)
-    auto fetch_k = [&](int kt) __attribute__((always_inline)) {
-        const uint32_t *kp = p.kpool + kv_page_tile_words(page_of(kt), kvh, p.n_kv, R);
-        const int n_live = T - kt * kPpT;  // positions of this tile below the key count (>= 1); units wholly at or past it are not read
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + 256 * i, r = idx >> 4, u = idx & 15;
-            const bool on = 4 * u < n_live;
-            if (KV16) {
-                kraw[i] = on ? *reinterpret_cast<const u32x4 *>(kp + r * 64 + 4 * u) : (u32x4){0u, 0u, 0u, 0u};
-            } else {
-                kraw[2 * i] = on ? *reinterpret_cast<const u32x4 *>(kp + (2 * r) * 64 + 4 * u) : (u32x4){0u, 0u, 0u, 0u};
-                kraw[2 * i + 1] = on ? *reinterpret_cast<const u32x4 *>(kp + (2 * r + 1) * 64 + 4 * u) : (u32x4){0u, 0u, 0u, 0u};
-            }
-        }
-    };
-    auto fetch_v = [&](int kt) __attribute__((always_inline)) {
-        const uint32_t *vp = p.vpool + kv_page_tile_words(page_of(kt), kvh, p.n_kv, R);
-        const int n_live = T - kt * kPpT;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int pos = 4 * (wave + 4 * i) + e;
-                if (KV16) {
-                    vraw[4 * i + e] = pos < n_live ? vp[pos * R + lane] : 0u;
-                } else {
-                    const uint2 w = pos < n_live ? *reinterpret_cast<const uint2 *>(vp + pos * R + 2 * lane) : uint2{0u, 0u};
-                    vraw[8 * i + 2 * e] = w.x, vraw[8 * i + 2 * e + 1] = w.y;
-                }
-            }
-    };
-    auto commit_k = [&](int kt, int buf) __attribute__((always_inline)) {
-        uint8_t *ks = kv_lds + buf * kPpBufBytes;
-        const int n_live = T - kt * kPpT;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + 256 * i, r = idx >> 4, u = idx & 15;
-            u32x4 w;
-            if (KV16) {
-                w = kraw[i];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) w[e] = pack_h2(__uint_as_float(kraw[2 * i][e]), __uint_as_float(kraw[2 * i + 1][e]));
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = 4 * u + e < n_live ? w[e] : 0u;  // a unit that straddles the key count
-            *reinterpret_cast<u32x4 *>(ks + (r * 64 + ((4 * u) ^ (((r >> 2) & 3) << 4))) * 4) = w;
-        }
-    };
-    auto commit_v = [&](int buf) __attribute__((always_inline)) {
-        uint8_t *vs = kv_lds + buf * kPpBufBytes + kPpTileBytes;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int t4 = wave + 4 * i, slot = 32 * (t4 >> 3) + 8 * (t4 & 3) + 4 * ((t4 >> 2) & 1);
-            uint32_t lo[2], hi[2];  // 4 keys of dim 2 lane, 4 keys of dim 2 lane + 1
-            if (KV16) {
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const uint32_t w0 = vraw[4 * i + 2 * e], w1 = vraw[4 * i + 2 * e + 1];
-                    lo[e] = (w0 & 0xffffu) | (w1 << 16);
-                    hi[e] = (w0 >> 16) | (w1 & 0xffff0000u);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    lo[e] = pack_h2(__uint_as_float(vraw[8 * i + 4 * e]), __uint_as_float(vraw[8 * i + 4 * e + 2]));
-                    hi[e] = pack_h2(__uint_as_float(vraw[8 * i + 4 * e + 1]), __uint_as_float(vraw[8 * i + 4 * e + 3]));
-                }
-            }
-            const int off = (((slot >> 3) ^ (lane & 7)) * 16) + (slot & 7) * 2;
-            *reinterpret_cast<uint2 *>(vs + (2 * lane) * 128 + off) = uint2{lo[0], lo[1]};
-            *reinterpret_cast<uint2 *>(vs + (2 * lane + 1) * 128 + off) = uint2{hi[0], hi[1]};
-        }
-    };
+    auto fetch_k = [&](int kt) __attribute__((always_inline)) { st.fetch_k(p.kpool + kv_page_tile_words(page_of(kt), kvh, p.n_kv, R), T - kt * kPpT, tid); };
+    auto fetch_v = [&](int kt) __attribute__((always_inline)) { st.fetch_v(p.vpool + kv_page_tile_words(page_of(kt), kvh, p.n_kv, R), T - kt * kPpT, wave, lane); };
+    auto commit_k = [&](int kt, int buf) __attribute__((always_inline)) { st.commit_k(kv_lds + buf * kPpBufBytes, T - kt * kPpT, tid); };
+    auto commit_v = [&](int buf) __attribute__((always_inline)) { st.commit_v(kv_lds + buf * kPpBufBytes + kPpTileBytes, wave, lane); };
 
     fetch_k(0);
     fetch_v(0);

@@ -1237,9 +1237,19 @@ int Decoder::prompt_attention(Layer &L, size_t N, void *out, bool out_f16, const
         // count for (N, NK, key_bound); the position pointers are the wide tables' row
         const PagedAttn &pg = *op.paged;
         const int rflags = (op.kv_f16 ? BITNET_HIP_ATTN_CACHE_F16 : 0) | (out_f16 ? BITNET_HIP_ATTN_OUT_F16 : 0);
-        BCHK(bitnet_hip_attention_decode_paged_dev(pf_qkv_, rope_sin_, rope_cos_, pg.kpools[li], pg.vpools[li], pg.n_pages, pg.tables,
-                                                   reinterpret_cast<const int32_t *const *>(op.tables + 2 * layers_.size() * BITNET_HIP_WIDE_MAX), N, NH, NK, D, MP,
-                                                   op.key_bound, 0, pg.scratch, rflags, out, stream_));
+        const int32_t *const *pos_t = reinterpret_cast<const int32_t *const *>(op.tables + 2 * layers_.size() * BITNET_HIP_WIDE_MAX);
+        if (pg.leader) {  // fork groups: their shared pages once per group, then the same attention over every row's private pages
+            BCHK(bitnet_hip_attention_decode_paged_shared_dev(pf_qkv_, rope_sin_, rope_cos_, pg.kpools[li], pg.vpools[li], pg.n_pages, pg.tables, pos_t, N, NH, NK, D, MP,
+                                                              op.key_bound, 0, pg.scratch, rflags, out, pg.leader, pg.shared_pages, 0, stream_));
+            if (pg.shared_layer_rows) {
+                size_t rows = 0;
+                for (size_t i = 0; i < N; ++i) rows += pg.shared_pages[i] > 0;
+                pg.shared_layer_rows[li] = rows;
+            }
+        } else {
+            BCHK(bitnet_hip_attention_decode_paged_dev(pf_qkv_, rope_sin_, rope_cos_, pg.kpools[li], pg.vpools[li], pg.n_pages, pg.tables, pos_t, N, NH, NK, D, MP,
+                                                       op.key_bound, 0, pg.scratch, rflags, out, stream_));
+        }
     } else if (op.kind == AttnOp::Pack) {
         // a pack (prefill_packed): the N rows are several members' segments, each over its OWN caches of this layer
         void *kc[BITNET_HIP_PACK_MAX], *vc[BITNET_HIP_PACK_MAX];

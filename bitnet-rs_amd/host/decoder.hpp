@@ -78,7 +78,11 @@ struct PagedAttn {
     void *const *kpools = nullptr, *const *vpools = nullptr;
     size_t n_pages = 0;
     const uint32_t *const *tables = nullptr;
-    void *scratch = nullptr;  // bitnet_hip_attention_paged_scratch_bytes for the largest split count, zero-filled once
+    void *scratch = nullptr;  // bitnet_hip_attention_paged_shared_scratch_bytes for the largest split counts, zero-filled once
+    // Fork groups (PagedBatch::set_share; include/bitnet_hip_pagedshared.h): HOST arrays over the dense rows, or null -- then every layer is
+    // bitnet_hip_attention_decode_paged_dev as ever.  shared_layer_rows[l], when given, receives the rows layer l sent through the shared pass.
+    const int32_t *leader = nullptr, *shared_pages = nullptr;
+    size_t *shared_layer_rows = nullptr;
 };
 
 // The tail of a wide step when a WideBatch drives it (Decoder::wide_forward): the device pointer tables in wide_forward's own layout, built and

@@ -51,7 +51,7 @@ PagedBatch::PagedBatch(Decoder &root, size_t n_pages, int n_slots) {
     const size_t pb = bitnet_hip_kv_pool_bytes(n_pages, NK, (size_t)c.head_dim, kv_f16_ ? 1 : 0);
     chunks_ = ((size_t)c.max_pos + 63) / 64;
     const size_t max_splits = chunks_ < 16 ? chunks_ : 16;  // the library's own choice never exceeds 16 (csrc/paged_splits.hpp)
-    const size_t sb = bitnet_hip_attention_paged_scratch_bytes((size_t)n_slots, NK, max_splits);
+    const size_t sb = bitnet_hip_attention_paged_shared_scratch_bytes((size_t)n_slots, NK, max_splits, max_splits);  // shared splits: at most 16 too
     if (!pb || !sb) {
         err_ = "paged batch: n_pages / the model's attention geometry is not one the paged attention takes";
         return;
@@ -80,6 +80,7 @@ PagedBatch::PagedBatch(Decoder &root, size_t n_pages, int n_slots) {
         return;
     }
     wide_->set_paged(&attn_);
+    leader_.assign(BITNET_HIP_WIDE_MAX, 0), shared_pages_.assign(BITNET_HIP_WIDE_MAX, 0), layer_rows_.assign(NL, 0);
     root_ = &root;
     root_->refs_++;
     n_ = n_slots;
@@ -295,6 +296,45 @@ int PagedBatch::prefill(const int *slots, const int *n, int count, bool with_log
     return rc;
 }
 
+int PagedBatch::set_share(int min_pages) {
+    if (dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;
+    if (min_pages < 0) return fail_arg("paged batch: set_share: min_pages must be 0 (off) or at least 1");
+    share_min_ = min_pages;
+    return 0;
+}
+
+// Dense row i = the i-th occupied slot.  A group = the rows whose page lists start with the same page; its run = their longest common leading run,
+// capped at min position >> 6 (the page that takes an append is never in it, now or later in the step: positions only grow).
+void PagedBatch::find_groups(const int *pos) {
+    int rows[BITNET_HIP_WIDE_MAX], M = 0;
+    for (int b = 0; b < n_; ++b)
+        if (slot_[b]) rows[M++] = b;
+    bool seen[BITNET_HIP_WIDE_MAX] = {}, any = false;
+    for (int i = 0; i < M; ++i) leader_[(size_t)i] = i, shared_pages_[(size_t)i] = 0;
+    for (int i = 0; i < M; ++i) {
+        if (seen[i]) continue;
+        const std::vector<uint32_t> &lead = pool_->find(seq_[rows[i]])->pages;
+        if (lead.empty()) continue;
+        std::vector<int> members;
+        size_t run = lead.size();
+        for (int j = i; j < M; ++j) {
+            const std::vector<uint32_t> &pg = pool_->find(seq_[rows[j]])->pages;
+            if (seen[j] || pg.empty() || pg[0] != lead[0]) continue;
+            seen[j] = true;
+            members.push_back(j);
+            size_t k = 0, cap = (size_t)pos[rows[j]] >> 6;
+            if (cap > pg.size()) cap = pg.size();
+            if (cap > run) cap = run;
+            while (k < cap && pg[k] == lead[k]) ++k;
+            run = k;
+        }
+        if (members.size() < 2 || run < (size_t)share_min_) continue;
+        for (int j : members) leader_[(size_t)j] = i, shared_pages_[(size_t)j] = (int32_t)run;
+        any = true;
+    }
+    if (any) attn_.leader = leader_.data(), attn_.shared_pages = shared_pages_.data(), attn_.shared_layer_rows = layer_rows_.data();
+}
+
 int PagedBatch::step(int n, int digits, float *elapsed_ms) {
     if (elapsed_ms) *elapsed_ms = 0.f;
     if (dead_) return BITNET_HIP_ERR_INVALID_ARGUMENT;
@@ -353,8 +393,13 @@ int PagedBatch::step(int n, int digits, float *elapsed_ms) {
         HCHK(hipMemcpy(table_ptrs_, t, sizeof(t), hipMemcpyHostToDevice));
         dense_stale_ = false;
     }
+    attn_.leader = attn_.shared_pages = nullptr, attn_.shared_layer_rows = nullptr;
+    shared_rows_ = 0;
+    layer_rows_.assign(layer_rows_.size(), 0);
+    if (share_min_ > 0) find_groups(pos);
     const int rc = wide_->step(n, digits, elapsed_ms);
     if (rc) err_ = wide_->error();
+    for (size_t r : layer_rows_) shared_rows_ += r;
     return rc;
 }
 
@@ -394,6 +439,8 @@ void *bitnet_host_paged_batch_member(void *b, int slot) {
     if (m) m->refs_++;
     return m;
 }
+int bitnet_host_paged_batch_set_share(void *b, int min_pages) { return b ? static_cast<PagedBatch *>(b)->set_share(min_pages) : BITNET_HIP_ERR_INVALID_ARGUMENT; }
+int64_t bitnet_host_paged_batch_shared_rows(void *b) { return b ? (int64_t) static_cast<PagedBatch *>(b)->shared_rows() : -1; }
 int64_t bitnet_host_paged_batch_pages_in_use(void *b) { return b ? (int64_t) static_cast<PagedBatch *>(b)->pages_in_use() : -1; }
 int64_t bitnet_host_paged_batch_pages_free(void *b) { return b ? (int64_t) static_cast<PagedBatch *>(b)->pages_free() : -1; }
 uint64_t bitnet_host_paged_batch_pool_bytes(void *b) { return b ? (uint64_t) static_cast<PagedBatch *>(b)->pool_bytes() : 0; }

@@ -26,8 +26,12 @@
 //                         most ONE bitnet_hip_kv_page_copy_dev launch for the forks that diverge, a table upload only for tables that changed,
 //                         then WideBatch's step: Decoder::wide_forward with AttnOp::Paged in every layer -- bitnet_hip_attention_decode_paged_dev
 //                         in place of the rows attention -- and WideBatch's one-launch tails.
-// Not here: eviction, paged forms of shift / beam / the snapshot movers (extract is the bridge),
-// reading a shared page once for several sequences.  SINGLE-THREADED USE, as every batch of this layer.
+//   set_share(min_pages)  0 (the default): step as above.  >= 1: after its reservation and copy-on-write launch step finds the FORK GROUPS from the
+//                         host page lists -- members with the same first page; the run is their longest common leading run of pages, capped at
+//                         min over members of position >> 6; fewer than 2 members or a run below min_pages = ungrouped -- once for all n steps
+//                         (only tail entries change while stepping), and every layer calls bitnet_hip_attention_decode_paged_shared_dev: the
+//                         group's shared pages are read once per group.  With no group found the step is the default one.
+// Not here: eviction, paged forms of shift / beam / the snapshot movers (extract is the bridge).  SINGLE-THREADED USE, as every batch of this layer.
 #pragma once
 
 #include <memory>
@@ -53,6 +57,8 @@ class PagedBatch {
     int release(int slot);
     int extract(int slot, Decoder &dst);  // dst as a destination of Decoder::fork
     int step(int n, int digits, float *elapsed_ms);
+    int set_share(int min_pages);                        // refused when negative
+    size_t shared_rows() const { return shared_rows_; }  // rows x layers the last step sent through the shared pass
     int open(int slot);
     int prefill(const int *slots, const int *n, int count, bool with_logits, int digits, float *elapsed_ms);
     Decoder *member(int slot) const { return slot >= 0 && slot < n_ ? slot_[slot] : nullptr; }
@@ -86,6 +92,11 @@ class PagedBatch {
     bool dense_stale_ = true;
     DevBuf<void> scratch_;
     PagedAttn attn_;
+    int share_min_ = 0;
+    size_t shared_rows_ = 0;
+    std::vector<int32_t> leader_, shared_pages_;  // [BITNET_HIP_WIDE_MAX] over the dense rows
+    std::vector<size_t> layer_rows_;              // [n_layers]
+    void find_groups(const int *pos);             // fills leader_ / shared_pages_, points attn_ at them when a group exists
     std::unique_ptr<WideBatch> wide_;
 };
 
@@ -103,6 +114,8 @@ int bitnet_host_paged_batch_step(void *b, int n, int digits, float *elapsed_ms);
 int bitnet_host_paged_batch_open(void *b, int slot);
 int bitnet_host_paged_batch_prefill(void *b, const int32_t *slots, const int32_t *n, int count, int with_logits, int digits, float *elapsed_ms);
 void *bitnet_host_paged_batch_member(void *b, int slot);  // the slot's decoder with one reference MORE (bitnet_host_destroy drops it), or NULL
+int bitnet_host_paged_batch_set_share(void *b, int min_pages);
+int64_t bitnet_host_paged_batch_shared_rows(void *b);
 int64_t bitnet_host_paged_batch_pages_in_use(void *b);
 int64_t bitnet_host_paged_batch_pages_free(void *b);
 uint64_t bitnet_host_paged_batch_pool_bytes(void *b);

@@ -1118,5 +1118,6 @@ int bitnet_hip_hbm_read_ceiling(size_t bytes, int iters, double *best_gbs, doubl
 #include "bitnet_hip_beam.h"    /* beam search: the select launch, the in-place KV permute and their state object, seven more */
 #include "bitnet_hip_paged.h"   /* the paged KV cache: pool sizes, the attention over page tables, the page movers, seven more */
 #include "bitnet_hip_pagedprefill.h" /* prompt attention over page tables: prefill and extend straight into KV pages, two more */
+#include "bitnet_hip_pagedshared.h" /* the paged decode attention for fork groups: shared pages read once per group, three more */
 
 #endif /* BITNET_HIP_H */
